@@ -10,11 +10,21 @@ bounces (the reference's own unit; about 5.37 M per step).  Inputs are resident 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W      # N ranks: interleaved row tiles + one RCCL reduce per run
 
-Prints ONE JSON line on rank 0.  Extra objects: "roofline" (dominant kernel, algorithmic bytes / measured launch time)
-and "cpu_baseline" (the oracle, single thread, on this host), see DESIGN.md "Measurement".  With N > 1 the same line also carries,
-all OUTSIDE the timed region: "long_run" (200 steps of the same tile split: the regime where eight GPUs pay), "exchange_alt_ms"
-(the gather and the reduce spelling of the one exchange, each timed alone on the same buffers) and "c5" (BASELINE configs[4]: the
-3840x2160 textured-mesh scene traced as N row-tile ranks with its exchange).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps
+(into a cleared accumulation buffer), and the line -- metric, value, unit, higher_is_better, dtype, ms_per_step, config.
+
+    --dump-outputs DIR   after the timed steps, what they computed as DIR/<name>.npy: image.npy (H x W x 3 float32, the
+                         accumulation buffer a caller of pathtrace reads: the sum of the K timed iterations) and
+                         rays_per_bounce.npy (float64, paths entering each bounce in the last timed step).  The same
+                         arguments give the same inputs and iterations every run, so two builds compare output for output.
+    --full               also every leg outside the headline figure, all OUTSIDE the timed region, in the same line:
+                         "roofline" (dominant kernel, algorithmic bytes / measured launch time; the K steps once more with
+                         per-launch events), "cpu_baseline" (the oracle, single thread, on this host), see DESIGN.md
+                         "Measurement"; with one GPU "long_run", "dropin_per_call", "arith_levels", "c5" and "stream_compaction";
+                         with N > 1 "long_run" (200 steps of the same tile split: the regime where eight GPUs pay),
+                         "exchange_alt_ms" (the gather and the reduce spelling of the one exchange, each timed alone on the same
+                         buffers) and "c5" (BASELINE configs[4]: the 3840x2160 textured-mesh scene traced as N row-tile ranks with
+                         its exchange).  --no-cpu-baseline / --no-extra-legs leave parts of it out.
 """
 import argparse
 import json
@@ -59,6 +69,28 @@ def own_layout_bytes(rpb, with_direction=1.0, with_normal=1.0, index_bytes=4):
         stored = n[k + 1]
         b += n[k] * (index_bytes + rec) + stored * (rec + 4 + index_bytes + 4) + (n[k] - stored) * LIT_SHARE_OF_ENDED * 13.0
     return b / tot
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 kept as it is, anything else as float64; refuses more than
+    DUMP_LIMIT_BYTES in all.  Returns the paths written."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    paths = []
+    for name, a in out.items():
+        paths.append(os.path.join(dirname, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
 
 
 def usable_cores():
@@ -356,7 +388,15 @@ def main():
                     help="launch sets in flight (ptx_options.lanes): 0 = library default (3: kernels of different batches of iterations "
                     "fill each other's tails); 1 = one at a time, kernels back to back (what the roofline leg always uses, "
                     "because a kernel's duration is only meaningful when it has the GPU to itself)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, every other leg (roofline, CPU baseline, long run, per-call, arithmetic levels, C5, "
+                    "stream compaction; N > 1: long run, both exchanges, C5), outside the timed region; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed as DIR/image.npy (float32, the frame they accumulated) and "
+                    "DIR/rays_per_bounce.npy (float64, the last step's paths per bounce)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` without a launcher (no RANK in the environment): start the N ranks ourselves, as a CHILD
     # process (never an exec) and before anything here has touched the GPU, and hand on rank 0's JSON line and the exit code.
@@ -456,6 +496,10 @@ def main():
         clock_warmup_steps += 36
     if dist_on:                                     # warm the collective too
         reduce_frame(image.clone())
+    # the timed steps accumulate into a cleared frame: what they leave in it depends on the arguments alone, not on how many clock
+    # warm-up steps ran before them (the tracer's stream is idle here; the clear has landed before the first timed launch)
+    image.zero_()
+    torch.cuda.current_stream(device).synchronize()
     rays0 = T.stats()["rays_total"]
     barrier()
     t0 = time.perf_counter()
@@ -470,14 +514,21 @@ def main():
     rays = st["rays_total"] - rays0
     loop_ms = T.last_loop_ms()
     t_render_max = t_render
+    rpb_last = torch.tensor(st["rays_per_bounce"], dtype=torch.int64)      # paths entering each bounce in the last timed step
     if dist_on:
         t_render_max = float(all_reduce_scalar(t_render, torch.float64, dist.ReduceOp.MAX))
         dt = float(all_reduce_scalar(dt, torch.float64, dist.ReduceOp.MAX))
         rays = int(all_reduce_scalar(rays, torch.int64, dist.ReduceOp.SUM))
+        if args.dump_outputs:
+            rpb_last = rpb_last.to(device if args.backend == "nccl" else "cpu")
+            dist.all_reduce(rpb_last, op=dist.ReduceOp.SUM)
+    if args.dump_outputs and rank == 0:             # the frame on rank 0 after the exchange, before any other leg renders into it
+        write_outputs(args.dump_outputs, dict(image=image[:W * H * 3].view(H, W, 3).cpu().numpy(),
+                                              rays_per_bounce=rpb_last.cpu().numpy()))
 
     # ---- N > 1 only, OUTSIDE the timed region, same JSON line: what a single short scaling run cannot say by itself -------------
     multi = None
-    if dist_on and not by_iter:
+    if args.full and dist_on and not by_iter:
         # (multigpu.all_ok / agreed_phase / RankFailed: every rank's verdict on a phase it ran LOCALLY, agreed on by all -- a failure of
         # one rank is then every rank's failure at the same point; tests/test_multigpu_gloo.py runs the protocol with 2 gloo ranks)
         flag_dev = device if args.backend == "nccl" else None
@@ -600,127 +651,131 @@ def main():
                     pass
             del img5, warm5
 
-    # roofline leg: the same K steps again with hipEvents around every launch (on the tracer's stream)
-    T.set_kernel_timing(True)
-    render_steps(args.warmup + args.steps + 1, args.steps)
-    kt = T.kernel_times()
-    T.set_kernel_timing(False)
-    st2 = T.stats()
-    rays_leg = st2["rays_total"] - st["rays_total"]
-    rpb = st2["rays_per_bounce"]
-    names = {k: v for k, v in kt.items() if v[1] > 0}
-    dominant = max(names, key=lambda k: names[k][0]) if names else "k_bounce"
-    dom_ms, dom_n = kt[dominant]
-    if dominant == "k_bounce":
-        units = rays_leg * (sum(rpb[1:]) / max(sum(rpb), 1)) / max(dom_n, 1)       # rays per launch, bounces >= 1
-    else:
-        units = rays_leg * (rpb[0] / max(sum(rpb), 1)) / max(dom_n, 1)
-    avg_s = dom_ms / max(dom_n, 1) * 1e-3
-    sp = max(st2.get("stored_paths", 0) - st.get("stored_paths", 0), 0)
-    f_dir = (st2.get("stored_with_direction", 0) - st.get("stored_with_direction", 0)) / sp if sp else 1.0
-    f_nrm = 1.0 - (st2.get("stored_with_normal_code", 0) - st.get("stored_with_normal_code", 0)) / sp if sp else 1.0
-    rec_bytes = 32.0 + 16.0 * f_nrm + 16.0 * f_dir
-    own_bytes = own_layout_bytes(rpb, f_dir, f_nrm) if dominant == "k_bounce" else rec_bytes + 4 + 4 + 4      # (first bounce: nothing read, mostly stored)
-    achieved = own_bytes * units / avg_s if avg_s > 0 else 0.0
-    contract = CONTRACT_BYTES_BOUNCE_KERNEL * units / avg_s if avg_s > 0 else 0.0
-    # HBM bytes and instruction counts per launch come from PMC counters, which need rocprofv3: they are NOT measured in this run but
-    # taken from the committed profile of the same kernels (tools/profile_round.sh, tools/pmc_sq.sh -> profiles/), scaled from that
-    # profile's rays per launch to this run's, and labelled as such.
-    traffic = traffic_source = tjd = None
-    tj = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tj):
-        try:
-            tjd = json.load(open(tj))
-            per_launch = tjd.get(dominant)
-            ref_units = (tjd.get("_units_per_launch") or {}).get(dominant)
-            if per_launch is not None:
-                traffic = per_launch * (units / ref_units) if ref_units else per_launch
-                traffic_source = ("profiles/traffic_latest.json = %s, not this run; %s" % (
-                    tjd.get("_how", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python3 bench.py --lanes 1 --steps 24 --warmup 12 --no-cpu-baseline`"),
-                    "scaled by rays per launch %.3g / %.3g" % (units, ref_units) if ref_units else "per launch of that profile, unscaled"))
-        except Exception:
-            traffic = None
-    # The WALL-level HBM figure (round 5): `frac` / `physical_frac` describe k_bounce alone, one launch set at a time, while `value` is
-    # wall time with three launch sets overlapped.  Counter bytes of ALL kernels of a launch set (the committed FETCH_SIZE / WRITE_SIZE
-    # profile: depth - 1 launches of k_bounce, the camera bounce, the gather; per launch of `_iterations_per_launch` iterations) per
-    # iteration, over this run's wall time per step, over the 8 TB/s peak.
-    physical_wall = None
-    try:
-        if tjd and all(k in tjd for k in ("k_bounce", "k_bounce<first>", "k_gather")) and world == 1:
-            ipl = float(tjd.get("_iterations_per_launch", 12))
-            set_bytes = (DEPTH - 1) * tjd["k_bounce"] + tjd["k_bounce<first>"] + tjd["k_gather"]
-            physical_wall = dict(bytes_per_step=set_bytes / ipl, TBps=set_bytes / ipl / (dt / args.steps) / 1e12,
-                                 frac=set_bytes / ipl / (dt / args.steps) / HBM_PEAK,
-                                 source="profiles/traffic_latest.json: (%d x k_bounce + k_bounce<first> + k_gather) counter bytes per launch of %d iterations, "
-                                        "/ this run's ms_per_step / 8 TB/s" % (DEPTH - 1, int(ipl)))
-    except Exception:
+    # ---- --full only, OUTSIDE the timed region: the roofline leg and the legs below ----------------------------------------------
+    rpb = st["rays_per_bounce"]
+    roofline = None
+    if args.full:
+        # roofline leg: the same K steps again with hipEvents around every launch (on the tracer's stream)
+        T.set_kernel_timing(True)
+        render_steps(args.warmup + args.steps + 1, args.steps)
+        kt = T.kernel_times()
+        T.set_kernel_timing(False)
+        st2 = T.stats()
+        rays_leg = st2["rays_total"] - st["rays_total"]
+        rpb = st2["rays_per_bounce"]
+        names = {k: v for k, v in kt.items() if v[1] > 0}
+        dominant = max(names, key=lambda k: names[k][0]) if names else "k_bounce"
+        dom_ms, dom_n = kt[dominant]
+        if dominant == "k_bounce":
+            units = rays_leg * (sum(rpb[1:]) / max(sum(rpb), 1)) / max(dom_n, 1)       # rays per launch, bounces >= 1
+        else:
+            units = rays_leg * (rpb[0] / max(sum(rpb), 1)) / max(dom_n, 1)
+        avg_s = dom_ms / max(dom_n, 1) * 1e-3
+        sp = max(st2.get("stored_paths", 0) - st.get("stored_paths", 0), 0)
+        f_dir = (st2.get("stored_with_direction", 0) - st.get("stored_with_direction", 0)) / sp if sp else 1.0
+        f_nrm = 1.0 - (st2.get("stored_with_normal_code", 0) - st.get("stored_with_normal_code", 0)) / sp if sp else 1.0
+        rec_bytes = 32.0 + 16.0 * f_nrm + 16.0 * f_dir
+        own_bytes = own_layout_bytes(rpb, f_dir, f_nrm) if dominant == "k_bounce" else rec_bytes + 4 + 4 + 4      # (first bounce: nothing read, mostly stored)
+        achieved = own_bytes * units / avg_s if avg_s > 0 else 0.0
+        contract = CONTRACT_BYTES_BOUNCE_KERNEL * units / avg_s if avg_s > 0 else 0.0
+        # HBM bytes and instruction counts per launch come from PMC counters, which need rocprofv3: they are NOT measured in this run but
+        # taken from the committed profile of the same kernels (tools/profile_round.sh, tools/pmc_sq.sh -> profiles/), scaled from that
+        # profile's rays per launch to this run's, and labelled as such.
+        traffic = traffic_source = tjd = None
+        tj = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tj):
+            try:
+                tjd = json.load(open(tj))
+                per_launch = tjd.get(dominant)
+                ref_units = (tjd.get("_units_per_launch") or {}).get(dominant)
+                if per_launch is not None:
+                    traffic = per_launch * (units / ref_units) if ref_units else per_launch
+                    traffic_source = ("profiles/traffic_latest.json = %s, not this run; %s" % (
+                        tjd.get("_how", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python3 bench.py --lanes 1 --steps 24 --warmup 12 --no-cpu-baseline`"),
+                        "scaled by rays per launch %.3g / %.3g" % (units, ref_units) if ref_units else "per launch of that profile, unscaled"))
+            except Exception:
+                traffic = None
+        # The WALL-level HBM figure (round 5): `frac` / `physical_frac` describe k_bounce alone, one launch set at a time, while `value` is
+        # wall time with three launch sets overlapped.  Counter bytes of ALL kernels of a launch set (the committed FETCH_SIZE / WRITE_SIZE
+        # profile: depth - 1 launches of k_bounce, the camera bounce, the gather; per launch of `_iterations_per_launch` iterations) per
+        # iteration, over this run's wall time per step, over the 8 TB/s peak.
         physical_wall = None
-    valu_issue = None
-    sj = os.path.join(ROOT, "profiles", "sq_latest.json")
-    if os.path.exists(sj):
         try:
-            sq = json.load(open(sj))
-            k = sq.get(dominant) or {}
-            ref_units = (sq.get("_units_per_launch") or {}).get(dominant)
-            if k.get("SQ_INSTS_VALU") and avg_s > 0:
-                insts = k["SQ_INSTS_VALU"] * (units / ref_units if ref_units else 1.0)
-                lane_slots = insts * 64 / avg_s
-                valu_issue = dict(achieved=lane_slots / 1e12, peak=VALU_PEAK / 1e12, unit="T lane-slots/s", frac=lane_slots / VALU_PEAK,
-                                  wave_instructions_per_launch=insts, lanes_active=(k.get("_derived") or {}).get("valu_lane_utilisation"),
-                                  # `peak` is the textbook one instruction per 4 cycles and SIMD.  Measured on this chip (tools/micro/valu_rates.hip,
-                                  # wall clock, 8 waves per SIMD; profiles/round4_valu_rates.txt): plain fp32 / integer-add / logic instructions
-                                  # retire one per 2.5 cycles, min / max / select / compare / shift / binary64 / packed ones one per 4.1, a stream
-                                  # mixed like k_bounce's one per 3.06 -- the capacity the second fraction is taken of
-                                  cycles_per_instruction_per_simd=avg_s * 2.4e9 * 1024 / insts,
-                                  measured_capacity_cycles_per_instruction=dict(plain=2.54, second_class=4.09, k_bounce_like_mix=3.06,
-                                                                                source="profiles/round4_valu_rates.txt"),
-                                  frac_of_measured_mix_capacity=3.06 / (avg_s * 2.4e9 * 1024 / insts),
-                                  source="profiles/sq_latest.json (SQ_INSTS_VALU per launch from %s, not this run%s) x 64 lanes / this run's "
-                                         "launch time / (256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz)" % (
-                                             sq.get("_how", "tools/pmc_sq.sh"), "; scaled by rays per launch" if ref_units else ""))
+            if tjd and all(k in tjd for k in ("k_bounce", "k_bounce<first>", "k_gather")) and world == 1:
+                ipl = float(tjd.get("_iterations_per_launch", 12))
+                set_bytes = (DEPTH - 1) * tjd["k_bounce"] + tjd["k_bounce<first>"] + tjd["k_gather"]
+                physical_wall = dict(bytes_per_step=set_bytes / ipl, TBps=set_bytes / ipl / (dt / args.steps) / 1e12,
+                                     frac=set_bytes / ipl / (dt / args.steps) / HBM_PEAK,
+                                     source="profiles/traffic_latest.json: (%d x k_bounce + k_bounce<first> + k_gather) counter bytes per launch of %d iterations, "
+                                            "/ this run's ms_per_step / 8 TB/s" % (DEPTH - 1, int(ipl)))
         except Exception:
-            valu_issue = None
-    # were the committed counter profiles taken with the kernel sources this run was built from?  (they are scaled into `traffic`,
-    # `valu_issue` and `bound` below: a stale profile would silently describe another kernel)
-    profiles_stale = None
-    try:
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        from profile_meta import source_sha16
-        now = source_sha16()
-        shas = {}
-        for nm in ("traffic_latest.json", "sq_latest.json"):
-            f = os.path.join(ROOT, "profiles", nm)
-            if os.path.exists(f):
-                shas[nm] = json.load(open(f)).get("_source_sha16")
-        profiles_stale = dict(kernel_sources_now=now, **{k: (v if v else "unrecorded (profile older than round 4)") for k, v in shas.items()},
-                              stale=any(v != now for v in shas.values()))
-        if rank == 0 and profiles_stale["stale"]:
-            print("bench.py: profiles/*_latest.json were collected with other kernel sources than this build's: traffic / valu_issue / bound "
-                  "describe THAT profile's kernels", file=sys.stderr)
-    except Exception as e:
-        profiles_stale = dict(error=str(e)[:120])
-    loop_contract = CONTRACT_BYTES_LOOP * rays / (loop_ms * 1e-3) if loop_ms > 0 else 0.0
-    # One read tells what bounds the kernel: `bound` names it (vector-instruction issue -- valu_issue.frac of the issue peak), achieved /
-    # frac / traffic are the HBM side of the same launches by this design's own bytes; the contract's record sizes are under contract_*.
-    roofline = dict(schema="r3+: achieved / frac / algorithmic_bytes_per_unit are THIS design's own layout bytes (r3: ~120 B per ray; end of r4 ~85: records "
-                           "of 32-64 B by what the next bounce can need, record_bytes; r5 ~71: one-word index entries, no zeros for paths that end black); rounds 1-2 put the "
-                           "contract's 196 B there, which now lives under contract_196B_frac -- BENCH_r02's frac compares with contract_196B_frac, not with frac",
-                    measured_in_this_run=["achieved", "frac", "avg_launch_us", "launches", "units_per_launch", "kernels_ms_per_step", "contract_*", "loop_ms_per_step"],
-                    from_committed_profiles=["traffic", "traffic_over_algorithmic", "physical_frac", "physical_frac_wall (bytes; the time is this run's)", "valu_issue", "bound"], profiles=profiles_stale,
-                    bound="valu" if valu_issue and valu_issue["frac"] > achieved / HBM_PEAK else "hbm", kernel=dominant,
-                    achieved=achieved / 1e9, peak=HBM_PEAK / 1e9, unit="GB/s", frac=achieved / HBM_PEAK,
-                    algorithmic_bytes_per_unit=own_bytes, record_bytes=dict(mean=rec_bytes, with_direction=f_dir, with_normal=f_nrm), traffic=traffic, traffic_source=traffic_source,
-                    traffic_over_algorithmic=(traffic / (own_bytes * units)) if traffic and own_bytes else None,
-                    physical_frac=(traffic / avg_s / HBM_PEAK) if traffic and avg_s > 0 else None,
-                    physical_frac_wall=physical_wall["frac"] if physical_wall else None, physical_wall=physical_wall,
-                    valu_issue=valu_issue,
-                    contract_196B_frac=contract / HBM_PEAK,            # 196 B/ray of the reference's AoS records / launch time / 8 TB/s
-                    contract_436B_loop_ratio=loop_contract / (HBM_PEAK * world),     # a RATIO (may exceed 1): the reference layout's loop bytes
-                                                                                     # per ray / wall time of the bounce loop / 8 TB/s
-                    avg_launch_us=avg_s * 1e6, launches=dom_n, units_per_launch=units, loop_ms_per_step=loop_ms / args.steps,
-                    kernels_ms_per_step={k: v[0] / args.steps for k, v in kt.items()},
-                    timing="kernel durations: hipEvents around every launch, one launch set at a time (lanes 1), NOT additive to ms_per_step: "
-                           "value, ms_per_step and loop_ms_per_step are wall time with %d launch set(s) in flight" % (args.lanes if args.lanes >= 1 else 3))
+            physical_wall = None
+        valu_issue = None
+        sj = os.path.join(ROOT, "profiles", "sq_latest.json")
+        if os.path.exists(sj):
+            try:
+                sq = json.load(open(sj))
+                k = sq.get(dominant) or {}
+                ref_units = (sq.get("_units_per_launch") or {}).get(dominant)
+                if k.get("SQ_INSTS_VALU") and avg_s > 0:
+                    insts = k["SQ_INSTS_VALU"] * (units / ref_units if ref_units else 1.0)
+                    lane_slots = insts * 64 / avg_s
+                    valu_issue = dict(achieved=lane_slots / 1e12, peak=VALU_PEAK / 1e12, unit="T lane-slots/s", frac=lane_slots / VALU_PEAK,
+                                      wave_instructions_per_launch=insts, lanes_active=(k.get("_derived") or {}).get("valu_lane_utilisation"),
+                                      # `peak` is the textbook one instruction per 4 cycles and SIMD.  Measured on this chip (tools/micro/valu_rates.hip,
+                                      # wall clock, 8 waves per SIMD; profiles/round4_valu_rates.txt): plain fp32 / integer-add / logic instructions
+                                      # retire one per 2.5 cycles, min / max / select / compare / shift / binary64 / packed ones one per 4.1, a stream
+                                      # mixed like k_bounce's one per 3.06 -- the capacity the second fraction is taken of
+                                      cycles_per_instruction_per_simd=avg_s * 2.4e9 * 1024 / insts,
+                                      measured_capacity_cycles_per_instruction=dict(plain=2.54, second_class=4.09, k_bounce_like_mix=3.06,
+                                                                                    source="profiles/round4_valu_rates.txt"),
+                                      frac_of_measured_mix_capacity=3.06 / (avg_s * 2.4e9 * 1024 / insts),
+                                      source="profiles/sq_latest.json (SQ_INSTS_VALU per launch from %s, not this run%s) x 64 lanes / this run's "
+                                             "launch time / (256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz)" % (
+                                                 sq.get("_how", "tools/pmc_sq.sh"), "; scaled by rays per launch" if ref_units else ""))
+            except Exception:
+                valu_issue = None
+        # were the committed counter profiles taken with the kernel sources this run was built from?  (they are scaled into `traffic`,
+        # `valu_issue` and `bound` below: a stale profile would silently describe another kernel)
+        profiles_stale = None
+        try:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            from profile_meta import source_sha16
+            now = source_sha16()
+            shas = {}
+            for nm in ("traffic_latest.json", "sq_latest.json"):
+                f = os.path.join(ROOT, "profiles", nm)
+                if os.path.exists(f):
+                    shas[nm] = json.load(open(f)).get("_source_sha16")
+            profiles_stale = dict(kernel_sources_now=now, **{k: (v if v else "unrecorded (profile older than round 4)") for k, v in shas.items()},
+                                  stale=any(v != now for v in shas.values()))
+            if rank == 0 and profiles_stale["stale"]:
+                print("bench.py: profiles/*_latest.json were collected with other kernel sources than this build's: traffic / valu_issue / bound "
+                      "describe THAT profile's kernels", file=sys.stderr)
+        except Exception as e:
+            profiles_stale = dict(error=str(e)[:120])
+        loop_contract = CONTRACT_BYTES_LOOP * rays / (loop_ms * 1e-3) if loop_ms > 0 else 0.0
+        # One read tells what bounds the kernel: `bound` names it (vector-instruction issue -- valu_issue.frac of the issue peak), achieved /
+        # frac / traffic are the HBM side of the same launches by this design's own bytes; the contract's record sizes are under contract_*.
+        roofline = dict(schema="r3+: achieved / frac / algorithmic_bytes_per_unit are THIS design's own layout bytes (r3: ~120 B per ray; end of r4 ~85: records "
+                               "of 32-64 B by what the next bounce can need, record_bytes; r5 ~71: one-word index entries, no zeros for paths that end black); rounds 1-2 put the "
+                               "contract's 196 B there, which now lives under contract_196B_frac -- BENCH_r02's frac compares with contract_196B_frac, not with frac",
+                        measured_in_this_run=["achieved", "frac", "avg_launch_us", "launches", "units_per_launch", "kernels_ms_per_step", "contract_*", "loop_ms_per_step"],
+                        from_committed_profiles=["traffic", "traffic_over_algorithmic", "physical_frac", "physical_frac_wall (bytes; the time is this run's)", "valu_issue", "bound"], profiles=profiles_stale,
+                        bound="valu" if valu_issue and valu_issue["frac"] > achieved / HBM_PEAK else "hbm", kernel=dominant,
+                        achieved=achieved / 1e9, peak=HBM_PEAK / 1e9, unit="GB/s", frac=achieved / HBM_PEAK,
+                        algorithmic_bytes_per_unit=own_bytes, record_bytes=dict(mean=rec_bytes, with_direction=f_dir, with_normal=f_nrm), traffic=traffic, traffic_source=traffic_source,
+                        traffic_over_algorithmic=(traffic / (own_bytes * units)) if traffic and own_bytes else None,
+                        physical_frac=(traffic / avg_s / HBM_PEAK) if traffic and avg_s > 0 else None,
+                        physical_frac_wall=physical_wall["frac"] if physical_wall else None, physical_wall=physical_wall,
+                        valu_issue=valu_issue,
+                        contract_196B_frac=contract / HBM_PEAK,            # 196 B/ray of the reference's AoS records / launch time / 8 TB/s
+                        contract_436B_loop_ratio=loop_contract / (HBM_PEAK * world),     # a RATIO (may exceed 1): the reference layout's loop bytes
+                                                                                         # per ray / wall time of the bounce loop / 8 TB/s
+                        avg_launch_us=avg_s * 1e6, launches=dom_n, units_per_launch=units, loop_ms_per_step=loop_ms / args.steps,
+                        kernels_ms_per_step={k: v[0] / args.steps for k, v in kt.items()},
+                        timing="kernel durations: hipEvents around every launch, one launch set at a time (lanes 1), NOT additive to ms_per_step: "
+                               "value, ms_per_step and loop_ms_per_step are wall time with %d launch set(s) in flight" % (args.lanes if args.lanes >= 1 else 3))
 
     out = dict(metric="Mrays/s", value=rays / dt / 1e6, unit="Mrays/s", n_gpus=n_gpus, steps=args.steps, warmup=args.warmup,
                ms_per_step=dt / args.steps * 1e3, higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32",
@@ -733,11 +788,12 @@ def main():
                            exchange_and_barrier_ms=(dt - t_render_max) * 1e3 if dist_on else 0.0,
                            parallelism=("1 GPU" if world == 1 else
                                         "%d ranks taking turns over the iterations of the full frame + 1 RCCL reduce/run" % world if by_iter else
-                                        "%d row-tile ranks (%d-row interleaved blocks) + 1 RCCL %s/run" % (world, multigpu.TILE_ROWS, args.exchange))),
-               roofline=roofline)
+                                        "%d row-tile ranks (%d-row interleaved blocks) + 1 RCCL %s/run" % (world, multigpu.TILE_ROWS, args.exchange))))
+    if roofline is not None:
+        out["roofline"] = roofline
     if multi:
         out.update(multi)
-    elif rank == 0 and not args.no_extra_legs:
+    elif args.full and rank == 0 and not args.no_extra_legs:
         # one GPU: the same 200-step run the N-rank lines carry as "long_run", so that their speed-up has its denominator on record
         r0 = T.stats()["rays_total"]
         torch.cuda.synchronize()
@@ -746,10 +802,10 @@ def main():
         T.synchronize()
         lt = time.perf_counter() - a
         out["long_run"] = dict(steps=200, ms_per_step=lt / 200 * 1e3, value=(T.stats()["rays_total"] - r0) / lt / 1e6, unit="Mrays/s")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, args.cpu_iters)
     T.close()
-    if rank == 0 and world == 1 and not args.no_extra_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_legs:
         # two more driver-visible figures, outside the timed region: the reference's one-iteration-per-call shape with the frame
         # read back every call (PCIe-inclusive: never `value`), and BASELINE configs[4] (4K, textured BVH mesh, DoF) on one GPU
         try:
@@ -781,7 +837,7 @@ def main():
         except Exception as e:
             out["c5_ms_per_iteration"] = None
             out["c5"] = dict(error=str(e)[:200])
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         out["stream_compaction"] = stream_compaction_device(torch, pt, device)
     if rank == 0:
         print(json.dumps(out))

@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B timing of prebuilt library variants (abx/lib*.so) on one GPU box: bash tools/ab_bench.sh A B C ...
 # (the variant is loaded through PTX_AB_LIBRARY: the in-tree product library is never overwritten)
+# (--full: the roofline leg's kernels_ms_per_step and the C5 leg, read below)
+AB_BENCH_ARGS="--full ${AB_BENCH_ARGS:-}"
 for rep in $(seq 1 ${AB_REPS:-2}); do
 for v in "$@"; do
   PTX_DEV=1 PTX_AB_LIBRARY=$PWD/abx/lib$v.so python bench.py --no-cpu-baseline ${AB_BENCH_ARGS:-} > gpurun_out/ab_$v.log 2>&1

@@ -6,7 +6,8 @@ TAG=$1
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 # (PMC_EXTRA_ARGS="--arith 1": the same passes over another arithmetic level's code object; PMC_GROUPS="a": only that group of counters)
-ARGS="--lanes 1 --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs $PMC_EXTRA_ARGS"
+# (--full: the roofline leg, whose kernel and rays per launch collect_sq.py reads from the line; --no-*: nothing else of it)
+ARGS="--full --lanes 1 --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs $PMC_EXTRA_ARGS"
 A="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU"
 B="SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_INSTS_SALU SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM"
 C="SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_INSTS_LDS SQ_WAIT_INST_LDS"

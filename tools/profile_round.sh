@@ -6,7 +6,8 @@ set -e
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_stats $R/gpurun_out/prof_fetch $R/gpurun_out/prof_write
-PMCARGS="--lanes 1 --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs"
+# (--full: the roofline leg, whose kernel and rays per launch collect_profiles.py reads from the fetch pass's line)
+PMCARGS="--full --lanes 1 --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs"
 # what the counter passes ran, for the collectors' _how (tools/profile_meta.py: how_of)
 for k in fetch write; do
   echo "rocprofv3 --pmc $(echo $k | tr a-z A-Z)_SIZE (a pass of its own, no tracing) -- python3 bench.py $PMCARGS: cornellObj.txt 1920x1080 depth 8 (C4), one launch set at a time; a launch covers 12 iterations (the default batch at 1080p)" > $R/gpurun_out/prof_${k}_how.txt
