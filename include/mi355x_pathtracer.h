@@ -259,6 +259,45 @@ int ptx_unpin_host_buffer(void *p);
 int ptx_set_kernel_timing(ptx_tracer *t, int on);
 int ptx_get_kernel_times(ptx_tracer *t, double ms_by_kind[4], int64_t launches_by_kind[4]);
 
+/* ---- denoiser: edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on the device, csrc/pt_denoise.hip -------------
+ * The GPU counterpart of the OIDN step of apps/src/main.cpp:167-219 (colour + albedo in, state.output out).  Guide images come from a
+ * G-buffer pass: per pixel the pixel-centre pinhole ray (no antialiasing jitter, no depth of field -- with DoF on, the guides are the
+ * sharp pinhole view) through the same intersection as the path, giving hit flag, world position o + t*d, shading normal (bump-mapped
+ * where the path's is), albedo (the apps-variant AOV's rule) and material / geom ids.  It is computed on the tracer's stream on the
+ * first ptx_denoise after ptx_create or a ptx_set_camera that changed the camera, into buffers allocated on that first use.
+ *
+ * The filter, exactly (tests/atrous_ref.py restates it):
+ *   c = rgb / spp per channel (mean radiance); demodulate: c / max(albedo, 1e-3) per channel on hit pixels.
+ *   pass i = 0 .. passes-1, step s = 2^i, for every hit pixel p:
+ *     out_p = sum_q w_q c_q / sum_q w_q over the 5x5 taps q = clamp_to_frame(p + s*(dx, dy)), dx, dy in -2..2, miss taps excluded,
+ *     w_q = b[dx] b[dy] exp(-|c_p - c_q|^2 / (phi_color * 2^-i)) exp(-(|n_p - n_q|^2 / s^2) / phi_normal) exp(-|x_p - x_q|^2 / phi_position),
+ *     b = (1/16, 1/4, 3/8, 1/4, 1/16).  The centre tap weighs 9/64, so the sum is never 0.  Miss pixels keep c in every pass.
+ *   result = the last pass, multiplied back by max(albedo, 1e-3) on hit pixels when demodulating: W*H*3 fp32 mean radiance (what
+ *   RenderState.output holds in apps/src, so ptx_write_denoised_pbo* / sendToGPU take it without dividing by the iteration count).
+ * ptx_multi_* has no denoiser; a tracer that renders a row tile (tile_world > 1) is refused: its frame holds only its own rows. */
+typedef struct ptx_denoise_params {
+    int32_t passes;          /* 1 .. 10; default 5 (steps 1, 2, 4, 8, 16: a 125-pixel footprint)                            */
+    int32_t demodulate;      /* != 0: filter colour / albedo (texture detail survives); default 1                              */
+    float phi_color;         /* > 0, squared mean-radiance units, halved every pass; see DESIGN.md 10 for the chosen defaults  */
+    float phi_normal;        /* > 0, squared unit-normal difference per squared step                                          */
+    float phi_position;      /* > 0, squared scene units (the Cornell scenes are about 10 units across)                       */
+} ptx_denoise_params;
+void ptx_default_denoise_params(ptx_denoise_params *p);
+size_t ptx_sizeof_denoise_params(void);
+/* Enqueues G-buffer (when stale) + filter of the accumulation buffer / spp on the tracer's stream and returns; p NULL = defaults.
+ * The accumulation buffer, statistics and what later iterations compute are untouched. */
+int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *p, int spp);
+int ptx_read_denoised(ptx_tracer *t, float *host_rgb);                  /* W*H*3 mean radiance of the last ptx_denoise (waits for it) */
+float *ptx_device_denoised(ptx_tracer *t);                               /* device pointer of that frame; NULL before the first denoise */
+int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4);   /* sendToGPU of that frame without a host round trip (enqueues) */
+/* The G-buffer as the last ptx_denoise used it (computed now if stale): W*H*3 floats each of position, normal, albedo, W*H*2 int32
+ * (material id, geom id), W*H floats of t and W*H bytes of hit flag; any pointer may be NULL.  Misses read as zeros. */
+int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1);
+/* The filter alone over caller-owned host buffers (W*H*3 floats; hit W*H bytes, != 0 = hit): rgb is mean radiance (spp = 1), out_rgb
+ * receives the result.  alb3 may be NULL when p->demodulate is 0.  Runs on `device`, synchronously; PTX_ERR_NODEVICE without one. */
+int ptx_denoise_buffers(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, const float *pos3,
+                        const uint8_t *hit, const ptx_denoise_params *p, float *out_rgb);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);

@@ -12,13 +12,16 @@ from .api import (  # noqa: F401
     LIB_PATH,
     PathTracerError,
     Options,
+    DenoiseParams,
     Scene,
     Tracer,
     MultiTracer,
     StreamCompaction,
     build_library,
+    default_denoise_params,
+    denoise_buffers,
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "Scene", "Tracer", "MultiTracer", "StreamCompaction", "build_library",
-           "load_library"]
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "Scene", "Tracer", "MultiTracer", "StreamCompaction", "build_library",
+           "default_denoise_params", "denoise_buffers", "load_library"]

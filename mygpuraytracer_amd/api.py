@@ -80,6 +80,44 @@ class Stats(C.Structure):
                 ("stored_paths", C.c_int64), ("stored_with_direction", C.c_int64), ("stored_with_normal_code", C.c_int64)]
 
 
+class DenoiseParams(C.Structure):
+    """ptx_denoise_params: the a-trous denoiser's knobs (include/mi355x_pathtracer.h; defaults from ptx_default_denoise_params)."""
+    _fields_ = [("passes", C.c_int32), ("demodulate", C.c_int32), ("phi_color", C.c_float), ("phi_normal", C.c_float),
+                ("phi_position", C.c_float)]
+
+
+def default_denoise_params(**kw):
+    """ptx_default_denoise_params with keyword overrides (passes, demodulate, phi_color, phi_normal, phi_position)."""
+    p = DenoiseParams()
+    load_library().ptx_default_denoise_params(C.byref(p))
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v) if k in ("passes", "demodulate") else float(v))
+    return p
+
+
+def denoise_buffers(rgb, albedo, normal, position, hit, device=0, **params):
+    """The a-trous filter alone (ptx_denoise_buffers) on host arrays of one (H, W) frame: rgb = mean radiance, albedo / normal / position
+    (..., 3), hit (...) bool.  Returns the filtered mean radiance as (H, W, 3) float32 when rgb is (H, W, 3), else rgb's shape.  Needs a
+    HIP device: there is no CPU path."""
+    L = load_library()
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise PathTracerError("denoise_buffers: rgb must be (H, W, 3)")
+    h, w = rgb.shape[:2]
+    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
+    alb, nrm, pos = as3(albedo), as3(normal), as3(position)
+    hit = np.ascontiguousarray(np.asarray(hit).reshape(h * w) != 0, np.uint8)
+    out = np.zeros((h, w, 3), np.float32)
+    p = default_denoise_params(**params)
+    _check(L.ptx_denoise_buffers(int(device), w, h, _ptr(rgb), None if alb is None else _ptr(alb), _ptr(nrm), _ptr(pos), _ptr(hit),
+                                 C.byref(p), _ptr(out)), "ptx_denoise_buffers")
+    return out
+
+
 def debug_tile_geoms(camera, boxes6, depth_of_field=False, tile=None):
     """CPU only: the per-tile geom masks of the camera-ray bounce (ptx_debug_tile_geoms) for a ctypes Camera, an (n, 6) array of world
     boxes (lo xyz, hi xyz) and an optional row-tile split (rows, rank, world).  Returns a uint32 array, one word per tile of 256 owned
@@ -163,6 +201,10 @@ def load_library():
     if L.ptx_abi_version() != ABI_VERSION or L.ptx_sizeof_options() != C.sizeof(Options) or L.ptx_sizeof_stats() != C.sizeof(Stats):
         raise PathTracerError("%s has ABI %d (options %d B, stats %d B), this module expects %d (%d B, %d B): rebuild the library" % (
             LIB_PATH, L.ptx_abi_version(), L.ptx_sizeof_options(), L.ptx_sizeof_stats(), ABI_VERSION, C.sizeof(Options), C.sizeof(Stats)))
+    L.ptx_sizeof_denoise_params.restype = C.c_size_t
+    if L.ptx_sizeof_denoise_params() != C.sizeof(DenoiseParams):
+        raise PathTracerError("%s has a ptx_denoise_params of %d B, this module expects %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_denoise_params(), C.sizeof(DenoiseParams)))
     L.ptx_last_error.restype = C.c_char_p
     L.ptx_device_count.restype = i
     L.ptx_default_options.argtypes = [C.POINTER(Options)]
@@ -207,6 +249,14 @@ def load_library():
     L.ptx_write_pbo.restype, L.ptx_write_pbo.argtypes = i, [vp, i, vp]
     L.ptx_write_pbo_device.restype, L.ptx_write_pbo_device.argtypes = i, [vp, i, vp]
     L.ptx_last_loop_ms.restype, L.ptx_last_loop_ms.argtypes = C.c_double, [vp]
+    L.ptx_default_denoise_params.argtypes = [C.POINTER(DenoiseParams)]
+    L.ptx_denoise.restype, L.ptx_denoise.argtypes = i, [vp, C.POINTER(DenoiseParams), i]
+    L.ptx_read_denoised.restype, L.ptx_read_denoised.argtypes = i, [vp, vp]
+    L.ptx_device_denoised.restype, L.ptx_device_denoised.argtypes = vp, [vp]
+    L.ptx_write_denoised_pbo_from_device.restype, L.ptx_write_denoised_pbo_from_device.argtypes = i, [vp, vp]
+    L.ptx_read_gbuffer.restype, L.ptx_read_gbuffer.argtypes = i, [vp, vp, vp, vp, vp, vp, vp]
+    L.ptx_denoise_buffers.restype = i
+    L.ptx_denoise_buffers.argtypes = [i, i, i, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -629,6 +679,35 @@ class Tracer:
         """sendToGPU (apps/src/pathtrace.cu:673-685): host frame -> 8-bit preview in a device buffer (address as int)"""
         rgb = np.ascontiguousarray(rgb, np.float32).reshape(self.width * self.height, 3)
         _check(self.lib.ptx_write_denoised_pbo_device(self.h, _ptr(rgb), device_pbo), "ptx_write_denoised_pbo_device")
+
+    # --- denoiser (include/mi355x_pathtracer.h: ptx_denoise ...) ------------------------------------------
+    def denoise(self, spp, read=True, passes=None, demodulate=None, phi_color=None, phi_normal=None, phi_position=None):
+        """a-trous denoise of the accumulation buffer / spp on the device; returns the (H, W, 3) float32 mean radiance (read=False:
+        only enqueues it -- device_denoised_ptr / denoised_pbo_from_device then use it where it is)"""
+        p = default_denoise_params(passes=passes, demodulate=demodulate, phi_color=phi_color, phi_normal=phi_normal, phi_position=phi_position)
+        _check(self.lib.ptx_denoise(self.h, C.byref(p), int(spp)), "ptx_denoise")
+        return self.read_denoised() if read else None
+
+    def read_denoised(self):
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        _check(self.lib.ptx_read_denoised(self.h, _ptr(out)), "ptx_read_denoised")
+        return out
+
+    def device_denoised_ptr(self):
+        return self.lib.ptx_device_denoised(self.h)
+
+    def denoised_pbo_from_device(self, device_pbo):
+        """sendToGPU of the last denoise (still on the device) into a device pbo (address as int); enqueued on the tracer's stream"""
+        _check(self.lib.ptx_write_denoised_pbo_from_device(self.h, device_pbo), "ptx_write_denoised_pbo_from_device")
+
+    def gbuffer(self):
+        """The denoiser's G-buffer of the current camera: dict of (H, W, ...) arrays position, normal, albedo (float32 x 3), material,
+        geom (int32), t (float32), hit (bool)"""
+        h, w = self.height, self.width
+        pos, nrm, alb = (np.zeros((h, w, 3), np.float32) for _ in range(3))
+        ids, t, hit = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.float32), np.zeros((h, w), np.uint8)
+        _check(self.lib.ptx_read_gbuffer(self.h, _ptr(pos), _ptr(nrm), _ptr(alb), _ptr(ids), _ptr(t), _ptr(hit)), "ptx_read_gbuffer")
+        return dict(position=pos, normal=nrm, albedo=alb, material=ids[..., 0].copy(), geom=ids[..., 1].copy(), t=t, hit=hit != 0)
 
     def pbo(self, iteration):
         out = np.zeros((self.width * self.height, 4), np.uint8)

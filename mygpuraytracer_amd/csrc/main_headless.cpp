@@ -9,6 +9,7 @@
 //                                  [--orbit "left:DX,DY;right:DY;middle:DX,DY;space"]   (the mouse of main.cpp:166-212, scripted)
 //                                  [--per-call [--no-render-ahead]]   (one pathtrace(pbo, frame, iter) per iteration with the frame read
 //                                                                      back after each, exactly the reference's runCuda loop)
+//                                  [--denoise [--denoise-passes N]]   (also <out>.denoised.png / .pfm: the a-trous denoiser, ptx_denoise)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -35,11 +36,12 @@ static std::string currentTimeString() {          // src/preview.cpp:13-19
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]]\n", argv[0]);
         return 1;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
-    bool pfm = false, hdr = false, per_call = false;
+    bool pfm = false, hdr = false, per_call = false, denoise = false;
+    ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script;
     int ckpt_every = 0;
     ptx_options &opt = pathtraceOptions();
@@ -64,6 +66,8 @@ int main(int argc, char **argv) {
         else if (a == "--no-cache") opt.cache_first_bounce = 0;
         else if (a == "--per-call") per_call = true;
         else if (a == "--no-render-ahead") pathtraceRenderAhead() = false;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-passes") { need(1); dparams.passes = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
     }
     Scene *scene = nullptr;
@@ -130,6 +134,14 @@ int main(int argc, char **argv) {
     if (!ptimg::write_png_rgb8(ss.str() + ".png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.png\n", ss.str().c_str()); return 1; }
     printf("Saved %s.png.\n", ss.str().c_str());
     if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", ss.str().c_str()); }
+    if (denoise && n > 0) {                     // the denoised frame next to it: mean radiance already, so divided by 1
+        std::vector<float> den((size_t)width * height * 3);
+        if (ptx_denoise(t, &dparams, n) != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
+        ptimg::to_rgb8_mirrored(width, height, den.data(), 1.0f, rgb8);
+        if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
+        printf("Saved %s.denoised.png.\n", ss.str().c_str());
+        if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den.data(), 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
+    }
     if (hdr) {                                                                          // img.saveHDR, main.cpp:101
         std::vector<float> mean;
         ptimg::to_mean_mirrored(width, height, &scene->state.image[0].x, (float)n, mean);

@@ -19,6 +19,10 @@ bool g_albedo_read = false;          // several devices, apps variant: state.alb
 void *g_pinned[3] = {nullptr, nullptr, nullptr};      // state.image / state.albedo page-locked for the per-iteration read-back
 ptx_options g_options;
 bool g_options_init = false;
+int g_last_iter = 0;                 // iteration of the last pathtrace() call: the spp GPUdenoise divides by
+bool g_output_on_device = false;     // GPUdenoise(true) ran since the last pathtrace(): sendToGPU shows the device frame
+ptx_denoise_params g_denoise;
+bool g_denoise_init = false;
 
 void check(int rc, const char *what) {
     if (rc == PTX_OK) return;
@@ -163,9 +167,16 @@ float PerformanceTimer::getGpuElapsedTimeForPreviousOperation() {
     return (float)ms;
 }
 
+ptx_denoise_params &denoiseParams() {
+    if (!g_denoise_init) { ptx_default_denoise_params(&g_denoise); g_denoise_init = true; }
+    return g_denoise;
+}
+
 void pathtraceInit(Scene *scene) {
     hst_scene = scene;
     g_albedo_read = false;
+    g_last_iter = 0;
+    g_output_on_device = false;
     const std::vector<int> &devs = pathtraceDevices();
     if (devs.size() > 1) {
         // the C ABI's multi-device layer takes the loaded scene: hand it the caller's camera and depth first
@@ -202,6 +213,8 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
     (void)frame;                 // unused by the reference as well
     if (!g_tracer || !hst_scene) { fprintf(stderr, "pathtrace called before pathtraceInit\n"); exit(EXIT_FAILURE); }
     mi355x_timer_note_pathtrace(timer());
+    g_last_iter = iter;
+    g_output_on_device = false;
     // the reference re-reads camera and traceDepth on every call (src/pathtrace.cu:434-436)
     const bool apps = pathtraceOptions().apps_variant != 0;
     if (g_multi) {               // several devices: every device its tile, then the row blocks into device 0's frame
@@ -231,7 +244,21 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
 void mi355x::sendToGPU_raw(void *pbo, int iter) {
     (void)iter;                  // passed to the kernel but unused there as well (apps/src/pathtrace.cu:96-116)
     if (!g_tracer || !hst_scene) { fprintf(stderr, "sendToGPU called before pathtraceInit\n"); exit(EXIT_FAILURE); }
+    if (g_output_on_device) {
+        check(ptx_write_denoised_pbo_from_device(g_tracer, pbo), "sendToGPU");
+        check(ptx_synchronize(g_tracer), "sendToGPU");
+        return;
+    }
     check(ptx_write_denoised_pbo_device(g_tracer, &hst_scene->state.output[0].x, pbo), "sendToGPU");
+}
+
+void GPUdenoise(bool keep_on_device) {
+    if (!g_tracer || !hst_scene) { fprintf(stderr, "GPUdenoise called before pathtraceInit\n"); exit(EXIT_FAILURE); }
+    if (g_multi) { fprintf(stderr, "GPUdenoise: the denoiser runs on one device; pathtraceDevices() names several\n"); exit(EXIT_FAILURE); }
+    if (g_last_iter < 1) { fprintf(stderr, "GPUdenoise called before the first pathtrace\n"); exit(EXIT_FAILURE); }
+    check(ptx_denoise(g_tracer, &denoiseParams(), g_last_iter), "GPUdenoise");
+    g_output_on_device = keep_on_device;
+    if (!keep_on_device) check(ptx_read_denoised(g_tracer, &hst_scene->state.output[0].x), "GPUdenoise readback");
 }
 
 // the same two under the reference's names, for translation units without HIP's vector types (see pathtrace_api.h)

@@ -250,9 +250,19 @@ void pathtraceInit(Scene *scene);                       // src/pathtrace.h:7
 void pathtraceFree();                                   // src/pathtrace.h:8
 ptx_tracer *pathtraceHandle();                          // the C-ABI handle behind the module-static state (device 0's with several devices)
 
+// CPUdenoise of apps/src/main.cpp:167-219 (OIDN on the host, colour + albedo) on the device instead: the edge-avoiding a-trous filter of
+// ptx_denoise over state.image / iteration of the last pathtrace() call, guided by the G-buffer of the current camera.  The reference's
+// `CPUdenoise(); sendToGPU(pbo, iteration);` ports as `GPUdenoise(); sendToGPU(pbo, iteration);`.
+//   keep_on_device = false: the W*H mean-radiance frame lands in scene->state.output, as CPUdenoise leaves it.
+//   keep_on_device = true : it stays on the device (no frame-sized copy to the host and back) and the next sendToGPU takes it from there;
+//                           state.output is not written.  A pathtrace() call in between returns sendToGPU to state.output.
+// One device only: with several pathtraceDevices() it prints an error and exits, as every other failure of the veneer does.
+void GPUdenoise(bool keep_on_device = false);
+ptx_denoise_params &denoiseParams();                    // what GPUdenoise filters with (ptx_default_denoise_params until changed)
+
 namespace mi355x {
 void pathtrace_raw(void *pbo, int frame, int iteration);   // what both spellings below run; pbo = device uchar4*, may be NULL (no preview)
-void sendToGPU_raw(void *pbo, int iter);                   // state.output -> 8-bit preview in the device pbo
+void sendToGPU_raw(void *pbo, int iter);                   // state.output (or GPUdenoise(true)'s device frame) -> 8-bit preview in the device pbo
 }
 #if defined(HIP_INCLUDE_HIP_HIP_VECTOR_TYPES_H) || defined(HIP_INCLUDE_HIP_AMD_DETAIL_HIP_VECTOR_TYPES_H)
 // uchar4 is known here: the reference's own signatures and nothing else under these names

@@ -45,6 +45,7 @@
 #include "../../include/mi355x_pathtracer.h"
 #include "pt_device.h"
 #include "pt_bvh.h"
+#include "pt_denoise.h"
 
 using namespace ptd;
 
@@ -2060,6 +2061,35 @@ extern "C" const void *PT_ARITH_EXPORT(PT_ARITH)(void) { return &g_kernels_here;
 extern "C" const void *ptx_arith_kernels_1(void) __attribute__((weak));
 extern "C" const void *ptx_arith_kernels_2(void) __attribute__((weak));
 
+namespace {
+// G-buffer of the denoiser (ptx_denoise; layout in pt_denoise.h), compiled here only, at the exact level: per pixel the pixel-centre
+// pinhole ray (generateRay without jitter or lens, whatever the tracer's options), the path's own intersection (intersectScene, as
+// k_kat_intersect: meshes through their BVH), the shade point o + t*d in the order shadeFakeMaterial forms it (src/pathtrace.cu:392),
+// the Hit normal (bump-mapped as the intersection returns it) and write_albedo's albedo.  Misses: all zeros.
+__global__ __launch_bounds__(256) void k_gbuffer(const DScene sc, const DCamera cam, int traceDepth, float4 *nh, float4 *xt, float4 *alb, int2 *ids) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cam.resx * cam.resy) return;
+    const int y = i / cam.resx, x = i - y * cam.resx;
+    PathState ps;
+    generateRay(cam, 1, traceDepth, /*aa*/ false, /*dof*/ false, x, y, ps);
+    Ray r; r.o = ps.o; r.d = ps.d;
+    Hit h;
+    intersectScene(sc, r, h);
+    if (h.t > 0.f) {
+        float a[3];
+        write_albedo(sc, h, a);
+        const vec3 p = add(r.o, scale(r.d, h.t));
+        nh[i] = make_float4(h.n.x, h.n.y, h.n.z, 1.f);
+        xt[i] = make_float4(p.x, p.y, p.z, h.t);
+        alb[i] = make_float4(a[0], a[1], a[2], 0.f);
+        ids[i] = make_int2(h.mat, h.geom);
+    } else {
+        nh[i] = xt[i] = alb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        ids[i] = make_int2(0, 0);
+    }
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------------------
 struct ptx_tracer {
     int device = 0;
@@ -2135,6 +2165,11 @@ struct ptx_tracer {
     uchar4 *d_pbo = nullptr;                             // ptx_write_pbo's device staging (allocated on first use)
     float *d_denoised = nullptr;                         // ptx_write_denoised_pbo_device's copy of the host frame (first use)
     float *d_albedo = nullptr;                           // apps variant only: W*H*3
+    // denoiser (ptx_denoise), all allocated on its first call: G-buffer [nh | xt | alb] x W*H float4 then W*H int2 ids (pt_denoise.h),
+    // the filter's two float4 colour buffers, its W*H*3 result
+    float4 *d_gbuf = nullptr, *d_dn_tmp = nullptr;
+    float *d_dn_out = nullptr;
+    bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
     unsigned long long *d_stamps = nullptr;              // diagnostic build only
     float *d_part = nullptr;                             // [kmax][W*H*3] per-iteration radiance (batched mode)
     int32_t *d_cache_totals = nullptr;                   // [2][nbins] of bounce 0 (cache)
@@ -2406,6 +2441,7 @@ int free_tracer(ptx_tracer *t) {
     hipFree(t->d_cache_chunk); hipFree(t->d_cache_super);
     hipFree(t->d_counts); hipFree(t->d_chunk); hipFree(t->d_totals); hipFree(t->d_cache_totals);
     hipFree(t->d_emit_count); hipFree(t->d_emit_pix); hipFree(t->d_emit_rgb); hipFree(t->d_stats); hipFree(t->d_cap); hipFree(t->d_cap_f); hipFree(t->d_part); hipFree(t->d_albedo); hipFree(t->d_stamps); hipFree(t->d_pbo); hipFree(t->d_denoised);
+    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out);
     for (hipEvent_t e : t->kev) hipEventDestroy(e);
     if (t->ev_start) hipEventDestroy(t->ev_start);
     if (t->ev_stop) hipEventDestroy(t->ev_stop);
@@ -3252,6 +3288,7 @@ int ptx_set_camera(ptx_tracer *t, const ptx_camera *camera, int trace_depth) {
     camera_to_device(*camera, t->cam);
     t->traceDepth = trace_depth;
     t->cache_valid = false;
+    t->gbuf_valid = false;                               // the denoiser's G-buffer is of the old view
     return update_tile_geoms(t);
 }
 
@@ -3475,6 +3512,88 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
         if (e != hipSuccess) rc = set_error(PTX_ERR_HIP, hipGetErrorString(e));
     }
     return rc;
+}
+
+// ---- denoiser (pt_denoise.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------------
+// The G-buffer of the current camera on the tracer's stream, buffers allocated on first use
+static int ensure_gbuffer(ptx_tracer *t) {
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (!t->d_gbuf) HIPCHECK(hipMalloc(&t->d_gbuf, sizeof(float4) * 3 * n + sizeof(int2) * n));
+    if (t->gbuf_valid) return PTX_OK;
+    const DScene sc = t->scene();
+    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, sc, t->cam, t->traceDepth,
+                       t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n));
+    HIPCHECK(hipGetLastError());
+    t->gbuf_valid = true;
+    return PTX_OK;
+}
+
+int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *params, int spp) {
+    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    ptx_denoise_params p;
+    if (params) p = *params;
+    else ptx_default_denoise_params(&p);
+    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise: spp must be >= 1 (the iterations summed in the accumulation buffer)");
+    if (const char *why = pt_denoise_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    HIPCHECK(hipSetDevice(t->device));
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
+    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
+    const int rc = ensure_gbuffer(t);
+    if (rc != PTX_OK) return rc;
+    HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, t->d_image, (float)spp, t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n,
+                               t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, p));
+    t->dn_done = true;
+    return PTX_OK;
+}
+
+int ptx_read_denoised(ptx_tracer *t, float *host_rgb) {
+    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_read_denoised: no ptx_denoise on this tracer yet");
+    HIPCHECK(hipSetDevice(t->device));
+    HIPCHECK(hipMemcpyAsync(host_rgb, t->d_dn_out, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return PTX_OK;
+}
+
+float *ptx_device_denoised(ptx_tracer *t) { return t && t->dn_done ? t->d_dn_out : nullptr; }
+
+int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4) {
+    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_write_denoised_pbo_from_device: no ptx_denoise on this tracer yet");
+    if (!device_uchar4) return PTX_OK;                    // NULL pbo => skip, like ptx_write_pbo_device
+    HIPCHECK(hipSetDevice(t->device));
+    const int n = t->cam.resx * t->cam.resy;
+    hipLaunchKernelGGL(k_pbo, dim3((n + 255) / 256), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, n, 1, t->d_dn_out);   // iter = 1: no /iter
+    HIPCHECK(hipGetLastError());
+    return PTX_OK;
+}
+
+int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1) {
+    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_read_gbuffer: this tracer renders a row tile (tile_world > 1); the denoiser needs the whole frame");
+    HIPCHECK(hipSetDevice(t->device));
+    const int rc = ensure_gbuffer(t);
+    if (rc != PTX_OK) return rc;
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    std::vector<float4> g(3 * n);
+    std::vector<int2> ids(n);
+    HIPCHECK(hipMemcpyAsync(g.data(), t->d_gbuf, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipMemcpyAsync(ids.data(), t->d_gbuf + 3 * n, sizeof(int2) * n, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    for (size_t i = 0; i < n; i++) {
+        const float4 &nh = g[i], &xt = g[n + i], &al = g[2 * n + i];
+        if (pos3) { pos3[3 * i] = xt.x; pos3[3 * i + 1] = xt.y; pos3[3 * i + 2] = xt.z; }
+        if (nrm3) { nrm3[3 * i] = nh.x; nrm3[3 * i + 1] = nh.y; nrm3[3 * i + 2] = nh.z; }
+        if (alb3) { alb3[3 * i] = al.x; alb3[3 * i + 1] = al.y; alb3[3 * i + 2] = al.z; }
+        if (ids2) { ids2[2 * i] = ids[i].x; ids2[2 * i + 1] = ids[i].y; }
+        if (t1) t1[i] = xt.w;
+        if (hit1) hit1[i] = nh.w != 0.f ? 1 : 0;
+    }
+    return PTX_OK;
 }
 
 double ptx_last_loop_ms(ptx_tracer *t) {
