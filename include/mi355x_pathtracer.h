@@ -340,6 +340,10 @@ int ptx_debug_record_masks(int nmaterials, const ptx_material *materials, int ng
 int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8);
 /* Debug: workgroups of the specialised later-bounce kernel that fit a CU with lds_bytes of dynamic LDS each (0: what this tracer launches). */
 int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes);
+/* Debug: after waiting for the tracer's streams, the nonzero words left in the per-iteration "lit" bit-planes (out3[0]) and in the
+ * per-bounce and group totals (out3[1]) of every lane's segments -- both 0 between launch sets, which clear what they read.  Segments
+ * of a traced-ahead batch not yet gathered are not counted, nor are the lanes marked for a full clear before their next set (out3[2]). */
+int ptx_debug_aux_nonzero(ptx_tracer *t, int64_t out3[3]);
 /* Debug capture: the sorted stream of paths that will be shaded at bounce+1, as it stands after the given bounce
  * of the next iteration(s). */
 int ptx_debug_set_capture(ptx_tracer *t, int bounce);   /* -1 = off */

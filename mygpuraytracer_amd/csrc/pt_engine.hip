@@ -334,17 +334,20 @@ __device__ __forceinline__ void st_rgb(float *base, uint32_t byteoff, float r, f
     *reinterpret_cast<RgbUnaligned *>(reinterpret_cast<char *>(base) + byteoff) = v;
 #endif
 }
-// Batched mode, round 5: only paths that end WITH radiance (a light hit, an emissive texel) write their 12 bytes, and set the pixel's byte
-// in the segment's "lit" flags, which lie behind the segment's radiance ([cap] floats x 3, then [cap] bytes; cleared per batch, 1 B per
-// pixel).  The many that end black -- misses, the last bounce: most path ends of a Cornell frame -- write nothing, and k_gather adds only
+// Batched mode, round 5: only paths that end WITH radiance (a light hit, an emissive texel) write their 12 bytes, and set the slot's bit
+// in the segment's "lit" plane, which lies behind the segment's radiance ([cap] floats x 3, then [cap / 32] words, bit s & 31 of word s / 32
+// for slot s).  The many that end black -- misses, the last bounce: most path ends of a Cornell frame -- write nothing, and k_gather adds only
 // flagged slots: adding the +0 they used to store changes no sum (the image holds no -0: it starts at +0 and only grows), so the frames
 // are the same bits.  C4 moved 12 B per path end and 12 B per pixel and iteration in k_gather for those zeros: 11 % of its HBM bytes.
-__device__ __forceinline__ uint8_t *lit_flags(float *part, uint32_t cap) { return reinterpret_cast<uint8_t *>(part + 3 * (size_t)cap); }
+// The planes are zero whenever no launch set is in flight: k_gather clears the words it reads (a full clear before a lane's next set
+// where that does not hold: ptx_tracer::aux_dirty).  32 slots share a word, so a bit is set with an atomic.
+__device__ __forceinline__ uint32_t *lit_flags(float *part, uint32_t cap) { return reinterpret_cast<uint32_t *>(part + 3 * (size_t)cap); }
+__device__ __forceinline__ void set_lit(float *part, uint32_t cap, uint32_t slot) { atomicOr(lit_flags(part, cap) + (slot >> 5), 1u << (slot & 31u)); }
 __device__ __forceinline__ void deposit(const TileMap &tm, float *image, float *part, bool batched, int pix, vec3 c, int apps, uint32_t cap) {
     if (apps) c = scale(c, 3.14159265358f);            // apps/src/pathtrace.cu:44,508: image += color * PI
     if (batched) {
         st_rgb(part, (uint32_t)pix * 12u, c.x, c.y, c.z);
-        st_u(lit_flags(part, cap), (uint32_t)pix, (uint8_t)1);
+        set_lit(part, cap, (uint32_t)pix);
     } else {
         float *px = image + (size_t)slot_to_pixel(tm, pix) * 3;
         px[0] += c.x; px[1] += c.y; px[2] += c.z;
@@ -1690,7 +1693,7 @@ __global__ void k_capture(PathSoA stage, const int32_t *chunk, int chunk_cap, in
 
 // replay of the cached bounce-0 light hits (first-bounce cache, iterations > 1)
 // add != 0: image[pix] += rgb (one iteration at a time); add == 0: store into the per-iteration radiance buffer of each of
-// the nseg segments (batched mode; the buffers were cleared, so bounce-0 misses read as 0)
+// the nseg segments and set its lit bit (batched mode; a bounce-0 miss sets none, so k_gather adds nothing for it)
 __global__ void k_replay_emission(TileMap tm, const int32_t *count, const int32_t *pix, const float *rgb, float *dst, size_t seg_stride,
                                   int nseg, int add, uint32_t cap) {
     int n = *count;
@@ -1703,7 +1706,7 @@ __global__ void k_replay_emission(TileMap tm, const int32_t *count, const int32_
             for (int sg = 0; sg < nseg; sg++) {
                 float *px = dst + seg_stride * sg + (size_t)pix[k] * 3;
                 px[0] = r; px[1] = g; px[2] = b;
-                lit_flags(dst + seg_stride * sg, cap)[pix[k]] = 1;
+                set_lit(dst + seg_stride * sg, cap, (uint32_t)pix[k]);
             }
         }
     }
@@ -1715,19 +1718,44 @@ __global__ void k_seed_totals(int32_t *dst, size_t seg_totals, int nseg, const i
 }
 
 // batched mode: image[pix] += part[0][pix]; += part[1][pix]; ... in iteration order, over the pixels this device owns
-// (only the slots whose "lit" flag of that iteration is set hold anything: see deposit)
-__global__ void k_gather(TileMap tm, int resx, int nseg, size_t seg_part, const float *part, float *image, uint32_t cap) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < tm.owned; i += gridDim.x * blockDim.x) {
+// (only the slots whose lit bit of that iteration is set hold anything: see deposit), and the lit planes left zero behind it.
+// A wave takes 64 consecutive slots (i0 .. i0 + 63; i0 a multiple of 64, so i0 + 64 <= cap), i.e. two whole words of every plane:
+// lane 2s + h (and 64 + 2s + h, nseg > 32) loads word h of plane s -- all of them in one round trip -- and writes the zero back
+// if the word held a bit (it needs the value read: the store cannot pass the load).  It is the word's only reader, so no ordering
+// between waves is needed.  Each slot's lane then takes its bit of every plane from the lane that holds the word.
+__global__ void k_gather(TileMap tm, int resx, int nseg, size_t seg_part, float *part, float *image, uint32_t cap) {
+    const int lane = threadIdx.x & 63;
+    for (int i0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63; i0 < tm.owned; i0 += gridDim.x * blockDim.x) {      // (wave-uniform)
+        uint32_t *w_lo = lit_flags(part + seg_part * (lane >> 1), cap) + (i0 >> 5) + (lane & 1);      // planes 0 .. 31
+        uint32_t *w_hi = lit_flags(part + seg_part * (32 + (lane >> 1)), cap) + (i0 >> 5) + (lane & 1);      // planes 32 .. 63
+        const uint32_t lo = lane < 2 * nseg ? *w_lo : 0u, hi = lane + 64 < 2 * nseg ? *w_hi : 0u;
+        if (lo) *w_lo = 0u;
+        if (hi) *w_hi = 0u;
+        const int i = i0 + lane;
+        unsigned long long lit = 0;                      // bit s: iteration s of the batch ended this pixel's path on a light (nseg <= 64)
+        for (int s = 0; s < nseg; s++) {
+            const uint32_t src = s < 32 ? lo : hi;
+            const uint32_t w0 = __builtin_amdgcn_readlane(src, (2 * s) & 63), w1 = __builtin_amdgcn_readlane(src, (2 * s + 1) & 63);
+            lit |= (unsigned long long)(((lane < 32 ? w0 : w1) >> (lane & 31)) & 1u) << s;
+        }
+        if (i >= tm.owned || !lit) continue;             // (a pixel no iteration of the batch lit: its sum does not move)
         int x, y;
         owned_pixel(tm, i, x, y);
         const size_t o = ((size_t)x + (size_t)y * resx) * 3;
-        unsigned long long lit = 0;                      // bit s: iteration s of the batch ended this pixel's path on a light (nseg <= 64)
-        for (int s = 0; s < nseg; s++) lit |= (unsigned long long)(reinterpret_cast<const uint8_t *>(part + seg_part * s + 3 * (size_t)cap)[i] != 0) << s;
-        if (!lit) continue;                              // (a pixel no iteration of the batch lit: its sum does not move)
         float r = image[o], g = image[o + 1], b = image[o + 2];
-        for (; lit; lit &= lit - 1) {                    // in iteration order: the same fp32 sums as one iteration at a time
-            const float *ps = part + seg_part * (size_t)(__ffsll((long long)lit) - 1) + (size_t)i * 3;
-            r += ps[0]; g += ps[1]; b += ps[2];
+        const float *pi = part + (size_t)i * 3;
+        auto next_lit = [&]() { if (!lit) return -1; const int s = __ffsll((long long)lit) - 1; lit &= lit - 1; return s; };
+        auto rgb_of = [&](int s) { const float *ps = pi + seg_part * (size_t)s; return V3(ps[0], ps[1], ps[2]); };
+        while (lit) {                                    // in iteration order: the same fp32 sums as one iteration at a time
+            // (four segments' loads in flight at once, with the image's: a pixel lit by several iterations -- one that sees the light --
+            // is not a chain of dependent round trips)
+            const int s0 = next_lit(), s1 = next_lit(), s2 = next_lit(), s3 = next_lit();
+            const vec3 z = V3(0.f, 0.f, 0.f);          // (never added: only a segment that is there is)
+            const vec3 c0 = rgb_of(s0), c1 = s1 >= 0 ? rgb_of(s1) : z, c2 = s2 >= 0 ? rgb_of(s2) : z, c3 = s3 >= 0 ? rgb_of(s3) : z;
+            r += c0.x; g += c0.y; b += c0.z;
+            if (s1 >= 0) { r += c1.x; g += c1.y; b += c1.z; }
+            if (s2 >= 0) { r += c2.x; g += c2.y; b += c2.z; }
+            if (s3 >= 0) { r += c3.x; g += c3.y; b += c3.z; }
         }
         image[o] = r; image[o + 1] = g; image[o + 2] = b;
     }
@@ -1737,10 +1765,20 @@ __global__ void k_gather(TileMap tm, int resx, int nseg, size_t seg_part, const 
 // (bounce 0 is not counted on iterations that took it from the first-bounce cache: nothing was traced -- so the cached bounce-0 records
 // that every such iteration RE-READS are not part of stored_* either: the mix describes what was written, once.)
 // dir_bins / ntab_bins = the masks the batch's launches wrote with (enqueue_batch: batch_dir_bins), not the tracer's.
-__global__ void k_stats(const int32_t *totals, int nbins, int nbounces, int stride, int skip_first, int nseg, size_t seg_totals,
+// The last reader of the batch's totals: it leaves them zero for the lane's next batch -- the per-bounce totals it has summed, and the
+// group totals of bounces 0 .. nbounces - 1 (super_words per segment from super_off: read only by the bounce after the one that wrote
+// them), which workgroups 1 .. take.  Launch: dim3(1 + n), dim3(64).
+__global__ void k_stats(int32_t *totals, int nbins, int nbounces, int stride, int skip_first, int nseg, size_t seg_totals,
+                        size_t super_off, int super_words,
                         int64_t *last, int64_t *total, unsigned long long dir_bins, unsigned long long ntab_bins, int64_t *kinds) {
+    if (blockIdx.x != 0) {
+        const size_t n = (size_t)nseg * super_words;
+        for (size_t k = (size_t)(blockIdx.x - 1) * blockDim.x + threadIdx.x; k < n; k += (size_t)(gridDim.x - 1) * blockDim.x)
+            totals[seg_totals * (k / super_words) + super_off + k % super_words] = 0;
+        return;
+    }
     // one wave: lane j takes the (segment, bounce) pairs j, j + 64, ...
-    if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+    if (threadIdx.x >= 64) return;
     long long sum = 0, st = 0, sd = 0, sn = 0;      // rays; stored paths: all, with a direction, with a normal code (what the records weigh)
     for (int k = threadIdx.x; k < nseg * nbounces; k += 64) {
         const int sg = k / nbounces, b = k - sg * nbounces;
@@ -1755,6 +1793,7 @@ __global__ void k_stats(const int32_t *totals, int nbins, int nbounces, int stri
             }
         if (sg == nseg - 1 && b < 64) last[b] = s;      // per-bounce counts of the last iteration of the batch
         sum += s;
+        for (int q = 0; q < stride; q++) totals[seg_totals * sg + (size_t)b * stride + q] = 0;      // (read: by this lane, just now)
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { sum += __shfl_xor(sum, off); st += __shfl_xor(st, off); sd += __shfl_xor(sd, off); sn += __shfl_xor(sn, off); }
@@ -2157,6 +2196,10 @@ struct ptx_tracer {
     bool render_ahead = false;
     int last_ahead_lane = -1;                            // != -1: the previous operation was a call served from that lane's batch
     hipEvent_t ev_ahead0[MAX_LANES] = {}, ev_ahead1[MAX_LANES] = {};
+    // The lit planes and totals of a lane's segments are zero between its launch sets: the set's k_gather and k_stats clear what they
+    // read.  Where that may not hold -- nothing has run yet, a traced-ahead batch was dropped unfinished, a set ended early on an error,
+    // the image was reset -- the lane's next set starts with a full clear of both (enqueue_batch).
+    bool aux_dirty[MAX_LANES] = {};
     int uses_uv = 0;
     unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
     unsigned long long ntab_bins = 0ull;                 // BounceParams::ntab_bins (none: every record carries its normal)
@@ -2500,7 +2543,23 @@ int launch_bounce(const ptx_tracer *t, bool first, int mode, bool needs_albedo, 
 // Lane `lane` works on segments lane*kmax .. of every per-iteration buffer and on its own stream; the image is touched
 // only by k_gather, and the gathers of successive batches are chained by events (prev_lane = the lane the previous batch
 // ran on), so the fp32 sums happen in iteration order whatever the overlap.
+int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lane, int prev_lane, bool defer);
 int enqueue_batch(ptx_tracer *t, int iter_first, int K, int stride = 1, int lane = 0, int prev_lane = -1, bool defer = false) {
+    const int rc = enqueue_batch_body(t, iter_first, K, stride, lane, prev_lane, defer);
+    if (rc != PTX_OK) t->aux_dirty[lane] = true;       // (whatever it had launched may have left bits and totals behind)
+    return rc;
+}
+
+// k_stats over the nseg segments from segment seg, which leaves their totals zero behind it
+void launch_stats(ptx_tracer *t, hipStream_t stream, size_t seg, int nseg, bool skip_first, unsigned long long dir_bins, unsigned long long ntab_bins) {
+    const size_t super_off = 2 * (size_t)t->nbins * t->maxBounces;              // (t->d_super's offset in every segment)
+    const int super_words = t->traceDepth * 2 * t->nbins * t->nsuper;
+    const int nclear = (int)std::min<size_t>(128, ((size_t)nseg * super_words + 255) / 256);
+    hipLaunchKernelGGL(k_stats, dim3(1 + nclear), dim3(64), 0, stream, t->d_totals + seg * t->seg_totals, t->nbins, t->traceDepth, 2 * t->nbins,
+                       skip_first ? 1 : 0, nseg, t->seg_totals, super_off, super_words, t->d_stats, t->d_stats + 64, dir_bins, ntab_bins, t->d_stats + 66);
+}
+
+int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lane, int prev_lane, bool defer) {
     hipStream_t stream = lane == 0 ? t->stream : t->lane_stream[lane];
     const size_t seg0 = (size_t)lane * t->kmax;
     const int nb = t->nbins;
@@ -2570,12 +2629,15 @@ int enqueue_batch(ptx_tracer *t, int iter_first, int K, int stride = 1, int lane
     auto chunks = [&](int bounce) { return t->d_chunk + seg0 * seg_chunk + (size_t)(bounce & 1) * 3 * chunk_cap; };
     auto totals = [&](int bounce, int which) { return t->d_totals + seg0 * seg_totals + ((size_t)bounce * 2 + which) * nb; };
     auto supers = [&](int bounce, int which) { return t->d_super + seg0 * seg_totals + ((size_t)bounce * 2 + which) * nb * t->nsuper; };
-    // per-bounce totals and group totals are accumulated with atomics: clear them once per batch
-    HIPCHECK(hipMemsetAsync(t->d_totals + seg0 * seg_totals, 0, sizeof(int32_t) * seg_totals * (size_t)K, stream));
-    // ... and the batch's "lit" flags (behind each segment's radiance: cap bytes per segment, one strided memset)
-    if (K > 1 || t->lanes > 1)
-        HIPCHECK(hipMemset2DAsync(reinterpret_cast<char *>(t->d_part + seg0 * t->seg_part) + sizeof(float) * 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
-                                  (size_t)t->cap, (size_t)K, stream));
+    // per-bounce totals and group totals are accumulated with atomics, and the lit planes are set bit by bit: the lane's previous set
+    // left them zero (k_stats, k_gather) -- unless the lane is marked, then all of its segments are cleared here, once
+    if (t->aux_dirty[lane]) {
+        HIPCHECK(hipMemsetAsync(t->d_totals + seg0 * seg_totals, 0, sizeof(int32_t) * seg_totals * (size_t)t->kmax, stream));
+        if (t->d_part)                               // (the planes: behind each segment's radiance, cap / 32 words per segment)
+            HIPCHECK(hipMemset2DAsync(t->d_part + seg0 * t->seg_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
+                                      (size_t)t->cap / 8, (size_t)t->kmax, stream));
+        t->aux_dirty[lane] = false;
+    }
 
     // per-kernel timing brackets (only when switched on; costs two event records per launch)
     auto kt_begin = [&](int kind) -> int {
@@ -2711,8 +2773,7 @@ int enqueue_batch(ptx_tracer *t, int iter_first, int K, int stride = 1, int lane
     if (batched)
         hipLaunchKernelGGL(k_gather, dim3(std::min(2048, (t->tm.owned + 255) / 256)), dim3(256), 0, stream, t->tm, t->cam.resx, K,
                            t->seg_part, t->d_part + seg0 * t->seg_part, t->d_image, (uint32_t)t->cap);
-    hipLaunchKernelGGL(k_stats, dim3(1), dim3(64), 0, stream, t->d_totals + seg0 * seg_totals, nb, t->traceDepth, 2 * nb, use_cache ? 1 : 0, K,
-                       seg_totals, t->d_stats, t->d_stats + 64, batch_dir_bins, batch_ntab_bins, t->d_stats + 66);
+    launch_stats(t, stream, seg0, K, use_cache, batch_dir_bins, batch_ntab_bins);
     if (t->lanes > 1) HIPCHECK(hipEventRecord(t->ev_chain[lane], stream));
     HIPCHECK(hipGetLastError());
     t->iterations += K;
@@ -2735,6 +2796,7 @@ void ahead_fold_time(ptx_tracer *t, int lane) {
 void ahead_discard(ptx_tracer *t) {
     for (int l = 1; l < MAX_LANES; l++) {
         if (t->ahead[l].valid || t->ahead[l].unfolded) ahead_fold_time(t, l);
+        if (t->ahead[l].valid) t->aux_dirty[l] = true;       // (segments traced and never gathered keep their bits and totals)
         t->ahead[l].valid = false;
     }
     t->ahead_cur = t->ahead_nxt = -1;
@@ -2763,15 +2825,18 @@ int ahead_start(ptx_tracer *t, int lane, int first) {
 }
 
 // one iteration of a traced-ahead batch into the image: what the tail of enqueue_batch does for a whole batch
+// (its k_gather and k_stats leave the segment's plane and totals zero, as the tail of a whole batch does)
 int ahead_finish_segment(ptx_tracer *t, int lane, int seg) {
     const ptx_tracer::Ahead &a = t->ahead[lane];
     const size_t sg = (size_t)lane * t->kmax + seg, seg_part = t->seg_part;
+    const bool was_dirty = t->aux_dirty[lane];
+    t->aux_dirty[lane] = true;                           // (until both are enqueued)
     HIPCHECK(hipStreamWaitEvent(t->stream, t->ev_ahead1[lane], 0));
     hipLaunchKernelGGL(k_gather, dim3(std::min(2048, (t->tm.owned + 255) / 256)), dim3(256), 0, t->stream, t->tm, t->cam.resx, 1,
                        seg_part, t->d_part + sg * seg_part, t->d_image, (uint32_t)t->cap);
-    hipLaunchKernelGGL(k_stats, dim3(1), dim3(64), 0, t->stream, t->d_totals + sg * t->seg_totals, t->nbins, t->traceDepth, 2 * t->nbins,
-                       a.use_cache ? 1 : 0, 1, t->seg_totals, t->d_stats, t->d_stats + 64, a.dir_bins, a.ntab_bins, t->d_stats + 66);
+    launch_stats(t, t->stream, sg, 1, a.use_cache, a.dir_bins, a.ntab_bins);
     HIPCHECK(hipGetLastError());
+    t->aux_dirty[lane] = was_dirty;
     t->iterations += 1;
     return PTX_OK;
 }
@@ -3187,9 +3252,10 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         HC(hipMalloc(&t->d_ibuf[k], sizeof(int32_t) * SOA_INTS * stride));
         carve(t->soa[k], t->d_fbuf[k], t->d_ibuf[k], stride);
     }
-    t->seg_part = 3 * (size_t)t->cap + (size_t)t->cap / 4;      // per-iteration radiance of the OWNED pixels (slot-indexed), whole tiles, then the
-                                                                // iteration's "lit" flags, a byte per slot (cap is a multiple of 256)
+    t->seg_part = 3 * (size_t)t->cap + (size_t)t->cap / 32;     // per-iteration radiance of the OWNED pixels (slot-indexed), whole tiles, then the
+                                                                // iteration's lit plane, a bit per slot (cap is a multiple of 256)
     if (nseg > 1) HC(hipMalloc(&t->d_part, sizeof(float) * t->seg_part * nseg));
+    for (int l = 0; l < MAX_LANES; l++) t->aux_dirty[l] = true;      // (the planes are not cleared here: each lane's first set does it)
     {   // split mesh search: worth it when some mesh is big enough for a BVH; needs the candidate masks (cull, <= 32 geoms: a
         // parked ray carries one bit per mesh whose box it reaches) and a queue entry per ray in the worst case
         int nmesh = 0;
@@ -3298,6 +3364,7 @@ int ptx_reset_image(ptx_tracer *t) {
     HIPCHECK(hipMemsetAsync(t->d_image, 0, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, t->stream));
     HIPCHECK(hipMemsetAsync(t->d_stats, 0, sizeof(int64_t) * 69, t->stream));
     t->iterations = 0; t->loop_ms_total = 0.0; t->cache_valid = false;
+    for (int l = 0; l < MAX_LANES; l++) t->aux_dirty[l] = true;
     return PTX_OK;
 }
 
@@ -3979,6 +4046,33 @@ int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_bounce<false, 0, true>, TILE, lds) != hipSuccess) return -2;
     return n;
+}
+
+int ptx_debug_aux_nonzero(ptx_tracer *t, int64_t out3[3]) {
+    if (!t || !out3) return set_error(PTX_ERR_INVALID, "null argument");
+    HIPCHECK(hipSetDevice(t->device));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) HIPCHECK(hipStreamSynchronize(t->lane_stream[l]));
+    const size_t nseg = (size_t)t->kmax * t->lanes, words = (size_t)t->cap / 32;
+    std::vector<int32_t> tot(t->seg_totals * nseg);
+    std::vector<uint32_t> planes(t->d_part ? words * nseg : 0);
+    HIPCHECK(hipMemcpy(tot.data(), t->d_totals, t->totals_bytes, hipMemcpyDeviceToHost));
+    if (t->d_part)
+        HIPCHECK(hipMemcpy2D(planes.data(), sizeof(uint32_t) * words, t->d_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part,
+                             sizeof(uint32_t) * words, nseg, hipMemcpyDeviceToHost));
+    int64_t nz_planes = 0, nz_totals = 0, dirty = 0;
+    for (int l = 0; l < t->lanes; l++) {
+        if (t->aux_dirty[l]) { dirty++; continue; }
+        const ptx_tracer::Ahead &a = t->ahead[l];
+        for (int j = 0; j < t->kmax; j++) {
+            if (a.valid && j >= a.next - a.first) continue;      // traced ahead, not gathered yet
+            const size_t sg = (size_t)l * t->kmax + j;
+            for (size_t k = 0; k < t->seg_totals; k++) nz_totals += tot[sg * t->seg_totals + k] != 0;
+            if (t->d_part) for (size_t k = 0; k < words; k++) nz_planes += planes[sg * words + k] != 0;
+        }
+    }
+    out3[0] = nz_planes; out3[1] = nz_totals; out3[2] = dirty;
+    return PTX_OK;
 }
 
 int ptx_debug_set_capture(ptx_tracer *t, int bounce) {
