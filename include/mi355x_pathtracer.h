@@ -298,6 +298,49 @@ int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32
 int ptx_denoise_buffers(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, const float *pos3,
                         const uint8_t *hit, const ptx_denoise_params *p, float *out_rgb);
 
+/* ---- temporal reuse in front of the denoiser (in the spirit of SVGF, Schied et al., HPG 2017), csrc/pt_temporal.hip -----------------
+ * The previous view's result, reprojected through the G-buffer into the current view, blended with the current accumulation by sample
+ * count, then the a-trous filter above.  The history lives in a handle of its own, so it outlives the tracer: the reference's loop
+ * (apps/src/main.cpp:221-271) destroys and recreates the tracer on every camera change.  Definition (tests/temporal_ref.py
+ * restates it):
+ *   State: the camera (ptx_camera floats) and per pixel hit flag, world position, normal, geom id, material id (copied from the tracer's
+ *   G-buffer), D = mix / max(albedo, 1e-3) per channel on hit pixels (mix on miss pixels) and a float sample count n.  The handle keeps
+ *   `cur` (the state of its last call) and `hist` (the committed history).
+ *   Segments: each ptx_denoise_temporal compares the tracer's camera bit for bit with cur's.  Different: cur becomes hist and a new cur
+ *   starts.  Equal: the same segment -- cur is recomputed from the same hist and the tracer's current accumulation, so no sample is
+ *   counted twice (ptx_reset_image with the same camera included).  The first call, and the first after ptx_temporal_reset, has no hist.
+ *   Reprojection, every hit pixel p (position x_p, normal n_p, ids, albedo a_p), P = hist's camera: solve
+ *     x_p - P.position = s * (view - right*pl.x*(u - W/2) - up*pl.y*(v - H/2))        (generateRay's pixel-centre ray, unnormalised)
+ *   for (s, u, v) as a 3x3 linear system in (s, s*u, s*v) (right and up need not be orthonormal).  s <= 0: nothing.  Pixel centres are
+ *   at integer (u, v); the bilinear taps (floor(u) + i, floor(v) + j), i, j in {0, 1}, of non-zero weight w_q are accepted when inside
+ *   the frame, a hit in hist, of the same geom and material id, dot(n_p, n_q) >= normal_cos and |dot(n_p, x_q - x_p)| <=
+ *   plane_tolerance * |x_p - P.position|.  With specular_history == 0 a pixel whose material has hasReflective > 0 or hasRefractive > 0
+ *   accepts nothing.  Sum of accepted weights S > 0: n_h = min(sum w_q n_q / S, max_history), and when n_h > 0
+ *   h = sum w_q D_q / S * max(a_p, 1e-3) per channel; otherwise n_h = 0 and h = 0.
+ *   Mix: c = rgb / spp (the fp32 division of ptx_denoise).  Miss pixel or n_h == 0: mix = c exactly, n = spp.  Otherwise
+ *   mix = (spp*c + n_h*h) / (spp + n_h), n = spp + n_h.
+ *   Output: the a-trous filter of mix (spp = 1) with the tracer's G-buffer, into the tracer's denoised frame (ptx_read_denoised,
+ *   ptx_device_denoised, ptx_write_denoised_pbo_from_device take it).  Without hist, or with max_history == 0, that is bit for bit
+ *   ptx_denoise.
+ * A handle serves one W x H on one device, across tracers and streams: each call makes the tracer's stream wait for the handle's
+ * previous work and records an event after its own. */
+typedef struct ptx_temporal ptx_temporal;          /* opaque: history of one W x H view sequence on one device */
+typedef struct ptx_temporal_params {
+    int32_t max_history;       /* samples a pixel may inherit; 0 = no reuse (== ptx_denoise); default 16 */
+    int32_t specular_history;  /* 0 = reflective / refractive materials inherit nothing (default)        */
+    float   normal_cos;        /* default 0.9                                                            */
+    float   plane_tolerance;   /* relative to the distance from the previous camera; default 0.01        */
+} ptx_temporal_params;
+void   ptx_default_temporal_params(ptx_temporal_params *p);
+size_t ptx_sizeof_temporal_params(void);
+int  ptx_temporal_create(int device, int width, int height, ptx_temporal **out);   /* PTX_ERR_NODEVICE without a device */
+void ptx_temporal_destroy(ptx_temporal *h);        /* NULL is a no-op; waits for its last use */
+int  ptx_temporal_reset(ptx_temporal *h);          /* forget all history */
+/* Enqueues G-buffer (when stale) + reprojection + mix + filter on the tracer's stream; dp / tp NULL = defaults.  The accumulation buffer,
+ * statistics and what later iterations compute are untouched.  Refused: a handle of another device or size, tile_world > 1, spp < 1. */
+int  ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dp, const ptx_temporal_params *tp, int spp);
+int  ptx_temporal_read(ptx_temporal *h, float *hist_rgb3, float *hist_count1, float *mix_rgb3);   /* last call's h, n_h, mix; NULLs allowed; waits */
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);

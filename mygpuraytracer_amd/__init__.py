@@ -13,15 +13,18 @@ from .api import (  # noqa: F401
     PathTracerError,
     Options,
     DenoiseParams,
+    TemporalParams,
     Scene,
     Tracer,
+    Temporal,
     MultiTracer,
     StreamCompaction,
     build_library,
     default_denoise_params,
+    default_temporal_params,
     denoise_buffers,
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "Scene", "Tracer", "MultiTracer", "StreamCompaction", "build_library",
-           "default_denoise_params", "denoise_buffers", "load_library"]
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "Scene", "Tracer", "Temporal", "MultiTracer",
+           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "denoise_buffers", "load_library"]

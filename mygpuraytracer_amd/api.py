@@ -99,6 +99,68 @@ def default_denoise_params(**kw):
     return p
 
 
+class TemporalParams(C.Structure):
+    """ptx_temporal_params: temporal reuse in front of the denoiser (include/mi355x_pathtracer.h; defaults from
+    ptx_default_temporal_params)."""
+    _fields_ = [("max_history", C.c_int32), ("specular_history", C.c_int32), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float)]
+
+
+_TEMPORAL_INTS = ("max_history", "specular_history")
+
+
+def default_temporal_params(**kw):
+    """ptx_default_temporal_params with keyword overrides (max_history, specular_history, normal_cos, plane_tolerance)."""
+    p = TemporalParams()
+    load_library().ptx_default_temporal_params(C.byref(p))
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v) if k in _TEMPORAL_INTS else float(v))
+    return p
+
+
+class Temporal:
+    """The history of one W x H view sequence on one device (opaque ptx_temporal), for Tracer.denoise_temporal.  It outlives any
+    tracer: hand the same handle to a new Tracer after a camera change and the previous view's samples are reused."""
+
+    def __init__(self, device, width, height):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_temporal_create(int(device), int(width), int(height), C.byref(h)), "ptx_temporal_create")
+        self.h = h
+        self.device, self.width, self.height = int(device), int(width), int(height)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ptx_temporal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """forget all history: the next denoise_temporal is Tracer.denoise bit for bit"""
+        _check(self.lib.ptx_temporal_reset(self.h), "ptx_temporal_reset")
+
+    def read(self):
+        """The last call's reprojected history h (H, W, 3), its sample count n_h (H, W) and the mix (H, W, 3) the filter took."""
+        hh, ww = self.height, self.width
+        hist, count, mix = np.zeros((hh, ww, 3), np.float32), np.zeros((hh, ww), np.float32), np.zeros((hh, ww, 3), np.float32)
+        _check(self.lib.ptx_temporal_read(self.h, _ptr(hist), _ptr(count), _ptr(mix)), "ptx_temporal_read")
+        return dict(history=hist, count=count, mix=mix)
+
+
 def denoise_buffers(rgb, albedo, normal, position, hit, device=0, **params):
     """The a-trous filter alone (ptx_denoise_buffers) on host arrays of one (H, W) frame: rgb = mean radiance, albedo / normal / position
     (..., 3), hit (...) bool.  Returns the filtered mean radiance as (H, W, 3) float32 when rgb is (H, W, 3), else rgb's shape.  Needs a
@@ -205,6 +267,10 @@ def load_library():
     if L.ptx_sizeof_denoise_params() != C.sizeof(DenoiseParams):
         raise PathTracerError("%s has a ptx_denoise_params of %d B, this module expects %d B: rebuild the library" % (
             LIB_PATH, L.ptx_sizeof_denoise_params(), C.sizeof(DenoiseParams)))
+    L.ptx_sizeof_temporal_params.restype = C.c_size_t
+    if L.ptx_sizeof_temporal_params() != C.sizeof(TemporalParams):
+        raise PathTracerError("%s has a ptx_temporal_params of %d B, this module expects %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_temporal_params(), C.sizeof(TemporalParams)))
     L.ptx_last_error.restype = C.c_char_p
     L.ptx_device_count.restype = i
     L.ptx_default_options.argtypes = [C.POINTER(Options)]
@@ -257,6 +323,13 @@ def load_library():
     L.ptx_read_gbuffer.restype, L.ptx_read_gbuffer.argtypes = i, [vp, vp, vp, vp, vp, vp, vp]
     L.ptx_denoise_buffers.restype = i
     L.ptx_denoise_buffers.argtypes = [i, i, i, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
+    L.ptx_default_temporal_params.argtypes = [C.POINTER(TemporalParams)]
+    L.ptx_temporal_create.restype, L.ptx_temporal_create.argtypes = i, [i, i, i, C.POINTER(vp)]
+    L.ptx_temporal_destroy.restype, L.ptx_temporal_destroy.argtypes = None, [vp]
+    L.ptx_temporal_reset.restype, L.ptx_temporal_reset.argtypes = i, [vp]
+    L.ptx_denoise_temporal.restype = i
+    L.ptx_denoise_temporal.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), i]
+    L.ptx_temporal_read.restype, L.ptx_temporal_read.argtypes = i, [vp, vp, vp, vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -686,6 +759,17 @@ class Tracer:
         only enqueues it -- device_denoised_ptr / denoised_pbo_from_device then use it where it is)"""
         p = default_denoise_params(passes=passes, demodulate=demodulate, phi_color=phi_color, phi_normal=phi_normal, phi_position=phi_position)
         _check(self.lib.ptx_denoise(self.h, C.byref(p), int(spp)), "ptx_denoise")
+        return self.read_denoised() if read else None
+
+    def denoise_temporal(self, temporal, spp, read=True, passes=None, demodulate=None, phi_color=None, phi_normal=None,
+                         phi_position=None, max_history=None, specular_history=None, normal_cos=None, plane_tolerance=None):
+        """denoise() with temporal reuse (ptx_denoise_temporal): the previous view's samples in `temporal` (a Temporal) reprojected
+        into this view and mixed with the accumulation buffer / spp, then the a-trous filter.  Returns the (H, W, 3) float32 mean
+        radiance (read=False: only enqueues it); temporal.read() gives the history and the mix."""
+        dp = default_denoise_params(passes=passes, demodulate=demodulate, phi_color=phi_color, phi_normal=phi_normal, phi_position=phi_position)
+        tp = default_temporal_params(max_history=max_history, specular_history=specular_history, normal_cos=normal_cos,
+                                     plane_tolerance=plane_tolerance)
+        _check(self.lib.ptx_denoise_temporal(self.h, temporal.h, C.byref(dp), C.byref(tp), int(spp)), "ptx_denoise_temporal")
         return self.read_denoised() if read else None
 
     def read_denoised(self):

@@ -10,6 +10,11 @@
 //                                  [--per-call [--no-render-ahead]]   (one pathtrace(pbo, frame, iter) per iteration with the frame read
 //                                                                      back after each, exactly the reference's runCuda loop)
 //                                  [--denoise [--denoise-passes N]]   (also <out>.denoised.png / .pfm: the a-trous denoiser, ptx_denoise)
+//                                  [--frames K --frame-step "left:DX,DY;..."]   (K frames of an orbit: frame f applies the --orbit
+//                                                                      script, then the step script f-1 times, and runs the reference's
+//                                                                      camera-change loop: pathtraceFree/Init, --iterations N pathtrace
+//                                                                      calls, GPUdenoise with --denoise; <out>.fNNN.png [.denoised.png])
+//                                  [--temporal]   (with --denoise: GPUdenoise reuses the previous frame's samples, ptx_denoise_temporal)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -33,17 +38,56 @@ static std::string currentTimeString() {          // src/preview.cpp:13-19
     return std::string(buf);
 }
 
+// --frames: the camera-change loop of apps/src/main.cpp:221-271 over an orbit, one tracer per frame, the denoiser's history (with
+// --temporal) kept across them by the veneer
+static int run_frames(Scene *scene, int frames, const std::string &orbit_script, const std::string &frame_step, const std::string &out_prefix,
+                      bool denoise, bool temporal, bool pfm) {
+    denoiseTemporal() = temporal;
+    const Camera base = scene->state.camera;
+    const int width = base.resolution[0], height = base.resolution[1], n = (int)scene->state.iterations;
+    if (n < 1) { fprintf(stderr, "--frames needs --iterations N >= 1\n"); return 1; }
+    const std::string prefix = out_prefix.empty() ? scene->state.imageName : out_prefix;
+    std::string script = orbit_script;
+    std::vector<uint8_t> rgb8;
+    for (int f = 1; f <= frames; f++) {
+        if (f > 1) script += ";" + frame_step;
+        scene->state.camera = base;
+        if (!scene->runOrbitScript(script)) { fprintf(stderr, "bad --orbit / --frame-step script: %s\n", script.c_str()); return 1; }
+        pathtraceFree();                         // the camera changed: iteration = 0, a new tracer (main.cpp:229-240)
+        pathtraceInit(scene);
+        for (int it = 1; it <= n; it++) pathtrace(nullptr, 0, it);
+        char tag[16];
+        snprintf(tag, sizeof tag, ".f%03d", f);
+        const std::string name = prefix + tag;
+        ptimg::to_rgb8_mirrored(width, height, &scene->state.image[0].x, (float)n, rgb8);
+        if (!ptimg::write_png_rgb8(name + ".png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.png\n", name.c_str()); return 1; }
+        printf("Saved %s.png.\n", name.c_str());
+        if (pfm) { ptimg::write_pfm(name + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", name.c_str()); }
+        if (denoise) {
+            GPUdenoise();                        // state.output = the denoised mean radiance
+            ptimg::to_rgb8_mirrored(width, height, &scene->state.output[0].x, 1.0f, rgb8);
+            if (!ptimg::write_png_rgb8(name + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", name.c_str()); return 1; }
+            printf("Saved %s.denoised.png.\n", name.c_str());
+            if (pfm) { ptimg::write_pfm(name + ".denoised.pfm", width, height, &scene->state.output[0].x, 1.0f); printf("Saved %s.denoised.pfm.\n", name.c_str()); }
+        }
+    }
+    GPUdenoiseRelease();
+    pathtraceFree();
+    delete scene;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal]\n", argv[0]);
         return 1;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
-    bool pfm = false, hdr = false, per_call = false, denoise = false;
+    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false;
     ptx_denoise_params &dparams = denoiseParams();
-    std::string out_prefix, ckpt_path, resume_path, orbit_script;
-    int ckpt_every = 0;
+    std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
+    int ckpt_every = 0, frames = 0;
     ptx_options &opt = pathtraceOptions();
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
@@ -68,7 +112,16 @@ int main(int argc, char **argv) {
         else if (a == "--no-render-ahead") pathtraceRenderAhead() = false;
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-passes") { need(1); dparams.passes = atoi(argv[++i]); }
+        else if (a == "--frames") { need(1); frames = atoi(argv[++i]); }
+        else if (a == "--frame-step") { need(1); frame_step = argv[++i]; }
+        else if (a == "--temporal") temporal = true;
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
+    }
+    if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
+    if (frames < 0 || (frames == 0 && !frame_step.empty())) { fprintf(stderr, "--frame-step needs --frames K, K >= 1\n"); return 1; }
+    if (frames > 0 && (per_call || hdr || !ckpt_path.empty() || !resume_path.empty())) {
+        fprintf(stderr, "--frames does not combine with --per-call, --hdr, --checkpoint or --resume\n");
+        return 1;
     }
     Scene *scene = nullptr;
     try {
@@ -80,6 +133,7 @@ int main(int argc, char **argv) {
     if (resw > 0 && resh > 0) scene->setResolution(resw, resh);
     if (depth > 0) scene->state.traceDepth = depth;
     if (iterations > 0) scene->state.iterations = (unsigned)iterations;
+    if (frames > 0) return run_frames(scene, frames, orbit_script, frame_step, out_prefix, denoise, temporal, pfm);
     if (orbit_script.empty()) scene->applyRunCudaCamera();
     else if (!scene->runOrbitScript(orbit_script)) { fprintf(stderr, "bad --orbit script: %s\n", orbit_script.c_str()); return 1; }
     const int width = scene->state.camera.resolution[0], height = scene->state.camera.resolution[1];

@@ -23,6 +23,11 @@ int g_last_iter = 0;                 // iteration of the last pathtrace() call: 
 bool g_output_on_device = false;     // GPUdenoise(true) ran since the last pathtrace(): sendToGPU shows the device frame
 ptx_denoise_params g_denoise;
 bool g_denoise_init = false;
+ptx_temporal_params g_temporal_params;
+bool g_temporal_params_init = false;
+ptx_temporal *g_temporal = nullptr;  // GPUdenoise's history with denoiseTemporal() on: kept across pathtraceFree / pathtraceInit
+int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
+int g_device = 0;                    // the device of g_tracer
 
 void check(int rc, const char *what) {
     if (rc == PTX_OK) return;
@@ -172,6 +177,21 @@ ptx_denoise_params &denoiseParams() {
     return g_denoise;
 }
 
+bool &denoiseTemporal() {
+    static bool on = false;
+    return on;
+}
+
+ptx_temporal_params &temporalParams() {
+    if (!g_temporal_params_init) { ptx_default_temporal_params(&g_temporal_params); g_temporal_params_init = true; }
+    return g_temporal_params;
+}
+
+void GPUdenoiseRelease() {
+    ptx_temporal_destroy(g_temporal);
+    g_temporal = nullptr;
+}
+
 void pathtraceInit(Scene *scene) {
     hst_scene = scene;
     g_albedo_read = false;
@@ -192,6 +212,8 @@ void pathtraceInit(Scene *scene) {
                          scene->state.camera.c_abi(), scene->state.traceDepth, &o, nullptr, nullptr, &g_tracer),
               "pathtraceInit");
         check(ptx_set_render_ahead(g_tracer, pathtraceRenderAhead() ? 1 : 0), "pathtraceInit");
+        g_device = o.device;
+        if (g_device < 0 && hipGetDevice(&g_device) != hipSuccess) g_device = 0;     // -1: the current device, which ptx_create used
     }
     // the reference copies the whole fp32 frame into scene->state.image after every iteration (src/pathtrace.cu:555-556):
     // page-lock the destination once, so that each of those copies is one DMA at PCIe rate (not fatal if it cannot be)
@@ -256,7 +278,18 @@ void GPUdenoise(bool keep_on_device) {
     if (!g_tracer || !hst_scene) { fprintf(stderr, "GPUdenoise called before pathtraceInit\n"); exit(EXIT_FAILURE); }
     if (g_multi) { fprintf(stderr, "GPUdenoise: the denoiser runs on one device; pathtraceDevices() names several\n"); exit(EXIT_FAILURE); }
     if (g_last_iter < 1) { fprintf(stderr, "GPUdenoise called before the first pathtrace\n"); exit(EXIT_FAILURE); }
-    check(ptx_denoise(g_tracer, &denoiseParams(), g_last_iter), "GPUdenoise");
+    if (denoiseTemporal()) {
+        const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+        const int key[3] = {g_device, w, h};
+        if (g_temporal && memcmp(key, g_temporal_key, sizeof key) != 0) GPUdenoiseRelease();     // another device or resolution
+        if (!g_temporal) {
+            check(ptx_temporal_create(g_device, w, h, &g_temporal), "GPUdenoise");
+            memcpy(g_temporal_key, key, sizeof key);
+        }
+        check(ptx_denoise_temporal(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), g_last_iter), "GPUdenoise");
+    } else {
+        check(ptx_denoise(g_tracer, &denoiseParams(), g_last_iter), "GPUdenoise");
+    }
     g_output_on_device = keep_on_device;
     if (!keep_on_device) check(ptx_read_denoised(g_tracer, &hst_scene->state.output[0].x), "GPUdenoise readback");
 }

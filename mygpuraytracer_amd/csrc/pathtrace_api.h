@@ -259,6 +259,13 @@ ptx_tracer *pathtraceHandle();                          // the C-ABI handle behi
 // One device only: with several pathtraceDevices() it prints an error and exits, as every other failure of the veneer does.
 void GPUdenoise(bool keep_on_device = false);
 ptx_denoise_params &denoiseParams();                    // what GPUdenoise filters with (ptx_default_denoise_params until changed)
+// Temporal reuse (ptx_denoise_temporal): off by default.  When on, GPUdenoise mixes the previous view's samples, reprojected, into the
+// current accumulation before filtering, through a module-level history created on first use and KEPT across pathtraceFree /
+// pathtraceInit -- so the reference's loop, which recreates the tracer on every camera change, reuses them unchanged.  It is recreated
+// when the device or the resolution changes; GPUdenoiseRelease() frees it.
+bool &denoiseTemporal();
+ptx_temporal_params &temporalParams();                  // what it reprojects with (ptx_default_temporal_params until changed)
+void GPUdenoiseRelease();
 
 namespace mi355x {
 void pathtrace_raw(void *pbo, int frame, int iteration);   // what both spellings below run; pbo = device uchar4*, may be NULL (no preview)

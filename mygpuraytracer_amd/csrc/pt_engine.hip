@@ -46,6 +46,7 @@
 #include "pt_device.h"
 #include "pt_bvh.h"
 #include "pt_denoise.h"
+#include "pt_temporal.h"
 
 using namespace ptd;
 
@@ -2213,6 +2214,8 @@ struct ptx_tracer {
     float4 *d_gbuf = nullptr, *d_dn_tmp = nullptr;
     float *d_dn_out = nullptr;
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
+    std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
+    uint8_t *d_spec = nullptr;                           // its device copy, on the first ptx_denoise_temporal
     unsigned long long *d_stamps = nullptr;              // diagnostic build only
     float *d_part = nullptr;                             // [kmax][W*H*3] per-iteration radiance (batched mode)
     int32_t *d_cache_totals = nullptr;                   // [2][nbins] of bounce 0 (cache)
@@ -2484,7 +2487,7 @@ int free_tracer(ptx_tracer *t) {
     hipFree(t->d_cache_chunk); hipFree(t->d_cache_super);
     hipFree(t->d_counts); hipFree(t->d_chunk); hipFree(t->d_totals); hipFree(t->d_cache_totals);
     hipFree(t->d_emit_count); hipFree(t->d_emit_pix); hipFree(t->d_emit_rgb); hipFree(t->d_stats); hipFree(t->d_cap); hipFree(t->d_cap_f); hipFree(t->d_part); hipFree(t->d_albedo); hipFree(t->d_stamps); hipFree(t->d_pbo); hipFree(t->d_denoised);
-    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out);
+    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out); hipFree(t->d_spec);
     for (hipEvent_t e : t->kev) hipEventDestroy(e);
     if (t->ev_start) hipEventDestroy(t->ev_start);
     if (t->ev_stop) hipEventDestroy(t->ev_stop);
@@ -3131,6 +3134,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     std::vector<DMaterial> hm((size_t)std::max(nmaterials, 1));
     static_assert(sizeof(DMaterial) == sizeof(ptx_material), "material layout");
     if (nmaterials) memcpy(hm.data(), materials, sizeof(DMaterial) * (size_t)nmaterials);
+    for (const DMaterial &m : hm) t->h_spec.push_back(m.hasReflective > 0.0f || m.hasRefractive > 0.0f ? 1 : 0);
     {   // which records carry what (record_masks); off: more than 64 bins, no material, or PTX_DEBUG_NO_DIR_SKIP
         unsigned long long need = ~0ull, cubes = 0ull;
         const bool off = t->nbins > 64 || nmaterials < 1 || getenv("PTX_DEBUG_NO_DIR_SKIP") != nullptr;
@@ -3612,6 +3616,60 @@ int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *params, int spp) {
     if (rc != PTX_OK) return rc;
     HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, t->d_image, (float)spp, t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n,
                                t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, p));
+    t->dn_done = true;
+    return PTX_OK;
+}
+
+// ---- temporal reuse (pt_temporal.hip; definition in include/mi355x_pathtracer.h) ----------------------------------------------------
+static_assert(sizeof(DCamera) == sizeof(ptx_camera), "camera layout");
+
+int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams, int spp) {
+    ptx_denoise_params dp;
+    ptx_temporal_params tp;
+    if (dparams) dp = *dparams;
+    else ptx_default_denoise_params(&dp);
+    if (tparams) tp = *tparams;
+    else ptx_default_temporal_params(&tp);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
+    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: spp must be >= 1 (the iterations summed in the accumulation buffer)");
+    if (!t || !h) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: null tracer or temporal handle");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (h->device != t->device)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: the temporal handle was created on device " + std::to_string(h->device) +
+                                              ", the tracer runs on device " + std::to_string(t->device));
+    if (h->w != t->cam.resx || h->h != t->cam.resy)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
+                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
+    HIPCHECK(hipSetDevice(t->device));
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
+    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
+    if (!t->d_spec) {
+        HIPCHECK(hipMalloc(&t->d_spec, t->h_spec.size()));
+        HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
+    }
+    const int rc = ensure_gbuffer(t);
+    if (rc != PTX_OK) return rc;
+    if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));     // the handle's last work, maybe on another tracer's stream
+    ptx_camera cam;
+    memcpy(&cam, &t->cam, sizeof cam);
+    if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {     // a new segment: cur becomes hist
+        if (h->cur_valid) { h->cur ^= 1; h->hist_valid = true; }
+        h->cam[h->cur] = cam;
+        h->cur_valid = true;
+    }
+    const int hi = h->cur ^ 1;
+    const PtTemporalCam pc = pt_temporal_camera(h->cam[hi], h->hist_valid);
+    const float4 *g = t->d_gbuf;
+    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, pc, tp, t->d_image, (float)spp, g, g + n, g + 2 * n,
+                                 reinterpret_cast<const int2 *>(g + 3 * n), t->d_spec, (int)t->h_spec.size(), h->st[h->cur], h->st[hi],
+                                 h->d_mix, h->d_hn));
+    HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, h->d_mix, 1.0f, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n,
+                               t->d_dn_out, dp));
+    HIPCHECK(hipEventRecord(h->ev, t->stream));
+    h->used = h->done = true;
     t->dn_done = true;
     return PTX_OK;
 }

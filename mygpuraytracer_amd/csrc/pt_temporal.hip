@@ -1,0 +1,238 @@
+// pt_temporal.hip -- temporal reuse in front of the a-trous denoiser (in the spirit of SVGF, Schied et al., HPG 2017): the history
+// handle of include/mi355x_pathtracer.h (ptx_temporal_*) and its one kernel.  ptx_denoise_temporal itself is pt_engine.hip's: it needs
+// the tracer's G-buffer and accumulation buffer.
+//
+// k_temporal_reproject: one thread per pixel of the current G-buffer, workgroups of 64 x 4 pixels as k_atrous_pass (a wave is one
+// 64-pixel row segment, so its bilinear taps into hist are two contiguous runs of records).  fp32, plain vector loads and stores.
+// Per pixel: reproject into hist's camera, accept / reject up to four taps, mix with rgb / spp, write the new cur record, the mix and
+// (h, n_h).  It copies what the next segment needs out of the G-buffer, which ensure_gbuffer rewrites in place on the next view.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+#include <string>
+
+#include "pt_temporal.h"
+
+extern "C" void ptx_internal_set_error(const char *msg);
+
+namespace {
+
+constexpr int BX = 64, BY = 4;
+
+__global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
+        int w, int h, const PtTemporalCam cam, float max_history, int specular_history, float normal_cos, float plane_tolerance,
+        const float *__restrict__ rgb, float spp, const float4 *__restrict__ gnh, const float4 *__restrict__ gxt,
+        const float4 *__restrict__ galb, const int2 *__restrict__ gids, const uint8_t *__restrict__ spec, int nmats,
+        float4 *__restrict__ cnh, float4 *__restrict__ cxn, float4 *__restrict__ cdd, int2 *__restrict__ cids,
+        const float4 *__restrict__ hnh, const float4 *__restrict__ hxn, const float4 *__restrict__ hdd, const int2 *__restrict__ hids,
+        float *__restrict__ mix, float4 *__restrict__ hn) {
+    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const int p = y * w + x;
+    const float4 np = gnh[p], xp = gxt[p];
+    const int2 id = gids[p];
+    const bool hit = np.w != 0.f;
+    const float c0 = rgb[3 * (size_t)p] / spp, c1 = rgb[3 * (size_t)p + 1] / spp, c2 = rgb[3 * (size_t)p + 2] / spp;   // = k_atrous_prep
+    float4 a = make_float4(1.f, 1.f, 1.f, 0.f);
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f, nhist = 0.f;
+    if (hit) {
+        const float4 al = galb[p];
+        a = make_float4(fmaxf(al.x, 1e-3f), fmaxf(al.y, 1e-3f), fmaxf(al.z, 1e-3f), 0.f);
+        const bool specular = id.x >= 0 && id.x < nmats && spec[id.x] != 0;
+        if (cam.valid && (specular_history || !specular)) {
+            const float dx = xp.x - cam.pos[0], dy = xp.y - cam.pos[1], dz = xp.z - cam.pos[2];
+            const float s = cam.minv[0] * dx + cam.minv[1] * dy + cam.minv[2] * dz;
+            const float su = cam.minv[3] * dx + cam.minv[4] * dy + cam.minv[5] * dz;
+            const float sv = cam.minv[6] * dx + cam.minv[7] * dy + cam.minv[8] * dz;
+            const float u = su / s, v = sv / s;
+            // (a NaN fails every comparison: no tap)
+            if (s > 0.f && u > -1.f && u < (float)w && v > -1.f && v < (float)h) {
+                const float uf = floorf(u), vf = floorf(v);
+                const int u0 = (int)uf, v0 = (int)vf;
+                const float fu = u - uf, fv = v - vf;
+                const float lim = plane_tolerance * sqrtf(dx * dx + dy * dy + dz * dz);
+                float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f;
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int qx = u0 + i, qy = v0 + j;
+                        const float wt = (i ? fu : 1.f - fu) * (j ? fv : 1.f - fv);
+                        if (!(wt > 0.f) || qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                        const int q = qy * w + qx;
+                        const float4 nq = hnh[q];
+                        if (nq.w == 0.f) continue;
+                        const int2 iq = hids[q];
+                        if (iq.x != id.x || iq.y != id.y) continue;
+                        if (!(np.x * nq.x + np.y * nq.y + np.z * nq.z >= normal_cos)) continue;
+                        const float4 xq = hxn[q];
+                        const float pl = np.x * (xq.x - xp.x) + np.y * (xq.y - xp.y) + np.z * (xq.z - xp.z);
+                        if (!(fabsf(pl) <= lim)) continue;
+                        const float4 dq = hdd[q];
+                        sr += wt * dq.x; sg += wt * dq.y; sb += wt * dq.z; sn += wt * xq.w; sw += wt;
+                    }
+                }
+                if (sw > 0.f) {
+                    nhist = fminf(sn / sw, max_history);
+                    if (nhist > 0.f) { h0 = sr / sw * a.x; h1 = sg / sw * a.y; h2 = sb / sw * a.z; }
+                    else nhist = 0.f;
+                }
+            }
+        }
+    }
+    float m0 = c0, m1 = c1, m2 = c2, n = spp;            // a miss, or nothing inherited: mix is c exactly
+    if (nhist > 0.f) {
+        const float tot = spp + nhist;
+        m0 = (spp * c0 + nhist * h0) / tot; m1 = (spp * c1 + nhist * h1) / tot; m2 = (spp * c2 + nhist * h2) / tot;
+        n = tot;
+    }
+    cnh[p] = np;
+    cxn[p] = make_float4(xp.x, xp.y, xp.z, n);
+    cdd[p] = hit ? make_float4(m0 / a.x, m1 / a.y, m2 / a.z, 0.f) : make_float4(m0, m1, m2, 0.f);
+    cids[p] = id;
+    mix[3 * (size_t)p] = m0; mix[3 * (size_t)p + 1] = m1; mix[3 * (size_t)p + 2] = m2;
+    hn[p] = make_float4(h0, h1, h2, nhist);
+}
+
+int fail(int code, const std::string &msg) { ptx_internal_set_error(msg.c_str()); return code; }
+
+}  // namespace
+
+const char *pt_temporal_params_problem(const ptx_temporal_params &p) {
+    if (p.max_history < 0) return "ptx_temporal_params.max_history must be >= 0";
+    if (!(p.normal_cos >= -1.f && p.normal_cos <= 1.f)) return "ptx_temporal_params.normal_cos must be in -1 .. 1";
+    if (!(p.plane_tolerance >= 0.f) || isinf(p.plane_tolerance)) return "ptx_temporal_params.plane_tolerance must be finite and >= 0";
+    return nullptr;
+}
+
+PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist) {
+    PtTemporalCam k;
+    memset(&k, 0, sizeof k);
+    const double W = c.resolution[0], H = c.resolution[1];
+    double R[3], U[3], A[3];
+    for (int i = 0; i < 3; i++) {
+        R[i] = (double)c.right[i] * c.pixelLength[0];
+        U[i] = (double)c.up[i] * c.pixelLength[1];
+        A[i] = (double)c.view[i] + R[i] * (W * 0.5) + U[i] * (H * 0.5);
+    }
+    const double m[3][3] = {{A[0], -R[0], -U[0]}, {A[1], -R[1], -U[1]}, {A[2], -R[2], -U[2]}};
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    double inv[9];
+    inv[0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det;
+    inv[1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det;
+    inv[2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
+    inv[3] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det;
+    inv[4] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det;
+    inv[5] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
+    inv[6] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) / det;
+    inv[7] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det;
+    inv[8] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+    bool ok = have_hist && det != 0.0 && std::isfinite(det);
+    for (int i = 0; i < 9; i++) {
+        k.minv[i] = (float)inv[i];
+        ok = ok && std::isfinite(k.minv[i]);
+    }
+    for (int i = 0; i < 3; i++) k.pos[i] = c.position[i];
+    k.valid = ok ? 1 : 0;
+    return k;
+}
+
+hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
+                               float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
+                               const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
+                               float4 *hn) {
+    const dim3 grid((unsigned)((w + BX - 1) / BX), (unsigned)((h + BY - 1) / BY)), block(BX, BY);
+    hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
+                       p.normal_cos, p.plane_tolerance, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cur.nh, cur.xn, cur.dd, cur.ids,
+                       (const float4 *)hist.nh, (const float4 *)hist.xn, (const float4 *)hist.dd, (const int2 *)hist.ids, mix, hn);
+    return hipGetLastError();
+}
+
+extern "C" {
+
+void ptx_default_temporal_params(ptx_temporal_params *p) {
+    if (!p) return;
+    p->max_history = 16;           // the sweep of tools/gpu_temporal_quality.py
+    p->specular_history = 0;
+    p->normal_cos = 0.9f;
+    p->plane_tolerance = 0.01f;
+}
+
+size_t ptx_sizeof_temporal_params(void) { return sizeof(ptx_temporal_params); }
+
+static void free_temporal(ptx_temporal *t) {
+    for (PtTemporalState &s : t->st) { (void)hipFree(s.nh); (void)hipFree(s.xn); (void)hipFree(s.dd); (void)hipFree(s.ids); }
+    (void)hipFree(t->d_mix);
+    (void)hipFree(t->d_hn);
+    if (t->ev) (void)hipEventDestroy(t->ev);
+    delete t;
+}
+
+int ptx_temporal_create(int device, int width, int height, ptx_temporal **out) {
+    if (!out) return fail(PTX_ERR_INVALID, "ptx_temporal_create: out is NULL");
+    *out = nullptr;
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 3) return fail(PTX_ERR_INVALID, "ptx_temporal_create: bad frame size");
+    if (device < 0) return fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        return fail(PTX_ERR_NODEVICE, "no HIP device available; the temporal denoiser has no CPU path");
+    }
+    if (device >= ndev) return fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
+    ptx_temporal *t = new ptx_temporal();
+    t->device = device; t->w = width; t->h = height;
+    const size_t n = (size_t)width * height;
+#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { free_temporal(t); return fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    HC(hipSetDevice(device));
+    for (PtTemporalState &s : t->st) {
+        HC(hipMalloc(&s.nh, sizeof(float4) * n)); HC(hipMalloc(&s.xn, sizeof(float4) * n));
+        HC(hipMalloc(&s.dd, sizeof(float4) * n)); HC(hipMalloc(&s.ids, sizeof(int2) * n));
+    }
+    HC(hipMalloc(&t->d_mix, sizeof(float) * 3 * n));
+    HC(hipMalloc(&t->d_hn, sizeof(float4) * n));
+    HC(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
+#undef HC
+    *out = t;
+    return PTX_OK;
+}
+
+void ptx_temporal_destroy(ptx_temporal *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    if (t->used) (void)hipEventSynchronize(t->ev);
+    free_temporal(t);
+}
+
+int ptx_temporal_reset(ptx_temporal *t) {
+    if (!t) return fail(PTX_ERR_INVALID, "null temporal handle");
+    t->cur_valid = t->hist_valid = false;    // (the buffers are only read behind these flags; the next call waits for the last)
+    return PTX_OK;
+}
+
+int ptx_temporal_read(ptx_temporal *t, float *hist_rgb3, float *hist_count1, float *mix_rgb3) {
+    if (!t) return fail(PTX_ERR_INVALID, "null temporal handle");
+    if (!t->done) return fail(PTX_ERR_INVALID, "ptx_temporal_read: no ptx_denoise_temporal with this handle yet");
+    const size_t n = (size_t)t->w * t->h;
+#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+    HC(hipSetDevice(t->device));
+    HC(hipEventSynchronize(t->ev));
+    if (mix_rgb3) HC(hipMemcpy(mix_rgb3, t->d_mix, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+    if (hist_rgb3 || hist_count1) {
+        float4 *hn = new float4[n];
+        const hipError_t e = hipMemcpy(hn, t->d_hn, sizeof(float4) * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            for (size_t i = 0; i < n; i++) {
+                if (hist_rgb3) { hist_rgb3[3 * i] = hn[i].x; hist_rgb3[3 * i + 1] = hn[i].y; hist_rgb3[3 * i + 2] = hn[i].z; }
+                if (hist_count1) hist_count1[i] = hn[i].w;
+            }
+        delete[] hn;
+        HC(e);
+    }
+#undef HC
+    return PTX_OK;
+}
+
+}  // extern "C"
