@@ -341,6 +341,48 @@ int  ptx_temporal_reset(ptx_temporal *h);          /* forget all history */
 int  ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dp, const ptx_temporal_params *tp, int spp);
 int  ptx_temporal_read(ptx_temporal *h, float *hist_rgb3, float *hist_count1, float *mix_rgb3);   /* last call's h, n_h, mix; NULLs allowed; waits */
 
+/* ---- variance guidance of the a-trous filter (the middle of SVGF, Schied et al., HPG 2017), csrc/pt_variance.hip ---------------------
+ * A per-pixel estimate of the variance of the filter's input replaces the fixed phi_color: the colour weight becomes a luminance weight
+ * normalised by the local standard deviation, and the variance is filtered along.  Definition (tests/variance_ref.py
+ * restates it).  l(c) = 0.2126 r + 0.7152 g + 0.0722 b; every variance is one of the luminance of the filter's input in the filter's
+ * colour space (demodulated by max(albedo, 1e-3) when demodulate != 0).
+ *   Stored per pixel: V, an estimate of the PER-SAMPLE luminance variance (the variance of a mean of n samples is V / n), in the fourth
+ *   float of the temporal state's D record; the handle remembers per state whether that float holds a V (ptx_denoise_temporal writes 0
+ *   there and marks the state as carrying none).
+ *   Spatial estimate var_s(p) of a hit pixel: over the (2r+1)^2 window (r = spatial_radius, taps clamped to the frame), weights
+ *   w_q = exp(-|n_p - n_q|^2 / phi_normal) exp(-|x_p - x_q|^2 / phi_position) for hit taps of the same geom and material id, else 0:
+ *   lbar = sum w l_q / sum w, var_s = sum w (l_q - lbar)^2 / sum w.  Miss pixels: 0.
+ *   Without history (no handle, no hist, n_h == 0, or a hist without V): V = n * var_s(l(mix)), n the pixel's sample count.
+ *   With history (taps, weights w, accepted sum S, n_h of ptx_denoise_temporal): V_h = sum w V_q / S, mu_h = l(sum w D_q / S),
+ *   l_c = l(c / a): e = (l_c - mu_h)^2 * n_h * spp / (n_h + spp), V = (n_h * V_h + spp * e) / (n_h + spp).
+ *   The filter's input variance is v0 = V / n.  Pass i, step s = 2^i, hit pixel p, colour c and variance v of the previous pass:
+ *     g_p = 3x3 Gaussian (1/4, 1/2, 1/4 per axis, neighbours at distance 1, clamped to the frame) of v over hit taps, renormalised over
+ *           the taps used (prefilter == 0: g_p = v_p),
+ *     w_q = b[dx] b[dy] exp(-|l(c_p) - l(c_q)| / (phi_luminance * sqrt(g_p) + epsilon)) * (normal term) * (position term of ptx_denoise),
+ *     c_out = sum w c_q / sum w, v_out = sum w^2 v_q / (sum w)^2.  Miss pixels keep c, with v = 0.  phi_color is not used.
+ *   Result: as ptx_denoise, into the tracer's denoised frame. */
+typedef struct ptx_variance_params {
+    float   phi_luminance;     /* > 0, in standard deviations of the filtered luminance; default 4   */
+    float   epsilon;           /* > 0, added to phi_luminance * sigma; default 1e-4                                  */
+    int32_t spatial_radius;    /* 1 .. 3: the spatial estimate's window is (2r+1)^2; default 3                      */
+    int32_t prefilter;         /* != 0: 3x3 Gaussian of the variance before it normalises the weight; default 1     */
+} ptx_variance_params;
+void   ptx_default_variance_params(ptx_variance_params *p);
+size_t ptx_sizeof_variance_params(void);
+/* ptx_denoise (h NULL) or ptx_denoise_temporal (h a handle) with the variance-guided filter; dp / tp / vp NULL = defaults.  Refused
+ * like those, and with a handle when dp->demodulate == 0: the state's moments are in demodulated space.  A handle may be used by
+ * ptx_denoise_temporal and ptx_denoise_variance in any order; after the former the next call here takes the spatial estimate. */
+int  ptx_denoise_variance(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dp, const ptx_temporal_params *tp,
+                          const ptx_variance_params *vp, int spp);
+/* v0 and the last pass's v of the last ptx_denoise_variance, W*H floats each; NULLs allowed; waits */
+int  ptx_read_variance(ptx_tracer *t, float *input_var1, float *output_var1);
+/* The variance-guided filter alone over host buffers (as ptx_denoise_buffers): ids2 = W*H*2 int32 (material, geom), NULL = the spatial
+ * estimate skips its id test; var1 = W*H floats of v0 (negative values read as 0), NULL = the spatial estimate with n = 1; out_var1
+ * (W*H floats, may be NULL) receives the last pass's v. */
+int  ptx_denoise_buffers_variance(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, const float *pos3,
+                                  const uint8_t *hit, const int32_t *ids2, const float *var1, const ptx_denoise_params *dp,
+                                  const ptx_variance_params *vp, float *out_rgb, float *out_var1);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     Options,
     DenoiseParams,
     TemporalParams,
+    VarianceParams,
     Scene,
     Tracer,
     Temporal,
@@ -22,9 +23,12 @@ from .api import (  # noqa: F401
     build_library,
     default_denoise_params,
     default_temporal_params,
+    default_variance_params,
     denoise_buffers,
+    denoise_buffers_variance,
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "Scene", "Tracer", "Temporal", "MultiTracer",
-           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "denoise_buffers", "load_library"]
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "Scene", "Tracer", "Temporal", "MultiTracer",
+           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "denoise_buffers",
+           "denoise_buffers_variance", "load_library"]

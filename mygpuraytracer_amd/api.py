@@ -121,6 +121,41 @@ def default_temporal_params(**kw):
     return p
 
 
+class VarianceParams(C.Structure):
+    """ptx_variance_params: variance guidance of the a-trous filter (include/mi355x_pathtracer.h; defaults from
+    ptx_default_variance_params)."""
+    _fields_ = [("phi_luminance", C.c_float), ("epsilon", C.c_float), ("spatial_radius", C.c_int32), ("prefilter", C.c_int32)]
+
+
+_VARIANCE_INTS = ("spatial_radius", "prefilter")
+_DENOISE_KEYS = ("passes", "demodulate", "phi_color", "phi_normal", "phi_position")
+_TEMPORAL_KEYS = ("max_history", "specular_history", "normal_cos", "plane_tolerance")
+_VARIANCE_KEYS = ("phi_luminance", "epsilon", "spatial_radius", "prefilter")
+
+
+def default_variance_params(**kw):
+    """ptx_default_variance_params with keyword overrides (phi_luminance, epsilon, spatial_radius, prefilter)."""
+    p = VarianceParams()
+    load_library().ptx_default_variance_params(C.byref(p))
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v) if k in _VARIANCE_INTS else float(v))
+    return p
+
+
+def _split_variance_params(fn, params):
+    """keyword arguments of the variance entry points -> (DenoiseParams, TemporalParams, VarianceParams)"""
+    for k in params:
+        if k not in _DENOISE_KEYS + _TEMPORAL_KEYS + _VARIANCE_KEYS:
+            raise TypeError("%s: unknown parameter %r" % (fn, k))
+    pick = lambda keys: {k: v for k, v in params.items() if k in keys}
+    return (default_denoise_params(**pick(_DENOISE_KEYS)), default_temporal_params(**pick(_TEMPORAL_KEYS)),
+            default_variance_params(**pick(_VARIANCE_KEYS)))
+
+
 class Temporal:
     """The history of one W x H view sequence on one device (opaque ptx_temporal), for Tracer.denoise_temporal.  It outlives any
     tracer: hand the same handle to a new Tracer after a camera change and the previous view's samples are reused."""
@@ -178,6 +213,28 @@ def denoise_buffers(rgb, albedo, normal, position, hit, device=0, **params):
     _check(L.ptx_denoise_buffers(int(device), w, h, _ptr(rgb), None if alb is None else _ptr(alb), _ptr(nrm), _ptr(pos), _ptr(hit),
                                  C.byref(p), _ptr(out)), "ptx_denoise_buffers")
     return out
+
+
+def denoise_buffers_variance(rgb, albedo, normal, position, hit, ids=None, variance=None, device=0, **params):
+    """The variance-guided filter alone (ptx_denoise_buffers_variance) on host arrays of one (H, W) frame, as denoise_buffers: ids
+    (H, W, 2) int32 of (material, geom) or None (the spatial estimate then skips its id test), variance (H, W) = v0 or None (the
+    spatial estimate).  Returns the filtered mean radiance (H, W, 3) and the last pass's variance (H, W), float32."""
+    L = load_library()
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise PathTracerError("denoise_buffers_variance: rgb must be (H, W, 3)")
+    h, w = rgb.shape[:2]
+    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
+    alb, nrm, pos = as3(albedo), as3(normal), as3(position)
+    hit = np.ascontiguousarray(np.asarray(hit).reshape(h * w) != 0, np.uint8)
+    ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(h * w, 2)
+    var = None if variance is None else np.ascontiguousarray(variance, np.float32).reshape(h * w)
+    out, vout = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+    dp, _, vpar = _split_variance_params("denoise_buffers_variance", params)
+    opt = lambda a: None if a is None else _ptr(a)
+    _check(L.ptx_denoise_buffers_variance(int(device), w, h, _ptr(rgb), opt(alb), _ptr(nrm), _ptr(pos), _ptr(hit), opt(ids), opt(var),
+                                          C.byref(dp), C.byref(vpar), _ptr(out), _ptr(vout)), "ptx_denoise_buffers_variance")
+    return out, vout
 
 
 def debug_tile_geoms(camera, boxes6, depth_of_field=False, tile=None):
@@ -267,6 +324,10 @@ def load_library():
     if L.ptx_sizeof_denoise_params() != C.sizeof(DenoiseParams):
         raise PathTracerError("%s has a ptx_denoise_params of %d B, this module expects %d B: rebuild the library" % (
             LIB_PATH, L.ptx_sizeof_denoise_params(), C.sizeof(DenoiseParams)))
+    L.ptx_sizeof_variance_params.restype = C.c_size_t
+    if L.ptx_sizeof_variance_params() != C.sizeof(VarianceParams):
+        raise PathTracerError("%s has a ptx_variance_params of %d B, this module expects %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_variance_params(), C.sizeof(VarianceParams)))
     L.ptx_sizeof_temporal_params.restype = C.c_size_t
     if L.ptx_sizeof_temporal_params() != C.sizeof(TemporalParams):
         raise PathTracerError("%s has a ptx_temporal_params of %d B, this module expects %d B: rebuild the library" % (
@@ -330,6 +391,12 @@ def load_library():
     L.ptx_denoise_temporal.restype = i
     L.ptx_denoise_temporal.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), i]
     L.ptx_temporal_read.restype, L.ptx_temporal_read.argtypes = i, [vp, vp, vp, vp]
+    L.ptx_default_variance_params.argtypes = [C.POINTER(VarianceParams)]
+    L.ptx_denoise_variance.restype = i
+    L.ptx_denoise_variance.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams), i]
+    L.ptx_read_variance.restype, L.ptx_read_variance.argtypes = i, [vp, vp, vp]
+    L.ptx_denoise_buffers_variance.restype = i
+    L.ptx_denoise_buffers_variance.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), vp, vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -771,6 +838,21 @@ class Tracer:
                                      plane_tolerance=plane_tolerance)
         _check(self.lib.ptx_denoise_temporal(self.h, temporal.h, C.byref(dp), C.byref(tp), int(spp)), "ptx_denoise_temporal")
         return self.read_denoised() if read else None
+
+    def denoise_variance(self, spp, temporal=None, read=True, **params):
+        """denoise() / denoise_temporal() with the variance-guided filter (ptx_denoise_variance): the luminance weight of every pass is
+        normalised by a per-pixel estimate of the input's variance instead of phi_color.  temporal: a Temporal or None; params: any
+        field of ptx_denoise_params, ptx_temporal_params and ptx_variance_params.  variance() gives the estimate."""
+        dp, tp, vpar = _split_variance_params("denoise_variance", params)
+        _check(self.lib.ptx_denoise_variance(self.h, None if temporal is None else temporal.h, C.byref(dp), C.byref(tp), C.byref(vpar),
+                                             int(spp)), "ptx_denoise_variance")
+        return self.read_denoised() if read else None
+
+    def variance(self):
+        """The last denoise_variance's input variance v0 = V / n and the last pass's variance, (H, W) float32 each."""
+        vin, vout = np.zeros((self.height, self.width), np.float32), np.zeros((self.height, self.width), np.float32)
+        _check(self.lib.ptx_read_variance(self.h, _ptr(vin), _ptr(vout)), "ptx_read_variance")
+        return dict(input=vin, output=vout)
 
     def read_denoised(self):
         out = np.zeros((self.height, self.width, 3), np.float32)

@@ -15,6 +15,8 @@
 //                                                                      camera-change loop: pathtraceFree/Init, --iterations N pathtrace
 //                                                                      calls, GPUdenoise with --denoise; <out>.fNNN.png [.denoised.png])
 //                                  [--temporal]   (with --denoise: GPUdenoise reuses the previous frame's samples, ptx_denoise_temporal)
+//                                  [--variance [--phi-luminance X]]   (with --denoise: the variance-guided filter, ptx_denoise_variance;
+//                                                                      combines with --temporal and --frames)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -41,8 +43,9 @@ static std::string currentTimeString() {          // src/preview.cpp:13-19
 // --frames: the camera-change loop of apps/src/main.cpp:221-271 over an orbit, one tracer per frame, the denoiser's history (with
 // --temporal) kept across them by the veneer
 static int run_frames(Scene *scene, int frames, const std::string &orbit_script, const std::string &frame_step, const std::string &out_prefix,
-                      bool denoise, bool temporal, bool pfm) {
+                      bool denoise, bool temporal, bool variance, bool pfm) {
     denoiseTemporal() = temporal;
+    denoiseVariance() = variance;
     const Camera base = scene->state.camera;
     const int width = base.resolution[0], height = base.resolution[1], n = (int)scene->state.iterations;
     if (n < 1) { fprintf(stderr, "--frames needs --iterations N >= 1\n"); return 1; }
@@ -80,11 +83,11 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]]\n", argv[0]);
         return 1;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
-    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false;
+    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false;
     ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
     int ckpt_every = 0, frames = 0;
@@ -115,9 +118,12 @@ int main(int argc, char **argv) {
         else if (a == "--frames") { need(1); frames = atoi(argv[++i]); }
         else if (a == "--frame-step") { need(1); frame_step = argv[++i]; }
         else if (a == "--temporal") temporal = true;
+        else if (a == "--variance") variance = true;
+        else if (a == "--phi-luminance") { need(1); varianceParams().phi_luminance = (float)atof(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
     }
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
+    if (variance && !denoise) { fprintf(stderr, "--variance needs --denoise\n"); return 1; }
     if (frames < 0 || (frames == 0 && !frame_step.empty())) { fprintf(stderr, "--frame-step needs --frames K, K >= 1\n"); return 1; }
     if (frames > 0 && (per_call || hdr || !ckpt_path.empty() || !resume_path.empty())) {
         fprintf(stderr, "--frames does not combine with --per-call, --hdr, --checkpoint or --resume\n");
@@ -133,7 +139,7 @@ int main(int argc, char **argv) {
     if (resw > 0 && resh > 0) scene->setResolution(resw, resh);
     if (depth > 0) scene->state.traceDepth = depth;
     if (iterations > 0) scene->state.iterations = (unsigned)iterations;
-    if (frames > 0) return run_frames(scene, frames, orbit_script, frame_step, out_prefix, denoise, temporal, pfm);
+    if (frames > 0) return run_frames(scene, frames, orbit_script, frame_step, out_prefix, denoise, temporal, variance, pfm);
     if (orbit_script.empty()) scene->applyRunCudaCamera();
     else if (!scene->runOrbitScript(orbit_script)) { fprintf(stderr, "bad --orbit script: %s\n", orbit_script.c_str()); return 1; }
     const int width = scene->state.camera.resolution[0], height = scene->state.camera.resolution[1];
@@ -190,7 +196,8 @@ int main(int argc, char **argv) {
     if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", ss.str().c_str()); }
     if (denoise && n > 0) {                     // the denoised frame next to it: mean radiance already, so divided by 1
         std::vector<float> den((size_t)width * height * 3);
-        if (ptx_denoise(t, &dparams, n) != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
+        const int rc = variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);
+        if (rc != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         ptimg::to_rgb8_mirrored(width, height, den.data(), 1.0f, rgb8);
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());

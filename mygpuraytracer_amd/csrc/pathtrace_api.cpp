@@ -25,6 +25,8 @@ ptx_denoise_params g_denoise;
 bool g_denoise_init = false;
 ptx_temporal_params g_temporal_params;
 bool g_temporal_params_init = false;
+ptx_variance_params g_variance_params;
+bool g_variance_params_init = false;
 ptx_temporal *g_temporal = nullptr;  // GPUdenoise's history with denoiseTemporal() on: kept across pathtraceFree / pathtraceInit
 int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
 int g_device = 0;                    // the device of g_tracer
@@ -187,6 +189,16 @@ ptx_temporal_params &temporalParams() {
     return g_temporal_params;
 }
 
+bool &denoiseVariance() {
+    static bool on = false;
+    return on;
+}
+
+ptx_variance_params &varianceParams() {
+    if (!g_variance_params_init) { ptx_default_variance_params(&g_variance_params); g_variance_params_init = true; }
+    return g_variance_params;
+}
+
 void GPUdenoiseRelease() {
     ptx_temporal_destroy(g_temporal);
     g_temporal = nullptr;
@@ -286,7 +298,12 @@ void GPUdenoise(bool keep_on_device) {
             check(ptx_temporal_create(g_device, w, h, &g_temporal), "GPUdenoise");
             memcpy(g_temporal_key, key, sizeof key);
         }
-        check(ptx_denoise_temporal(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), g_last_iter), "GPUdenoise");
+        if (denoiseVariance())
+            check(ptx_denoise_variance(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), &varianceParams(), g_last_iter), "GPUdenoise");
+        else
+            check(ptx_denoise_temporal(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), g_last_iter), "GPUdenoise");
+    } else if (denoiseVariance()) {
+        check(ptx_denoise_variance(g_tracer, nullptr, &denoiseParams(), nullptr, &varianceParams(), g_last_iter), "GPUdenoise");
     } else {
         check(ptx_denoise(g_tracer, &denoiseParams(), g_last_iter), "GPUdenoise");
     }

@@ -265,6 +265,11 @@ ptx_denoise_params &denoiseParams();                    // what GPUdenoise filte
 // when the device or the resolution changes; GPUdenoiseRelease() frees it.
 bool &denoiseTemporal();
 ptx_temporal_params &temporalParams();                  // what it reprojects with (ptx_default_temporal_params until changed)
+// Variance guidance (ptx_denoise_variance): off by default.  When on, GPUdenoise filters with the luminance weight normalised by the
+// per-pixel variance estimate instead of phi_color -- with denoiseTemporal() through the same module-level history, without it from
+// the spatial estimate alone.
+bool &denoiseVariance();
+ptx_variance_params &varianceParams();                  // what it filters with (ptx_default_variance_params until changed)
 void GPUdenoiseRelease();
 
 namespace mi355x {

@@ -47,6 +47,7 @@
 #include "pt_bvh.h"
 #include "pt_denoise.h"
 #include "pt_temporal.h"
+#include "pt_variance.h"
 
 using namespace ptd;
 
@@ -2216,6 +2217,8 @@ struct ptx_tracer {
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
     uint8_t *d_spec = nullptr;                           // its device copy, on the first ptx_denoise_temporal
+    float *d_var = nullptr;                              // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
+    bool var_done = false;
     unsigned long long *d_stamps = nullptr;              // diagnostic build only
     float *d_part = nullptr;                             // [kmax][W*H*3] per-iteration radiance (batched mode)
     int32_t *d_cache_totals = nullptr;                   // [2][nbins] of bounce 0 (cache)
@@ -2487,7 +2490,7 @@ int free_tracer(ptx_tracer *t) {
     hipFree(t->d_cache_chunk); hipFree(t->d_cache_super);
     hipFree(t->d_counts); hipFree(t->d_chunk); hipFree(t->d_totals); hipFree(t->d_cache_totals);
     hipFree(t->d_emit_count); hipFree(t->d_emit_pix); hipFree(t->d_emit_rgb); hipFree(t->d_stats); hipFree(t->d_cap); hipFree(t->d_cap_f); hipFree(t->d_part); hipFree(t->d_albedo); hipFree(t->d_stamps); hipFree(t->d_pbo); hipFree(t->d_denoised);
-    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out); hipFree(t->d_spec);
+    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out); hipFree(t->d_spec); hipFree(t->d_var);
     for (hipEvent_t e : t->kev) hipEventDestroy(e);
     if (t->ev_start) hipEventDestroy(t->ev_start);
     if (t->ev_stop) hipEventDestroy(t->ev_stop);
@@ -3669,8 +3672,93 @@ int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_param
     HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, h->d_mix, 1.0f, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n,
                                t->d_dn_out, dp));
     HIPCHECK(hipEventRecord(h->ev, t->stream));
+    h->has_v[h->cur] = false;                            // dd.w = 0: a later ptx_denoise_variance takes its spatial estimate
     h->used = h->done = true;
     t->dn_done = true;
+    return PTX_OK;
+}
+
+// ---- variance guidance (pt_variance.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------
+int ptx_denoise_variance(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams,
+                         const ptx_variance_params *vparams, int spp) {
+    ptx_denoise_params dp;
+    ptx_temporal_params tp;
+    ptx_variance_params vp;
+    if (dparams) dp = *dparams;
+    else ptx_default_denoise_params(&dp);
+    if (tparams) tp = *tparams;
+    else ptx_default_temporal_params(&tp);
+    if (vparams) vp = *vparams;
+    else ptx_default_variance_params(&vp);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
+    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: spp must be >= 1 (the iterations summed in the accumulation buffer)");
+    if (h && !dp.demodulate)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: with a temporal handle ptx_denoise_params.demodulate must be != 0 "
+                                          "(the state's moments are in demodulated space)");
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: null tracer");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (h && h->device != t->device)
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: the temporal handle was created on device " + std::to_string(h->device) +
+                                              ", the tracer runs on device " + std::to_string(t->device));
+    if (h && (h->w != t->cam.resx || h->h != t->cam.resy))
+        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
+                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
+    HIPCHECK(hipSetDevice(t->device));
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
+    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
+    if (!t->d_var) HIPCHECK(hipMalloc(&t->d_var, sizeof(float) * 2 * n));
+    if (h && !t->d_spec) {
+        HIPCHECK(hipMalloc(&t->d_spec, t->h_spec.size()));
+        HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
+    }
+    const int rc = ensure_gbuffer(t);
+    if (rc != PTX_OK) return rc;
+    const float4 *g = t->d_gbuf;
+    const int2 *gids = reinterpret_cast<const int2 *>(g + 3 * n);
+    if (h) {
+        if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));
+        ptx_camera cam;
+        memcpy(&cam, &t->cam, sizeof cam);
+        if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {     // a new segment: cur becomes hist (as ptx_denoise_temporal)
+            if (h->cur_valid) { h->cur ^= 1; h->hist_valid = true; }
+            h->cam[h->cur] = cam;
+            h->cur_valid = true;
+        }
+        const int hi = h->cur ^ 1;
+        const PtTemporalCam pc = pt_temporal_camera(h->cam[hi], h->hist_valid);
+        const PtTemporalState &cur = h->st[h->cur];
+        HIPCHECK(pt_temporal_enqueue(t->stream, W, H, pc, tp, t->d_image, (float)spp, g, g + n, g + 2 * n, gids, t->d_spec,
+                                     (int)t->h_spec.size(), cur, h->st[hi], h->d_mix, h->d_hn, 1, h->hist_valid && h->has_v[hi] ? 1 : 0));
+        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, cur.nh, cur.xn, cur.ids, 1, cur.dd));
+        HIPCHECK(pt_variance_prep_state_enqueue(t->stream, (int)n, cur, t->d_dn_tmp));
+        h->has_v[h->cur] = true;
+    } else {
+        HIPCHECK(pt_variance_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, nullptr, t->d_dn_tmp));
+        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, gids, 0, t->d_dn_tmp));
+    }
+    HIPCHECK(pt_atrous_var_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, t->d_var, t->d_var + n,
+                                   dp, vp));
+    if (h) {
+        HIPCHECK(hipEventRecord(h->ev, t->stream));
+        h->used = h->done = true;
+    }
+    t->dn_done = t->var_done = true;
+    return PTX_OK;
+}
+
+int ptx_read_variance(ptx_tracer *t, float *input_var1, float *output_var1) {
+    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t->var_done) return set_error(PTX_ERR_INVALID, "ptx_read_variance: no ptx_denoise_variance on this tracer yet");
+    HIPCHECK(hipSetDevice(t->device));
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (input_var1) HIPCHECK(hipMemcpyAsync(input_var1, t->d_var, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
+    if (output_var1) HIPCHECK(hipMemcpyAsync(output_var1, t->d_var + n, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
     return PTX_OK;
 }
 

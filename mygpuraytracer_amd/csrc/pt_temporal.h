@@ -5,7 +5,8 @@
 // pixelIndex = x + y*W:
 //   nh[i]  = float4(normal xyz, hit ? 1 : 0)          (copied from the tracer's G-buffer)
 //   xn[i]  = float4(world position xyz, sample count n)
-//   dd[i]  = float4(D rgb, 0)                          (D = mix / max(albedo, 1e-3) on hit pixels, mix on miss pixels)
+//   dd[i]  = float4(D rgb, V)                          (D = mix / max(albedo, 1e-3) on hit pixels, mix on miss pixels; V = the per-sample
+//                                                        luminance variance when ptx_denoise_variance wrote the state, else 0)
 //   ids[i] = int2(material id, geom id)
 // 56 B per pixel: a bilinear tap reads one whole record.
 #pragma once
@@ -33,6 +34,7 @@ struct ptx_temporal {
     int cur = 0;                          // st[cur] is cur, st[cur ^ 1] is hist
     ptx_camera cam[2];                    // the camera of each state
     bool cur_valid = false, hist_valid = false;
+    bool has_v[2] = {false, false};       // st[i].dd.w holds a V (written by ptx_denoise_variance, not by ptx_denoise_temporal)
     float *d_mix = nullptr;               // W*H*3: the last call's mix (the filter's input)
     float4 *d_hn = nullptr;               // W*H: the last call's (h rgb, n_h)
     hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
@@ -47,7 +49,12 @@ PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist);
 
 // Enqueues the reprojection + mix on `st`: reads the tracer's G-buffer (gnh, gxt, galb, gids; pt_denoise.h layout) and accumulation
 // rgb / spp, writes st_cur, mix (W*H*3) and hn (W*H).  spec: one byte per material (!= 0: reflective or refractive).
+// variance != 0: cur.dd.w = V where hist supplies one (hist_has_v != 0 and n_h > 0), -1 on the other hit pixels (pt_variance.h:
+// pt_variance_spatial_enqueue fills those in); variance == 0: dd.w = 0.
 hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
                                float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
                                const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
-                               float4 *hn);
+                               float4 *hn, int variance = 0, int hist_has_v = 0);
+
+// Rec. 709 luminance, the one every variance of the denoiser is a variance of
+__host__ __device__ inline float pt_luminance(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }

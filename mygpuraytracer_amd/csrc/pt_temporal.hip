@@ -6,6 +6,8 @@
 // 64-pixel row segment, so its bilinear taps into hist are two contiguous runs of records).  fp32, plain vector loads and stores.
 // Per pixel: reproject into hist's camera, accept / reject up to four taps, mix with rgb / spp, write the new cur record, the mix and
 // (h, n_h).  It copies what the next segment needs out of the G-buffer, which ensure_gbuffer rewrites in place on the next view.
+// k_reproject_variance (ptx_denoise_variance) is the same pixel function, reproject_pixel<true>: the same arithmetic plus the per-sample luminance variance V in dd.w: inherited
+// and updated where the history carries one, -1 (= "pt_variance.hip's spatial estimate fills this in") on the other hit pixels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -21,8 +23,10 @@ namespace {
 
 constexpr int BX = 64, BY = 4;
 
-__global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
+template <bool VAR>
+__device__ __forceinline__ void reproject_pixel(
         int w, int h, const PtTemporalCam cam, float max_history, int specular_history, float normal_cos, float plane_tolerance,
+        int hist_has_v,
         const float *__restrict__ rgb, float spp, const float4 *__restrict__ gnh, const float4 *__restrict__ gxt,
         const float4 *__restrict__ galb, const int2 *__restrict__ gids, const uint8_t *__restrict__ spec, int nmats,
         float4 *__restrict__ cnh, float4 *__restrict__ cxn, float4 *__restrict__ cdd, int2 *__restrict__ cids,
@@ -37,6 +41,7 @@ __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
     const float c0 = rgb[3 * (size_t)p] / spp, c1 = rgb[3 * (size_t)p + 1] / spp, c2 = rgb[3 * (size_t)p + 2] / spp;   // = k_atrous_prep
     float4 a = make_float4(1.f, 1.f, 1.f, 0.f);
     float h0 = 0.f, h1 = 0.f, h2 = 0.f, nhist = 0.f;
+    float var = hit ? -1.f : 0.f;                        // VAR only: V, or -1 where the spatial estimate has to supply it
     if (hit) {
         const float4 al = galb[p];
         a = make_float4(fmaxf(al.x, 1e-3f), fmaxf(al.y, 1e-3f), fmaxf(al.z, 1e-3f), 0.f);
@@ -53,7 +58,7 @@ __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
                 const int u0 = (int)uf, v0 = (int)vf;
                 const float fu = u - uf, fv = v - vf;
                 const float lim = plane_tolerance * sqrtf(dx * dx + dy * dy + dz * dz);
-                float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f;
+                float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f, sv = 0.f;
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
 #pragma unroll
@@ -72,12 +77,19 @@ __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
                         if (!(fabsf(pl) <= lim)) continue;
                         const float4 dq = hdd[q];
                         sr += wt * dq.x; sg += wt * dq.y; sb += wt * dq.z; sn += wt * xq.w; sw += wt;
+                        if (VAR) sv += wt * dq.w;
                     }
                 }
                 if (sw > 0.f) {
                     nhist = fminf(sn / sw, max_history);
                     if (nhist > 0.f) { h0 = sr / sw * a.x; h1 = sg / sw * a.y; h2 = sb / sw * a.z; }
                     else nhist = 0.f;
+                    if (VAR && hist_has_v && nhist > 0.f) {
+                        // the pairwise update of a per-sample variance: between-batch term e, then the mean by sample counts
+                        const float mu = pt_luminance(sr / sw, sg / sw, sb / sw), lc = pt_luminance(c0 / a.x, c1 / a.y, c2 / a.z);
+                        const float d = lc - mu, tot = nhist + spp, e = d * d * nhist * spp / tot;
+                        var = (nhist * (sv / sw) + spp * e) / tot;
+                    }
                 }
             }
         }
@@ -90,11 +102,26 @@ __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(
     }
     cnh[p] = np;
     cxn[p] = make_float4(xp.x, xp.y, xp.z, n);
-    cdd[p] = hit ? make_float4(m0 / a.x, m1 / a.y, m2 / a.z, 0.f) : make_float4(m0, m1, m2, 0.f);
+    cdd[p] = hit ? make_float4(m0 / a.x, m1 / a.y, m2 / a.z, VAR ? var : 0.f) : make_float4(m0, m1, m2, 0.f);
     cids[p] = id;
     mix[3 * (size_t)p] = m0; mix[3 * (size_t)p + 1] = m1; mix[3 * (size_t)p + 2] = m2;
     hn[p] = make_float4(h0, h1, h2, nhist);
 }
+
+#define REPROJECT_PARAMS \
+        int w, int h, const PtTemporalCam cam, float max_history, int specular_history, float normal_cos, float plane_tolerance, \
+        int hist_has_v, const float *__restrict__ rgb, float spp, const float4 *__restrict__ gnh, const float4 *__restrict__ gxt, \
+        const float4 *__restrict__ galb, const int2 *__restrict__ gids, const uint8_t *__restrict__ spec, int nmats, \
+        float4 *__restrict__ cnh, float4 *__restrict__ cxn, float4 *__restrict__ cdd, int2 *__restrict__ cids, \
+        const float4 *__restrict__ hnh, const float4 *__restrict__ hxn, const float4 *__restrict__ hdd, const int2 *__restrict__ hids, \
+        float *__restrict__ mix, float4 *__restrict__ hn
+#define REPROJECT_ARGS \
+        w, h, cam, max_history, specular_history, normal_cos, plane_tolerance, hist_has_v, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cnh, \
+        cxn, cdd, cids, hnh, hxn, hdd, hids, mix, hn
+
+__global__ __launch_bounds__(BX * BY) void k_temporal_reproject(REPROJECT_PARAMS) { reproject_pixel<false>(REPROJECT_ARGS); }
+// ptx_denoise_variance's: the same pixel function with V
+__global__ __launch_bounds__(BX * BY) void k_reproject_variance(REPROJECT_PARAMS) { reproject_pixel<true>(REPROJECT_ARGS); }
 
 int fail(int code, const std::string &msg) { ptx_internal_set_error(msg.c_str()); return code; }
 
@@ -143,11 +170,12 @@ PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist) {
 hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
                                float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
                                const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
-                               float4 *hn) {
+                               float4 *hn, int variance, int hist_has_v) {
     const dim3 grid((unsigned)((w + BX - 1) / BX), (unsigned)((h + BY - 1) / BY)), block(BX, BY);
-    hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
-                       p.normal_cos, p.plane_tolerance, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cur.nh, cur.xn, cur.dd, cur.ids,
-                       (const float4 *)hist.nh, (const float4 *)hist.xn, (const float4 *)hist.dd, (const int2 *)hist.ids, mix, hn);
+    const auto kernel = variance ? k_reproject_variance : k_temporal_reproject;
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
+                       p.normal_cos, p.plane_tolerance, hist_has_v, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cur.nh, cur.xn, cur.dd,
+                       cur.ids, (const float4 *)hist.nh, (const float4 *)hist.xn, (const float4 *)hist.dd, (const int2 *)hist.ids, mix, hn);
     return hipGetLastError();
 }
 
