@@ -341,7 +341,7 @@ int  ptx_temporal_reset(ptx_temporal *h);          /* forget all history */
 int  ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dp, const ptx_temporal_params *tp, int spp);
 int  ptx_temporal_read(ptx_temporal *h, float *hist_rgb3, float *hist_count1, float *mix_rgb3);   /* last call's h, n_h, mix; NULLs allowed; waits */
 
-/* ---- variance guidance of the a-trous filter (the middle of SVGF, Schied et al., HPG 2017), csrc/pt_variance.hip ---------------------
+/* ---- variance guidance of the a-trous filter (the middle of SVGF, Schied et al., HPG 2017), csrc/pt_denoise.hip ----------------------
  * A per-pixel estimate of the variance of the filter's input replaces the fixed phi_color: the colour weight becomes a luminance weight
  * normalised by the local standard deviation, and the variance is filtered along.  Definition (tests/variance_ref.py
  * restates it).  l(c) = 0.2126 r + 0.7152 g + 0.0722 b; every variance is one of the luminance of the filter's input in the filter's

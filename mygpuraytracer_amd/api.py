@@ -86,17 +86,22 @@ class DenoiseParams(C.Structure):
                 ("phi_position", C.c_float)]
 
 
-def default_denoise_params(**kw):
-    """ptx_default_denoise_params with keyword overrides (passes, demodulate, phi_color, phi_normal, phi_position)."""
-    p = DenoiseParams()
-    load_library().ptx_default_denoise_params(C.byref(p))
+def _default_params(struct, c_function, int_fields, **kw):
+    """a parameter struct filled by the library's ptx_default_* function, then the keyword overrides that are not None"""
+    p = struct()
+    getattr(load_library(), c_function)(C.byref(p))
     for k, v in kw.items():
         if v is None:
             continue
         if not hasattr(p, k):
             raise AttributeError(k)
-        setattr(p, k, int(v) if k in ("passes", "demodulate") else float(v))
+        setattr(p, k, int(v) if k in int_fields else float(v))
     return p
+
+
+def default_denoise_params(**kw):
+    """ptx_default_denoise_params with keyword overrides (passes, demodulate, phi_color, phi_normal, phi_position)."""
+    return _default_params(DenoiseParams, "ptx_default_denoise_params", ("passes", "demodulate"), **kw)
 
 
 class TemporalParams(C.Structure):
@@ -105,20 +110,9 @@ class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_int32), ("specular_history", C.c_int32), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float)]
 
 
-_TEMPORAL_INTS = ("max_history", "specular_history")
-
-
 def default_temporal_params(**kw):
     """ptx_default_temporal_params with keyword overrides (max_history, specular_history, normal_cos, plane_tolerance)."""
-    p = TemporalParams()
-    load_library().ptx_default_temporal_params(C.byref(p))
-    for k, v in kw.items():
-        if v is None:
-            continue
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, int(v) if k in _TEMPORAL_INTS else float(v))
-    return p
+    return _default_params(TemporalParams, "ptx_default_temporal_params", ("max_history", "specular_history"), **kw)
 
 
 class VarianceParams(C.Structure):
@@ -127,7 +121,6 @@ class VarianceParams(C.Structure):
     _fields_ = [("phi_luminance", C.c_float), ("epsilon", C.c_float), ("spatial_radius", C.c_int32), ("prefilter", C.c_int32)]
 
 
-_VARIANCE_INTS = ("spatial_radius", "prefilter")
 _DENOISE_KEYS = ("passes", "demodulate", "phi_color", "phi_normal", "phi_position")
 _TEMPORAL_KEYS = ("max_history", "specular_history", "normal_cos", "plane_tolerance")
 _VARIANCE_KEYS = ("phi_luminance", "epsilon", "spatial_radius", "prefilter")
@@ -135,15 +128,7 @@ _VARIANCE_KEYS = ("phi_luminance", "epsilon", "spatial_radius", "prefilter")
 
 def default_variance_params(**kw):
     """ptx_default_variance_params with keyword overrides (phi_luminance, epsilon, spatial_radius, prefilter)."""
-    p = VarianceParams()
-    load_library().ptx_default_variance_params(C.byref(p))
-    for k, v in kw.items():
-        if v is None:
-            continue
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, int(v) if k in _VARIANCE_INTS else float(v))
-    return p
+    return _default_params(VarianceParams, "ptx_default_variance_params", ("spatial_radius", "prefilter"), **kw)
 
 
 def _split_variance_params(fn, params):
@@ -196,22 +181,31 @@ class Temporal:
         return dict(history=hist, count=count, mix=mix)
 
 
+def _frame_arrays(fn, rgb, albedo, normal, position, hit):
+    """one (H, W) frame as the ptx_denoise_buffers* entry points take it: h, w, rgb (H, W, 3) float32, albedo (or None) / normal /
+    position (H*W, 3) float32, hit (H*W) uint8"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise PathTracerError("%s: rgb must be (H, W, 3)" % fn)
+    h, w = rgb.shape[:2]
+    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
+    return h, w, rgb, as3(albedo), as3(normal), as3(position), np.ascontiguousarray(np.asarray(hit).reshape(h * w) != 0, np.uint8)
+
+
+def _opt_ptr(a):
+    return None if a is None else _ptr(a)
+
+
 def denoise_buffers(rgb, albedo, normal, position, hit, device=0, **params):
     """The a-trous filter alone (ptx_denoise_buffers) on host arrays of one (H, W) frame: rgb = mean radiance, albedo / normal / position
     (..., 3), hit (...) bool.  Returns the filtered mean radiance as (H, W, 3) float32 when rgb is (H, W, 3), else rgb's shape.  Needs a
     HIP device: there is no CPU path."""
     L = load_library()
-    rgb = np.ascontiguousarray(rgb, np.float32)
-    if rgb.ndim != 3 or rgb.shape[2] != 3:
-        raise PathTracerError("denoise_buffers: rgb must be (H, W, 3)")
-    h, w = rgb.shape[:2]
-    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
-    alb, nrm, pos = as3(albedo), as3(normal), as3(position)
-    hit = np.ascontiguousarray(np.asarray(hit).reshape(h * w) != 0, np.uint8)
+    h, w, rgb, alb, nrm, pos, hit = _frame_arrays("denoise_buffers", rgb, albedo, normal, position, hit)
     out = np.zeros((h, w, 3), np.float32)
     p = default_denoise_params(**params)
-    _check(L.ptx_denoise_buffers(int(device), w, h, _ptr(rgb), None if alb is None else _ptr(alb), _ptr(nrm), _ptr(pos), _ptr(hit),
-                                 C.byref(p), _ptr(out)), "ptx_denoise_buffers")
+    _check(L.ptx_denoise_buffers(int(device), w, h, _ptr(rgb), _opt_ptr(alb), _ptr(nrm), _ptr(pos), _ptr(hit), C.byref(p), _ptr(out)),
+           "ptx_denoise_buffers")
     return out
 
 
@@ -220,20 +214,13 @@ def denoise_buffers_variance(rgb, albedo, normal, position, hit, ids=None, varia
     (H, W, 2) int32 of (material, geom) or None (the spatial estimate then skips its id test), variance (H, W) = v0 or None (the
     spatial estimate).  Returns the filtered mean radiance (H, W, 3) and the last pass's variance (H, W), float32."""
     L = load_library()
-    rgb = np.ascontiguousarray(rgb, np.float32)
-    if rgb.ndim != 3 or rgb.shape[2] != 3:
-        raise PathTracerError("denoise_buffers_variance: rgb must be (H, W, 3)")
-    h, w = rgb.shape[:2]
-    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
-    alb, nrm, pos = as3(albedo), as3(normal), as3(position)
-    hit = np.ascontiguousarray(np.asarray(hit).reshape(h * w) != 0, np.uint8)
+    h, w, rgb, alb, nrm, pos, hit = _frame_arrays("denoise_buffers_variance", rgb, albedo, normal, position, hit)
     ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(h * w, 2)
     var = None if variance is None else np.ascontiguousarray(variance, np.float32).reshape(h * w)
     out, vout = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
     dp, _, vpar = _split_variance_params("denoise_buffers_variance", params)
-    opt = lambda a: None if a is None else _ptr(a)
-    _check(L.ptx_denoise_buffers_variance(int(device), w, h, _ptr(rgb), opt(alb), _ptr(nrm), _ptr(pos), _ptr(hit), opt(ids), opt(var),
-                                          C.byref(dp), C.byref(vpar), _ptr(out), _ptr(vout)), "ptx_denoise_buffers_variance")
+    _check(L.ptx_denoise_buffers_variance(int(device), w, h, _ptr(rgb), _opt_ptr(alb), _ptr(nrm), _ptr(pos), _ptr(hit), _opt_ptr(ids),
+                                          _opt_ptr(var), C.byref(dp), C.byref(vpar), _ptr(out), _ptr(vout)), "ptx_denoise_buffers_variance")
     return out, vout
 
 

@@ -1,21 +1,97 @@
-// pt_denoise.h -- internal interface between the tracer (pt_engine.hip: G-buffer pass, tracer-level entry points) and the
-// edge-avoiding a-trous filter (pt_denoise.hip).  Not part of the C ABI; include/mi355x_pathtracer.h has the public side.
+// pt_denoise.h -- internal interface between the tracer (pt_engine.hip: G-buffer pass, ptx_denoise / ptx_denoise_temporal /
+// ptx_denoise_variance), the a-trous filter with its variance guidance (pt_denoise.hip) and the temporal reprojection (pt_temporal.hip).
+// Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
 //
 // Device layout of the guide images, one record per pixel, pixelIndex = x + y*W (the frame's own order):
 //   nh[i]  = float4(shading normal xyz, hit ? 1 : 0)
 //   xt[i]  = float4(world position xyz, t)              (t is not read by the filter; ptx_read_gbuffer hands it out)
 //   alb[i] = float4(albedo rgb, 0)
-// Misses are all zeros.  The filter's colour ping-pong buffers are float4(rgb, 0) per pixel.
+// Misses are all zeros.  The filter's colour ping-pong buffers are float4(rgb, v) per pixel: v is 0 in the plain filter and the variance
+// of the pixel's luminance (v0 = V / n going in) in the variance-guided one.  Before that one runs, -1 in that float (a hit pixel's)
+// means "no estimate yet": pt_variance_spatial_enqueue replaces it.
+//
+// A temporal state (the handle keeps two, `cur` and `hist`, and swaps their pointers on a camera change), one record per pixel:
+//   nh[i]  = float4(normal xyz, hit ? 1 : 0)          (copied from the tracer's G-buffer)
+//   xn[i]  = float4(world position xyz, sample count n)
+//   dd[i]  = float4(D rgb, V)                          (D = mix / max(albedo, 1e-3) on hit pixels, mix on miss pixels; V = the per-sample
+//                                                        luminance variance when ptx_denoise_variance wrote the state, else 0)
+//   ids[i] = int2(material id, geom id)
+// 56 B per pixel: a bilinear tap reads one whole record.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string>
 
 #include "../../include/mi355x_pathtracer.h"
 
+struct PtTemporalState {
+    float4 *nh = nullptr, *xn = nullptr, *dd = nullptr;
+    int2 *ids = nullptr;
+};
+
+// hist's camera as the kernel takes it: the inverse of M = [A | -R | -U] (row major), A = view + R*W/2 + U*H/2, R = right*pl.x,
+// U = up*pl.y, so that (s, s*u, s*v) = minv * (x - position).  valid == 0: no history (first call, after a reset, singular camera).
+struct PtTemporalCam {
+    float pos[3];
+    float minv[9];
+    int32_t valid;
+};
+
+struct ptx_temporal {
+    int device = 0, w = 0, h = 0;
+    PtTemporalState st[2];
+    int cur = 0;                          // st[cur] is cur, st[cur ^ 1] is hist
+    ptx_camera cam[2];                    // the camera of each state
+    bool cur_valid = false, hist_valid = false;
+    bool has_v[2] = {false, false};       // st[i].dd.w holds a V (written by ptx_denoise_variance, not by ptx_denoise_temporal)
+    float *d_mix = nullptr;               // W*H*3: the last call's mix (the filter's input)
+    float4 *d_hn = nullptr;               // W*H: the last call's (h rgb, n_h)
+    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
+    bool used = false, done = false;      // ev was recorded / d_mix, d_hn hold a result
+};
+
+// Rec. 709 luminance, the one every variance of the denoiser is a variance of
+__host__ __device__ inline float pt_luminance(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
+// What pt_denoise.hip and pt_temporal.hip share: the pixel kernels' workgroup of 64 x 4 pixels (a wave is one 64-pixel row segment)
+// and its grid, the ptx_last_error of a failed call, and the checked HIP call of their entry points.
+constexpr int PT_BX = 64, PT_BY = 4;
+inline dim3 pt_pixel_grid(int w, int h) { return dim3((unsigned)((w + PT_BX - 1) / PT_BX), (unsigned)((h + PT_BY - 1) / PT_BY)); }
+extern "C" void ptx_internal_set_error(const char *msg);
+inline int pt_fail(int code, const std::string &msg) { ptx_internal_set_error(msg.c_str()); return code; }
+#define PT_HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return pt_fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
 // NULL when the parameters are usable, else what is wrong with them (the ptx_last_error message)
 const char *pt_denoise_params_problem(const ptx_denoise_params &p);
+const char *pt_temporal_params_problem(const ptx_temporal_params &p);
+const char *pt_variance_params_problem(const ptx_variance_params &p);
 
-// Enqueues the whole filter on `st`: colour = rgb / spp (rgb: W*H*3 floats, e.g. the accumulation buffer), optional demodulation by
-// max(albedo, 1e-3), p.passes a-trous passes ping-ponging between tmp0 and tmp1 (W*H float4 each), result W*H*3 floats of mean
-// radiance in out_rgb.  Launch errors come back as the hipError_t of the first launch that failed.
-hipError_t pt_atrous_enqueue(hipStream_t st, int w, int h, const float *rgb, float spp, const float4 *nh, const float4 *xt,
-                             const float4 *alb, float4 *tmp0, float4 *tmp1, float *out_rgb, const ptx_denoise_params &p);
+// c = float4(rgb / spp (/ max(albedo, 1e-3) on hit pixels when demodulating), v), rgb: W*H*3 floats, e.g. the accumulation buffer.
+// variance == 0: v = 0.  Else v = max(var1, 0) on hit pixels when var1 is given, -1 on hit pixels when it is NULL; 0 on miss pixels.
+hipError_t pt_atrous_prep_enqueue(hipStream_t st, int n, const float *rgb, float spp, const float4 *nh, const float4 *alb, int demod,
+                                  int variance, const float *var1, float4 *c);
+// The same from a temporal state whose dd.w holds V everywhere: c = float4(D, hit ? V / n : 0).
+hipError_t pt_variance_prep_state_enqueue(hipStream_t st, int n, const PtTemporalState &s, float4 *c);
+// The spatial estimate for every hit pixel whose cv[p].w is negative: cv[p].w = count * var_s(l(cv.rgb)), count = xn[p].w when
+// count_from_xn, else 1.  nh / xn: normal + hit flag and position (+ count) per pixel; ids may be NULL (no id test).
+hipError_t pt_variance_spatial_enqueue(hipStream_t st, int w, int h, const ptx_denoise_params &dp, const ptx_variance_params &vp,
+                                       const float4 *nh, const float4 *xn, const int2 *ids, int count_from_xn, float4 *cv);
+// dp.passes a-trous passes from tmp0 (filled by one of the preps), ping-ponging with tmp1 (W*H float4 each); result W*H*3 floats of mean
+// radiance in out_rgb, multiplied back by max(albedo, 1e-3) when demodulating.  vp == NULL: the plain filter (colour weight
+// |dc|^2 / phi_color).  Else the variance-guided one: var_in (may be NULL) receives v0, var_out (may be NULL) the last pass's v, W*H
+// floats each.  Launch errors come back as the hipError_t of the first launch that failed.
+hipError_t pt_atrous_enqueue(hipStream_t st, int w, int h, const float4 *nh, const float4 *xt, const float4 *alb, float4 *tmp0,
+                             float4 *tmp1, float *out_rgb, const ptx_denoise_params &dp, const ptx_variance_params *vp = nullptr,
+                             float *var_in = nullptr, float *var_out = nullptr);
+
+// hist's camera -> PtTemporalCam (in double, then rounded); valid = 0 when the system is singular or not finite
+PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist);
+
+// Enqueues the reprojection + mix on `st`: reads the tracer's G-buffer (gnh, gxt, galb, gids) and accumulation rgb / spp, writes
+// st_cur, mix (W*H*3) and hn (W*H).  spec: one byte per material (!= 0: reflective or refractive).
+// variance != 0: cur.dd.w = V where hist supplies one (hist_has_v != 0 and n_h > 0), -1 on the other hit pixels
+// (pt_variance_spatial_enqueue fills those in); variance == 0: dd.w = 0.
+hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
+                               float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
+                               const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
+                               float4 *hn, int variance = 0, int hist_has_v = 0);

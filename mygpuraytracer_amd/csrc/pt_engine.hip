@@ -46,8 +46,6 @@
 #include "pt_device.h"
 #include "pt_bvh.h"
 #include "pt_denoise.h"
-#include "pt_temporal.h"
-#include "pt_variance.h"
 
 using namespace ptd;
 
@@ -3588,7 +3586,7 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
     return rc;
 }
 
-// ---- denoiser (pt_denoise.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------------
+// ---- denoiser (pt_denoise.hip, pt_temporal.hip; definition in include/mi355x_pathtracer.h) --------------------------------------
 // The G-buffer of the current camera on the tracer's stream, buffers allocated on first use
 static int ensure_gbuffer(ptx_tracer *t) {
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
@@ -3602,151 +3600,137 @@ static int ensure_gbuffer(ptx_tracer *t) {
     return PTX_OK;
 }
 
-int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *params, int spp) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    ptx_denoise_params p;
-    if (params) p = *params;
-    else ptx_default_denoise_params(&p);
-    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise: spp must be >= 1 (the iterations summed in the accumulation buffer)");
-    if (const char *why = pt_denoise_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    HIPCHECK(hipSetDevice(t->device));
-    const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
-    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
-    const int rc = ensure_gbuffer(t);
-    if (rc != PTX_OK) return rc;
-    HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, t->d_image, (float)spp, t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n,
-                               t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, p));
-    t->dn_done = true;
-    return PTX_OK;
-}
-
-// ---- temporal reuse (pt_temporal.hip; definition in include/mi355x_pathtracer.h) ----------------------------------------------------
 static_assert(sizeof(DCamera) == sizeof(ptx_camera), "camera layout");
 
-int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams, int spp) {
-    ptx_denoise_params dp;
-    ptx_temporal_params tp;
-    if (dparams) dp = *dparams;
-    else ptx_default_denoise_params(&dp);
-    if (tparams) tp = *tparams;
-    else ptx_default_temporal_params(&tp);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: spp must be >= 1 (the iterations summed in the accumulation buffer)");
-    if (!t || !h) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: null tracer or temporal handle");
+// What the three ptx_denoise* entry points share; `fn` is the entry point's name, for its messages.
+extern "C++" template <class P> static P params_or_default(const P *given, void (*defaults)(P *)) {
+    P p;
+    if (given) p = *given;
+    else defaults(&p);
+    return p;
+}
+
+static int bad_spp(const std::string &fn) {
+    return set_error(PTX_ERR_INVALID, fn + ": spp must be >= 1 (the iterations summed in the accumulation buffer)");
+}
+
+// The checks on the tracer (not NULL) and on the handle (may be NULL), then the buffers the filter needs, allocated on first use, and
+// the G-buffer of the current camera.  variance: ptx_denoise_variance's d_var too.
+static int denoise_begin(const std::string &fn, ptx_tracer *t, const ptx_temporal *h, bool variance) {
     if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (h->device != t->device)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: the temporal handle was created on device " + std::to_string(h->device) +
+        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (h && h->device != t->device)
+        return set_error(PTX_ERR_INVALID, fn + ": the temporal handle was created on device " + std::to_string(h->device) +
                                               ", the tracer runs on device " + std::to_string(t->device));
-    if (h->w != t->cam.resx || h->h != t->cam.resy)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
+    if (h && (h->w != t->cam.resx || h->h != t->cam.resy))
+        return set_error(PTX_ERR_INVALID, fn + ": the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
                                               " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
     HIPCHECK(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
     if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
-    if (!t->d_spec) {
+    if (variance && !t->d_var) HIPCHECK(hipMalloc(&t->d_var, sizeof(float) * 2 * n));
+    if (h && !t->d_spec) {
         HIPCHECK(hipMalloc(&t->d_spec, t->h_spec.size()));
         HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
     }
-    const int rc = ensure_gbuffer(t);
-    if (rc != PTX_OK) return rc;
+    return ensure_gbuffer(t);
+}
+
+// The handle's step on the tracer's stream: wait for the handle's last work, start a new segment when the camera changed (cur becomes
+// hist), then reproject hist into the current view and mix (with V when variance).
+static int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_params &tp, int spp, bool variance) {
     if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));     // the handle's last work, maybe on another tracer's stream
     ptx_camera cam;
     memcpy(&cam, &t->cam, sizeof cam);
-    if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {     // a new segment: cur becomes hist
+    if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {
         if (h->cur_valid) { h->cur ^= 1; h->hist_valid = true; }
         h->cam[h->cur] = cam;
         h->cur_valid = true;
     }
     const int hi = h->cur ^ 1;
-    const PtTemporalCam pc = pt_temporal_camera(h->cam[hi], h->hist_valid);
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
     const float4 *g = t->d_gbuf;
-    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, pc, tp, t->d_image, (float)spp, g, g + n, g + 2 * n,
-                                 reinterpret_cast<const int2 *>(g + 3 * n), t->d_spec, (int)t->h_spec.size(), h->st[h->cur], h->st[hi],
-                                 h->d_mix, h->d_hn));
-    HIPCHECK(pt_atrous_enqueue(t->stream, t->cam.resx, t->cam.resy, h->d_mix, 1.0f, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n,
-                               t->d_dn_out, dp));
+    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, pt_temporal_camera(h->cam[hi], h->hist_valid), tp, t->d_image,
+                                 (float)spp, g, g + n, g + 2 * n, reinterpret_cast<const int2 *>(g + 3 * n), t->d_spec,
+                                 (int)t->h_spec.size(), h->st[h->cur], h->st[hi], h->d_mix, h->d_hn, variance ? 1 : 0,
+                                 variance && h->hist_valid && h->has_v[hi] ? 1 : 0));
+    return PTX_OK;
+}
+
+// The handle's end of a call: its event after the call's work
+static int temporal_done(ptx_tracer *t, ptx_temporal *h) {
     HIPCHECK(hipEventRecord(h->ev, t->stream));
-    h->has_v[h->cur] = false;                            // dd.w = 0: a later ptx_denoise_variance takes its spatial estimate
     h->used = h->done = true;
+    return PTX_OK;
+}
+
+int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *params, int spp) {
+    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    const ptx_denoise_params p = params_or_default(params, ptx_default_denoise_params);
+    if (spp < 1) return bad_spp("ptx_denoise");
+    if (const char *why = pt_denoise_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
+    if (const int rc = denoise_begin("ptx_denoise", t, nullptr, false)) return rc;
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    const float4 *g = t->d_gbuf;
+    HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, p.demodulate ? 1 : 0, 0, nullptr, t->d_dn_tmp));
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, p));
     t->dn_done = true;
     return PTX_OK;
 }
 
-// ---- variance guidance (pt_variance.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------
+// ---- temporal reuse (pt_temporal.hip; definition in include/mi355x_pathtracer.h) ----------------------------------------------------
+int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams, int spp) {
+    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
+    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
+    if (spp < 1) return bad_spp("ptx_denoise_temporal");
+    if (!t || !h) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: null tracer or temporal handle");
+    if (const int rc = denoise_begin("ptx_denoise_temporal", t, h, false)) return rc;
+    if (const int rc = temporal_step(t, h, tp, spp, false)) return rc;
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    const float4 *g = t->d_gbuf;
+    HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, h->d_mix, 1.0f, g, g + 2 * n, dp.demodulate ? 1 : 0, 0, nullptr, t->d_dn_tmp));
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp));
+    if (const int rc = temporal_done(t, h)) return rc;
+    h->has_v[h->cur] = false;                            // dd.w = 0: a later ptx_denoise_variance takes its spatial estimate
+    t->dn_done = true;
+    return PTX_OK;
+}
+
+// ---- variance guidance (pt_denoise.hip; definition in include/mi355x_pathtracer.h) --------------------------------------------------
 int ptx_denoise_variance(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams,
                          const ptx_variance_params *vparams, int spp) {
-    ptx_denoise_params dp;
-    ptx_temporal_params tp;
-    ptx_variance_params vp;
-    if (dparams) dp = *dparams;
-    else ptx_default_denoise_params(&dp);
-    if (tparams) tp = *tparams;
-    else ptx_default_temporal_params(&tp);
-    if (vparams) vp = *vparams;
-    else ptx_default_variance_params(&vp);
+    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
+    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
+    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
     if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
     if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
     if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: spp must be >= 1 (the iterations summed in the accumulation buffer)");
+    if (spp < 1) return bad_spp("ptx_denoise_variance");
     if (h && !dp.demodulate)
         return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: with a temporal handle ptx_denoise_params.demodulate must be != 0 "
                                           "(the state's moments are in demodulated space)");
     if (!t) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: null tracer");
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (h && h->device != t->device)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: the temporal handle was created on device " + std::to_string(h->device) +
-                                              ", the tracer runs on device " + std::to_string(t->device));
-    if (h && (h->w != t->cam.resx || h->h != t->cam.resy))
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
-                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
-    HIPCHECK(hipSetDevice(t->device));
+    if (const int rc = denoise_begin("ptx_denoise_variance", t, h, true)) return rc;
     const int W = t->cam.resx, H = t->cam.resy;
     const size_t n = (size_t)W * H;
-    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
-    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
-    if (!t->d_var) HIPCHECK(hipMalloc(&t->d_var, sizeof(float) * 2 * n));
-    if (h && !t->d_spec) {
-        HIPCHECK(hipMalloc(&t->d_spec, t->h_spec.size()));
-        HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
-    }
-    const int rc = ensure_gbuffer(t);
-    if (rc != PTX_OK) return rc;
     const float4 *g = t->d_gbuf;
-    const int2 *gids = reinterpret_cast<const int2 *>(g + 3 * n);
     if (h) {
-        if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));
-        ptx_camera cam;
-        memcpy(&cam, &t->cam, sizeof cam);
-        if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {     // a new segment: cur becomes hist (as ptx_denoise_temporal)
-            if (h->cur_valid) { h->cur ^= 1; h->hist_valid = true; }
-            h->cam[h->cur] = cam;
-            h->cur_valid = true;
-        }
-        const int hi = h->cur ^ 1;
-        const PtTemporalCam pc = pt_temporal_camera(h->cam[hi], h->hist_valid);
+        if (const int rc = temporal_step(t, h, tp, spp, true)) return rc;
         const PtTemporalState &cur = h->st[h->cur];
-        HIPCHECK(pt_temporal_enqueue(t->stream, W, H, pc, tp, t->d_image, (float)spp, g, g + n, g + 2 * n, gids, t->d_spec,
-                                     (int)t->h_spec.size(), cur, h->st[hi], h->d_mix, h->d_hn, 1, h->hist_valid && h->has_v[hi] ? 1 : 0));
         HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, cur.nh, cur.xn, cur.ids, 1, cur.dd));
         HIPCHECK(pt_variance_prep_state_enqueue(t->stream, (int)n, cur, t->d_dn_tmp));
         h->has_v[h->cur] = true;
     } else {
-        HIPCHECK(pt_variance_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, nullptr, t->d_dn_tmp));
-        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, gids, 0, t->d_dn_tmp));
+        HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, 1, nullptr, t->d_dn_tmp));
+        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
     }
-    HIPCHECK(pt_atrous_var_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, t->d_var, t->d_var + n,
-                                   dp, vp));
-    if (h) {
-        HIPCHECK(hipEventRecord(h->ev, t->stream));
-        h->used = h->done = true;
-    }
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
+    if (const int rc = h ? temporal_done(t, h) : PTX_OK) return rc;
     t->dn_done = t->var_done = true;
     return PTX_OK;
 }

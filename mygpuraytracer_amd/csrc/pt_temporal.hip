@@ -7,7 +7,7 @@
 // Per pixel: reproject into hist's camera, accept / reject up to four taps, mix with rgb / spp, write the new cur record, the mix and
 // (h, n_h).  It copies what the next segment needs out of the G-buffer, which ensure_gbuffer rewrites in place on the next view.
 // k_reproject_variance (ptx_denoise_variance) is the same pixel function, reproject_pixel<true>: the same arithmetic plus the per-sample luminance variance V in dd.w: inherited
-// and updated where the history carries one, -1 (= "pt_variance.hip's spatial estimate fills this in") on the other hit pixels.
+// and updated where the history carries one, -1 (= "pt_denoise.hip's spatial estimate fills this in") on the other hit pixels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -15,13 +15,11 @@
 #include <string.h>
 #include <string>
 
-#include "pt_temporal.h"
-
-extern "C" void ptx_internal_set_error(const char *msg);
+#include "pt_denoise.h"
 
 namespace {
 
-constexpr int BX = 64, BY = 4;
+constexpr int BX = PT_BX, BY = PT_BY;
 
 template <bool VAR>
 __device__ __forceinline__ void reproject_pixel(
@@ -123,8 +121,6 @@ __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(REPROJECT_PARAMS
 // ptx_denoise_variance's: the same pixel function with V
 __global__ __launch_bounds__(BX * BY) void k_reproject_variance(REPROJECT_PARAMS) { reproject_pixel<true>(REPROJECT_ARGS); }
 
-int fail(int code, const std::string &msg) { ptx_internal_set_error(msg.c_str()); return code; }
-
 }  // namespace
 
 const char *pt_temporal_params_problem(const ptx_temporal_params &p) {
@@ -171,9 +167,8 @@ hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam
                                float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
                                const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
                                float4 *hn, int variance, int hist_has_v) {
-    const dim3 grid((unsigned)((w + BX - 1) / BX), (unsigned)((h + BY - 1) / BY)), block(BX, BY);
     const auto kernel = variance ? k_reproject_variance : k_temporal_reproject;
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
+    hipLaunchKernelGGL(kernel, pt_pixel_grid(w, h), dim3(BX, BY), 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
                        p.normal_cos, p.plane_tolerance, hist_has_v, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cur.nh, cur.xn, cur.dd,
                        cur.ids, (const float4 *)hist.nh, (const float4 *)hist.xn, (const float4 *)hist.dd, (const int2 *)hist.ids, mix, hn);
     return hipGetLastError();
@@ -199,30 +194,34 @@ static void free_temporal(ptx_temporal *t) {
     delete t;
 }
 
+static int alloc_temporal(ptx_temporal *t) {
+    const size_t n = (size_t)t->w * t->h;
+    PT_HC(hipSetDevice(t->device));
+    for (PtTemporalState &s : t->st) {
+        PT_HC(hipMalloc(&s.nh, sizeof(float4) * n)); PT_HC(hipMalloc(&s.xn, sizeof(float4) * n));
+        PT_HC(hipMalloc(&s.dd, sizeof(float4) * n)); PT_HC(hipMalloc(&s.ids, sizeof(int2) * n));
+    }
+    PT_HC(hipMalloc(&t->d_mix, sizeof(float) * 3 * n));
+    PT_HC(hipMalloc(&t->d_hn, sizeof(float4) * n));
+    PT_HC(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
+    return PTX_OK;
+}
+
 int ptx_temporal_create(int device, int width, int height, ptx_temporal **out) {
-    if (!out) return fail(PTX_ERR_INVALID, "ptx_temporal_create: out is NULL");
+    if (!out) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: out is NULL");
     *out = nullptr;
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 3) return fail(PTX_ERR_INVALID, "ptx_temporal_create: bad frame size");
-    if (device < 0) return fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
+    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 3) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: bad frame size");
+    if (device < 0) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
         (void)hipGetLastError();
-        return fail(PTX_ERR_NODEVICE, "no HIP device available; the temporal denoiser has no CPU path");
+        return pt_fail(PTX_ERR_NODEVICE, "no HIP device available; the temporal denoiser has no CPU path");
     }
-    if (device >= ndev) return fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
+    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
     ptx_temporal *t = new ptx_temporal();
     t->device = device; t->w = width; t->h = height;
-    const size_t n = (size_t)width * height;
-#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { free_temporal(t); return fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    HC(hipSetDevice(device));
-    for (PtTemporalState &s : t->st) {
-        HC(hipMalloc(&s.nh, sizeof(float4) * n)); HC(hipMalloc(&s.xn, sizeof(float4) * n));
-        HC(hipMalloc(&s.dd, sizeof(float4) * n)); HC(hipMalloc(&s.ids, sizeof(int2) * n));
-    }
-    HC(hipMalloc(&t->d_mix, sizeof(float) * 3 * n));
-    HC(hipMalloc(&t->d_hn, sizeof(float4) * n));
-    HC(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
-#undef HC
+    const int rc = alloc_temporal(t);
+    if (rc != PTX_OK) { free_temporal(t); return rc; }
     *out = t;
     return PTX_OK;
 }
@@ -235,19 +234,18 @@ void ptx_temporal_destroy(ptx_temporal *t) {
 }
 
 int ptx_temporal_reset(ptx_temporal *t) {
-    if (!t) return fail(PTX_ERR_INVALID, "null temporal handle");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null temporal handle");
     t->cur_valid = t->hist_valid = false;    // (the buffers are only read behind these flags; the next call waits for the last)
     return PTX_OK;
 }
 
 int ptx_temporal_read(ptx_temporal *t, float *hist_rgb3, float *hist_count1, float *mix_rgb3) {
-    if (!t) return fail(PTX_ERR_INVALID, "null temporal handle");
-    if (!t->done) return fail(PTX_ERR_INVALID, "ptx_temporal_read: no ptx_denoise_temporal with this handle yet");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null temporal handle");
+    if (!t->done) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_read: no ptx_denoise_temporal with this handle yet");
     const size_t n = (size_t)t->w * t->h;
-#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-    HC(hipSetDevice(t->device));
-    HC(hipEventSynchronize(t->ev));
-    if (mix_rgb3) HC(hipMemcpy(mix_rgb3, t->d_mix, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipEventSynchronize(t->ev));
+    if (mix_rgb3) PT_HC(hipMemcpy(mix_rgb3, t->d_mix, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
     if (hist_rgb3 || hist_count1) {
         float4 *hn = new float4[n];
         const hipError_t e = hipMemcpy(hn, t->d_hn, sizeof(float4) * n, hipMemcpyDeviceToHost);
@@ -257,9 +255,8 @@ int ptx_temporal_read(ptx_temporal *t, float *hist_rgb3, float *hist_count1, flo
                 if (hist_count1) hist_count1[i] = hn[i].w;
             }
         delete[] hn;
-        HC(e);
+        PT_HC(e);
     }
-#undef HC
     return PTX_OK;
 }
 

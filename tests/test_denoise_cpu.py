@@ -1,17 +1,13 @@
 """CPU: the denoiser's definition (tests/atrous_ref.py checked by hand), its C-ABI surface without a device, and what the compiler made of
 its kernels.  The device is held to the same restatement by tests/test_gpu_denoise.py."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from atrous_ref import atrous, bspline_atrous, random_frame
+from resource_usage import kernels_named, resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIG = 1e30
 
 
@@ -89,29 +85,14 @@ def test_denoise_buffers_has_no_cpu_fallback(product):
         product.denoise_buffers(f["rgb"], f["albedo"], f["normal"], f["position"], f["hit"])
 
 
-def _resource_usage(target):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    assert hipcc, "no hipcc: the library cannot have been built here"
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "mygpuraytracer_amd", "csrc"), target, "HIPCC=" + hipcc],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in (r.stdout + r.stderr).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgprs", r"\bVGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
+PASSES = tuple("k_atrous_passILb%dELb%dEE" % (var, last) for var in (0, 1) for last in (0, 1))
 
 
 def test_denoiser_kernels_do_not_spill():
-    filt = {k: v for k, v in _resource_usage("resource-usage-denoise").items() if "k_atrous" in k}
-    assert len(filt) == 3, list(filt)                 # prep + the two instances of the pass
-    gbuf = {k: v for k, v in _resource_usage("resource-usage").items() if "k_gbuffer" in k}
-    assert len(gbuf) == 1, list(gbuf)
+    filt = kernels_named(resource_usage("resource-usage-denoise"), ("k_atrous_prep",) + PASSES)
+    assert len(filt) == 5, list(filt)                 # prep + the four instances of the pass
+    gbuf = kernels_named(resource_usage("resource-usage"), ("k_gbuffer",))
     for k, v in {**filt, **gbuf}.items():
         assert v["scratch"] == 0, (k, v)
+    for k in PASSES[:2]:
+        assert filt[k]["lds"] == 0, (k, filt[k])      # the plain instances: no prefilter tile

@@ -1,17 +1,13 @@
 """CPU: the temporal reuse's definition (tests/temporal_ref.py checked by hand on synthetic frames), its C-ABI surface without a device,
 and what the compiler made of its kernel.  The device is held to the same restatement by tests/test_gpu_temporal.py."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from resource_usage import kernels_named, resource_usage
 from temporal_ref import mix, plane_gbuffer, project, reproject, state, synthetic_camera
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _plane_frames(shift_px=(3, 2), W=64, H=48, seed=0):
@@ -154,21 +150,7 @@ def test_temporal_create_has_no_cpu_fallback(product):
 
 
 def test_temporal_kernel_does_not_spill():
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    assert hipcc, "no hipcc: the library cannot have been built here"
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "mygpuraytracer_amd", "csrc"), "resource-usage-temporal", "HIPCC=" + hipcc],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in (r.stdout + r.stderr).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and cur is not None:
-            cur["scratch"] = int(m.group(1))
-    kernels = {k: v for k, v in out.items() if "k_temporal" in k}
-    assert len(kernels) == 1, list(out)
+    kernels = kernels_named(resource_usage("resource-usage-temporal"), ("k_temporal_reproject", "k_reproject_variance"))
+    assert len(kernels) == 2, list(kernels)
     for k, v in kernels.items():
         assert v.get("scratch") == 0, (k, v)

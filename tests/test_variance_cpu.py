@@ -2,18 +2,14 @@
 surface without a device, and what the compiler made of its kernels.  The device is held to the same restatement by
 tests/test_gpu_variance.py."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from atrous_ref import atrous, random_frame
+from resource_usage import kernels_named, resource_usage
 from variance_ref import atrous_variance, denoise_buffers_variance, lum, spatial_variance, update
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("batches", [[2] * 8, [2, 2, 2, 64], [1, 7, 3, 20, 2]])
@@ -149,28 +145,12 @@ def test_variance_filter_has_no_cpu_fallback(product):
 
 
 def test_variance_kernels_do_not_spill():
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    assert hipcc, "no hipcc: the library cannot have been built here"
-    found = {}
-    for target, names in (("resource-usage-variance", ("k_variance_prep", "k_variance_spatial", "k_atrous_pass_var")),
-                          ("resource-usage-temporal", ("k_reproject_variance",))):
-        r = subprocess.run(["make", "-C", os.path.join(ROOT, "mygpuraytracer_amd", "csrc"), target, "HIPCC=" + hipcc],
-                           capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        cur = None
-        for line in (r.stdout + r.stderr).splitlines():
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                cur = found.setdefault(m.group(1), {}) if any(n in m.group(1) for n in names) else None
-                continue
-            for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
-                             ("waves", r"Occupancy \[waves/SIMD\]: (\d+)")):
-                m = re.search(pat, line)
-                if m and cur is not None:
-                    cur[key] = int(m.group(1))
+    found = kernels_named(resource_usage("resource-usage-denoise"),
+                          ("k_atrous_prep", "k_variance_prep_state", "k_variance_spatial", "k_atrous_passILb1ELb0EE", "k_atrous_passILb1ELb1EE"))
+    found.update(kernels_named(resource_usage("resource-usage-temporal"), ("k_reproject_variance",)))
     assert len(found) == 6, list(found)          # two preps, the spatial estimate, two passes, the reprojection with V
     for k, v in found.items():
         assert v.get("scratch") == 0, (k, v)
-    spatial = [v for k, v in found.items() if "k_variance_spatial" in k][0]
+    spatial = found["k_variance_spatial"]
     # 28 KB of LDS per workgroup, five workgroups (20 waves) per CU of 160 KiB
     assert spatial["lds"] <= 160 * 1024 // 5 and spatial["waves"] >= 5, spatial
