@@ -48,7 +48,7 @@ thread_local float g_gpu_ms = 0.f, g_cpu_ms = 0.f;
 int sc_fail(const std::string &m) { ptx_internal_set_error(m.c_str()); return PTX_ERR_HIP; }
 #define SC_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
-// inclusive prefix sum over the lanes of a wave in the vector ALU's own lane network (DPP), as pt_engine.hip's waveInclusiveScan: four
+// inclusive prefix sum over the lanes of a wave in the vector ALU's own lane network (DPP), as pt_kernels.hip's waveInclusiveScan: four
 // shifted adds inside the rows of 16 lanes, lane 15 of a row broadcast into the next row (rows 1 and 3), lane 31 into the upper half.
 // Six dependent vector instructions where __shfl_up made six ds_bpermute round trips through the LDS crossbar (rounds 1-4) -- at frame
 // sizes (2 M elements) the kernel is a chain of such latencies, not a stream.

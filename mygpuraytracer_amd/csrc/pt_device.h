@@ -26,8 +26,8 @@
 // 2  FAST: level 1 + the hardware's approximate reciprocal / square root / reciprocal square root (v_rcp_f32, v_sqrt_f32, v_rsq_f32:
 //    one ulp each, quotients a*rcp(b) about 2.5 ulp; -fno-hip-fp32-correctly-rounded-divide-sqrt) and its sine / cosine / exp2 / log2
 //    instructions.
-// Levels 1 and 2 are separate code objects (csrc/pt_arith.hip includes pt_engine.hip with PT_ARITH set and `ptd` renamed, so that no
-// inline function of theirs can ever be the copy the exact translation unit links) and promise a STATISTICAL tolerance against
+// Every level is a code object of its own (csrc/pt_kernels.hip compiled with PT_ARITH set, and for levels 1 and 2 `ptd` renamed, so that no
+// inline function of theirs can ever be the copy the exact translation units link); levels 1 and 2 promise a STATISTICAL tolerance against
 // level 0 (tests/test_gpu_parity.py::test_contracted_arithmetic_*), never bits.
 #ifndef PT_ARITH
 #define PT_ARITH 0
@@ -741,7 +741,7 @@ PT_HD float bvhNearestOrdered(const BvhQuad *__restrict__ nodes, const float *__
 // the binary tree, for the root box and the slack.
 // The walk is written as a state (WideWalk) and two steps -- wideNodeStep: one four-wide node; wideLeafStep: the triangles of the leaf
 // in hand, all of them or one -- so that the SAME code serves two schedules: bvhNearestWide below (one ray to its end: "while-while")
-// and k_mesh's refilling waves (pt_engine.hip), where a lane whose walk has ended takes the next parked ray instead of idling.
+// and k_mesh's refilling waves (pt_kernels.hip), where a lane whose walk has ended takes the next parked ray instead of idling.
 constexpr int32_t WIDE_DONE = (int32_t)0x80000000;           // (a leaf reference with count 0: no leaf is encoded like this)
 struct WideWalk {
     vec3 o, d;                                               // object-space ray (d normalised the way meshTestCore does)
@@ -815,8 +815,8 @@ PT_HD void wideNodeStep(WideWalk &w, const BvhWide4 *__restrict__ wide, int32_t 
     w.sp = sp; w.n = n;
 }
 // The leaf in hand (w.n: bit 31, count << 24, first triangle): ALL its triangles (ONE = false), or the first of them, the rest staying
-// in hand as a shorter leaf (ONE = true: k_mesh's refilling waves, where a lane with a one-triangle leaf should not wait for its
-// neighbour's four).  The per-triangle arithmetic and the (distance, face index) minimum are meshTestCore's.
+// in hand as a shorter leaf (ONE = true: the finest schedule of the same steps, which ptx_debug_bvh_check replays on the host; k_mesh's
+// refilling waves were measured with it and test all).  The per-triangle arithmetic and the (distance, face index) minimum are meshTestCore's.
 template <bool ONE>
 PT_HD void wideLeafStep(WideWalk &w, const float *__restrict__ tris, int32_t *stack, int stride, int *visited = nullptr, int *trace = nullptr) {
     const int count = (int)(((uint32_t)w.n >> 24) & 0x7fu), first = w.n & 0x00ffffff;
@@ -1073,7 +1073,7 @@ PT_DEV void intersectScene(const DScene &sc, Ray ray, Hit &h) {
 // error, see make_world_aabb in pt_engine.hip), then the wave loops "each lane takes ITS next cube or sphere" with the
 // geom tables gathered per lane from LDS.  The exact tests and their arithmetic are unchanged, so is the result:
 // nearest t > 0, lowest geom index on ties (the reference's strict `t_min > t` in index order).  The kernels go one
-// step further (tileIntersect in pt_engine.hip): the (ray, geom) pairs of a whole 256-path tile are pooled in LDS and
+// step further (tileIntersect in pt_kernels.hip): the (ray, geom) pairs of a whole 256-path tile are pooled in LDS and
 // worked off by dense waves.
 
 // xyz of mat4*vec4 for a matrix stored as 3 rows of 4 (same products and sums as multiplyMV)

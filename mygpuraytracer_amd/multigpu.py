@@ -48,7 +48,7 @@ def agreed_phase(fn, device=None):
 
 
 def owned_rows(height, tile_rows, rank, world):
-    """Rows y with (y // tile_rows) % world == rank -- the same rule the kernels apply (pt_engine.hip owned_pixel)."""
+    """Rows y with (y // tile_rows) % world == rank -- the same rule the kernels apply (pt_kernels.h owned_pixel)."""
     return [y for y in range(height) if (y // tile_rows) % world == rank]
 
 

@@ -1,5 +1,5 @@
 """What the compiler made of the kernels of one `make resource-usage*` target of mygpuraytracer_amd/csrc (hipcc's
--Rpass-analysis=kernel-resource-usage remarks), for the spill tests of the denoiser."""
+-Rpass-analysis=kernel-resource-usage remarks), for the spill tests of the path kernels and the denoiser."""
 import os
 import re
 import shutil
@@ -10,15 +10,20 @@ FIELDS = (("vgprs", r"\bVGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]
           ("waves", r"Occupancy \[waves/SIMD\]: (\d+)"))
 
 
-def resource_usage(target):
-    """{mangled kernel name: {vgprs, scratch, lds, waves}} of every kernel the target compiles"""
+def remarks(target):
+    """what `make <target>` printed: the compiler's remarks, each behind the `file:line:column:` of the kernel it describes"""
     hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
     assert hipcc, "no hipcc: the library cannot have been built here"
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "mygpuraytracer_amd", "csrc"), target, "HIPCC=" + hipcc],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    return r.stdout + r.stderr
+
+
+def parse_usage(text):
+    """{mangled kernel name: {vgprs, scratch, lds, waves}} of every kernel the remarks describe"""
     out, cur = {}, None
-    for line in (r.stdout + r.stderr).splitlines():
+    for line in text.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = out.setdefault(m.group(1), {})
@@ -27,6 +32,21 @@ def resource_usage(target):
             m = re.search(pat, line)
             if m and cur is not None:
                 cur[key] = int(m.group(1))
+    return out
+
+
+def resource_usage(target):
+    """{mangled kernel name: {vgprs, scratch, lds, waves}} of every kernel the target compiles"""
+    return parse_usage(remarks(target))
+
+
+def kernels_by_file(text):
+    """{source file name: set of mangled kernel names}, from the `file:line:column:` prefix of the "Function Name" remarks"""
+    out = {}
+    for line in text.splitlines():
+        m = re.match(r"(?:.*/)?([^/:\s]+):\d+:\d+: remark: Function Name: (\S+)", line)
+        if m:
+            out.setdefault(m.group(1), set()).add(m.group(2))
     return out
 
 

@@ -1,5 +1,5 @@
 """GPU: the opt-in arithmetic levels (ptx_options.arith 1 = CONTRACTED, 2 = FAST: the same kernels as second / third code objects,
-csrc/pt_arith.hip) against the EXACT level on the same device.
+csrc/pt_kernels.hip compiled with PT_ARITH = 1 / 2; every level's table reaches the host the same way) against the EXACT level on the same device.
 
 The exact level is bit-identical to the CPU oracle (tests/test_gpu_parity.py) and stays the default and the headline.  The other two
 run the kind of arithmetic the reference's REAL build runs (nvcc fuses multiply-adds by default) or a faster one, and promise the

@@ -1,13 +1,14 @@
-"""Static facts about the kernels of pt_engine.hip as hipcc builds them for gfx950: registers, spills, scratch, occupancy (the
+"""Static facts about the kernels of pt_kernels.hip (at the arithmetic level the flags select) and, at the exact level, of pt_engine.hip
+as hipcc builds them for gfx950: registers, spills, scratch, occupancy (the
 compiler's -Rpass-analysis=kernel-resource-usage remarks) and the number of instructions by class from the disassembly.  CPU only.
-usage: python tools/kernel_resources.py [EXTRA flags...]      e.g.  python tools/kernel_resources.py -DPT_ARITH_FMA=1 -ffp-contract=fast"""
+usage: python tools/kernel_resources.py [EXTRA flags...]      e.g.  python tools/kernel_resources.py -DPT_ARITH=1 -ffp-contract=fast"""
 import os, re, subprocess, sys, tempfile, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mygpuraytracer_amd", "csrc")
 OPT = "-Os -fno-unroll-loops -fno-slp-vectorize -mllvm -disable-machine-licm".split()
 
 
-def main(extra, src="pt_engine.hip"):
+def main(extra, src):
     base = ["hipcc", "--offload-arch=gfx950", "-std=c++17", *OPT, "-fPIC", "-ffp-contract=off", *extra, "-Wno-unused-function", "-Wno-unused-value"]
     with tempfile.TemporaryDirectory() as td:
         r = subprocess.run(base + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S", src, "-o", os.path.join(td, "k.s")],
@@ -49,4 +50,6 @@ def main(extra, src="pt_engine.hip"):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    main(sys.argv[1:], "pt_kernels.hip")
+    if not any(a.startswith("-DPT_ARITH=") and a != "-DPT_ARITH=0" for a in sys.argv[1:]):      # (the host unit's kernels exist at the exact level only)
+        main(sys.argv[1:], "pt_engine.hip")

@@ -11,7 +11,7 @@ KERNELS = {"k_bounce<false,0,FAST>": "_ZN12_GLOBAL__N_18k_bounceILb0ELi0ELb1EEEv
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "k.s")
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-std=c++17", *OPT, "-fPIC", "-ffp-contract=off", *sys.argv[1:], "-Rpass-analysis=kernel-resource-usage",
-                        "--cuda-device-only", "-S", "pt_engine.hip", "-o", out], cwd=CSRC, capture_output=True, text=True)
+                        "--cuda-device-only", "-S", "pt_kernels.hip", "-o", out], cwd=CSRC, capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])
     text = open(out).read().splitlines()
