@@ -1,12 +1,12 @@
 // pt_engine.hip -- the host unit of the MI355X (gfx950) path-tracing engine behind include/mi355x_pathtracer.h: the ptx_tracer struct, scene
-// upload, buffers, launch plans, every ptx_* entry point, and the kernels that are the same at every arithmetic level (debug capture,
-// cache replay, gather, statistics, preview, G-buffer, k_kat_fast_exact, k_hold).
+// upload, buffers, launch plans, every ptx_* entry point that needs a device, and the kernels that are the same at every arithmetic
+// level (debug capture, cache replay, gather, statistics, preview, G-buffer, k_kat_fast_exact, k_hold).  Scene preparation: pt_scene.hip.
 //
 // What belongs here: everything that is level 0 by nature.  This file is compiled ONCE, at the exact level; the kernels whose results
 // depend on the arithmetic level (k_bounce, k_mesh, k_finish, the per-stage test kernels) are pt_kernels.hip's, one code object per
 // level, and are launched only through that level's table (ptx_tracer::ks) -- see pt_kernels.hip for the engine's design.  The tables
-// the host computes with the device's own functions (tabulated normals, ptx_debug_bvh_check's walks) are computed HERE and are
-// therefore the exact ones at every level.  What both units must agree on is pt_kernels.h.
+// the host computes with the device's own functions (tabulated normals, ptx_debug_bvh_check's walks) are computed in pt_scene.hip,
+// compiled once with this file's flags, and are therefore the exact ones at every level.  What both units must agree on is pt_kernels.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -18,6 +18,7 @@
 
 #include "../../include/mi355x_pathtracer.h"
 #include "pt_kernels.h"
+#include "pt_scene.h"
 #include "pt_denoise.h"
 
 namespace {
@@ -247,8 +248,24 @@ extern "C" const void *ptx_arith_kernels_0(void);
 extern "C" const void *ptx_arith_kernels_1(void) __attribute__((weak));
 extern "C" const void *ptx_arith_kernels_2(void) __attribute__((weak));
 
+// An owned device array -- every device buffer of the tracer, the scratch of the per-stage entry points -- freed when its owner goes, on
+// every way out (a HIPCHECK that fails returns from the middle).  Each step hands back the hipError_t: ptx_create looks for out-of-memory.
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;                              // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t count) { n = count; return hipMalloc(&p, sizeof(T) * count); }      // (once per buffer; contents undefined)
+    hipError_t zero() { return hipMemset(p, 0, sizeof(T) * n); }
+    hipError_t upload(const void *src, size_t count) { const hipError_t e = alloc(count); return e != hipSuccess ? e : hipMemcpy(p, src, sizeof(T) * count, hipMemcpyHostToDevice); }
+    hipError_t upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
+    hipError_t download(void *dst) const { return hipMemcpy(dst, p, sizeof(T) * n, hipMemcpyDeviceToHost); }
+};
+
 // ---------------------------------------------------------------------------------------------------------------
-struct ptx_tracer {
+struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it is traced, pt_scene.h: ntri, cull, tri_lds, split_mesh, the masks ...)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -264,38 +281,32 @@ struct ptx_tracer {
     int dbg_extra_lds = 0;
     int dbg_total_wg_per_cu = 0, dbg_nsets = 0; // PTX_DEBUG_TOTAL_WG_PER_CU / PTX_DEBUG_NSETS: tuning experiments (grid of a whole launch; sets of a short run)
     // device memory
-    DGeom *d_geoms = nullptr; DMaterial *d_mats = nullptr; float *d_faces = nullptr; uint8_t *d_texels = nullptr;
-    float *d_image = nullptr; bool own_image = false;
-    float *d_fbuf[3] = {nullptr, nullptr, nullptr};      // stream, stage, cache
-    int32_t *d_ibuf[3] = {nullptr, nullptr, nullptr};
+    DevBuf<DGeom> d_geoms; DevBuf<DMaterial> d_mats; DevBuf<float> d_faces; DevBuf<uint8_t> d_texels;
+    float *d_image = nullptr; DevBuf<float> d_image_own; // d_image: the caller's buffer, or d_image_own
+    DevBuf<float> d_fbuf[3];                             // stream, stage, cache
+    DevBuf<int32_t> d_ibuf[3];
     PathSoA soa[3];                                      // 0, 1 = the two stages (bounce b writes soa[1 - (b & 1)], b + 1 reads it), 2 = first-bounce cache
-    int32_t *d_counts = nullptr;                         // per segment: [2][nbins][maxTiles] prefix tables + [maxTiles] stored paths per tile
-    int32_t *d_chunk = nullptr;                          // [segments][2 (bounce parity)][3][nbins x grid_seg]: the run tables (BounceParams::chunk)
-    int32_t *d_cache_chunk = nullptr;                    // [3][nbins x grid_seg]: the cached bounce 0's
-    int32_t *d_cache_super = nullptr;                    // [2][nbins][nsuper]: the cached bounce 0's
+    DevBuf<int32_t> d_counts;                            // per segment: [2][nbins][maxTiles] prefix tables + [maxTiles] stored paths per tile
+    DevBuf<int32_t> d_chunk;                             // [segments][2 (bounce parity)][3][nbins x grid_seg]: the run tables (BounceParams::chunk)
+    DevBuf<int32_t> d_cache_chunk;                       // [3][nbins x grid_seg]: the cached bounce 0's
+    DevBuf<int32_t> d_cache_super;                       // [2][nbins][nsuper]: the cached bounce 0's
     int cache_gx = 0;                                    // workgroups per segment of the launch that filled the cache (its run tables' width)
-    int32_t *d_totals = nullptr;                         // [maxBounces][2][nbins] then [maxBounces][2][nbins][nsuper]
+    DevBuf<int32_t> d_totals;                            // [maxBounces][2][nbins] then [maxBounces][2][nbins][nsuper]
     int32_t *d_super = nullptr;                          // (points into d_totals' allocation)
-    float *d_tri9 = nullptr, *d_gtab = nullptr, *d_aabb = nullptr;
+    DevBuf<float> d_tri9, d_gtab, d_aabb;
     std::vector<float> h_aabb;                           // host copy of the world boxes (update_tile_geoms)
-    uint32_t *d_tile_geoms = nullptr; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
-    uint32_t cube_bits = 0, sphere_bits = 0, mesh_bits = 0;   // geoms 0..31 by kind, for the candidate masks
-    BvhQuad *d_bvh_nodes = nullptr; float *d_bvh_tris = nullptr; int32_t *d_bvh_root = nullptr, *d_bvh_depth = nullptr;   // pt_bvh.h (NULL: no mesh has one)
-    BvhWide4 *d_bvh_wide = nullptr; int32_t *d_bvh_wroot = nullptr, *d_bvh_wneed = nullptr;                                  // four-wide nodes of the same trees (k_mesh)
-    int ntri_lds = 0, bvh_nodes = 0, bvh_meshes = 0, bvh_stack = BVH_STACK;
-    int mesh_chunks = 1;                                 // see DScene::mesh_chunks
-    float *d_fnorm = nullptr, *d_cnorm = nullptr;        // precomputed normals (DScene::fnorm / cnorm)
-    float *d_ldsblob = nullptr;                          // DScene::ldsblob for the ntri_lds k_bounce is launched with
-    uint32_t bump_bits = 0;
-    bool split_mesh = false;                             // k_bounce as MODE 1 + k_mesh + k_finish + MODE 2 (scenes with BVH meshes)
+    DevBuf<uint32_t> d_tile_geoms; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
+    DevBuf<BvhQuad> d_bvh_nodes; DevBuf<float> d_bvh_tris; DevBuf<int32_t> d_bvh_root, d_bvh_depth;                          // pt_bvh.h (NULL: no mesh has one)
+    DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
+    DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
+    DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
     bool no_fast = false;                                // PTX_DEBUG_NO_FAST: always the general k_bounce (A/B timing, tests of both variants)
     bool force_fast = false;                             // PTX_DEBUG_FORCE_FAST: ask for the specialised variant at every launch (refused
                                                          // with PTX_ERR_INVALID where its preconditions do not hold; tests only)
-    unsigned long long *d_keys = nullptr; uint32_t *d_items = nullptr; int32_t *d_item_count = nullptr;
-    int32_t *d_tile_done = nullptr;                      // split first bounce: [segments][maxTiles], see BounceParams::tile_done
+    DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_items; DevBuf<int32_t> d_item_count;
+    DevBuf<int32_t> d_tile_done;                         // split first bounce: [segments][maxTiles], see BounceParams::tile_done
     size_t seg_items = 0;
-    int cull = 0;
-    int nsuper = 1, ntri = 0, tri_lds = 0;
+    int nsuper = 1;
     size_t totals_bytes = 0, seg_totals = 0, field_stride = 0, seg_part = 0;
     int kmax = 1;                                        // iterations per launch set (segments)
     long long split_min_paths = 1LL << 20;               // ptx_render_strided: smallest launch set a short run is cut into
@@ -318,28 +329,25 @@ struct ptx_tracer {
     // read.  Where that may not hold -- nothing has run yet, a traced-ahead batch was dropped unfinished, a set ended early on an error,
     // the image was reset -- the lane's next set starts with a full clear of both (enqueue_batch).
     bool aux_dirty[MAX_LANES] = {};
-    int uses_uv = 0;
-    unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
-    unsigned long long ntab_bins = 0ull;                 // BounceParams::ntab_bins (none: every record carries its normal)
     unsigned long long cache_dir_bins = ~0ull, cache_ntab_bins = 0ull;      // ... as the cached camera bounce was written
     int cache_idx16 = 0;                                                    // ... and its local index (BounceParams::idx16)
-    uchar4 *d_pbo = nullptr;                             // ptx_write_pbo's device staging (allocated on first use)
-    float *d_denoised = nullptr;                         // ptx_write_denoised_pbo_device's copy of the host frame (first use)
-    float *d_albedo = nullptr;                           // apps variant only: W*H*3
+    DevBuf<uchar4> d_pbo;                                // ptx_write_pbo's device staging (allocated on first use)
+    DevBuf<float> d_denoised;                            // ptx_write_denoised_pbo_device's copy of the host frame (first use)
+    DevBuf<float> d_albedo;                              // apps variant only: W*H*3
     // denoiser (ptx_denoise), all allocated on its first call: G-buffer [nh | xt | alb] x W*H float4 then W*H int2 ids (pt_denoise.h),
     // the filter's two float4 colour buffers, its W*H*3 result
-    float4 *d_gbuf = nullptr, *d_dn_tmp = nullptr;
-    float *d_dn_out = nullptr;
+    DevBuf<float4> d_gbuf, d_dn_tmp;
+    DevBuf<float> d_dn_out;
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
-    uint8_t *d_spec = nullptr;                           // its device copy, on the first ptx_denoise_temporal
-    float *d_var = nullptr;                              // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
+    DevBuf<uint8_t> d_spec;                              // its device copy, on the first ptx_denoise_temporal
+    DevBuf<float> d_var;                                 // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
     bool var_done = false;
-    unsigned long long *d_stamps = nullptr;              // diagnostic build only
-    float *d_part = nullptr;                             // [kmax][W*H*3] per-iteration radiance (batched mode)
-    int32_t *d_cache_totals = nullptr;                   // [2][nbins] of bounce 0 (cache)
-    int32_t *d_emit_count = nullptr, *d_emit_pix = nullptr; float *d_emit_rgb = nullptr;
-    int64_t *d_stats = nullptr;                          // [64] last iteration, [64] = running total, [65] = fenced indices (BounceParams::fenced), [66..68] = stored paths: all, with direction, with normal code
+    DevBuf<unsigned long long> d_stamps;                 // diagnostic build only
+    DevBuf<float> d_part;                                // [kmax][W*H*3] per-iteration radiance (batched mode)
+    DevBuf<int32_t> d_cache_totals;                      // [2][nbins] of bounce 0 (cache)
+    DevBuf<int32_t> d_emit_count, d_emit_pix; DevBuf<float> d_emit_rgb;
+    DevBuf<int64_t> d_stats;                             // [64] last iteration, [64] = running total, [65] = fenced indices (BounceParams::fenced), [66..68] = stored paths: all, with direction, with normal code
     uint32_t fence_slots = 0;                            // = cap; PTX_DEBUG_FENCE_SLOTS lowers it (test of the counter: entries beyond it are fenced)
     int maxBounces = 0;
     bool cache_valid = false;
@@ -352,8 +360,8 @@ struct ptx_tracer {
     size_t kev_used = 0;
     // debug capture
     int capture_bounce = -1;
-    int32_t *d_cap = nullptr;                            // pix, idx, mg [cap each] + totals
-    float *d_cap_f = nullptr;                            // the 15 float fields [cap each]
+    DevBuf<int32_t> d_cap;                               // pix, idx, mg [cap each] + totals
+    DevBuf<float> d_cap_f;                               // the 15 float fields [cap each]
     bool cap_filled = false;
     DScene scene() const {
         DScene s; s.geoms = d_geoms; s.mats = d_mats; s.faces = d_faces; s.tri9 = d_tri9; s.texels = d_texels; s.ngeoms = ngeoms; s.nmats = nmats;
@@ -389,206 +397,13 @@ void fastdiv_magic(uint32_t d, uint32_t &mul, uint32_t &sh) {
     mul = (uint32_t)(((1ull << (31 + l)) / d) + 1);
 }
 
-void camera_to_device(const ptx_camera &c, DCamera &d) {
-    d.resx = c.resolution[0]; d.resy = c.resolution[1];
-    memcpy(d.position, c.position, 12); memcpy(d.lookAt, c.lookAt, 12); memcpy(d.view, c.view, 12);
-    memcpy(d.up, c.up, 12); memcpy(d.right, c.right, 12); memcpy(d.fov, c.fov, 8); memcpy(d.pixelLength, c.pixelLength, 8);
-}
-
-// Conservative world-space box of a geom for the candidate pre-test of intersectSceneCull: the transformed unit cube
-// (which also contains the radius-0.5 sphere) or the transformed mesh vertices, evaluated in double and inflated by
-// 1e-3 + 1e-4 * |coordinate| -- three orders of magnitude more than the fp32 error of the exact tests or of the slab
-// pre-test itself, so a ray the exact test would report as a hit always reaches the box.  Anything non-finite gives an
-// unbounded box (never culled).
-void make_world_aabb(const DGeom &d, const std::vector<float> &faces, float out6[6]) {
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    bool ok = true;
-    auto add = [&](double x, double y, double z) {
-        for (int r = 0; r < 3; r++) {
-            double v = (double)d.xf[0 * 4 + r] * x + (double)d.xf[1 * 4 + r] * y + (double)d.xf[2 * 4 + r] * z + (double)d.xf[3 * 4 + r];
-            if (!(v == v) || v > 1e30 || v < -1e30) ok = false;
-            lo[r] = std::min(lo[r], v); hi[r] = std::max(hi[r], v);
-        }
-    };
-    if (d.type == G_OBJ) {
-        if (d.faceCount == 0) ok = false;
-        for (int j = 0; j < d.faceCount; j++)
-            for (int k = 0; k < 3; k++) {
-                const float *p = &faces[((size_t)d.faceStart + j) * 15 + k * 5];
-                add(p[0], p[1], p[2]);
-            }
-    } else {
-        for (int c = 0; c < 8; c++) add((c & 1) ? 0.5 : -0.5, (c & 2) ? 0.5 : -0.5, (c & 4) ? 0.5 : -0.5);
-    }
-    for (int r = 0; r < 3; r++) {
-        if (!ok) { out6[r] = -INFINITY; out6[3 + r] = INFINITY; continue; }
-        double m = 1e-3 + 1e-4 * std::max(std::fabs(lo[r]), std::fabs(hi[r]));
-        out6[r] = nextafterf((float)(lo[r] - m), -INFINITY);
-        out6[3 + r] = nextafterf((float)(hi[r] + m), INFINITY);
-    }
-}
-
-// Which material bins' records must carry the incoming direction to the next bounce -- scatterRay (pt_device.h) reads it in its
-// reflective and refractive branches and for every hit on an OBJ geom (Schlick's cosine), never for a diffuse cube or sphere hit --
-// and which bins' hits are all cube hits (the material is on cubes only): their records carry a code for the cube's tabulated normal
-// instead of the normal.  The next bounce tells the kinds of record apart by sorted position, at most two ranges each, so a mask keeps
-// at most two runs of set bits: gaps between the runs of the first are FILLED (a direction more is harmless), runs beyond the second
-// of the other are CLEARED.  nmaterials <= 64 bins (bin = nmaterials - 1 - material when sorting, else one bin).
-void record_masks(int nmaterials, const DMaterial *mats, int ngeoms, const int *geom_type, const int *geom_material, bool sort,
-                  unsigned long long &dir_bins, unsigned long long &ntab_bins) {
-    unsigned long long need = 0, cubes = 0;
-    const int nbins = sort ? nmaterials : 1;
-    for (int m = 0; m < nmaterials; m++) {
-        bool nd = mats[m].hasReflective > 0 || mats[m].hasRefractive > 0, on_cube = false, on_other = false;
-        for (int i = 0; i < ngeoms; i++)
-            if (geom_material[i] == m) { nd = nd || geom_type[i] == G_OBJ; (geom_type[i] == G_CUBE ? on_cube : on_other) = true; }
-        const int b = sort ? nmaterials - 1 - m : 0;
-        if (nd) need |= 1ull << b;
-        if (on_cube && !on_other && sort) cubes |= 1ull << b;
-    }
-    auto runs = [&](unsigned long long mask) { int n = 0; for (int b = 0; b < nbins; b++) n += ((mask >> b) & 1) && !(b && ((mask >> (b - 1)) & 1)); return n; };
-    while (runs(need) > 2) {                          // fill the gap behind the first run
-        int b = 0;
-        while (!((need >> b) & 1)) b++;
-        while ((need >> b) & 1) b++;
-        need |= 1ull << b;
-    }
-    while (runs(cubes) > 2) cubes &= ~(1ull << (63 - __builtin_clzll(cubes)));      // drop the highest set bin
-    dir_bins = need; ntab_bins = cubes;
-}
-
-// The same box as the device's candidate pre-test reads it (cullMask): centre and half extent.  The half extent grows by what the two
-// roundings can lose (half an ulp of the centre, half an ulp of itself) and then some; an unbounded box is centre 0, half extent inf.
-void world_box_centre_half(const float lohi8[8], float out8[8]) {
-    for (int r = 0; r < 3; r++) {
-        const double lo = lohi8[r], hi = lohi8[4 + r];
-        if (!(lo > -1e30 && hi < 1e30)) { out8[r] = 0.f; out8[4 + r] = INFINITY; continue; }
-        const float c = (float)(0.5 * (lo + hi));
-        const double h = std::max(hi - (double)c, (double)c - lo);
-        out8[r] = c;
-        out8[4 + r] = nextafterf((float)(h + 2e-7 * (std::fabs((double)c) + h)), INFINITY);
-    }
-    out8[3] = out8[7] = 0.f;
-}
-
-// Which geoms can the camera rays of a tile reach at all?  Per geom the pixel rectangle that its conservative world box projects
-// into (double precision, widened by the antialiasing jitter and two more pixels); a corner at or behind the eye plane makes it the
-// whole frame.  A tile is 256 consecutive OWNED pixels: one span of a row, or -- when it wraps -- whole rows.  Bit g of a tile's
-// word is cleared only when geom g's rectangle misses the tile's: a superset of what any of its rays can hit, so the candidate
-// masks built from it (cullMask<SUBSET>) hold exactly the bits the full loop would set for those rays.  Recomputed when the camera
-// changes; not where the candidate masks are off.
-// With depth of field (generateRay: src/pathtrace.cu:236-251) a pixel's rays leave a lens -- the eye moved by up to lensRadius 0.8 in
-// WORLD x / y -- towards the pixel's focus point pFocus on the plane z = eye.z +- 11.  A point c is on such a ray iff
-// c = e + mu (pFocus - e), mu = (c.z - eye.z) / (+-11) > 0, i.e. pFocus = centre(c) + l (1 - 1/mu) with centre(c) the perspective
-// image of c on the focus plane and |l| <= 0.8: a disc of radius rho(c) = 0.8 |1 - 1/mu| around it.  Over a box, centre() is a
-// projective map (the hull of the corners' images) and rho is extremal at a corner, so the box's focus points lie within the corners'
-// images widened by the LARGEST corner radius; each is then projected to pixels through the pinhole (the relation between a pixel and
-// its focus point) at the four corners of its bounding square.  Anything doubtful -- a corner not in front of the lens plane, a frame
-// whose pixels do not all look towards the same side of it -- keeps the whole frame.
-// (pure host arithmetic: ptx_debug_tile_geoms hands it to the CPU tests, which check the superset property ray by ray)
-void tile_geom_masks(const DCamera &c, const TileMap &tm, int maxTiles, int ngeoms, const float *aabb8, bool dof, std::vector<uint32_t> &masks) {
-    const int W = c.resx, H = c.resy;
-    // p - eye = l * (view - R sx - U sy),  R = right * pixelLength.x, U = up * pixelLength.y,  sx = x - W/2, sy = y - H/2  (generateRay)
-    const double V[3] = {c.view[0], c.view[1], c.view[2]};
-    const double R[3] = {(double)c.right[0] * c.pixelLength[0], (double)c.right[1] * c.pixelLength[0], (double)c.right[2] * c.pixelLength[0]};
-    const double U[3] = {(double)c.up[0] * c.pixelLength[1], (double)c.up[1] * c.pixelLength[1], (double)c.up[2] * c.pixelLength[1]};
-    // solve [V  -R  -U] (l, l sx, l sy)^T = p - eye by Cramer's rule
-    auto det3 = [](const double *a, const double *b, const double *d) {
-        return a[0] * (b[1] * d[2] - b[2] * d[1]) - b[0] * (a[1] * d[2] - a[2] * d[1]) + d[0] * (a[1] * b[2] - a[2] * b[1]);
-    };
-    const double nR[3] = {-R[0], -R[1], -R[2]}, nU[3] = {-U[0], -U[1], -U[2]};
-    const double D = det3(V, nR, nU);
-    // pixel coordinates of the point eye + p; false: not safely in front of the eye
-    auto project = [&](const double p[3], double &x, double &y) {
-        const double l = det3(p, nR, nU) / D, lsx = det3(V, p, nU) / D, lsy = det3(V, nR, p) / D;
-        // in front of the eye by a margin relative to the point's distance (|view| = 1): otherwise the projection is meaningless
-        if (!(l > 1e-6 * (std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2])) && l > 1e-12)) return false;
-        x = lsx / l + W * 0.5; y = lsy / l + H * 0.5;
-        return std::isfinite(x) && std::isfinite(y);
-    };
-    double zsign = 0.0;                                      // depth of field: the side of the lens plane every pixel looks to
-    bool dof_ok = true;
-    if (dof) {
-        for (int k = 0; k < 4; k++) {                        // the frame's corner pixels (+- the jitter): z of the unnormalised direction
-            const double sx = ((k & 1) ? W + 1.0 : -1.0) - W * 0.5, sy = ((k & 2) ? H + 1.0 : -1.0) - H * 0.5;
-            const double dx = V[0] - R[0] * sx - U[0] * sy, dy = V[1] - R[1] * sx - U[1] * sy, dz = V[2] - R[2] * sx - U[2] * sy;
-            const double z = dz / std::sqrt(dx * dx + dy * dy + dz * dz);
-            if (!(std::fabs(z) > 0.05) || (zsign != 0.0 && (z > 0) != (zsign > 0))) dof_ok = false;
-            zsign = z > 0 ? 1.0 : -1.0;
-        }
-    }
-    std::vector<int> rect((size_t)ngeoms * 4);
-    for (int g = 0; g < ngeoms; g++) {
-        int *r = &rect[(size_t)g * 4];
-        r[0] = 0; r[1] = W - 1; r[2] = 0; r[3] = H - 1;                  // x0, x1, y0, y1: the whole frame unless proven smaller
-        const float *b = aabb8 + (size_t)g * 8;
-        bool ok = std::isfinite(D) && std::fabs(D) > 1e-30 && dof_ok;
-        double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300;
-        double cp[8][3], rho = 0.0;
-        for (int k = 0; k < 8 && ok; k++) {
-            cp[k][0] = (double)((k & 1) ? b[4] : b[0]) - c.position[0]; cp[k][1] = (double)((k & 2) ? b[5] : b[1]) - c.position[1];
-            cp[k][2] = (double)((k & 4) ? b[6] : b[2]) - c.position[2];
-            if (!std::isfinite(cp[k][0]) || !std::isfinite(cp[k][1]) || !std::isfinite(cp[k][2])) ok = false;
-            if (ok && dof) {
-                const double mu = cp[k][2] / (zsign * 11.0);             // focalDistance 11 (src/pathtrace.cu:238)
-                if (!(mu > 1e-3)) { ok = false; break; }                 // not in front of the lens plane: no bound from this corner
-                rho = std::max(rho, 0.8 * std::fabs(1.0 - 1.0 / mu) * 1.0001 + 1e-6);      // lensRadius .8 (:237)
-            }
-        }
-        for (int k = 0; k < 8 && ok; k++) {
-            if (!dof) {
-                double x, y;
-                if (!project(cp[k], x, y)) { ok = false; break; }
-                xlo = std::min(xlo, x); xhi = std::max(xhi, x); ylo = std::min(ylo, y); yhi = std::max(yhi, y);
-                continue;
-            }
-            const double mu = cp[k][2] / (zsign * 11.0);
-            const double fx = cp[k][0] / mu, fy = cp[k][1] / mu;         // the corner's image on the focus plane (relative to the eye)
-            for (int q = 0; q < 4 && ok; q++) {
-                const double p[3] = {fx + ((q & 1) ? rho : -rho), fy + ((q & 2) ? rho : -rho), zsign * 11.0};
-                double x, y;
-                if (!project(p, x, y)) { ok = false; break; }
-                xlo = std::min(xlo, x); xhi = std::max(xhi, x); ylo = std::min(ylo, y); yhi = std::max(yhi, y);
-            }
-        }
-        if (!ok || !(xlo <= xhi) || !(ylo <= yhi)) continue;
-        // a pixel's rays cover [x - 0.5, x + 0.5] (antialiasing jitter, generateRay); two more pixels for the fp32 ray arithmetic
-        const double m = 2.5;
-        r[0] = (int)std::max(0.0, std::min((double)W, std::floor(xlo - m)));
-        r[1] = (int)std::max(-1.0, std::min((double)W - 1, std::ceil(xhi + m)));
-        r[2] = (int)std::max(0.0, std::min((double)H, std::floor(ylo - m)));
-        r[3] = (int)std::max(-1.0, std::min((double)H - 1, std::ceil(yhi + m)));
-    }
-    masks.assign((size_t)maxTiles, 0u);
-    auto owned_xy = [&](int i, int &x, int &y) {                        // = owned_pixel (device)
-        const int r = i / W;
-        x = i - r * W;
-        if (tm.tile_world <= 1) { y = r; return; }
-        const int k = r / tm.tile_rows;
-        y = (k * tm.tile_world + tm.tile_rank) * tm.tile_rows + (r - k * tm.tile_rows);
-    };
-    for (int tile = 0; tile < maxTiles; tile++) {
-        const int i0 = tile * TILE, i1 = std::min(i0 + TILE, tm.owned) - 1;
-        if (i1 < i0) { masks[tile] = 0xffffffffu; continue; }
-        int x0, y0, x1, y1;
-        owned_xy(i0, x0, y0); owned_xy(i1, x1, y1);
-        if (y0 != y1) { x0 = 0; x1 = W - 1; }                            // wraps: whole rows y0 .. y1 (rows of other ranks in between included)
-        uint32_t m = 0;
-        for (int g = 0; g < ngeoms; g++) {
-            const int *r = &rect[(size_t)g * 4];
-            if (!(r[1] < x0 || r[0] > x1 || r[3] < y0 || r[2] > y1)) m |= 1u << g;
-        }
-        masks[tile] = m;
-    }
-}
-
 int update_tile_geoms(ptx_tracer *t) {
     t->tile_geoms_valid = false;
     if (!t->cull || t->ngeoms > 32 || t->ngeoms < 1 || getenv("PTX_DEBUG_NO_TILE_GEOMS")) return PTX_OK;
     const bool dof = t->opt.depth_of_field != 0;
     if (dof && getenv("PTX_DEBUG_NO_TILE_GEOMS_DOF")) return PTX_OK;
     std::vector<uint32_t> masks;
-    tile_geom_masks(t->cam, t->tm, t->maxTiles, t->ngeoms, t->h_aabb.data(), dof, masks);
+    tile_geom_masks(t->cam, t->tm.tile_rows, t->tm.tile_rank, t->tm.tile_world, t->tm.owned, t->maxTiles, t->ngeoms, t->h_aabb.data(), dof, masks);
     HIPCHECK(hipMemcpyAsync(t->d_tile_geoms, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));      // (masks is a local)
     t->tile_geoms_valid = true;
@@ -600,13 +415,6 @@ int free_tracer(ptx_tracer *t) {
     hipSetDevice(t->device);
     if (t->stream) hipStreamSynchronize(t->stream);
     for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) hipStreamSynchronize(t->lane_stream[l]);      // work traced ahead
-    hipFree(t->d_geoms); hipFree(t->d_mats); hipFree(t->d_faces); hipFree(t->d_tri9); hipFree(t->d_gtab); hipFree(t->d_aabb); hipFree(t->d_tile_geoms); hipFree(t->d_bvh_nodes); hipFree(t->d_bvh_tris); hipFree(t->d_bvh_root); hipFree(t->d_bvh_depth); hipFree(t->d_bvh_wide); hipFree(t->d_bvh_wroot); hipFree(t->d_bvh_wneed); hipFree(t->d_keys); hipFree(t->d_tile_done); hipFree(t->d_items); hipFree(t->d_item_count); hipFree(t->d_fnorm); hipFree(t->d_cnorm); hipFree(t->d_ldsblob); hipFree(t->d_texels);
-    if (t->own_image) hipFree(t->d_image);
-    for (int k = 0; k < 3; k++) { hipFree(t->d_fbuf[k]); hipFree(t->d_ibuf[k]); }
-    hipFree(t->d_cache_chunk); hipFree(t->d_cache_super);
-    hipFree(t->d_counts); hipFree(t->d_chunk); hipFree(t->d_totals); hipFree(t->d_cache_totals);
-    hipFree(t->d_emit_count); hipFree(t->d_emit_pix); hipFree(t->d_emit_rgb); hipFree(t->d_stats); hipFree(t->d_cap); hipFree(t->d_cap_f); hipFree(t->d_part); hipFree(t->d_albedo); hipFree(t->d_stamps); hipFree(t->d_pbo); hipFree(t->d_denoised);
-    hipFree(t->d_gbuf); hipFree(t->d_dn_tmp); hipFree(t->d_dn_out); hipFree(t->d_spec); hipFree(t->d_var);
     for (hipEvent_t e : t->kev) hipEventDestroy(e);
     if (t->ev_start) hipEventDestroy(t->ev_start);
     if (t->ev_stop) hipEventDestroy(t->ev_stop);
@@ -617,7 +425,7 @@ int free_tracer(ptx_tracer *t) {
     for (hipEvent_t e : t->ev_ahead0) if (e) hipEventDestroy(e);
     for (hipEvent_t e : t->ev_ahead1) if (e) hipEventDestroy(e);
     if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
-    delete t;
+    delete t;                                            // (the device buffers go with it: DevBuf)
     return PTX_OK;
 }
 
@@ -963,16 +771,6 @@ int ahead_finish_segment(ptx_tracer *t, int lane, int seg) {
     return PTX_OK;
 }
 
-// device scratch of the per-stage entry points: freed on every way out (a HIPCHECK that fails returns from the middle)
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    operator T *() const { return p; }
-};
-
 }  // namespace
 
 extern "C" {
@@ -1014,9 +812,56 @@ int ptx_create(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_mate
     }
 }
 
+// Iterations per launch set and launch sets in flight, from sizes alone: the explicit option, or the rule below (about 24 M paths per
+// set, within a quarter of the device's memory: mem_free / mem_total, 0 = unknown; budget_mb > 0 = PTX_DEBUG_MEM_BUDGET_MB, tests only),
+// then the cap of the out-of-memory retry (kmax_cap > 0), 64, and the 4 GiB of the prefix tables.  refusal: non-empty = nothing fits.
+struct LaunchPlan { int kmax = 1, lanes = 1; std::string refusal; };
+static LaunchPlan plan_launch_sets(int owned_pixels, int nbins, int maxTiles, const ptx_options &opt, int kmax_cap, size_t mem_free, size_t mem_total,
+                                   long long budget_mb) {
+    LaunchPlan p;
+    // three launch sets in flight (one per stream) unless told otherwise: kernels of different sets overlap and
+    // kernel tails are filled (C4, iterations per set x sets: 8 x 1 0.41, 8 x 2 0.30, 12 x 3 0.276, 12 x 4 0.31 ms per
+    // iteration); also with one iteration per launch set, i.e. frames so large that only one fits the memory rule below
+    // (7680 x 4320: 6.2 -> 4.75 ms per iteration); needs the per-iteration radiance buffers
+    p.lanes = opt.lanes >= 1 ? std::min(opt.lanes, MAX_LANES) : 3;
+    // With the first-bounce cache the iterations of a batch all start from the one cached bounce-0 stream
+    int kmax = opt.batch;
+    if (kmax <= 0) {
+        // about 24 M paths per launch set, at least 12 iterations: 12 of a 1080p frame, up to 32 of a small frame or of one rank's tile
+        // (1/8 of 1080p: 0.058 -> 0.048 ms per iteration with 32 instead of 8), fewer only where the streams of all launch sets in
+        // flight (two stages of 19 words + radiance + the split search's keys and queue = 176 B per path and iteration) would pass
+        // 64 GB of the 288.  Round 4: 12 instead of 5 at 3840x2160 (the rule was 16 GB with a guessed 400 B per path): every kernel of the
+        // split bounce gets 2.4x the work per launch -- C5 1.23 -> 1.17 ms per iteration with round 3's kernels, and what the refilling
+        // k_mesh needs: 1.4 M parked rays per launch instead of 0.6 M for the chip's 330 k lanes.
+        // Round 5: the 64 GB are a ceiling, not a constant -- a quarter of what the device (a CPX / NPS partition, a GPU shared by
+        // several ranks) has free or in total, whichever is less; and an allocation that still fails is retried with half the
+        // iterations per set (ptx_create) before the caller is told.
+        const long long owned = std::max(owned_pixels, 1);
+        long long want = ((24LL << 20) + owned / 2) / owned;
+        want = std::min<long long>(32, std::max<long long>(12, want));
+        long long budget = 64LL << 30;
+        if (mem_total > 0) budget = std::min<long long>(budget, (long long)(std::min(mem_free, mem_total) / 4));
+        if (budget_mb > 0) budget = budget_mb << 20;
+        kmax = (int)std::min<long long>(want, std::max<long long>(1, budget / (176LL * p.lanes * owned)));
+    }
+    if (kmax_cap > 0 && kmax > kmax_cap) kmax = kmax_cap;      // (the retry after an allocation failed)
+    if (kmax > 64) kmax = 64;
+    // the per-tile prefix tables grow with bins x tiles x iterations in flight: keep them under 4 GiB by putting fewer
+    // iterations into a launch set, then fewer launch sets in flight
+    auto counts_bytes = [&](int k, int l) { return sizeof(int32_t) * (2 * (size_t)nbins + 1) * maxTiles * (size_t)k * l; };
+    while (counts_bytes(kmax, p.lanes) > (4ULL << 30) && kmax > 1) kmax /= 2;
+    if (counts_bytes(kmax, p.lanes) > (4ULL << 30)) p.lanes = 1;
+    if (counts_bytes(kmax, 1) > (4ULL << 30))
+        p.refusal = "material sort over " + std::to_string(nbins) + " materials on " + std::to_string(maxTiles) +
+                    " tiles needs more than 4 GiB of prefix tables: render with sort_by_material = 0";
+    p.kmax = kmax;
+    return p;
+}
+
 static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials,
                          const ptx_camera *camera, int trace_depth, const ptx_options *options, float *external_image,
                          void *stream, ptx_tracer **out, int kmax_cap, bool *oom, int *kmax_used) {
+    // ---- 1. the arguments
     if (!out) return set_error(PTX_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (ngeoms < 0 || nmaterials < 0 || (ngeoms && !geoms) || (nmaterials && !materials) || !camera)
@@ -1035,6 +880,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
             return set_error(PTX_ERR_INVALID, "geom " + std::to_string(i) + " refers to a material that does not exist");
         if (geoms[i].faceSize < 0 || (geoms[i].faceSize > 0 && !geoms[i].faces)) return set_error(PTX_ERR_INVALID, "bad face array");
     }
+    // ---- 2. the device and the code object of the arithmetic level
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return set_error(PTX_ERR_NODEVICE, "no HIP device available; this library has no CPU path");
@@ -1042,7 +888,6 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     if (dev < 0) HIPCHECK(hipGetDevice(&dev));
     if (dev >= ndev) return set_error(PTX_ERR_INVALID, "device ordinal out of range");
     HIPCHECK(hipSetDevice(dev));
-
     const KernelSet *ks = static_cast<const KernelSet *>(ptx_arith_kernels_0());
     if (opt.arith != PTX_ARITH_EXACT) {
         const void *tab = opt.arith == 1 ? (ptx_arith_kernels_1 ? ptx_arith_kernels_1() : nullptr)
@@ -1053,37 +898,59 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         if (ks->arith != opt.arith) return set_error(PTX_ERR_HIP, "arithmetic code object mismatch");
     }
     ptx_tracer *t = new ptx_tracer;
+    auto fail = [&](int code) { free_tracer(t); return code; };
+#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(PTX_ERR_HIP); } } while (0)
     t->ks = ks;
-    t->device = dev; t->opt = opt; t->traceDepth = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
+    t->device = dev; t->opt = opt; t->traceDepth = t->maxBounces = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
+    hipDeviceProp_t prop;
+    HC(hipGetDeviceProperties(&prop, dev));
+    // ---- 3. tile split: rows owned by this device, and the grid its tiles can use
     camera_to_device(*camera, t->cam);
     const int W = t->cam.resx, H = t->cam.resy;
-    // tile split: rows owned by this device
     t->tm.W = W; t->tm.H = H; t->tm.tile_world = opt.tile_world; t->tm.tile_rank = opt.tile_rank;
     t->tm.tile_rows = opt.tile_world > 1 ? opt.tile_rows : H;
     fastdiv_magic((uint32_t)W, t->tm.w_mul, t->tm.w_sh);
     fastdiv_magic((uint32_t)t->tm.tile_rows, t->tm.rows_mul, t->tm.rows_sh);
-    int owned_rows = 0;
-    if (opt.tile_world <= 1) owned_rows = H;
-    else for (int y = 0; y < H; y++) if ((y / opt.tile_rows) % opt.tile_world == opt.tile_rank) owned_rows++;
-    t->tm.owned = owned_rows * W;
+    t->tm.owned = owned_pixels(W, H, t->tm.tile_rows, opt.tile_rank, opt.tile_world);
     t->maxTiles = (std::max(t->tm.owned, 1) + TILE - 1) / TILE;
     t->cap = t->maxTiles * TILE;                          // whole tiles: the stage is written tile by tile
     t->nbins = opt.sort_by_material ? (nmaterials > 0 ? nmaterials : 1) : 1;
-    t->maxBounces = trace_depth;
-    hipDeviceProp_t prop;
-    auto fail = [&](int code) { free_tracer(t); return code; };
-#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(PTX_ERR_HIP); } } while (0)
-    HC(hipGetDeviceProperties(&prop, dev));
     {
         int per_cu = 16;                      // upper bound (sizes the per-workgroup tables); enqueue_batch picks 7, 8 or 16 per CU
         if (const char *e = getenv("PTX_DEBUG_WG_PER_CU")) { per_cu = std::max(1, atoi(e)); t->grid_forced = true; }      // tuning experiments only
         t->cus = prop.multiProcessorCount;
         // (also for K segments in one launch: a 1/8 tile's ten iterations as 10 x 101 workgroups of 10 tiles run 6 % FASTER than as
         // 10 x 128 of 8 -- a grid that does not quite fill the chip leaves room for the other launch set's kernel to start)
-        t->grid = std::min(t->maxTiles, prop.multiProcessorCount * per_cu);
+        t->grid = std::max(1, std::min(t->maxTiles, prop.multiProcessorCount * per_cu));
     }
-    if (t->grid < 1) t->grid = 1;
     t->grid_seg = std::max(1, std::min(t->grid, t->maxTiles));      // what one segment (iteration) can use: sizes its tables
+    t->nsuper = (t->grid_seg + 63) / 64;
+    // ---- 4. the scene's tables, on the host (pt_scene.hip)
+    HostScene hs;
+    SceneSwitches sw;
+    sw.no_wide_bvh = getenv("PTX_DEBUG_NO_WIDE_BVH") != nullptr; sw.no_chunks = getenv("PTX_DEBUG_NO_CHUNKS") != nullptr;
+    sw.no_dir_skip = getenv("PTX_DEBUG_NO_DIR_SKIP") != nullptr; sw.no_normal_codes = getenv("PTX_DEBUG_NO_NORMAL_CODES") != nullptr;
+    sw.force_split = getenv("PTX_DEBUG_FORCE_SPLIT") != nullptr;
+    if (const int rc = pt_prepare_scene(ngeoms, geoms, nmaterials, materials, opt, t->tm.owned, t->nbins, prop.sharedMemPerBlock, sw, hs)) return fail(rc);
+    static_cast<SceneFacts &>(*t) = hs;
+    // ---- 5. iterations per launch set, launch sets in flight
+    {
+        size_t mem_free = 0, mem_total = 0;
+        if (opt.batch <= 0 && hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { mem_free = mem_total = 0; (void)hipGetLastError(); }
+        const char *e = getenv("PTX_DEBUG_MEM_BUDGET_MB");      // tests only
+        const LaunchPlan plan = plan_launch_sets(t->tm.owned, t->nbins, t->maxTiles, opt, kmax_cap, mem_free, mem_total, e ? std::max(1LL, atoll(e)) : 0);
+        if (!plan.refusal.empty()) { set_error(PTX_ERR_UNSUPPORTED, plan.refusal); return fail(PTX_ERR_UNSUPPORTED); }
+        t->kmax = *kmax_used = plan.kmax;
+        t->lanes = plan.lanes;
+    }
+    t->no_fast = getenv("PTX_DEBUG_NO_FAST") != nullptr;
+    t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
+    if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
+    if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));
+    if (const char *e = getenv("PTX_DEBUG_EXTRA_LDS")) t->dbg_extra_lds = std::max(0, std::min(atoi(e), 32768)) & ~15;
+    if (const char *e = getenv("PTX_DEBUG_MESH_WG_PER_CU")) t->dbg_mesh_wg_per_cu = std::max(0, atoi(e));
+    if (const char *e = getenv("PTX_DEBUG_SPLIT_MIN")) t->split_min_paths = std::max(1LL, atoll(e));      // tuning experiments only
+    // ---- 6. streams and events
     if (stream) { t->stream = (hipStream_t)stream; t->own_stream = false; }
     else {
         // the main stream carries what a caller waits for (per-call gather, preview, frame read-back) while the other lanes
@@ -1096,256 +963,6 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         t->own_stream = true;
     }
     HC(hipEventCreate(&t->ev_start)); HC(hipEventCreate(&t->ev_stop));
-
-    // scene upload (pathtraceInit, src/pathtrace.cu:111-146) -- flattened, no host struct is mutated
-    std::vector<DGeom> hg((size_t)std::max(ngeoms, 1));
-    std::vector<float> hfaces;
-    std::vector<uint8_t> htex;
-    for (int i = 0; i < ngeoms; i++) {
-        const ptx_geom &g = geoms[i];
-        DGeom &d = hg[i];
-        memset(&d, 0, sizeof d);
-        memcpy(d.xf, g.transform, 64); memcpy(d.inv, g.inverseTransform, 64); memcpy(d.invT, g.invTranspose, 64);
-        d.type = g.type; d.materialid = g.materialid;
-        d.faceStart = (int32_t)(hfaces.size() / 15); d.faceCount = g.faceSize;
-        if (g.faceSize) hfaces.insert(hfaces.end(), g.faces, g.faces + (size_t)g.faceSize * 15);
-        const ptx_texture *tx[4] = {&g.kd, &g.ks, &g.ke, &g.bump};
-        for (int k = 0; k < 4; k++) {
-            DTex &dt = d.tex[k];
-            if (tx[k]->channels > 0 && tx[k]->image && tx[k]->width > 0 && tx[k]->height > 0) {
-                if (tx[k]->channels < 3) { set_error(PTX_ERR_UNSUPPORTED, "textures need >= 3 channels"); return fail(PTX_ERR_UNSUPPORTED); }
-                dt.w = tx[k]->width; dt.h = tx[k]->height; dt.ch = tx[k]->channels; dt.off = htex.size();
-                t->uses_uv = 1;
-                size_t nbytes = (size_t)dt.w * dt.h * dt.ch;
-                htex.insert(htex.end(), tx[k]->image, tx[k]->image + nbytes);
-            }
-        }
-    }
-    // upload-time triangle table for the intersection loop: v0, e1 = v1 - v0, e2 = v2 - v0
-    t->ntri = (int)(hfaces.size() / 15);
-    std::vector<float> htri9((size_t)std::max(t->ntri, 1) * 9, 0.f);
-    for (int j = 0; j < t->ntri; j++) {
-        const float *f = &hfaces[(size_t)j * 15];
-        float *o = &htri9[(size_t)j * 9];
-        for (int k = 0; k < 3; k++) { o[k] = f[k]; o[3 + k] = f[5 + k] - f[k]; o[6 + k] = f[10 + k] - f[k]; }
-    }
-    // a BVH for every mesh with enough faces to repay it (pt_bvh.h); its nodes and leaf triangles stay in global memory
-    {
-        BvhBuild bb;
-        std::vector<int32_t> roots((size_t)std::max(ngeoms, 1), -1), depths((size_t)std::max(ngeoms, 1), 0);
-        std::vector<int32_t> wroots((size_t)std::max(ngeoms, 1), -1), wneeds((size_t)std::max(ngeoms, 1), 0);
-        const bool use_wide = getenv("PTX_DEBUG_NO_WIDE_BVH") == nullptr;          // (A/B timing, tests of both walks)
-        for (int i = 0; i < ngeoms; i++)
-            if (hg[i].type == G_OBJ && hg[i].faceCount >= BVH_MIN_FACES && !opt.no_bvh) {
-                roots[i] = bvhBuild(hfaces.data(), htri9.data(), hg[i].faceStart, hg[i].faceCount, bb, &depths[i], &wroots[i], &wneeds[i]);
-                if (!use_wide) wroots[i] = -1;
-                t->bvh_meshes++;
-            }
-        t->bvh_nodes = (int)(bb.nodes.size() / 2);
-        {   // stack entries per lane for k_mesh: deepest tree + 1 (a tree of depth d needs d + 1), at least 8, at most BVH_STACK
-            int deepest = 0;
-            // (a tree walks its four-wide nodes when their walk fits BVH_STACK entries, else the binary tree front to back when
-            // that fits, else the skip links: the stack is as long as the longest walk that is taken)
-            for (int i = 0; i < ngeoms; i++) {
-                if (roots[i] < 0) continue;
-                if (wroots[i] >= 0 && wneeds[i] <= BVH_STACK) deepest = std::max(deepest, wneeds[i] - 1);
-                else if (depths[i] < BVH_STACK) deepest = std::max(deepest, depths[i]);
-            }
-            t->bvh_stack = std::min(BVH_STACK, std::max(8, deepest + 1));
-        }
-        if (!t->bvh_meshes && !getenv("PTX_DEBUG_NO_CHUNKS"))          // spread the loops of small meshes over lanes (tileIntersect)
-            for (int i = 0; i < ngeoms; i++)
-                if (hg[i].type == G_OBJ) t->mesh_chunks = std::max(t->mesh_chunks, (hg[i].faceCount + MESH_CHUNK - 1) / MESH_CHUNK);
-        if (t->bvh_meshes) {
-            HC(hipMalloc(&t->d_bvh_nodes, sizeof(BvhQuad) * bb.nodes.size()));
-            HC(hipMemcpy(t->d_bvh_nodes, bb.nodes.data(), sizeof(BvhQuad) * bb.nodes.size(), hipMemcpyHostToDevice));
-            HC(hipMalloc(&t->d_bvh_tris, sizeof(float) * bb.tris.size()));
-            HC(hipMemcpy(t->d_bvh_tris, bb.tris.data(), sizeof(float) * bb.tris.size(), hipMemcpyHostToDevice));
-            HC(hipMalloc(&t->d_bvh_root, sizeof(int32_t) * roots.size()));
-            HC(hipMemcpy(t->d_bvh_root, roots.data(), sizeof(int32_t) * roots.size(), hipMemcpyHostToDevice));
-            HC(hipMalloc(&t->d_bvh_depth, sizeof(int32_t) * depths.size()));
-            HC(hipMemcpy(t->d_bvh_depth, depths.data(), sizeof(int32_t) * depths.size(), hipMemcpyHostToDevice));
-            if (use_wide && !bb.wide.empty()) {
-                HC(hipMalloc(&t->d_bvh_wide, sizeof(BvhWide4) * bb.wide.size()));
-                HC(hipMemcpy(t->d_bvh_wide, bb.wide.data(), sizeof(BvhWide4) * bb.wide.size(), hipMemcpyHostToDevice));
-                HC(hipMalloc(&t->d_bvh_wroot, sizeof(int32_t) * wroots.size()));
-                HC(hipMemcpy(t->d_bvh_wroot, wroots.data(), sizeof(int32_t) * wroots.size(), hipMemcpyHostToDevice));
-                HC(hipMalloc(&t->d_bvh_wneed, sizeof(int32_t) * wneeds.size()));
-                HC(hipMemcpy(t->d_bvh_wneed, wneeds.data(), sizeof(int32_t) * wneeds.size(), hipMemcpyHostToDevice));
-            }
-        }
-    }
-    // materials and geom tables go to LDS; the triangle tables join them when that leaves room for at least 2 workgroups
-    // per CU (160 KB LDS, ~19 KB of sort buffers) -- otherwise they are read from global memory (L2-resident)
-    t->tri_lds = (((size_t)nmaterials * 11 + (size_t)ngeoms * 58) * 4 <= 56 * 1024 && !opt.no_lds_triangles) ? 1 : 0;
-    t->ntri_lds = (t->tri_lds && ((size_t)t->ntri * 27 + (size_t)nmaterials * 11 + (size_t)ngeoms * 58) * 4 <= 56 * 1024) ? t->ntri : 0;
-    {   // k_bounce's dynamic LDS grows with the scene (tables) and with the number of material bins (ranking histogram):
-        // check it against the device limit here, where the caller can be told, not at the first launch.  Step down first
-        // (triangle tables, then all tables, to global memory: the plain per-ray loop over the geoms takes over), refuse
-        // only what cannot run at all.
-        const size_t limit = prop.sharedMemPerBlock;
-        auto need = [&]() { return sizeof(int32_t) * (bounceLdsWords(t->tri_lds ? sceneTableWords(t->ntri_lds, nmaterials, ngeoms) : 0, t->nbins) + QUEUE_WORDS); };
-        if (need() > limit && t->ntri_lds) t->ntri_lds = 0;
-        if (need() > limit && t->tri_lds) t->tri_lds = 0;
-        if (need() > limit) {
-            set_error(PTX_ERR_UNSUPPORTED, "material sort over " + std::to_string(t->nbins) + " materials needs " + std::to_string(need()) +
-                      " bytes of LDS per workgroup, the device offers " + std::to_string(limit) + ": render with sort_by_material = 0 (same image "
-                      "only if the reference is built with SORT_BY_MATERIAL 0 too)");
-            return fail(PTX_ERR_UNSUPPORTED);
-        }
-    }
-    // per-geom table for the per-lane gathers (rows 0-2 of the three matrices) and conservative world boxes
-    std::vector<float> hgtab((size_t)std::max(ngeoms, 1) * 40, 0.f), haabb((size_t)std::max(ngeoms, 1) * 8, 0.f);
-    for (int i = 0; i < ngeoms; i++) {
-        const DGeom &d = hg[i];
-        float *o = &hgtab[(size_t)i * 40];
-        const float *mats3[3] = {d.inv, d.xf, d.invT};
-        for (int m = 0; m < 3; m++)
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 4; c++) o[m * 12 + r * 4 + c] = mats3[m][c * 4 + r];
-        int32_t ints[4] = {d.type, d.materialid, d.faceStart, d.faceCount};
-        memcpy(o + 36, ints, sizeof ints);
-        float box[6];
-        make_world_aabb(d, hfaces, box);
-        for (int k = 0; k < 3; k++) { haabb[(size_t)i * 8 + k] = box[k]; haabb[(size_t)i * 8 + 4 + k] = box[3 + k]; }
-        if (i < 32) {
-            if (d.type == G_OBJ) t->mesh_bits |= 1u << i;
-            else if (d.type == G_CUBE) t->cube_bits |= 1u << i;
-            else if (d.type == G_SPHERE) t->sphere_bits |= 1u << i;
-        }
-    }
-    t->cull = (t->tri_lds && ngeoms >= 1 && ngeoms <= 32 && !opt.no_cull) ? 1 : 0;
-    {   // normals that do not depend on the ray, computed once with the device's own functions (compiled for the host with
-        // the same flags: no contraction, IEEE divide and square root), so the kernels read what they would have computed
-        std::vector<float> hfn((size_t)std::max(t->ntri, 1) * 3, 0.f), hcn((size_t)std::max(ngeoms, 1) * 18, 0.f);
-        for (int i = 0; i < ngeoms; i++) {
-            const DGeom &d = hg[i];
-            if (d.type == G_OBJ) {
-                if (d.tex[3].ch && i < 32) t->bump_bits |= 1u << i;
-                for (int j = 0; j < d.faceCount; j++) {          // meshIntersectionTest, src/intersections.h:237-243
-                    const float *tri = &hfaces[((size_t)d.faceStart + j) * 15];
-                    const vec3 e1 = sub(ld3(tri + 5), ld3(tri)), e2 = sub(ld3(tri + 10), ld3(tri));
-                    const vec3 objN = normalize(cross(e1, e2));
-                    const vec3 n = normalize(multiplyMV(d.invT, objN, 0.f));
-                    float *o = &hfn[((size_t)d.faceStart + j) * 3];
-                    o[0] = n.x; o[1] = n.y; o[2] = n.z;
-                }
-            } else if (d.type == G_CUBE) {                       // boxIntersectionTest, src/intersections.h:86
-                const float *invT = &hgtab[(size_t)i * 40 + 24];
-                for (int side = 0; side < 6; side++) {
-                    const int axis = side >> 1;
-                    const float sgn = (side & 1) ? 1.f : -1.f;
-                    const vec3 e = V3(axis == 0 ? sgn : 0.f, axis == 1 ? sgn : 0.f, axis == 2 ? sgn : 0.f);
-                    const vec3 n = normalize(mulRows(invT, e, 0.0f));
-                    float *o = &hcn[(size_t)i * 18 + side * 3];
-                    o[0] = n.x; o[1] = n.y; o[2] = n.z;
-                }
-            }
-        }
-        if (ngeoms > 32) t->bump_bits = 0xffffffffu;          // (no per-geom bit beyond 32 geoms: such scenes do not take the tile path)
-        HC(hipMalloc(&t->d_fnorm, sizeof(float) * hfn.size()));
-        HC(hipMemcpy(t->d_fnorm, hfn.data(), sizeof(float) * hfn.size(), hipMemcpyHostToDevice));
-        HC(hipMalloc(&t->d_cnorm, sizeof(float) * hcn.size()));
-        HC(hipMemcpy(t->d_cnorm, hcn.data(), sizeof(float) * hcn.size(), hipMemcpyHostToDevice));
-    }
-    if (hfaces.empty()) hfaces.resize(15, 0.f);
-    if (htex.empty()) htex.resize(16, 0);
-    std::vector<DMaterial> hm((size_t)std::max(nmaterials, 1));
-    static_assert(sizeof(DMaterial) == sizeof(ptx_material), "material layout");
-    if (nmaterials) memcpy(hm.data(), materials, sizeof(DMaterial) * (size_t)nmaterials);
-    for (const DMaterial &m : hm) t->h_spec.push_back(m.hasReflective > 0.0f || m.hasRefractive > 0.0f ? 1 : 0);
-    {   // which records carry what (record_masks); off: more than 64 bins, no material, or PTX_DEBUG_NO_DIR_SKIP
-        unsigned long long need = ~0ull, cubes = 0ull;
-        const bool off = t->nbins > 64 || nmaterials < 1 || getenv("PTX_DEBUG_NO_DIR_SKIP") != nullptr;
-        if (!off) {
-            std::vector<int> gt((size_t)ngeoms), gm((size_t)ngeoms);
-            for (int i = 0; i < ngeoms; i++) { gt[i] = hg[i].type; gm[i] = hg[i].materialid; }
-            record_masks(nmaterials, hm.data(), ngeoms, gt.data(), gm.data(), opt.sort_by_material != 0, need, cubes);
-        }
-        t->dir_bins = off ? ~0ull : need;
-        // (the code rides in bits 28-30 of the pixel slot; the tabulated normals are what the tile path's decodeKey reads)
-        t->ntab_bins = (off || !t->cull || t->tm.owned >= (1 << 28) || getenv("PTX_DEBUG_NO_NORMAL_CODES")) ? 0ull : cubes;
-    }
-    HC(hipMalloc(&t->d_geoms, sizeof(DGeom) * hg.size()));
-    HC(hipMemcpy(t->d_geoms, hg.data(), sizeof(DGeom) * hg.size(), hipMemcpyHostToDevice));
-    HC(hipMalloc(&t->d_mats, sizeof(DMaterial) * hm.size()));
-    HC(hipMemcpy(t->d_mats, hm.data(), sizeof(DMaterial) * hm.size(), hipMemcpyHostToDevice));
-    HC(hipMalloc(&t->d_faces, sizeof(float) * hfaces.size()));
-    HC(hipMemcpy(t->d_faces, hfaces.data(), sizeof(float) * hfaces.size(), hipMemcpyHostToDevice));
-    HC(hipMalloc(&t->d_tri9, sizeof(float) * htri9.size()));
-    HC(hipMemcpy(t->d_tri9, htri9.data(), sizeof(float) * htri9.size(), hipMemcpyHostToDevice));
-    HC(hipMalloc(&t->d_gtab, sizeof(float) * hgtab.size()));
-    HC(hipMemcpy(t->d_gtab, hgtab.data(), sizeof(float) * hgtab.size(), hipMemcpyHostToDevice));
-    {   // (the device reads the boxes as centre + half extent; the host keeps corners for the camera tile masks)
-        std::vector<float> hch(haabb.size(), 0.f);
-        for (int i = 0; i < ngeoms; i++) world_box_centre_half(&haabb[(size_t)i * 8], &hch[(size_t)i * 8]);
-        HC(hipMalloc(&t->d_aabb, sizeof(float) * hch.size()));
-        HC(hipMemcpy(t->d_aabb, hch.data(), sizeof(float) * hch.size(), hipMemcpyHostToDevice));
-    }
-    t->h_aabb = haabb;
-    HC(hipMalloc(&t->d_texels, htex.size()));
-    HC(hipMemcpy(t->d_texels, htex.data(), htex.size(), hipMemcpyHostToDevice));
-
-    const size_t npix = (size_t)W * H;
-    if (external_image) { t->d_image = external_image; t->own_image = false; }
-    else {
-        HC(hipMalloc(&t->d_image, sizeof(float) * 3 * npix));
-        HC(hipMemset(t->d_image, 0, sizeof(float) * 3 * npix));
-        t->own_image = true;
-    }
-    // iterations per launch set: explicit option, or the rule below (about 24 M paths per set, within a quarter of the device's
-    // memory).  With the first-bounce cache the iterations of a batch all start from the one cached bounce-0 stream
-    int kmax = opt.batch;
-    if (kmax <= 0) {
-        // about 24 M paths per launch set, at least 12 iterations: 12 of a 1080p frame, up to 32 of a small frame or of one rank's tile
-        // (1/8 of 1080p: 0.058 -> 0.048 ms per iteration with 32 instead of 8), fewer only where the streams of all launch sets in
-        // flight (two stages of 19 words + radiance + the split search's keys and queue = 176 B per path and iteration) would pass
-        // 64 GB of the 288.  Round 4: 12 instead of 5 at 3840x2160 (the rule was 16 GB with a guessed 400 B per path): every kernel of the
-        // split bounce gets 2.4x the work per launch -- C5 1.23 -> 1.17 ms per iteration with round 3's kernels, and what the refilling
-        // k_mesh needs: 1.4 M parked rays per launch instead of 0.6 M for the chip's 330 k lanes.
-        // Round 5: the 64 GB are a ceiling, not a constant -- a quarter of what the device (a CPX / NPS partition, a GPU shared by
-        // several ranks) has free or in total, whichever is less; and an allocation that still fails is retried with half the
-        // iterations per set (ptx_create below) before the caller is told.
-        const long long owned = std::max(t->tm.owned, 1);
-        long long want = ((24LL << 20) + owned / 2) / owned;
-        want = std::min<long long>(32, std::max<long long>(12, want));
-        const long long nl = opt.lanes >= 1 ? std::min(opt.lanes, MAX_LANES) : 3;
-        long long budget = 64LL << 30;
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_total > 0) budget = std::min<long long>(budget, (long long)(std::min(mem_free, mem_total) / 4));
-        else (void)hipGetLastError();
-        if (const char *e = getenv("PTX_DEBUG_MEM_BUDGET_MB")) budget = std::max(1LL, atoll(e)) << 20;      // tests only
-        kmax = (int)std::min<long long>(want, std::max<long long>(1, budget / (176LL * nl * owned)));
-    }
-    if (kmax_cap > 0 && kmax > kmax_cap) kmax = kmax_cap;      // (the retry after an allocation failed)
-    if (kmax > 64) kmax = 64;
-    // the per-tile prefix tables grow with bins x tiles x iterations in flight: keep them under 4 GiB by putting fewer
-    // iterations into a launch set, then fewer launch sets in flight
-    {
-        const int want_lanes = opt.lanes >= 1 ? std::min(opt.lanes, MAX_LANES) : 3;
-        auto counts_bytes = [&](int k, int l) { return sizeof(int32_t) * (2 * (size_t)t->nbins + 1) * t->maxTiles * (size_t)k * l; };
-        while (counts_bytes(kmax, want_lanes) > (4ULL << 30) && kmax > 1) kmax /= 2;
-        if (counts_bytes(kmax, want_lanes) > (4ULL << 30)) opt.lanes = t->opt.lanes = 1;
-        if (counts_bytes(kmax, 1) > (4ULL << 30) && opt.lanes == 1) {
-            set_error(PTX_ERR_UNSUPPORTED, "material sort over " + std::to_string(t->nbins) + " materials on " + std::to_string(t->maxTiles) +
-                      " tiles needs more than 4 GiB of prefix tables: render with sort_by_material = 0");
-            return fail(PTX_ERR_UNSUPPORTED);
-        }
-    }
-    t->kmax = kmax;
-    *kmax_used = kmax;
-    // three launch sets in flight (one per stream) unless told otherwise: kernels of different sets overlap and
-    // kernel tails are filled (C4, iterations per set x sets: 8 x 1 0.41, 8 x 2 0.30, 12 x 3 0.276, 12 x 4 0.31 ms per
-    // iteration); also with one iteration per launch set, i.e. frames so large that only one fits the memory rule above
-    // (7680 x 4320: 6.2 -> 4.75 ms per iteration); needs the per-iteration radiance buffers
-    t->lanes = opt.lanes >= 1 ? std::min(opt.lanes, MAX_LANES) : 3;
-    t->no_fast = getenv("PTX_DEBUG_NO_FAST") != nullptr;
-    t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
-    if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_EXTRA_LDS")) t->dbg_extra_lds = std::max(0, std::min(atoi(e), 32768)) & ~15;
-    if (const char *e = getenv("PTX_DEBUG_MESH_WG_PER_CU")) t->dbg_mesh_wg_per_cu = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_SPLIT_MIN")) t->split_min_paths = std::max(1LL, atoll(e));      // tuning experiments only
     if (t->lanes > 1) {
         HC(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
         for (int l = 0; l < t->lanes; l++) {
@@ -1366,84 +983,63 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
             if (l) { HC(hipEventCreate(&t->ev_ahead0[l])); HC(hipEventCreate(&t->ev_ahead1[l])); }
         }
     }
-    const size_t nseg = (size_t)kmax * t->lanes;
+    // ---- 7. upload the scene, allocate the streams' buffers
+    HC(t->d_geoms.upload(hs.geoms)); HC(t->d_mats.upload(hs.mats)); HC(t->d_faces.upload(hs.faces)); HC(t->d_texels.upload(hs.texels));
+    HC(t->d_tri9.upload(hs.tri9)); HC(t->d_gtab.upload(hs.gtab)); HC(t->d_aabb.upload(hs.aabb_ch));
+    HC(t->d_fnorm.upload(hs.fnorm)); HC(t->d_cnorm.upload(hs.cnorm));
+    if (t->bvh_meshes) {
+        HC(t->d_bvh_nodes.upload(hs.bvh.nodes)); HC(t->d_bvh_tris.upload(hs.bvh.tris));
+        HC(t->d_bvh_root.upload(hs.roots)); HC(t->d_bvh_depth.upload(hs.depths));
+        if (!hs.bvh.wide.empty()) {
+            HC(t->d_bvh_wide.upload(hs.bvh.wide)); HC(t->d_bvh_wroot.upload(hs.wroots)); HC(t->d_bvh_wneed.upload(hs.wneeds));
+        }
+    }
+    if (t->tri_lds) {
+        HC(t->d_ldsblob.alloc(std::max<size_t>(hs.ldsblob.size(), 4)));
+        if (!hs.ldsblob.empty()) HC(hipMemcpy(t->d_ldsblob, hs.ldsblob.data(), sizeof(float) * hs.ldsblob.size(), hipMemcpyHostToDevice));
+    }
+    t->h_aabb = std::move(hs.aabb);                       // (the host keeps corners for the camera tile masks)
+    t->h_spec = std::move(hs.h_spec);
+    const size_t npix = (size_t)W * H, nseg = (size_t)t->kmax * t->lanes, nb = (size_t)t->nbins;
+    if (external_image) t->d_image = external_image;
+    else { HC(t->d_image_own.alloc(3 * npix)); HC(t->d_image_own.zero()); t->d_image = t->d_image_own; }
+    if (opt.apps_variant) { HC(t->d_albedo.alloc(3 * npix)); HC(t->d_albedo.zero()); }
     t->field_stride = nseg * t->cap;
-    const int nsoa = t->cache_active() ? 3 : 2;
-    for (int k = 0; k < nsoa; k++) {
+    for (int k = 0; k < (t->cache_active() ? 3 : 2); k++) {
         const size_t stride = k == 2 ? (size_t)t->cap : t->field_stride;
-        HC(hipMalloc(&t->d_fbuf[k], sizeof(float) * SOA_FLOATS * stride));
-        HC(hipMalloc(&t->d_ibuf[k], sizeof(int32_t) * SOA_INTS * stride));
+        HC(t->d_fbuf[k].alloc(SOA_FLOATS * stride));
+        HC(t->d_ibuf[k].alloc(SOA_INTS * stride));
         carve(t->soa[k], t->d_fbuf[k], t->d_ibuf[k], stride);
     }
     t->seg_part = 3 * (size_t)t->cap + (size_t)t->cap / 32;     // per-iteration radiance of the OWNED pixels (slot-indexed), whole tiles, then the
                                                                 // iteration's lit plane, a bit per slot (cap is a multiple of 256)
-    if (nseg > 1) HC(hipMalloc(&t->d_part, sizeof(float) * t->seg_part * nseg));
+    if (nseg > 1) HC(t->d_part.alloc(t->seg_part * nseg));
     for (int l = 0; l < MAX_LANES; l++) t->aux_dirty[l] = true;      // (the planes are not cleared here: each lane's first set does it)
-    {   // split mesh search: worth it when some mesh is big enough for a BVH; needs the candidate masks (cull, <= 32 geoms: a
-        // parked ray carries one bit per mesh whose box it reaches) and a queue entry per ray in the worst case
-        int nmesh = 0;
-        for (int i = 0; i < ngeoms; i++) nmesh += hg[i].type == G_OBJ ? 1 : 0;
-        t->split_mesh = t->bvh_meshes > 0 && t->cull && !opt.no_mesh_split;
-        if (getenv("PTX_DEBUG_FORCE_SPLIT")) t->split_mesh = t->cull && nmesh >= 1;      // timing experiments only
-        if (t->split_mesh) {
-            t->seg_items = (size_t)t->cap;
-            HC(hipMalloc(&t->d_keys, sizeof(unsigned long long) * (size_t)t->cap * nseg));
-            HC(hipMalloc(&t->d_items, sizeof(uint32_t) * t->seg_items * nseg));
-            HC(hipMalloc(&t->d_item_count, sizeof(int32_t) * 2 * nseg));      // [nseg] counts (pass 1), [nseg] cursors (k_mesh)
-            if (!getenv("PTX_DEBUG_NO_FIRST_FUSION")) {
-                HC(hipMalloc(&t->d_tile_done, sizeof(int32_t) * (size_t)t->maxTiles * nseg));
-                HC(hipMemset(t->d_tile_done, 0, sizeof(int32_t) * (size_t)t->maxTiles * nseg));
-            }
-        }
+    if (t->split_mesh) {                                  // a queue entry per ray in the worst case
+        t->seg_items = (size_t)t->cap;
+        HC(t->d_keys.alloc((size_t)t->cap * nseg));
+        HC(t->d_items.alloc(t->seg_items * nseg));
+        HC(t->d_item_count.alloc(2 * nseg));              // [nseg] counts (pass 1), [nseg] cursors (k_mesh)
+        if (!getenv("PTX_DEBUG_NO_FIRST_FUSION")) { HC(t->d_tile_done.alloc((size_t)t->maxTiles * nseg)); HC(t->d_tile_done.zero()); }
     }
-    if (t->tri_lds) {   // the scene tables as k_bounce stages them (split: without the triangle tables), in one array: DScene::ldsblob
-        const int nl = t->split_mesh ? 0 : t->ntri_lds;
-        const size_t n9 = (size_t)nl * 9, n15 = (size_t)nl * 15, nm = (size_t)nmaterials * 11, ng = (size_t)ngeoms * GTAB_WORDS, nf = (size_t)nl * 3, nc = (size_t)ngeoms * 18;
-        HC(hipMalloc(&t->d_ldsblob, sizeof(float) * std::max<size_t>(n9 + n15 + nm + ng + nf + nc, 4)));
-        float *o = t->d_ldsblob;
-        if (n9) HC(hipMemcpy(o, t->d_tri9, sizeof(float) * n9, hipMemcpyDeviceToDevice));
-        o += n9;
-        if (n15) HC(hipMemcpy(o, t->d_faces, sizeof(float) * n15, hipMemcpyDeviceToDevice));
-        o += n15;
-        if (nm) HC(hipMemcpy(o, t->d_mats, sizeof(float) * nm, hipMemcpyDeviceToDevice));
-        o += nm;
-        if (ng) HC(hipMemcpy(o, t->d_gtab, sizeof(float) * ng, hipMemcpyDeviceToDevice));
-        o += ng;
-        if (nf) HC(hipMemcpy(o, t->d_fnorm, sizeof(float) * nf, hipMemcpyDeviceToDevice));
-        o += nf;
-        if (nc) HC(hipMemcpy(o, t->d_cnorm, sizeof(float) * nc, hipMemcpyDeviceToDevice));
-    }
-    if (opt.apps_variant) {
-        HC(hipMalloc(&t->d_albedo, sizeof(float) * 3 * npix));
-        HC(hipMemset(t->d_albedo, 0, sizeof(float) * 3 * npix));
-    }
-    HC(hipMalloc(&t->d_counts, sizeof(int32_t) * (2 * (size_t)t->nbins + 1) * t->maxTiles * nseg));
-    t->nsuper = (t->grid_seg + 63) / 64;
-    HC(hipMalloc(&t->d_chunk, sizeof(int32_t) * 2 * 3 * (size_t)t->nbins * t->grid_seg * nseg));
-    HC(hipMemset(t->d_chunk, 0, sizeof(int32_t) * 2 * 3 * (size_t)t->nbins * t->grid_seg * nseg));
-    if (t->cache_active()) {
-        HC(hipMalloc(&t->d_cache_chunk, sizeof(int32_t) * 3 * (size_t)t->nbins * t->grid_seg));
-        HC(hipMemset(t->d_cache_chunk, 0, sizeof(int32_t) * 3 * (size_t)t->nbins * t->grid_seg));
-    }
-    t->seg_totals = 2 * (size_t)t->nbins * t->maxBounces * (1 + (size_t)t->nsuper);
+    HC(t->d_counts.alloc((2 * nb + 1) * t->maxTiles * nseg));
+    HC(t->d_chunk.alloc(2 * 3 * nb * t->grid_seg * nseg)); HC(t->d_chunk.zero());
+    if (t->cache_active()) { HC(t->d_cache_chunk.alloc(3 * nb * t->grid_seg)); HC(t->d_cache_chunk.zero()); }
+    t->seg_totals = 2 * nb * t->maxBounces * (1 + (size_t)t->nsuper);
     t->totals_bytes = sizeof(int32_t) * t->seg_totals * nseg;
-    HC(hipMalloc(&t->d_totals, t->totals_bytes));
-    HC(hipMemset(t->d_totals, 0, t->totals_bytes));
-    t->d_super = t->d_totals + 2 * (size_t)t->nbins * t->maxBounces;
-    HC(hipMalloc(&t->d_cache_totals, sizeof(int32_t) * 2 * (size_t)t->nbins));
-    HC(hipMalloc(&t->d_cache_super, sizeof(int32_t) * 2 * (size_t)t->nbins * t->nsuper));
-    HC(hipMalloc(&t->d_emit_count, sizeof(int32_t)));
-    HC(hipMemset(t->d_emit_count, 0, sizeof(int32_t)));
-    HC(hipMalloc(&t->d_emit_pix, sizeof(int32_t) * (size_t)t->cap));
-    HC(hipMalloc(&t->d_emit_rgb, sizeof(float) * 3 * (size_t)t->cap));
+    HC(t->d_totals.alloc(t->seg_totals * nseg)); HC(t->d_totals.zero());
+    t->d_super = t->d_totals + 2 * nb * t->maxBounces;
+    HC(t->d_cache_totals.alloc(2 * nb));
+    HC(t->d_cache_super.alloc(2 * nb * t->nsuper));
+    HC(t->d_emit_count.alloc(1)); HC(t->d_emit_count.zero());
+    HC(t->d_emit_pix.alloc((size_t)t->cap));
+    HC(t->d_emit_rgb.alloc(3 * (size_t)t->cap));
 #if defined(PT_STAMPS) || defined(PT_WGCLOCK)
-    HC(hipMalloc(&t->d_stamps, sizeof(unsigned long long) * (48 + 2 * 64 * 4096 * 5)));
-    HC(hipMemset(t->d_stamps, 0, sizeof(unsigned long long) * (48 + 2 * 64 * 4096 * 5)));
+    HC(t->d_stamps.alloc(48 + 2 * 64 * 4096 * 5)); HC(t->d_stamps.zero());
 #endif
-    HC(hipMalloc(&t->d_tile_geoms, sizeof(uint32_t) * (size_t)std::max(t->maxTiles, 1)));
+    HC(t->d_tile_geoms.alloc((size_t)std::max(t->maxTiles, 1)));
     if (update_tile_geoms(t) != PTX_OK) return fail(PTX_ERR_HIP);
-    HC(hipMalloc(&t->d_stats, sizeof(int64_t) * 69));
-    HC(hipMemset(t->d_stats, 0, sizeof(int64_t) * 69));
+    HC(t->d_stats.alloc(69)); HC(t->d_stats.zero());
     t->fence_slots = (uint32_t)t->cap;
     if (const char *e = getenv("PTX_DEBUG_FENCE_SLOTS")) t->fence_slots = (uint32_t)std::min<long long>(t->cap, std::max<long long>(1, atoll(e)));      // tests only
 #undef HC
@@ -1495,6 +1091,17 @@ int ptx_reset_image(ptx_tracer *t) {
 // before its first kernel starts -- what a replayed launch graph would look like from the device's side.  The loop timer starts behind it.
 namespace { __global__ void k_hold(long long ticks) { const long long t0 = wall_clock64(); while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32); } }
 
+// the previous ptx_render's time into the running total
+static int fold_render_time(ptx_tracer *t) {
+    if (!t->timing_valid) return PTX_OK;
+    float ms = 0.f;
+    HIPCHECK(hipEventSynchronize(t->ev_stop));
+    HIPCHECK(hipEventElapsedTime(&ms, t->ev_start, t->ev_stop));
+    t->loop_ms_total += ms;
+    t->timing_valid = false;
+    return PTX_OK;
+}
+
 int ptx_render(ptx_tracer *t, int iter_first, int count) { return ptx_render_strided(t, iter_first, count, 1); }
 
 int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
@@ -1503,13 +1110,7 @@ int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
     if (count <= 0) return PTX_OK;
     HIPCHECK(hipSetDevice(t->device));
     ahead_discard(t);
-    if (t->timing_valid) {          // fold the previous batch's time into the running total before reusing events
-        float ms = 0.f;
-        HIPCHECK(hipEventSynchronize(t->ev_stop));
-        HIPCHECK(hipEventElapsedTime(&ms, t->ev_start, t->ev_stop));
-        t->loop_ms_total += ms;
-        t->timing_valid = false;
-    }
+    if (const int rc = fold_render_time(t)) return rc;      // (before the events are reused)
     if (const char *e = getenv("PTX_DEBUG_PREQUEUE_US")) hipLaunchKernelGGL(k_hold, dim3(1), dim3(64), 0, t->stream, (long long)atoi(e) * 100);      // (100 MHz)
     HIPCHECK(hipEventRecord(t->ev_start, t->stream));
     // per-kernel timing and the debug capture look at one launch set at a time
@@ -1578,13 +1179,7 @@ int ptx_iterate(ptx_tracer *t, int iter) {
     if (t->ahead_cur < 0 || !t->ahead[t->ahead_cur].valid || t->ahead[t->ahead_cur].next != iter) {
         // nothing traced ahead for this iteration (first call, or the sequence jumped): start at it
         ahead_discard(t);
-        if (t->timing_valid) {      // the previous ptx_render's time, before "previous operation" becomes this call
-            float ms = 0.f;
-            HIPCHECK(hipEventSynchronize(t->ev_stop));
-            HIPCHECK(hipEventElapsedTime(&ms, t->ev_start, t->ev_stop));
-            t->loop_ms_total += ms;
-            t->timing_valid = false;
-        }
+        if (const int rc = fold_render_time(t)) return rc;      // (before "previous operation" becomes this call)
         int rc = ahead_start(t, 1, iter);
         if (rc != PTX_OK) return rc;
         t->ahead_cur = 1;
@@ -1648,14 +1243,13 @@ int ptx_write_denoised_pbo(ptx_tracer *t, const float *host_rgb, uint8_t *host_r
     if (!t || !host_rgb || !host_rgba) return set_error(PTX_ERR_INVALID, "null argument");
     HIPCHECK(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    float *d_in = nullptr; uchar4 *d_out = nullptr;
-    HIPCHECK(hipMalloc(&d_in, sizeof(float) * 3 * n));
-    HIPCHECK(hipMalloc(&d_out, 4 * n));
+    DevBuf<float> d_in; DevBuf<uchar4> d_out;
+    HIPCHECK(d_in.alloc(3 * n));
+    HIPCHECK(d_out.alloc(n));
     HIPCHECK(hipMemcpyAsync(d_in, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
-    hipLaunchKernelGGL(k_pbo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, d_out, (int)n, 1, d_in);   // iter = 1: pix / 1
+    hipLaunchKernelGGL(k_pbo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, d_out.p, (int)n, 1, d_in.p);   // iter = 1: pix / 1
     hipError_t e = hipMemcpyAsync(host_rgba, d_out, 4 * n, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    hipFree(d_in); hipFree(d_out);
     if (e != hipSuccess) return set_error(PTX_ERR_HIP, hipGetErrorString(e));
     return PTX_OK;
 }
@@ -1667,7 +1261,7 @@ int ptx_write_denoised_pbo_device(ptx_tracer *t, const float *host_rgb, void *de
     if (!device_uchar4) return PTX_OK;                    // NULL pbo => skip, like ptx_write_pbo_device
     HIPCHECK(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_denoised) HIPCHECK(hipMalloc(&t->d_denoised, sizeof(float) * 3 * n));      // dev_denoised_output, kept like the reference's
+    if (!t->d_denoised) HIPCHECK(t->d_denoised.alloc(3 * n));      // dev_denoised_output, kept like the reference's
     HIPCHECK(hipMemcpyAsync(t->d_denoised, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
     hipLaunchKernelGGL(k_pbo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, (int)n, 1, t->d_denoised);
     HIPCHECK(hipGetLastError());
@@ -1694,7 +1288,7 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
     HIPCHECK(hipSetDevice(t->device));
     size_t n = (size_t)t->cam.resx * t->cam.resy;
     // the staging buffer stays with the tracer: hipFree would wait for the whole device, i.e. for work traced ahead
-    if (!t->d_pbo) HIPCHECK(hipMalloc(&t->d_pbo, n * 4));
+    if (!t->d_pbo) HIPCHECK(t->d_pbo.alloc(n));
     int rc = ptx_write_pbo_device(t, iter, t->d_pbo);
     if (rc == PTX_OK) {
         hipError_t e = hipMemcpyAsync(host_rgba, t->d_pbo, n * 4, hipMemcpyDeviceToHost, t->stream);
@@ -1708,7 +1302,7 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
 // The G-buffer of the current camera on the tracer's stream, buffers allocated on first use
 static int ensure_gbuffer(ptx_tracer *t) {
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_gbuf) HIPCHECK(hipMalloc(&t->d_gbuf, sizeof(float4) * 3 * n + sizeof(int2) * n));
+    if (!t->d_gbuf) HIPCHECK(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
     const DScene sc = t->scene();
     hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, sc, t->cam, t->traceDepth,
@@ -1745,11 +1339,11 @@ static int denoise_begin(const std::string &fn, ptx_tracer *t, const ptx_tempora
                                               " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
     HIPCHECK(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_dn_tmp) HIPCHECK(hipMalloc(&t->d_dn_tmp, sizeof(float4) * 2 * n));
-    if (!t->d_dn_out) HIPCHECK(hipMalloc(&t->d_dn_out, sizeof(float) * 3 * n));
-    if (variance && !t->d_var) HIPCHECK(hipMalloc(&t->d_var, sizeof(float) * 2 * n));
+    if (!t->d_dn_tmp) HIPCHECK(t->d_dn_tmp.alloc(2 * n));
+    if (!t->d_dn_out) HIPCHECK(t->d_dn_out.alloc(3 * n));
+    if (variance && !t->d_var) HIPCHECK(t->d_var.alloc(2 * n));
     if (h && !t->d_spec) {
-        HIPCHECK(hipMalloc(&t->d_spec, t->h_spec.size()));
+        HIPCHECK(t->d_spec.alloc(t->h_spec.size()));
         HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
     }
     return ensure_gbuffer(t);
@@ -1967,45 +1561,31 @@ size_t ptx_sizeof_stats(void) { return sizeof(ptx_stats); }
     HIPCHECK(hipSetDevice(t->device));                                      \
     HIPCHECK(hipStreamSynchronize(t->stream));
 
-int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10) {
+// n rays against one geom, `width` floats out per ray: the whole intersection test (10) or its triangle part (8)
+static int kat_rays(ptx_tracer *t, int geom, int n, const float *rays6, float *out, int width) {
     KAT_PROLOGUE
     if (geom < 0 || geom >= t->ngeoms) return set_error(PTX_ERR_INVALID, "geom index out of range");
     if (n <= 0) return PTX_OK;
-    DevBuf<float> d_in; DevBuf<float> d_out;
-    HIPCHECK(hipMalloc(&d_in.p, sizeof(float) * 6 * (size_t)n));
-    HIPCHECK(hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
-    HIPCHECK(hipMemcpy(d_in, rays6, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
-    { const DScene sc = t->scene(); t->ks->kat_geom(dim3((n + 255) / 256), t->stream, &sc, geom, n, d_in, d_out); }
+    DevBuf<float> d_in, d_out;
+    HIPCHECK(d_in.upload(rays6, 6 * (size_t)n));
+    HIPCHECK(d_out.alloc(width * (size_t)n));
+    { const DScene sc = t->scene(); (width == 10 ? t->ks->kat_geom : t->ks->kat_obj_tri)(dim3((n + 255) / 256), t->stream, &sc, geom, n, d_in, d_out); }
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(out10, d_out, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_out.download(out));
     return PTX_OK;
 }
-
-int ptx_kat_obj_tri_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out8) {
-    KAT_PROLOGUE
-    if (geom < 0 || geom >= t->ngeoms) return set_error(PTX_ERR_INVALID, "geom index out of range");
-    if (n <= 0) return PTX_OK;
-    DevBuf<float> d_in; DevBuf<float> d_out;
-    HIPCHECK(hipMalloc(&d_in.p, sizeof(float) * 6 * (size_t)n));
-    HIPCHECK(hipMalloc(&d_out.p, sizeof(float) * 8 * (size_t)n));
-    HIPCHECK(hipMemcpy(d_in, rays6, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
-    { const DScene sc = t->scene(); t->ks->kat_obj_tri(dim3((n + 255) / 256), t->stream, &sc, geom, n, d_in.p, d_out.p); }
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(out8, d_out, sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost));
-    return PTX_OK;
-}
+int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10) { return kat_rays(t, geom, n, rays6, out10, 10); }
+int ptx_kat_obj_tri_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out8) { return kat_rays(t, geom, n, rays6, out8, 8); }
 
 int ptx_kat_jittered_hemisphere(ptx_tracer *t, int n, const float *normals3, const int32_t *seeds3, int max_iter, float *out3) {
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     if (max_iter < 1) return set_error(PTX_ERR_INVALID, "max_iter must be >= 1");
     DevBuf<float> d_n, d_o; DevBuf<int32_t> d_s;
-    HIPCHECK(hipMalloc(&d_n.p, 12 * (size_t)n)); HIPCHECK(hipMalloc(&d_o.p, 12 * (size_t)n)); HIPCHECK(hipMalloc(&d_s.p, 12 * (size_t)n));
-    HIPCHECK(hipMemcpy(d_n, normals3, 12 * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(d_s, seeds3, 12 * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(d_n.upload(normals3, 3 * (size_t)n)); HIPCHECK(d_o.alloc(3 * (size_t)n)); HIPCHECK(d_s.upload(seeds3, 3 * (size_t)n));
     t->ks->kat_jittered(dim3((n + 255) / 256), t->stream, n, d_n.p, d_s.p, max_iter, d_o.p);
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(out3, d_o, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_o.download(out3));
     return PTX_OK;
 }
 
@@ -2013,12 +1593,11 @@ int ptx_kat_compute_intersections(ptx_tracer *t, int n, const void *paths44, voi
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i;
-    HIPCHECK(hipMalloc(&d_p.p, sizeof(HostPath) * (size_t)n));
-    HIPCHECK(hipMalloc(&d_i.p, sizeof(HostIsect) * (size_t)n));
-    HIPCHECK(hipMemcpy(d_p, paths44, sizeof(HostPath) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(d_p.upload(paths44, (size_t)n));
+    HIPCHECK(d_i.alloc((size_t)n));
     { const DScene sc = t->scene(); t->ks->kat_intersect(dim3((n + 255) / 256), t->stream, &sc, n, d_p.p, d_i.p); }
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(isects32, d_i, sizeof(HostIsect) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_i.download(isects32));
     return PTX_OK;
 }
 
@@ -2028,9 +1607,8 @@ int ptx_kat_tile_intersect(ptx_tracer *t, int n, const void *paths44, void *isec
     if (!t->cull || !t->tri_lds) return set_error(PTX_ERR_UNSUPPORTED, "this scene does not take the tile path (candidate masks / LDS tables are off)");
     if (split && !t->d_bvh_root) return set_error(PTX_ERR_UNSUPPORTED, "no mesh of this scene has a BVH: nothing for the split mesh search to do");
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i;
-    HIPCHECK(hipMalloc(&d_p.p, sizeof(HostPath) * (size_t)n));
-    HIPCHECK(hipMalloc(&d_i.p, sizeof(HostIsect) * (size_t)n));
-    HIPCHECK(hipMemcpy(d_p, paths44, sizeof(HostPath) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(d_p.upload(paths44, (size_t)n));
+    HIPCHECK(d_i.alloc((size_t)n));
     // the scene as enqueue_batch hands it to k_bounce (tables staged; split: without the triangle tables) and as k_mesh gets it
     DScene sc = t->scene();
     sc.tri_lds = t->tri_lds; sc.ntri_lds = (split || t->split_mesh) ? 0 : t->ntri_lds; sc.cull = t->cull;
@@ -2050,7 +1628,7 @@ int ptx_kat_tile_intersect(ptx_tracer *t, int n, const void *paths44, void *isec
     t->ks->kat_tile(split ? 1 : 0, grid, lds, t->stream, &sc, &scg, n, d_p.p, d_i.p, t->uses_uv);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(isects32, d_i, sizeof(HostIsect) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_i.download(isects32));
     return PTX_OK;
 }
 
@@ -2058,15 +1636,10 @@ int ptx_kat_shade(ptx_tracer *t, int iter, int n, const int32_t *idx, const void
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i; DevBuf<int32_t> d_x;
-    HIPCHECK(hipMalloc(&d_p.p, sizeof(HostPath) * (size_t)n));
-    HIPCHECK(hipMalloc(&d_i.p, sizeof(HostIsect) * (size_t)n));
-    HIPCHECK(hipMalloc(&d_x.p, sizeof(int32_t) * (size_t)n));
-    HIPCHECK(hipMemcpy(d_p, paths44, sizeof(HostPath) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(d_i, isects32, sizeof(HostIsect) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(d_x, idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(d_p.upload(paths44, (size_t)n)); HIPCHECK(d_i.upload(isects32, (size_t)n)); HIPCHECK(d_x.upload(idx, (size_t)n));
     { const DScene sc = t->scene(); t->ks->kat_shade(dim3((n + 255) / 256), t->stream, &sc, iter, n, d_x.p, d_i.p, d_p.p); }
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(paths44, d_p, sizeof(HostPath) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_p.download(paths44));
     return PTX_OK;
 }
 
@@ -2074,10 +1647,10 @@ int ptx_kat_generate(ptx_tracer *t, int iter, void *paths44) {
     KAT_PROLOGUE
     int n = t->cam.resx * t->cam.resy;
     DevBuf<HostPath> d_p;
-    HIPCHECK(hipMalloc(&d_p.p, sizeof(HostPath) * (size_t)n));
+    HIPCHECK(d_p.alloc((size_t)n));
     t->ks->kat_generate(dim3((n + 255) / 256), t->stream, &t->cam, iter, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, d_p.p);
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(paths44, d_p, sizeof(HostPath) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(d_p.download(paths44));
     return PTX_OK;
 }
 
@@ -2086,18 +1659,12 @@ int ptx_kat_libm(ptx_tracer *t, int n, const float *x, float *sin_out, float *co
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<float> dx, ds, dc, dxy, dpo; DevBuf<double> dpw, dp5;
-    HIPCHECK(hipMalloc(&dx.p, 4 * (size_t)n)); HIPCHECK(hipMalloc(&ds.p, 4 * (size_t)n)); HIPCHECK(hipMalloc(&dc.p, 4 * (size_t)n));
-    HIPCHECK(hipMalloc(&dxy.p, 8 * (size_t)n)); HIPCHECK(hipMalloc(&dpo.p, 4 * (size_t)n));
-    HIPCHECK(hipMalloc(&dpw.p, 8 * (size_t)n)); HIPCHECK(hipMalloc(&dp5.p, 8 * (size_t)n));
-    HIPCHECK(hipMemcpy(dx, x, 4 * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dpw, pw_in, 8 * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dxy, powf_xy, 8 * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHECK(dx.upload(x, (size_t)n)); HIPCHECK(ds.alloc((size_t)n)); HIPCHECK(dc.alloc((size_t)n));
+    HIPCHECK(dxy.upload(powf_xy, 2 * (size_t)n)); HIPCHECK(dpo.alloc((size_t)n));
+    HIPCHECK(dpw.upload(pw_in, (size_t)n)); HIPCHECK(dp5.alloc((size_t)n));
     t->ks->kat_libm(dim3((n + 255) / 256), t->stream, n, dx.p, ds.p, dc.p, dpw.p, dp5.p, dxy.p, dpo.p);
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(sin_out, ds, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(cos_out, dc, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(pow5_out, dp5, 8 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(powf_out, dpo, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(ds.download(sin_out)); HIPCHECK(dc.download(cos_out)); HIPCHECK(dp5.download(pow5_out)); HIPCHECK(dpo.download(powf_out));
     return PTX_OK;
 }
 
@@ -2105,13 +1672,13 @@ int ptx_kat_fast_exact(ptx_tracer *t, int64_t mismatches[3]) {
     KAT_PROLOGUE
     if (!mismatches) return set_error(PTX_ERR_INVALID, "null argument");
     DevBuf<unsigned long long> d;
-    HIPCHECK(hipMalloc(&d.p, 3 * sizeof(unsigned long long)));
+    HIPCHECK(d.alloc(3));
     HIPCHECK(hipMemsetAsync(d.p, 0, 3 * sizeof(unsigned long long), t->stream));
     hipLaunchKernelGGL(k_kat_fast_exact, dim3(t->cus * 8), dim3(256), 0, t->stream, d.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(t->stream));
     unsigned long long h[3];
-    HIPCHECK(hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost));
+    HIPCHECK(d.download(h));
     for (int k = 0; k < 3; k++) mismatches[k] = (int64_t)h[k];
     return PTX_OK;
 }
@@ -2142,129 +1709,6 @@ int ptx_get_kernel_times(ptx_tracer *t, double ms_by_kind[4], int64_t launches_b
 }
 
 // diagnostic build (-DPT_STAMPS): cycles per phase of k_bounce summed over waves: [0..4] first bounce, [8..12] later bounces
-// CPU-only check of the mesh BVH: builds the tree of `nfaces` faces and searches `nrays` object-space rays (origin,
-// direction; the direction is normalised the way meshIntersectionTest does) with the tree and with the plain loop.
-static int64_t g_bvh_visits[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-int ptx_debug_bvh_check(const float *faces15, int nfaces, const float *rays6, int nrays, int32_t *face_loop, float *t_loop,
-                        int32_t *face_bvh, float *t_bvh, int64_t *stats4) {
-    if (!faces15 || !rays6 || !face_loop || !t_loop || !face_bvh || !t_bvh || nfaces < 1 || nrays < 0)
-        return set_error(PTX_ERR_INVALID, "ptx_debug_bvh_check: bad argument");
-    std::vector<float> tri9((size_t)nfaces * 9);
-    for (int j = 0; j < nfaces; j++) {
-        const float *f = faces15 + (size_t)j * 15;
-        float *o = &tri9[(size_t)j * 9];
-        for (int k = 0; k < 3; k++) { o[k] = f[k]; o[3 + k] = f[5 + k] - f[k]; o[6 + k] = f[10 + k] - f[k]; }
-    }
-    BvhBuild bb;
-    int depth = 0;
-    int wroot = -1, wneed = 0;
-    const int root = bvhBuild(faces15, tri9.data(), 0, nfaces, bb, &depth, &wroot, &wneed);
-    std::vector<int32_t> wstack((size_t)std::max(wneed, 1) + 1, 0x7fffffff);      // (+ a guard word: the walk must never reach it)
-    long long visited = 0, visited_ordered = 0, visited_wide = 0, mismatches = 0, group_max = 0, sum_group_max = 0, groups = 0, tris_wide = 0;
-    for (int i = 0; i < nrays; i++) {
-        const vec3 o = V3(rays6[i * 6 + 0], rays6[i * 6 + 1], rays6[i * 6 + 2]);
-        const vec3 d = normalize(V3(rays6[i * 6 + 3], rays6[i * 6 + 4], rays6[i * 6 + 5]));
-        int f0, f1, vis = 0;
-        float b0, b1;
-        t_loop[i] = loopNearestHost(faces15, tri9.data(), nfaces, o, d, f0);
-        t_bvh[i] = bvhNearest(bb.nodes.data(), bb.tris.data(), root, o, d, f1, b0, b1, &vis);
-        if (depth < BVH_STACK) {                // the front-to-back search must agree with the skip-link one
-            int f2, vis2 = 0;
-            float c0, c1;
-            int32_t stack[BVH_STACK];
-            const float t2 = bvhNearestOrdered(bb.nodes.data(), bb.tris.data(), root, o, d, f2, c0, c1, stack, 1, &vis2);
-            visited_ordered += vis2;
-            if (f2 != f1 || memcmp(&t2, &t_bvh[i], 4) != 0 || (f1 >= 0 && (memcmp(&c0, &b0, 4) != 0 || memcmp(&c1, &b1, 4) != 0))) mismatches++;
-        }
-        if (wroot >= 0) {                       // ... and so must the walk over the four-wide nodes
-            int f3, vis3 = 0;
-            float e0, e1;
-            const float t3 = bvhNearestWide(bb.nodes.data(), bb.wide.data(), bb.tris.data(), root, wroot, o, d, f3, e0, e1, wstack.data(), 1, &vis3);
-            visited_wide += vis3 & 0xffff;
-            tris_wide += vis3 >> 16;
-            group_max = std::max(group_max, (long long)(vis3 & 0xffff) / 4);
-            if (i % 64 == 63 || i == nrays - 1) { sum_group_max += group_max; group_max = 0; groups++; }
-            if (wstack[(size_t)std::max(wneed, 1)] != 0x7fffffff) mismatches += 1000000;      // the walk overran the stack bound the builder computed
-            if (f3 != f1 || memcmp(&t3, &t_bvh[i], 4) != 0 || (f1 >= 0 && (memcmp(&e0, &b0, 4) != 0 || memcmp(&e1, &b1, 4) != 0))) mismatches++;
-            {   // the same steps under the schedule of k_mesh's refilling waves: one node or ONE triangle per turn
-                WideWalk w;
-                wideStart(w, bb.nodes[2 * (size_t)root], bb.nodes[2 * (size_t)root + 1], wroot, o, d);
-                while (w.n != WIDE_DONE) {
-                    if (w.n >= 0) wideNodeStep(w, bb.wide.data(), wstack.data(), 1);
-                    else wideLeafStep<true>(w, bb.tris.data(), wstack.data(), 1);
-                }
-                if (wstack[(size_t)std::max(wneed, 1)] != 0x7fffffff) mismatches += 1000000;
-                if (w.face != f1 || memcmp(&w.tmin, &t_bvh[i], 4) != 0 || (f1 >= 0 && (memcmp(&w.b0, &b0, 4) != 0 || memcmp(&w.b1, &b1, 4) != 0))) mismatches++;
-            }
-        }
-        face_loop[i] = f0; face_bvh[i] = f1;
-        visited += vis;
-    }
-    if (stats4) { stats4[0] = (int64_t)(bb.nodes.size() / 2); stats4[1] = (int64_t)(bb.tris.size() / BVH_TRI); stats4[2] = visited; stats4[3] = mismatches; }
-    g_bvh_visits[0] = visited; g_bvh_visits[1] = visited_ordered; g_bvh_visits[2] = visited_wide / 4; g_bvh_visits[3] = wneed;
-    g_bvh_visits[4] = sum_group_max; g_bvh_visits[5] = groups; g_bvh_visits[6] = tris_wide;
-    return PTX_OK;
-}
-
-// node visits of the last ptx_debug_bvh_check: skip-link walk, front-to-back binary walk, four-wide walk (nodes), wide stack need,
-// CPU-only: ptx_create's rule for what a stored path's record carries (record_masks), for nmaterials <= 64 materials and ngeoms geoms
-// given by type and material: masks[0] = dir_bins, masks[1] = ntab_bins (before the conditions of a particular tracer: candidate masks
-// on, fewer than 2^28 owned pixels).
-int ptx_debug_record_masks(int nmaterials, const ptx_material *materials, int ngeoms, const int32_t *geom_type, const int32_t *geom_material,
-                           int sort_by_material, uint64_t masks[2]) {
-    if (nmaterials < 1 || nmaterials > 64 || !materials || ngeoms < 0 || (ngeoms && (!geom_type || !geom_material)) || !masks)
-    { set_error(PTX_ERR_INVALID, "ptx_debug_record_masks: bad argument"); return -1; }
-    unsigned long long d = 0, n = 0;
-    record_masks(nmaterials, reinterpret_cast<const DMaterial *>(materials), ngeoms, geom_type, geom_material, sort_by_material != 0, d, n);
-    masks[0] = d; masks[1] = n;
-    return 0;
-}
-
-// CPU-only: the candidate pre-test's table (world_box_centre_half) for n corner boxes (lo xyz, hi xyz): 8 floats each = centre xyz, 0,
-// half extent xyz, 0 -- what cullMask reads on the device.
-int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8) {
-    if (n < 0 || (n && (!boxes6 || !centre_half8))) { set_error(PTX_ERR_INVALID, "ptx_debug_cull_boxes: bad argument"); return -1; }
-    for (int g = 0; g < n; g++) {
-        const float lohi[8] = {boxes6[g * 6], boxes6[g * 6 + 1], boxes6[g * 6 + 2], 0.f, boxes6[g * 6 + 3], boxes6[g * 6 + 4], boxes6[g * 6 + 5], 0.f};
-        world_box_centre_half(lohi, centre_half8 + (size_t)g * 8);
-    }
-    return n;
-}
-
-// sum over groups of 64 consecutive rays of the longest four-wide walk in the group, number of groups, triangles the four-wide walk tested
-// CPU-only: the per-tile geom masks of the camera-ray bounce (update_tile_geoms) for a camera, a tile split and a list of world boxes
-// (6 floats each: lo xyz, hi xyz), without a tracer or a device.  masks_out[tile], tiles of 256 owned pixels; returns the number of tiles
-// (negative: bad argument).
-int ptx_debug_tile_geoms(const ptx_camera *camera, int ngeoms, const float *boxes6, int depth_of_field, int tile_rows, int tile_rank, int tile_world,
-                         uint32_t *masks_out, int max_tiles) {
-    if (!camera || !boxes6 || !masks_out || ngeoms < 1 || ngeoms > 32 || camera->resolution[0] < 1 || camera->resolution[1] < 1)
-    { set_error(PTX_ERR_INVALID, "ptx_debug_tile_geoms: bad argument"); return -1; }
-    DCamera cam;
-    camera_to_device(*camera, cam);
-    TileMap tm{};
-    const int W = cam.resx, H = cam.resy;
-    tm.W = W; tm.H = H; tm.tile_world = tile_world < 1 ? 1 : tile_world; tm.tile_rank = tile_rank; tm.tile_rows = tm.tile_world > 1 ? tile_rows : H;
-    if (tm.tile_world > 1 && (tile_rows < 1 || tile_rank < 0 || tile_rank >= tm.tile_world)) return -1;
-    int owned_rows = 0;
-    for (int y = 0; y < H; y++) if (tm.tile_world <= 1 || (y / tm.tile_rows) % tm.tile_world == tm.tile_rank) owned_rows++;
-    tm.owned = owned_rows * W;
-    const int ntiles = (std::max(tm.owned, 1) + TILE - 1) / TILE;
-    if (ntiles > max_tiles) return -1;
-    std::vector<float> a8((size_t)ngeoms * 8, 0.f);
-    for (int g = 0; g < ngeoms; g++)
-        for (int k = 0; k < 3; k++) { a8[(size_t)g * 8 + k] = boxes6[g * 6 + k]; a8[(size_t)g * 8 + 4 + k] = boxes6[g * 6 + 3 + k]; }
-    std::vector<uint32_t> masks;
-    tile_geom_masks(cam, tm, ntiles, ngeoms, a8.data(), depth_of_field != 0, masks);
-    memcpy(masks_out, masks.data(), sizeof(uint32_t) * (size_t)ntiles);
-    return ntiles;
-}
-
-int ptx_debug_bvh_visits(int64_t out8[8]) {
-    if (!out8) return set_error(PTX_ERR_INVALID, "null argument");
-    for (int k = 0; k < 8; k++) out8[k] = g_bvh_visits[k];
-    return PTX_OK;
-}
-
 int ptx_debug_read_stamps(ptx_tracer *t, unsigned long long out48[48]) {
     if (!t || !out48) return set_error(PTX_ERR_INVALID, "null argument");
     memset(out48, 0, sizeof(unsigned long long) * 48);
@@ -2328,8 +1772,8 @@ int ptx_debug_set_capture(ptx_tracer *t, int bounce) {
     t->cap_filled = false;
     if (bounce >= 0 && !t->d_cap) {
         // pix, stream index, material|geom [cap each], the bounce's totals [nbins], run prefixes of the capture [2][nbins x grid_seg + 1]
-        HIPCHECK(hipMalloc(&t->d_cap, sizeof(int32_t) * (3 * (size_t)t->cap + (size_t)t->nbins + 2 * ((size_t)t->nbins * t->grid_seg + 1))));
-        HIPCHECK(hipMalloc(&t->d_cap_f, sizeof(float) * SOA_LOGICAL_FLOATS * (size_t)t->cap));
+        HIPCHECK(t->d_cap.alloc(3 * (size_t)t->cap + (size_t)t->nbins + 2 * ((size_t)t->nbins * t->grid_seg + 1)));
+        HIPCHECK(t->d_cap_f.alloc(SOA_LOGICAL_FLOATS * (size_t)t->cap));
     }
     return PTX_OK;
 }

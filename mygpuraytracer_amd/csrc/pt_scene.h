@@ -1,0 +1,58 @@
+// pt_scene.h -- scene preparation (pt_scene.hip): everything ptx_create computes on the host from the caller's geoms and materials
+// before anything is uploaded.  The unit holds no kernel and calls no hip* runtime function, so a CPU program can link it without a GPU
+// (tests/scene_prep_check.cpp does, under the sanitizers).  Errors go through ptx_internal_set_error (pt_engine.hip holds the string).
+#pragma once
+#include "../../include/mi355x_pathtracer.h"
+#include "pt_device.h"
+#include "pt_bvh.h"
+
+namespace ptd {
+
+// The PTX_DEBUG_* variables this phase depends on, read by ptx_create (pt_prepare_scene reads no environment).
+struct SceneSwitches {
+    bool no_wide_bvh = false;          // PTX_DEBUG_NO_WIDE_BVH: no four-wide nodes (A/B timing, tests of both walks)
+    bool no_chunks = false;            // PTX_DEBUG_NO_CHUNKS: small meshes' loops are not spread over lanes
+    bool no_dir_skip = false;          // PTX_DEBUG_NO_DIR_SKIP: every record carries direction and normal
+    bool no_normal_codes = false;      // PTX_DEBUG_NO_NORMAL_CODES: every record carries its normal
+    bool force_split = false;          // PTX_DEBUG_FORCE_SPLIT: the split mesh search for any scene with a mesh (timing experiments only)
+};
+
+// What the scene decides about how it is traced: the tracer (ptx_tracer) keeps these by the same names.
+struct SceneFacts {
+    int ntri = 0, bvh_meshes = 0, bvh_nodes = 0, bvh_stack = BVH_STACK;
+    int mesh_chunks = 1;                                 // see DScene::mesh_chunks
+    int uses_uv = 0;
+    uint32_t cube_bits = 0, sphere_bits = 0, mesh_bits = 0;   // geoms 0..31 by kind, for the candidate masks
+    uint32_t bump_bits = 0;
+    int tri_lds = 0, ntri_lds = 0, cull = 0;
+    bool split_mesh = false;                             // k_bounce as MODE 1 + k_mesh + k_finish + MODE 2 (scenes with BVH meshes)
+    unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
+    unsigned long long ntab_bins = 0ull;                 // BounceParams::ntab_bins (none: every record carries its normal)
+};
+
+struct HostScene : SceneFacts {
+    std::vector<DGeom> geoms;
+    std::vector<DMaterial> mats;
+    std::vector<float> faces, tri9, gtab, fnorm, cnorm;
+    std::vector<uint8_t> texels;
+    std::vector<float> aabb, aabb_ch;                    // world boxes, 8 floats per geom: corners (lo xyz, 0, hi xyz, 0) / centre and half extent
+    std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
+    BvhBuild bvh;                                        // pt_bvh.h: binary nodes, leaf triangles, four-wide nodes of every mesh that has a tree
+    std::vector<int32_t> roots, depths, wroots, wneeds;  // per geom (-1 / 0: no tree)
+    std::vector<float> ldsblob;                          // DScene::ldsblob: tri9, faces, materials, gtab, fnorm, cnorm as k_bounce stages them
+                                                         // (split: without the triangle tables); empty when the tables are not staged
+};
+
+// Flattens ptx_geom / ptx_material into the device structs and builds every derived table.  owned = pixels this device owns, nbins =
+// material bins of the sort, lds_limit = the device's LDS per workgroup in bytes.  Returns PTX_OK or the error code, its text set.
+int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials, const ptx_options &opt, int owned,
+                     int nbins, size_t lds_limit, const SceneSwitches &sw, HostScene &out);
+
+// upload-time triangle table for the intersection loop, 9 floats per face: v0, e1 = v1 - v0, e2 = v2 - v0
+std::vector<float> triangle_table(const float *faces15, int nfaces);
+void tile_geom_masks(const DCamera &c, int tile_rows, int tile_rank, int tile_world, int owned, int maxTiles, int ngeoms, const float *aabb8,
+                     bool dof, std::vector<uint32_t> &masks);
+void camera_to_device(const ptx_camera &c, DCamera &d);
+int owned_pixels(int W, int H, int tile_rows, int tile_rank, int tile_world);      // pixels of the row blocks this rank owns
+
+}  // namespace ptd
