@@ -12,6 +12,9 @@
  *   StreamCompaction::Common::kernMapToBoolean  stream_compaction/common.cu:25   sc_map_to_boolean_device
  *   StreamCompaction::Common::kernScatter       stream_compaction/common.cu:40   sc_scatter_device
  *   <ns>::timer().getGpu/CpuElapsedTimeForPreviousOperation  common.h:48-132     sc_last_gpu_ms / sc_last_cpu_ms
+ *   thrust::sort_by_key(.., sortByMaterial())   src/pathtrace.cu:418-422,518     sc_sort_records_by_key_device
+ *   thrust::stable_partition(.., isTerminate()) src/pathtrace.cu:424-428,541     sc_partition_records_device
+ *   (the kept half of that partition alone)                                      sc_compact_records_device
  *
  * Same argument meaning as the reference: n elements, host pointers in and out (the GPU variants allocate and
  * copy internally, exactly like the reference's), exclusive prefix sum, compaction keeps non-zero elements in
@@ -48,6 +51,51 @@ int sc_compact_device(int n, int *d_odata, const int *d_idata, int *d_count, voi
  * bools[i] = idata[i] != 0 ? 1 : 0;   and   bools[i] == 1  =>  odata[indices[i]] = idata[i].   Enqueued on `stream`, no sync. */
 int sc_map_to_boolean_device(int n, int *d_bools, const int *d_idata, void *stream);
 int sc_scatter_device(int n, int *d_odata, const int *d_idata, const int *d_bools, const int *d_indices, void *stream);
+
+/* ---- records: what the reference's per-bounce loop asks of thrust, on records instead of ints ------------------------------
+ * A stable counting sort of n records by a small integer key.  The key of element i is the int at d_keys + i * key_stride_bytes,
+ * so it can be read straight out of a record array (materialId inside ShadeableIntersection: d_keys = records + 16, stride 32).
+ * A key outside [0, nkeys) is CLAMPED into the range before it is used (a negative one counts as 0, a large one as nkeys - 1): a
+ * bad key gives a defined order and never an address.  descending != 0 maps key k to nkeys - 1 - k; equal keys keep input order
+ * either way.  Up to two record arrays are permuted alike (b: NULL, NULL, 0 = one array); d_perm, if given, receives the source
+ * index of every output slot, d_key_totals the number of elements per (mapped) key.
+ * Limits: 1 <= nkeys <= 256; record_bytes a multiple of 4 in 4..256; key / flag stride a multiple of 4, >= 4; all pointers 4-byte
+ * aligned (records whose size is a multiple of 16 move as 16-byte accesses when both their pointers are 16-byte aligned); every
+ * output differs from, and does not overlap, every input and the keys: there is no in-place form.  Anything else returns
+ * PTX_ERR_INVALID with the offending value in ptx_last_error() and enqueues nothing; these checks come before the device check
+ * (PTX_ERR_NODEVICE).  Workspace: sc_records_workspace_bytes(n, nkeys) bytes of device memory, 8-byte aligned, contents arbitrary,
+ * reusable by later calls of any size it is large enough for (the size grows with n and with nkeys) and by sc_scan_device /
+ * sc_compact_device.  No allocation, no host synchronisation, no copy: three kernels and one memset on `stream`.  The result is
+ * the same on every run.  n == 0 writes zero totals / *d_count = 0 and nothing else. */
+int sc_records_tile_elements(void);                                    /* elements one workgroup ranks (tests sit on its edges) */
+unsigned long long sc_records_workspace_bytes(int n, int nkeys);       /* 0 for arguments outside the limits */
+
+/* thrust::sort_by_key(dev_intersections, dev_intersections + num_paths, dev_paths, sortByMaterial())  src/pathtrace.cu:418-422,518:
+ * nkeys = number of materials, descending = 1 */
+int sc_sort_records_by_key_device(int n, int nkeys, int descending,
+        const void *d_keys, int key_stride_bytes,
+        void *d_out_a, const void *d_in_a, int record_bytes_a,
+        void *d_out_b, const void *d_in_b, int record_bytes_b,
+        int *d_perm, int *d_key_totals,
+        void *d_workspace, void *stream);
+
+/* thrust::stable_partition(dev_paths, dev_paths + num_paths, isTerminate())  src/pathtrace.cu:424-428,541: the records whose flag
+ * (the int at d_flags + i * flag_stride_bytes; remainingBounces: d_flags = paths + 40, stride 44) is != 0 first, then those with
+ * flag == 0, both in input order; *d_count = the partition point */
+int sc_partition_records_device(int n, int record_bytes, void *d_out, const void *d_in,
+        const void *d_flags, int flag_stride_bytes, int *d_count, void *d_workspace, void *stream);
+
+/* the kept records only: nothing is written at or after d_out + count * record_bytes */
+int sc_compact_records_device(int n, int record_bytes, void *d_out, const void *d_in,
+        const void *d_flags, int flag_stride_bytes, int *d_count, void *d_workspace, void *stream);
+
+/* host-pointer forms of the three (allocate, copy and synchronise internally, like sc_efficient_compact); keys / flags: n ints.
+ * perm and key_totals may be NULL; count may not.  sc_compact_records writes *count records to out. */
+int sc_sort_records_by_key(int n, int nkeys, int descending, const int *keys,
+        void *out_a, const void *in_a, int record_bytes_a, void *out_b, const void *in_b, int record_bytes_b,
+        int *perm, int *key_totals);
+int sc_partition_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count);
+int sc_compact_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count);
 
 float sc_last_gpu_ms(void);      /* device time of the kernels of the previous GPU call (hipEvent), ms */
 float sc_last_cpu_ms(void);      /* wall time of the previous sc_cpu_* call, ms */

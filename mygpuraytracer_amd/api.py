@@ -433,6 +433,14 @@ def load_library():
     L.sc_compact_device.restype, L.sc_compact_device.argtypes = i, [i, vp, vp, vp, vp, vp]
     L.sc_map_to_boolean_device.restype, L.sc_map_to_boolean_device.argtypes = i, [i, vp, vp, vp]
     L.sc_scatter_device.restype, L.sc_scatter_device.argtypes = i, [i, vp, vp, vp, vp, vp]
+    L.sc_records_tile_elements.restype, L.sc_records_tile_elements.argtypes = i, []
+    L.sc_records_workspace_bytes.restype, L.sc_records_workspace_bytes.argtypes = C.c_ulonglong, [i, i]
+    L.sc_sort_records_by_key_device.restype, L.sc_sort_records_by_key_device.argtypes = i, [i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp]
+    for n in ("sc_partition_records_device", "sc_compact_records_device"):
+        getattr(L, n).restype, getattr(L, n).argtypes = i, [i, i, vp, vp, vp, i, vp, vp, vp]
+    L.sc_sort_records_by_key.restype, L.sc_sort_records_by_key.argtypes = i, [i, i, i, vp, vp, vp, i, vp, vp, i, vp, vp]
+    for n in ("sc_partition_records", "sc_compact_records"):
+        getattr(L, n).restype, getattr(L, n).argtypes = i, [i, i, vp, vp, vp, vp]
     L.sc_last_gpu_ms.restype = f
     L.sc_last_cpu_ms.restype = f
     L.sc_ilog2.restype, L.sc_ilog2.argtypes = i, [i]
@@ -1051,6 +1059,68 @@ class StreamCompaction:
 
     def scatter_device(self, n, d_out, d_in, d_bools, d_indices, stream=0):
         _check(self.lib.sc_scatter_device(int(n), d_out, d_in, d_bools, d_indices, stream), "sc_scatter_device")
+
+    # records: thrust::sort_by_key(.., sortByMaterial()) / thrust::stable_partition(.., isTerminate()) of src/pathtrace.cu:518,541
+    def records_tile(self):
+        return int(self.lib.sc_records_tile_elements())
+
+    def records_workspace_bytes(self, n, nkeys):
+        return int(self.lib.sc_records_workspace_bytes(int(n), int(nkeys)))
+
+    def sort_records_by_key_device(self, n, nkeys, descending, d_keys, key_stride_bytes, d_out_a, d_in_a, record_bytes_a,
+                                   d_out_b, d_in_b, record_bytes_b, d_perm, d_key_totals, d_workspace, stream=0):
+        _check(self.lib.sc_sort_records_by_key_device(int(n), int(nkeys), int(bool(descending)), d_keys, int(key_stride_bytes),
+                                                      d_out_a, d_in_a, int(record_bytes_a), d_out_b, d_in_b, int(record_bytes_b),
+                                                      d_perm, d_key_totals, d_workspace, stream), "sc_sort_records_by_key_device")
+
+    def partition_records_device(self, n, record_bytes, d_out, d_in, d_flags, flag_stride_bytes, d_count, d_workspace, stream=0):
+        _check(self.lib.sc_partition_records_device(int(n), int(record_bytes), d_out, d_in, d_flags, int(flag_stride_bytes), d_count,
+                                                    d_workspace, stream), "sc_partition_records_device")
+
+    def compact_records_device(self, n, record_bytes, d_out, d_in, d_flags, flag_stride_bytes, d_count, d_workspace, stream=0):
+        _check(self.lib.sc_compact_records_device(int(n), int(record_bytes), d_out, d_in, d_flags, int(flag_stride_bytes), d_count,
+                                                  d_workspace, stream), "sc_compact_records_device")
+
+    @staticmethod
+    def _records(a, n):
+        """a C-contiguous array of n records (any dtype, structured ones included) and the bytes of one record"""
+        a = np.ascontiguousarray(a)
+        if a.ndim < 1 or len(a) != n:
+            raise PathTracerError("records: every array needs one row per key (%d), got shape %r" % (n, a.shape))
+        return a, (a.nbytes // n if n else a.dtype.itemsize * int(np.prod(a.shape[1:], dtype=np.int64)))
+
+    def sort_records_by_key(self, keys, *arrays, nkeys, descending=False):
+        """Stable sort of one or two host record arrays by int keys in [0, nkeys) (clamped), ascending or descending.
+        Returns (the permuted arrays as a list, perm = source index of every output row, totals = rows per mapped key)."""
+        keys = np.ascontiguousarray(keys, np.int32)
+        if not 1 <= len(arrays) <= 2:
+            raise PathTracerError("sort_records_by_key: one or two record arrays, got %d" % len(arrays))
+        n = len(keys)
+        recs = [self._records(a, n) for a in arrays]
+        outs = [np.empty_like(a) for a, _ in recs]
+        perm = np.empty(n, np.int32)
+        totals = np.zeros(max(int(nkeys), 0), np.int32)
+        b = (_ptr(outs[1]), _ptr(recs[1][0]), recs[1][1]) if len(recs) == 2 else (None, None, 0)
+        _check(self.lib.sc_sort_records_by_key(n, int(nkeys), int(bool(descending)), _ptr(keys), _ptr(outs[0]), _ptr(recs[0][0]), recs[0][1],
+                                               b[0], b[1], b[2], _ptr(perm), _ptr(totals)), "sc_sort_records_by_key")
+        return outs, perm, totals
+
+    def _split_records(self, fn, what, records, flags):
+        flags = np.ascontiguousarray(flags, np.int32)
+        a, rb = self._records(records, len(flags))
+        out = np.empty_like(a)
+        count = C.c_int(0)
+        _check(fn(len(flags), rb, _ptr(out), _ptr(a), _ptr(flags), C.byref(count)), what)
+        return out, int(count.value)
+
+    def partition_records(self, records, flags):
+        """Rows with flag != 0 first, then those with flag == 0, both in order: (the partitioned array, the partition point)."""
+        return self._split_records(self.lib.sc_partition_records, "sc_partition_records", records, flags)
+
+    def compact_records(self, records, flags):
+        """The rows with flag != 0, in order."""
+        out, count = self._split_records(self.lib.sc_compact_records, "sc_compact_records", records, flags)
+        return out[:count].copy()
 
     def last_gpu_ms(self):
         return float(self.lib.sc_last_gpu_ms())

@@ -248,6 +248,279 @@ struct CpuTimer {
     ~CpuTimer() { g_cpu_ms = std::chrono::duration<float, std::milli>(std::chrono::high_resolution_clock::now() - t0).count(); }
 };
 
+
+// ---- records: a stable counting sort by a small integer key (sc_sort_records_by_key_device, sc_partition_records_device,
+// sc_compact_records_device) ------------------------------------------------------------------------------------------------------
+// What the reference's loop asks of thrust per bounce (src/pathtrace.cu:418-428, 518, 541): sort_by_key of 32-byte intersections by
+// materialId with the 44-byte path segments as values, then stable_partition of the segments by remainingBounces.  Both are ONE
+// mechanism here -- partition is the two-key case (kept = key 0), compaction is partition that never writes key 1 -- in three
+// kernels ordered by the stream:
+//   count: a workgroup takes the tile of SR_TILE consecutive elements, reads every key straight out of the caller's array (an int at
+//          keys + i * stride, so a field of a record serves) and leaves the tile's count per key in table[key][tile];
+//   scan : ONE exclusive scan over the key-major table (the library's own k_onepass, in place) makes table[key][tile] the global start
+//          of the tile's run of that key: everything of smaller keys, then the same key in earlier tiles;
+//   move : the same tile again.  An element's rank among the tile's elements of its key = ballot of the key over the wave + popcount
+//          below the lane (one trip per distinct key in the wave, as k_bounce ranks its bins), plus the counts of the earlier
+//          (round, wave) groups, scanned per key through LDS.  The tile is then ordered by (key, rank) INSIDE LDS -- source slot and
+//          global destination per sorted position -- and the records are copied in that order, a record's dwords (or quads) on
+//          consecutive lanes: every key's run of the tile is one contiguous store stream, the loads gather inside the tile.
+// No workgroup waits for another (the scan's look-back is the only one) and the only atomics add up the count kernel's LDS histogram:
+// a destination is a function of the keys alone, so the result is stable and the same on every run.  A key outside [0, nkeys) is clamped in both phases alike.
+constexpr int SR_THREADS = 256, SR_WAVES = SR_THREADS / 64, SR_ROUNDS = 8;
+constexpr int SR_TILE = SR_THREADS * SR_ROUNDS;                // 2048 elements: a 3840x2160 frame is 4050 tiles, its 7-key table 28350 ints
+constexpr int SR_RW = SR_ROUNDS * SR_WAVES;                    // (round, wave) groups of 64 consecutive elements
+constexpr int SR_MAXKEYS = 256, SR_MAXBYTES = 256;
+
+struct SrKeys {
+    const char *keys;
+    int stride, nkeys, flags, descending;                      // flags: key = value != 0 ? 0 : 1 (kept first)
+};
+struct SrArray {
+    void *out;
+    const void *in;
+    int units;                                                 // 16-byte or 4-byte units per record
+    unsigned magic;                                            // floor(2^32 / units) + 1: idx / units = umulhi(idx, magic) for idx < 2^17, units in 2..64
+    int vec16;
+};
+
+__device__ __forceinline__ int sr_key(const SrKeys &K, long long i) {
+    const int v = *reinterpret_cast<const int *>(K.keys + i * K.stride);
+    if (K.flags) return v != 0 ? 0 : 1;
+    const int c = min(max(v, 0), K.nkeys - 1);
+    return K.descending ? K.nkeys - 1 - c : c;
+}
+
+__global__ __launch_bounds__(SR_THREADS) void k_records_count(int n, int tiles, SrKeys K, int *__restrict__ table) {
+    __shared__ int s_hist[SR_WAVES][SR_MAXKEYS];               // a row per wave: its atomics only count, and only against its own later rounds
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
+    const long long tbase = (long long)tile * SR_TILE;
+    for (int k = lane; k < K.nkeys; k += 64) s_hist[wave][k] = 0;
+    int kk[SR_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        const long long i = tbase + r * SR_THREADS + tid;
+        kk[r] = i < n ? sr_key(K, i) : -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        unsigned long long remaining = __builtin_amdgcn_uicmp((uint32_t)kk[r], 0xffffffffu, 33);      // lanes with an element
+        while (remaining) {
+            const int leader = __ffsll((long long)remaining) - 1;
+            const int b = __builtin_amdgcn_readlane(kk[r], leader);
+            const unsigned long long m = __builtin_amdgcn_uicmp((uint32_t)kk[r], (uint32_t)b, 32);
+            if (lane == leader) atomicAdd(&s_hist[wave][b], (int)__popcll(m));
+            remaining &= ~m;
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < K.nkeys; k += SR_THREADS) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < SR_WAVES; w++) c += s_hist[w][k];
+        table[(size_t)k * tiles + tile] = c;
+    }
+}
+
+template <typename V>
+__device__ __forceinline__ void sr_copy(const SrArray &A, long long tbase, int placed, const uint16_t *s_src, const int *s_dst, int tid) {
+    const V *__restrict__ src = reinterpret_cast<const V *>(A.in) + tbase * A.units;
+    V *__restrict__ dst = reinterpret_cast<V *>(A.out);
+    const unsigned units = (unsigned)A.units, total = (unsigned)placed * units;
+#pragma unroll 4
+    for (unsigned idx = tid; idx < total; idx += SR_THREADS) {
+        const unsigned p = units == 1 ? idx : __umulhi(idx, A.magic), w = idx - p * units;
+        dst[(long long)s_dst[p] * units + w] = src[(unsigned)s_src[p] * units + w];
+    }
+}
+
+__global__ __launch_bounds__(SR_THREADS) void k_records_move(int n, int tiles, SrKeys K, const int *__restrict__ table, SrArray A, SrArray B,
+                                                            int *__restrict__ perm, int *__restrict__ totals, int ntotals, int compact) {
+    __shared__ uint16_t s_cnt[SR_RW * SR_MAXKEYS];             // [group][key] counts (<= 64), then per key their exclusive prefixes (< 2048)
+    __shared__ int s_kstart[SR_MAXKEYS], s_gbase[SR_MAXKEYS];  // where a key's run starts: in the tile's sorted order, and in the output
+    __shared__ uint16_t s_src[SR_TILE];                        // per sorted position of the tile: the element's slot in the tile
+    __shared__ int s_dst[SR_TILE];                             //                                  and its place in the output
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x, nkeys = K.nkeys;
+    const long long tbase = (long long)tile * SR_TILE;
+    const int cnt = (int)min((long long)SR_TILE, n - tbase);
+
+    for (int q = tid; q < SR_RW * nkeys / 2; q += SR_THREADS) reinterpret_cast<uint32_t *>(s_cnt)[q] = 0u;      // (SR_RW is even)
+    int kk[SR_ROUNDS], rk[SR_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        const long long i = tbase + r * SR_THREADS + tid;
+        kk[r] = i < n ? sr_key(K, i) : -1;
+    }
+    for (int k = tid; k < nkeys; k += SR_THREADS) s_gbase[k] = table[(size_t)k * tiles + tile];
+    if (tile == 0 && totals)                                   // elements per key = the distance between the keys' first starts
+        for (int k = tid; k < ntotals; k += SR_THREADS) totals[k] = (k + 1 < nkeys ? table[(size_t)(k + 1) * tiles] : n) - table[(size_t)k * tiles];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        rk[r] = 0;
+        unsigned long long remaining = __builtin_amdgcn_uicmp((uint32_t)kk[r], 0xffffffffu, 33);
+        while (remaining) {
+            const int leader = __ffsll((long long)remaining) - 1;
+            const int b = __builtin_amdgcn_readlane(kk[r], leader);
+            const unsigned long long m = __builtin_amdgcn_uicmp((uint32_t)kk[r], (uint32_t)b, 32);
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (kk[r] == b) rk[r] = below;
+            if (lane == leader) s_cnt[(r * SR_WAVES + wave) * nkeys + b] = (uint16_t)__popcll(m);
+            remaining &= ~m;
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < nkeys; k += SR_THREADS) {            // per key: exclusive prefix over the groups, in tile order
+        int run = 0;
+        for (int g = 0; g < SR_RW; g++) {
+            const int c = s_cnt[g * nkeys + k];
+            s_cnt[g * nkeys + k] = (uint16_t)run;
+            run += c;
+        }
+        s_kstart[k] = run;
+    }
+    __syncthreads();
+    if (wave == 0) {                                           // exclusive prefix over the keys' totals, four keys per lane
+        int t[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { t[j] = 4 * lane + j < nkeys ? s_kstart[4 * lane + j] : 0; sum += t[j]; }
+        int run = wave_inclusive_scan(sum, lane) - sum;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { if (4 * lane + j < nkeys) s_kstart[4 * lane + j] = run; run += t[j]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++)
+        if (kk[r] >= 0) {
+            const int off = s_cnt[(r * SR_WAVES + wave) * nkeys + kk[r]] + rk[r], p = s_kstart[kk[r]] + off;
+            s_src[p] = (uint16_t)(r * SR_THREADS + tid);
+            s_dst[p] = s_gbase[kk[r]] + off;
+        }
+    __syncthreads();
+    const int placed = compact ? s_kstart[1] : cnt;            // compaction: the kept ones (key 0) and nothing else
+    if (A.vec16) sr_copy<v4i>(A, tbase, placed, s_src, s_dst, tid); else sr_copy<int>(A, tbase, placed, s_src, s_dst, tid);
+    if (B.in) { if (B.vec16) sr_copy<v4i>(B, tbase, placed, s_src, s_dst, tid); else sr_copy<int>(B, tbase, placed, s_src, s_dst, tid); }
+    if (perm)
+        for (int p = tid; p < placed; p += SR_THREADS) perm[s_dst[p]] = (int)(tbase + s_src[p]);
+}
+
+inline int sr_tiles(int n) { return n > 0 ? (int)(((long long)n + SR_TILE - 1) / SR_TILE) : 1; }
+
+int sr_invalid(const char *what, const char *name, long long value, const char *rule) {
+    ptx_internal_set_error((std::string(what) + ": " + name + " = " + std::to_string(value) + " " + rule).c_str());
+    return PTX_ERR_INVALID;
+}
+
+// the limits that need no pointer and no device
+int sr_check_sizes(const char *what, int n, int nkeys, int stride, int bytes_a, int bytes_b, bool has_b) {
+    if (n < 0) return sr_invalid(what, "n", n, "is negative");
+    if (nkeys < 1 || nkeys > SR_MAXKEYS) return sr_invalid(what, "nkeys", nkeys, "is outside 1..256");
+    if (stride < 4 || stride % 4) return sr_invalid(what, "key_stride_bytes", stride, "must be a multiple of 4, at least 4");
+    if (bytes_a < 4 || bytes_a > SR_MAXBYTES || bytes_a % 4) return sr_invalid(what, "record_bytes", bytes_a, "must be a multiple of 4 in 4..256");
+    if (has_b && (bytes_b < 4 || bytes_b > SR_MAXBYTES || bytes_b % 4)) return sr_invalid(what, "record_bytes_b", bytes_b, "must be a multiple of 4 in 4..256");
+    if ((long long)nkeys * sr_tiles(n) > 0x7fffffffLL) return sr_invalid(what, "nkeys * tiles", (long long)nkeys * sr_tiles(n), "does not fit the scan's int");
+    return PTX_OK;
+}
+
+int sr_no_device(const char *what) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return PTX_OK;
+    ptx_internal_set_error((std::string(what) + ": no HIP device available; the record sort has no CPU path").c_str());
+    return PTX_ERR_NODEVICE;
+}
+
+SrArray sr_array(void *out, const void *in, int bytes) {
+    SrArray a;
+    a.out = out; a.in = in;
+    a.vec16 = in && bytes % 16 == 0 && (((uintptr_t)out | (uintptr_t)in) & 15) == 0;
+    a.units = bytes / (a.vec16 ? 16 : 4);
+    a.magic = a.units > 1 ? (unsigned)(0x100000000ULL / (unsigned)a.units) + 1u : 0u;
+    return a;
+}
+
+// one entry path: flags = partition / compaction (two keys, kept first), totals: ntotals ints (nkeys for the sort, the count otherwise)
+int records_device(const char *what, int n, int nkeys, int descending, bool flags, bool compact, const void *d_keys, int stride,
+                   void *d_out_a, const void *d_in_a, int bytes_a, void *d_out_b, const void *d_in_b, int bytes_b,
+                   int *d_perm, int *d_totals, int ntotals, void *d_ws, hipStream_t st) {
+    const bool has_b = d_out_b || d_in_b || bytes_b;
+    if (int rc = sr_check_sizes(what, n, nkeys, stride, bytes_a, bytes_b, has_b)) return rc;
+    if (n > 0) {
+        if (!d_keys || !d_out_a || !d_in_a || !d_ws || (has_b && (!d_out_b || !d_in_b))) return sr_invalid(what, "a device pointer", 0, "is null");
+        if (((uintptr_t)d_ws) & 7) return sr_invalid(what, "d_workspace", (long long)(uintptr_t)d_ws, "must be 8-byte aligned");
+        if ((((uintptr_t)d_keys | (uintptr_t)d_out_a | (uintptr_t)d_in_a | (uintptr_t)d_out_b | (uintptr_t)d_in_b | (uintptr_t)d_perm) & 3))
+            return sr_invalid(what, "a device pointer", 0, "is not 4-byte aligned");
+        if (d_out_a == d_in_a || (has_b && (d_out_b == d_in_b || d_out_b == d_in_a || d_out_a == d_in_b || d_out_a == d_out_b)))
+            return sr_invalid(what, "d_out", (long long)(uintptr_t)d_out_a, "is an input or the other output: there is no in-place form");
+    }
+    if (int rc = sr_no_device(what)) return rc;
+    if (n == 0) {
+        if (d_totals) SC_CHECK(hipMemsetAsync(d_totals, 0, sizeof(int) * (size_t)ntotals, st));
+        return PTX_OK;
+    }
+    const int tiles = sr_tiles(n), m = nkeys * tiles;
+    int *table = (int *)((char *)d_ws + sc_scan_workspace_bytes(m));
+    SrKeys K;
+    K.keys = (const char *)d_keys; K.stride = stride; K.nkeys = nkeys; K.flags = flags; K.descending = descending != 0;
+    hipLaunchKernelGGL(k_records_count, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, table);
+    SC_CHECK(hipGetLastError());
+    if (int rc = onepass_device(m, table, table, nullptr, d_ws, st, false)) return rc;
+    hipLaunchKernelGGL(k_records_move, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, (const int *)table, sr_array(d_out_a, d_in_a, bytes_a),
+                       sr_array(has_b ? d_out_b : nullptr, has_b ? d_in_b : nullptr, has_b ? bytes_b : 4), d_perm, d_totals, ntotals, compact ? 1 : 0);
+    SC_CHECK(hipGetLastError());
+    return PTX_OK;
+}
+
+// host-pointer forms: allocate, copy in, run on the null stream, copy out -- as sc_efficient_compact does for ints
+struct SrDeviceBuffers {
+    void *p[8] = {};
+    int used = 0;
+    ~SrDeviceBuffers() { for (int i = 0; i < used; i++) hipFree(p[i]); }
+    hipError_t get(void **out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 4);
+        if (e == hipSuccess) p[used++] = *out;
+        return e;
+    }
+};
+
+int records_host(const char *what, int n, int nkeys, int descending, bool flags, bool compact, const int *keys,
+                 void *out_a, const void *in_a, int bytes_a, void *out_b, const void *in_b, int bytes_b, int *perm, int *totals, int ntotals) {
+    const bool has_b = out_b || in_b || bytes_b;
+    if (int rc = sr_check_sizes(what, n, nkeys, 4, bytes_a, bytes_b, has_b)) return rc;
+    if (n > 0 && (!keys || !out_a || !in_a || (has_b && (!out_b || !in_b)))) return sr_invalid(what, "a host pointer", 0, "is null");
+    if (int rc = sr_no_device(what)) return rc;
+    if (n == 0) { for (int k = 0; totals && k < ntotals; k++) totals[k] = 0; return PTX_OK; }
+    SrDeviceBuffers dev;
+    void *d_keys = nullptr, *d_in_a = nullptr, *d_out_a = nullptr, *d_in_b = nullptr, *d_out_b = nullptr, *d_perm = nullptr, *d_tot = nullptr, *d_ws = nullptr;
+    const size_t na = (size_t)n * bytes_a, nb = has_b ? (size_t)n * bytes_b : 0;
+    SC_CHECK(dev.get(&d_keys, sizeof(int) * (size_t)n));
+    SC_CHECK(dev.get(&d_in_a, na)); SC_CHECK(dev.get(&d_out_a, na));
+    if (has_b) { SC_CHECK(dev.get(&d_in_b, nb)); SC_CHECK(dev.get(&d_out_b, nb)); }
+    if (perm) SC_CHECK(dev.get(&d_perm, sizeof(int) * (size_t)n));
+    SC_CHECK(dev.get(&d_tot, sizeof(int) * (size_t)ntotals));
+    SC_CHECK(dev.get(&d_ws, sc_records_workspace_bytes(n, nkeys)));
+    SC_CHECK(hipMemcpy(d_keys, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    SC_CHECK(hipMemcpy(d_in_a, in_a, na, hipMemcpyHostToDevice));
+    if (has_b) SC_CHECK(hipMemcpy(d_in_b, in_b, nb, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1;
+    SC_CHECK(hipEventCreate(&e0)); SC_CHECK(hipEventCreate(&e1));
+    SC_CHECK(hipEventRecord(e0, 0));
+    const int rc = records_device(what, n, nkeys, descending, flags, compact, d_keys, 4, d_out_a, d_in_a, bytes_a, d_out_b, d_in_b, bytes_b,
+                                  (int *)d_perm, (int *)d_tot, ntotals, d_ws, 0);
+    SC_CHECK(hipEventRecord(e1, 0));
+    SC_CHECK(hipEventSynchronize(e1));
+    SC_CHECK(hipEventElapsedTime(&g_gpu_ms, e0, e1));
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (rc != PTX_OK) return rc;
+    int first = 0;                                             // partition / compaction: the count; what compaction wrote ends there
+    SC_CHECK(hipMemcpy(&first, d_tot, sizeof(int), hipMemcpyDeviceToHost));
+    if (totals) SC_CHECK(hipMemcpy(totals, d_tot, sizeof(int) * (size_t)ntotals, hipMemcpyDeviceToHost));
+    const size_t written = compact ? (size_t)first : (size_t)n;
+    if (written) SC_CHECK(hipMemcpy(out_a, d_out_a, written * bytes_a, hipMemcpyDeviceToHost));
+    if (has_b && written) SC_CHECK(hipMemcpy(out_b, d_out_b, written * bytes_b, hipMemcpyDeviceToHost));
+    if (perm && written) SC_CHECK(hipMemcpy(perm, d_perm, sizeof(int) * written, hipMemcpyDeviceToHost));
+    return PTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -367,6 +640,55 @@ int sc_scatter_device(int n, int *d_odata, const int *d_idata, const int *d_bool
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)std::min(8192, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_odata, d_idata, d_bools, d_indices);
     SC_CHECK(hipGetLastError());
     return PTX_OK;
+}
+
+// ---- records (kernels and limits: k_records_count / k_records_move above) -----------------------------------------------------
+int sc_records_tile_elements(void) { return SR_TILE; }
+
+// [the scan's own workspace for nkeys * tiles ints][the table, nkeys * tiles ints, scanned in place]; 0 for arguments the calls refuse
+unsigned long long sc_records_workspace_bytes(int n, int nkeys) {
+    if (n < 0 || nkeys < 1 || nkeys > SR_MAXKEYS || (long long)nkeys * sr_tiles(n) > 0x7fffffffLL) return 0;
+    const int m = nkeys * sr_tiles(n);
+    return sc_scan_workspace_bytes(m) + ((sizeof(int) * (unsigned long long)m + 7) & ~7ull);
+}
+
+// thrust::sort_by_key(dev_intersections, ..., dev_paths, sortByMaterial())  src/pathtrace.cu:418-422,518
+int sc_sort_records_by_key_device(int n, int nkeys, int descending, const void *d_keys, int key_stride_bytes,
+                                  void *d_out_a, const void *d_in_a, int record_bytes_a, void *d_out_b, const void *d_in_b, int record_bytes_b,
+                                  int *d_perm, int *d_key_totals, void *d_workspace, void *stream) {
+    return records_device("sc_sort_records_by_key_device", n, nkeys, descending, false, false, d_keys, key_stride_bytes, d_out_a, d_in_a, record_bytes_a,
+                          d_out_b, d_in_b, record_bytes_b, d_perm, d_key_totals, nkeys, d_workspace, (hipStream_t)stream);
+}
+
+// thrust::stable_partition(dev_paths, ..., isTerminate())  src/pathtrace.cu:424-428,541
+int sc_partition_records_device(int n, int record_bytes, void *d_out, const void *d_in, const void *d_flags, int flag_stride_bytes, int *d_count,
+                                void *d_workspace, void *stream) {
+    if (!d_count) { ptx_internal_set_error("sc_partition_records_device: d_count is null"); return PTX_ERR_INVALID; }
+    return records_device("sc_partition_records_device", n, 2, 0, true, false, d_flags, flag_stride_bytes, d_out, d_in, record_bytes, nullptr, nullptr, 0,
+                          nullptr, d_count, 1, d_workspace, (hipStream_t)stream);
+}
+
+int sc_compact_records_device(int n, int record_bytes, void *d_out, const void *d_in, const void *d_flags, int flag_stride_bytes, int *d_count,
+                              void *d_workspace, void *stream) {
+    if (!d_count) { ptx_internal_set_error("sc_compact_records_device: d_count is null"); return PTX_ERR_INVALID; }
+    return records_device("sc_compact_records_device", n, 2, 0, true, true, d_flags, flag_stride_bytes, d_out, d_in, record_bytes, nullptr, nullptr, 0,
+                          nullptr, d_count, 1, d_workspace, (hipStream_t)stream);
+}
+
+int sc_sort_records_by_key(int n, int nkeys, int descending, const int *keys, void *out_a, const void *in_a, int record_bytes_a,
+                           void *out_b, const void *in_b, int record_bytes_b, int *perm, int *key_totals) {
+    return records_host("sc_sort_records_by_key", n, nkeys, descending, false, false, keys, out_a, in_a, record_bytes_a, out_b, in_b, record_bytes_b,
+                        perm, key_totals, nkeys);
+}
+
+int sc_partition_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count) {
+    if (!count) { ptx_internal_set_error("sc_partition_records: count is null"); return PTX_ERR_INVALID; }
+    return records_host("sc_partition_records", n, 2, 0, true, false, flags, out, in, record_bytes, nullptr, nullptr, 0, nullptr, count, 1);
+}
+
+int sc_compact_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count) {
+    if (!count) { ptx_internal_set_error("sc_compact_records: count is null"); return PTX_ERR_INVALID; }
+    return records_host("sc_compact_records", n, 2, 0, true, true, flags, out, in, record_bytes, nullptr, nullptr, 0, nullptr, count, 1);
 }
 
 float sc_last_gpu_ms(void) { return g_gpu_ms; }

@@ -15,10 +15,20 @@
 // compaction with <<<grid, block>>>; here they are ordinary functions on device pointers that enqueue the whole array on a
 // stream (default: the null stream), because this header must also compile in translation units without HIP:
 //     StreamCompaction::Common::kernMapToBoolean(n, dev_bools, dev_idata);              // was <<<blocks, 128>>>(n, ...)
+// StreamCompaction::Records is what the reference's path tracer asks of thrust per bounce (src/pathtrace.cu:518,541), on DEVICE pointers:
+//     Records::sortByKey(num_paths, nmaterials, 1, &dev_isects->materialId, sizeof(ShadeableIntersection), out_isects, dev_isects,
+//                        out_paths, dev_paths);                                           // was thrust::sort_by_key(.., sortByMaterial())
+//     int live = Records::stablePartition(num_paths, out_paths, dev_paths, &dev_paths->remainingBounces, sizeof(PathSegment));
+// It allocates its workspace with hipMalloc, so it exists only in translation units compiled for HIP (hipcc, or
+// -D__HIP_PLATFORM_AMD__ with the HIP headers on the include path).
 // Not carried over: startGpuTimer/endGpuTimer and their CPU twins (the library times its operations itself).
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
+#include <hip/hip_runtime_api.h>
+#include <type_traits>
+#endif
 
 #include "../../include/mi355x_pathtracer.h"
 #include "../../include/mi355x_stream_compaction.h"
@@ -101,4 +111,78 @@ inline void scan(int n, int *odata, const int *idata) {
     timer().mi355x_set(-1.f, sc_last_gpu_ms());
 }
 }  // namespace Thrust
+
+#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
+namespace Records {                                          // thrust::sort_by_key / stable_partition of src/pathtrace.cu:418-428,518,541
+// the workspace every call borrows: grown on demand (after a device synchronisation: an earlier call may still be using the old
+// one), freed by release()
+inline void *mi355x_workspace(unsigned long long bytes, bool free_it = false) {
+    static void *ws = nullptr;
+    static unsigned long long have = 0;
+    if (free_it || bytes > have) {
+        if (ws) { (void)hipDeviceSynchronize(); (void)hipFree(ws); }
+        ws = nullptr; have = 0;
+        if (!free_it) {
+            if (hipMalloc(&ws, bytes) != hipSuccess) { fprintf(stderr, "mi355x stream compaction error (Records): hipMalloc of %llu bytes failed\n", bytes); exit(EXIT_FAILURE); }
+            have = bytes;
+        }
+    }
+    return ws;
+}
+inline void release() { mi355x_workspace(0, true); }
+
+// the workspace of one call, with 8 bytes behind it for the count that stablePartition / compact read back
+inline void *mi355x_borrow(int n, int nkeys, int **count) {
+    const unsigned long long need = sc_records_workspace_bytes(n, nkeys);
+    char *ws = static_cast<char *>(mi355x_workspace(need + 8));
+    *count = reinterpret_cast<int *>(ws + need);
+    return ws;
+}
+
+template <typename T>
+inline void sortByKey(int n, int nkeys, int descending, const int *firstKey, int keyStride, T *outA, const T *inA, void *stream = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    int *count;
+    void *ws = mi355x_borrow(n, nkeys, &count);
+    Common::mi355x_check(sc_sort_records_by_key_device(n, nkeys, descending, firstKey, keyStride, outA, inA, (int)sizeof(T), nullptr, nullptr, 0,
+                                                       nullptr, nullptr, ws, stream), "Records::sortByKey");
+}
+template <typename T, typename U>
+inline void sortByKey(int n, int nkeys, int descending, const int *firstKey, int keyStride, T *outA, const T *inA, U *outB, const U *inB,
+                      void *stream = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    static_assert(std::is_trivially_copyable<U>::value && sizeof(U) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    int *count;
+    void *ws = mi355x_borrow(n, nkeys, &count);
+    Common::mi355x_check(sc_sort_records_by_key_device(n, nkeys, descending, firstKey, keyStride, outA, inA, (int)sizeof(T), outB, inB, (int)sizeof(U),
+                                                       nullptr, nullptr, ws, stream), "Records::sortByKey");
+}
+
+template <typename T>
+inline int mi355x_split(bool keptOnly, int n, T *out, const T *in, const int *firstFlag, int flagStride, void *stream) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    int *count, kept = 0;
+    void *ws = mi355x_borrow(n, 2, &count);
+    Common::mi355x_check((keptOnly ? sc_compact_records_device : sc_partition_records_device)(n, (int)sizeof(T), out, in, firstFlag, flagStride, count, ws, stream),
+                         keptOnly ? "Records::compact" : "Records::stablePartition");
+    // one synchronising read, as thrust's return value is
+    if (hipMemcpyAsync(&kept, count, sizeof(int), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)) != hipSuccess ||
+        hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) {
+        fprintf(stderr, "mi355x stream compaction error (Records): reading the count failed\n");
+        exit(EXIT_FAILURE);
+    }
+    return kept;
+}
+// flag != 0 first, then flag == 0, both in order; returns the partition point
+template <typename T>
+inline int stablePartition(int n, T *out, const T *in, const int *firstFlag, int flagStride, void *stream = nullptr) {
+    return mi355x_split(false, n, out, in, firstFlag, flagStride, stream);
+}
+// the kept records only; returns their number
+template <typename T>
+inline int compact(int n, T *out, const T *in, const int *firstFlag, int flagStride, void *stream = nullptr) {
+    return mi355x_split(true, n, out, in, firstFlag, flagStride, stream);
+}
+}  // namespace Records
+#endif
 }  // namespace StreamCompaction
