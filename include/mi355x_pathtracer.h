@@ -423,6 +423,9 @@ int ptx_debug_record_masks(int nmaterials, const ptx_material *materials, int ng
  * the device, for n corner boxes (lo xyz, hi xyz): 8 floats per box = centre xyz, 0, half extent xyz, 0.  The CPU tests check that it
  * contains the corner box and that the device's slab arithmetic on it never rejects a ray that reaches the corner box. */
 int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8);
+/* CPU-only: the geoms a path can end on with radiance, as ptx_create works them out: bit g of *bits_out (g < 32) = the material of geom g
+ * (geom_material[g]) has emittance > 0.  The last bounce of a path looks only for these geoms.  Returns 0, -1 on a bad argument. */
+int ptx_debug_light_bits(int nmaterials, const ptx_material *materials, int ngeoms, const int32_t *geom_material, uint32_t *bits_out);
 /* Debug: workgroups of the specialised later-bounce kernel that fit a CU with lds_bytes of dynamic LDS each (0: what this tracer launches). */
 int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes);
 /* Debug: after waiting for the tracer's streams, the nonzero words left in the per-iteration "lit" bit-planes (out3[0]) and in the

@@ -250,6 +250,18 @@ def debug_cull_boxes(boxes6):
     return out
 
 
+def debug_light_bits(materials, geom_material):
+    """CPU only: ptx_create's light_bits (ptx_debug_light_bits) for an (n, 11) float32 array of materials (struct Material: colour 3,
+    exponent, specular colour 3, reflective, refractive, ior, emittance) and the geoms' material indices: bit g = geom g's material emits."""
+    L = load_library()
+    m = np.ascontiguousarray(materials, np.float32).reshape(-1, 11)
+    gm = np.ascontiguousarray(geom_material, np.int32).reshape(-1)
+    out = np.zeros(1, np.uint32)
+    if L.ptx_debug_light_bits(len(m), _ptr(m), len(gm), _ptr(gm), _ptr(out)) < 0:
+        raise PathTracerError("ptx_debug_light_bits: bad argument")
+    return int(out[0])
+
+
 def build_library(force=False):
     """Compiles the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(LIB_PATH):
@@ -402,6 +414,8 @@ def load_library():
         L.ptx_debug_tile_geoms.restype, L.ptx_debug_tile_geoms.argtypes = i, [vp, i, vp, i, i, i, i, vp, i]
     if hasattr(L, "ptx_debug_cull_boxes"):
         L.ptx_debug_cull_boxes.restype, L.ptx_debug_cull_boxes.argtypes = i, [i, vp, vp]
+    if hasattr(L, "ptx_debug_light_bits"):
+        L.ptx_debug_light_bits.restype, L.ptx_debug_light_bits.argtypes = i, [i, vp, i, vp, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
         L.ptx_kat_fast_exact.restype, L.ptx_kat_fast_exact.argtypes = i, [vp, vp]
     L.ptx_debug_set_capture.restype, L.ptx_debug_set_capture.argtypes = i, [vp, i]

@@ -352,6 +352,8 @@ struct DScene {
                                         // invTranspose rows 0-2 (12), type, materialid, faceStart, faceCount
     const float *__restrict__ aabb;     // 8 floats per geom: conservative world-space box as (centre xyz, pad, half extent xyz, pad), or NULL
     uint32_t cube_bits, sphere_bits, mesh_bits;   // bit i: geom i is a cube / sphere / mesh (unknown types are in none)
+    uint32_t light_bits;                // bit i: geom i's material emits (emittance > 0): the geoms the light-only last bounce looks for (k_bounce's light-only variant).
+                                        // (It lies in what was padding behind the three masks: no other field of the block has moved)
     const BvhQuad *__restrict__ bvh_nodes;          // threaded BVH of the larger meshes (pt_bvh.h), or NULL
     const float *__restrict__ bvh_tris;             // BVH_TRI words per leaf triangle
     const int32_t *__restrict__ bvh_root;           // per geom: root node, -1 = plain loop over its faces

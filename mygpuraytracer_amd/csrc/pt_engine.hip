@@ -247,6 +247,9 @@ __global__ __launch_bounds__(256) void k_gbuffer(const DScene sc, const DCamera 
 extern "C" const void *ptx_arith_kernels_0(void);
 extern "C" const void *ptx_arith_kernels_1(void) __attribute__((weak));
 extern "C" const void *ptx_arith_kernels_2(void) __attribute__((weak));
+extern "C" const void *ptx_arith_last_0(void);      // (pt_kernels_last.hip: the light-only last bounce of each level)
+extern "C" const void *ptx_arith_last_1(void) __attribute__((weak));
+extern "C" const void *ptx_arith_last_2(void) __attribute__((weak));
 
 // An owned device array -- every device buffer of the tracer, the scratch of the per-stage entry points -- freed when its owner goes, on
 // every way out (a HIPCHECK that fails returns from the middle).  Each step hands back the hipError_t: ptx_create looks for out-of-memory.
@@ -301,6 +304,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
     DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
     bool no_fast = false;                                // PTX_DEBUG_NO_FAST: always the general k_bounce (A/B timing, tests of both variants)
+    bool no_last = false;                                // PTX_DEBUG_NO_LAST: the last bounce runs the full k_bounce like every other (A/B timing, tests of both)
     bool force_fast = false;                             // PTX_DEBUG_FORCE_FAST: ask for the specialised variant at every launch (refused
                                                          // with PTX_ERR_INVALID where its preconditions do not hold; tests only)
     DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_items; DevBuf<int32_t> d_item_count;
@@ -365,7 +369,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     bool cap_filled = false;
     DScene scene() const {
         DScene s; s.geoms = d_geoms; s.mats = d_mats; s.faces = d_faces; s.tri9 = d_tri9; s.texels = d_texels; s.ngeoms = ngeoms; s.nmats = nmats;
-        s.gtab = d_gtab; s.aabb = d_aabb; s.cull = 0; s.cube_bits = cube_bits; s.sphere_bits = sphere_bits; s.mesh_bits = mesh_bits;
+        s.gtab = d_gtab; s.aabb = d_aabb; s.cull = 0; s.cube_bits = cube_bits; s.sphere_bits = sphere_bits; s.mesh_bits = mesh_bits; s.light_bits = light_bits;
         s.bvh_nodes = d_bvh_nodes; s.bvh_tris = d_bvh_tris; s.bvh_root = d_bvh_root; s.bvh_depth = d_bvh_depth; s.bvh_wide = d_bvh_wide; s.bvh_wroot = d_bvh_wroot; s.bvh_wneed = d_bvh_wneed; s.bvh_stack = 0; s.ntri_lds = 0; s.mesh_chunks = mesh_chunks;
         s.fnorm = d_fnorm; s.cnorm = d_cnorm; s.bump_bits = bump_bits;
         s.tri_lds = 0; s.ntri = ntri;      // tri_lds is switched on only by launches that stage the table (k_bounce)
@@ -374,6 +378,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     }
     bool cache_active() const { return opt.cache_first_bounce && !opt.antialiasing && !opt.depth_of_field; }
     const KernelSet *ks = static_cast<const KernelSet *>(ptx_arith_kernels_0());      // the code object the arithmetic-bearing kernels are launched from (ptx_options.arith)
+    const LastKernelSet *ksl = static_cast<const LastKernelSet *>(ptx_arith_last_0());    // ... and the same level's light-only last bounce
 };
 
 namespace {
@@ -455,13 +460,33 @@ const char *fast_violation(const ptx_tracer *t, int mode, bool first, bool needs
     return nullptr;
 }
 
-// the one launch site of k_bounce: picks the variant by the predicate above
-int launch_bounce(const ptx_tracer *t, bool first, int mode, bool needs_albedo, dim3 grid, size_t lds, hipStream_t stream, const BounceParams &bp) {
+// The light-only variant k_bounce<false, 3, .> stores no path, ranks nothing and leaves no run table: right only for the launch whose paths all
+// end (bounce traceDepth - 1), and it finds its rays' candidates through the tile path alone.  The same shape as above: the first
+// assumption that does not hold (nullptr: all hold); launch_bounce takes the variant only then.  There is no switch that forces it.
+const char *last_violation(const ptx_tracer *t, int mode, bool first, const BounceParams &bp) {
+    if (bp.bounce != bp.traceDepth - 1) return "not the last bounce: paths that go on must be ranked and stored";
+    if (first) return "the camera bounce (depth 1)";
+    if (mode != 0 || t->split_mesh) return "the scene takes the split mesh search";
+    if (!bp.sc.cull || !bp.sc.tri_lds) return "candidate masks or LDS scene tables are off";
+    if (bp.sc.ngeoms > 32 || bp.sc.ngeoms < 1) return "more than 32 geoms: no bit per geom";
+    if (bp.uses_uv) return "textured scene (an emissive texel ends a path where it scatters)";
+    if (t->capture_bounce == bp.bounce) return "debug capture of this bounce";
+    return nullptr;
+}
+
+// the one launch site of k_bounce: picks the variant by the predicates above.  gx_last != 0: the workgroups per segment of the
+// light-only variant, where it is taken (it reads the previous launch's run tables and writes none: any grid will do).
+int launch_bounce(const ptx_tracer *t, bool first, int mode, bool needs_albedo, dim3 grid, size_t lds, hipStream_t stream, const BounceParams &bp, int gx_last = 0) {
     const char *why = fast_violation(t, mode, first, needs_albedo, bp);
     bool fast = !t->no_fast && !why;
     if (t->force_fast) {
         if (why) return set_error(PTX_ERR_INVALID, std::string("specialised k_bounce requested outside its preconditions: ") + why);
         fast = true;
+    }
+    if (!t->no_last && !last_violation(t, mode, first, bp)) {
+        if (gx_last > 0) grid.x = (unsigned)gx_last;
+        t->ksl->bounce_last(fast ? 1 : 0, grid, lds, stream, &bp);
+        return PTX_OK;
     }
     t->ks->bounce(first ? 1 : 0, mode, fast ? 1 : 0, grid, lds, stream, &bp);
     return PTX_OK;
@@ -526,13 +551,14 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
     // step, its long run 0.1415 -> 0.138 (three runs each of six plans on one box, gpurun_out/r4grid2.log; 28 / 14 was the choice while
     // the kernels moved 40 % more bytes and a chunk's tail of index traffic was worth spreading).
     // (traced ahead of per-call requests: five per CU, so that two slots stay free for the caller's own short kernels)
-    auto per_cu = [&](bool first_bounce) {
+    auto per_cu = [&](bool first_bounce, bool last_bounce = false) {
+        if (fast_unsplit && !defer && last_bounce) { if (const char *e = getenv("PTX_DEBUG_WG_LAST")) return std::max(1, atoi(e)); }      // tuning experiments
         if (fast_unsplit && !defer) { if (const char *e = getenv(first_bounce ? "PTX_DEBUG_WG_FIRST" : "PTX_DEBUG_WG_LATER")) return std::max(1, atoi(e)); }      // tuning experiments
         if (fast_unsplit) return defer ? PT_FAST_WAVES - 2 : first_bounce ? 20 : PT_FAST_WAVES;
         return t->split_mesh ? 32 : 8;
     };
-    auto gx_of = [&](bool first_bounce) {
-        int grid = t->grid_forced ? t->grid : t->cus * per_cu(first_bounce);
+    auto gx_of = [&](bool first_bounce, bool last_bounce = false) {
+        int grid = t->grid_forced ? t->grid : t->cus * per_cu(first_bounce, last_bounce);
         if (t->dbg_total_wg_per_cu > 0) grid = t->cus * t->dbg_total_wg_per_cu;      // tuning experiments
         int g = grid / K;                            // workgroups per segment
         if (!t->grid_forced && t->dbg_total_wg_per_cu <= 0) {
@@ -549,6 +575,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         return g < 1 ? 1 : g;
     };
     const int gx_first = gx_of(true), gx_later = gx_of(false);
+    const int gx_last = gx_of(false, true);      // (the light-only last bounce: the later bounces' grid -- 4 / 8 / 16 workgroups per CU measured alike, profiles/last_bounce_ab.txt)
     const int grid = t->cus * (t->dbg_total_wg_per_cu > 0 ? t->dbg_total_wg_per_cu : per_cu(false));      // (k_finish's grid-stride launch)
     const int gx = gx_later;
     const int nsuper = (gx + 63) / 64;
@@ -673,7 +700,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
             KT(3, { int rcl = launch_bounce(t, first, 2, needs_albedo, dim3(gx_b, K), lds_pass2, stream, bp); if (rcl != PTX_OK) return rcl; });
         } else {
             bp.keys = nullptr; bp.items = nullptr; bp.item_count = nullptr; bp.item_cursor = nullptr; bp.seg_keys = bp.seg_items = 0; bp.tile_done = nullptr;
-            KT(first ? 0 : 1, { int rcl = launch_bounce(t, first, 0, needs_albedo, dim3(gx_b, K), lds_bounce, stream, bp); if (rcl != PTX_OK) return rcl; });
+            KT(first ? 0 : 1, { int rcl = launch_bounce(t, first, 0, needs_albedo, dim3(gx_b, K), lds_bounce, stream, bp, gx_last); if (rcl != PTX_OK) return rcl; });
         }
 
         if (first && fill_cache) {
@@ -897,10 +924,15 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         ks = static_cast<const KernelSet *>(tab);
         if (ks->arith != opt.arith) return set_error(PTX_ERR_HIP, "arithmetic code object mismatch");
     }
+    // (a missing kernel is an error, never a quiet return to the full bounce)
+    const void *ltab = opt.arith == 1 ? (ptx_arith_last_1 ? ptx_arith_last_1() : nullptr) : opt.arith == 2 ? (ptx_arith_last_2 ? ptx_arith_last_2() : nullptr) : ptx_arith_last_0();
+    if (!ltab) return set_error(PTX_ERR_UNSUPPORTED, "this library was built without the last-bounce code object of arithmetic level " + std::to_string(opt.arith));
+    const LastKernelSet *ksl = static_cast<const LastKernelSet *>(ltab);
+    if (ksl->arith != opt.arith) return set_error(PTX_ERR_HIP, "arithmetic code object mismatch (last bounce)");
     ptx_tracer *t = new ptx_tracer;
     auto fail = [&](int code) { free_tracer(t); return code; };
 #define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(PTX_ERR_HIP); } } while (0)
-    t->ks = ks;
+    t->ks = ks; t->ksl = ksl;
     t->device = dev; t->opt = opt; t->traceDepth = t->maxBounces = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
     hipDeviceProp_t prop;
     HC(hipGetDeviceProperties(&prop, dev));
@@ -944,6 +976,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         t->lanes = plan.lanes;
     }
     t->no_fast = getenv("PTX_DEBUG_NO_FAST") != nullptr;
+    t->no_last = getenv("PTX_DEBUG_NO_LAST") != nullptr;
     t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
     if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
     if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));

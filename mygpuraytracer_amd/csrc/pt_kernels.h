@@ -378,5 +378,12 @@ struct KernelSet {
     void (*kat_libm)(dim3 grid, hipStream_t st, int n, const float *x, float *s, float *c, const double *pw, double *p5, const float *pxy, float *pout);
     int (*bounce_occupancy)(size_t lds);      // ptx_debug_bounce_occupancy: workgroups of the specialised later-bounce kernel per CU (< 0: error)
 };
+// The light-only last bounce, k_bounce<false, 3, .> -- the unsplit later bounce of a path's LAST intersection (bounce traceDepth - 1) -- is a
+// code object of its own per level (pt_kernels_last.hip), exported as ptx_arith_last_<level>(); lds = what `bounce` is given for the same
+// launch (last_violation, pt_engine.hip, says when it may be taken).
+struct LastKernelSet {
+    int arith;
+    void (*bounce_last)(int fast, dim3 grid, size_t lds, hipStream_t st, const void *bounce_params);
+};
 
 }  // namespace

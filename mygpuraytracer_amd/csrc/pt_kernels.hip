@@ -88,7 +88,8 @@ constexpr int ITEMS_PER_PASS = 4;                      // pairs a ray may contri
 #endif
 // DEFER: the mesh pairs are not worked off here; the caller gets the best key over cubes and spheres and the ray's
 // mesh candidates (split mesh search, see k_mesh), and `hit` is left alone.
-template <bool DEFER, bool PARK = false, bool SUBSET = false>
+// !DECODE: the caller wants the winning key only (the light-only last bounce: its geom's material is all that matters); `hit` is left alone.
+template <bool DEFER, bool PARK = false, bool SUBSET = false, bool DECODE = true>
 __device__ __forceinline__ void tileIntersect(const DScene &sc, bool alive, Ray ray, bool need_uv, Hit &hit, int32_t *scratch,
                                               int32_t *tcnt, int &q, int tid, int lane, int wave, unsigned long long &key_out,
                                               uint32_t &mesh_out TI_ARGS, uint32_t subset = 0xffffffffu) {
@@ -197,7 +198,7 @@ __device__ __forceinline__ void tileIntersect(const DScene &sc, bool alive, Ray 
         ray.o = V3(rayb[0 * TILE + tid], rayb[1 * TILE + tid], rayb[2 * TILE + tid]);
         ray.d = V3(rayb[3 * TILE + tid], rayb[4 * TILE + tid], rayb[5 * TILE + tid]);
     }
-    if (!DEFER) decodeKey(sc, gtab, key_out, ray, need_uv, hit);
+    if (!DEFER && DECODE) decodeKey(sc, gtab, key_out, ray, need_uv, hit);
     TI_STAMP(7);
 }
 
@@ -349,9 +350,22 @@ __device__ __forceinline__ void flushQueue(const BounceParams &p, int seg, const
 // untaken side, is gone (C4: k_bounce -6 %, the first bounce -11 %, fewer registers).  The host picks the variant per launch
 // (enqueue_batch); everything else takes the general kernel, same results.  For the two halves of the split bounce (MODE 1, 2)
 // FAST bakes only the subset that textured scenes with BVH meshes satisfy as well.
-template <bool FIRST, int MODE, bool FAST = false>
-__global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE == 1 ? PT_FAST_WAVES_SPLIT : MODE == 2 ? PT_FAST_WAVES_SPLIT2 : FIRST ? PT_FAST_WAVES_FIRST : PT_FAST_WAVES) void k_bounce(const BounceParams p_in) {      // (the camera-ray
+// LAST (later bounce, MODE 0 only): the launch is the paths' last intersection (bounce traceDepth - 1), where classifyPath
+// never stores a path: it ends with radiance if its nearest hit emits, and black -- nothing written at all -- otherwise.  No later launch
+// reads a rank, a key, a record, a prefix or a run table of this bounce.  So, behind the unchanged head (run search, gather,
+// scatterRay with the stored stream index): only the rays that reach the inflated box of some emitting geom (sc.light_bits; the same
+// slab test as the candidate masks, so a miss there is a miss of the geom in the full test too) go on, to the pair tests against ALL
+// their candidates -- an occluder must win -- and the winner's material alone decides: emissive => the deposit classifyPath makes,
+// otherwise nothing.  No normal, no ranking, no epilogue, no tail; the bounce's ray count, which k_stats sums over the bins, goes to bin 0.
+// It is MODE_ 3 of this template (MODE_LAST) and MODE 0 in everything but the above: the other instantiations do not see it.  It is
+// instantiated by pt_kernels_last.hip alone (this source with PT_KERNELS_LAST_UNIT, see the end of the file), one more code object per level.
+constexpr int MODE_LAST = 3;
+template <bool FIRST, int MODE_, bool FAST = false>
+__global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAST_WAVES_SPLIT : MODE_ == 2 ? PT_FAST_WAVES_SPLIT2 : FIRST ? PT_FAST_WAVES_FIRST : PT_FAST_WAVES) void k_bounce(const BounceParams p_in) {      // (the camera-ray
                                                                                    // variant needs 65 registers: seven waves without spilling)
+    constexpr bool LAST = MODE_ == MODE_LAST;
+    constexpr int MODE = LAST ? 0 : MODE_;
+    static_assert(MODE_ >= 0 && MODE_ <= MODE_LAST && !(LAST && FIRST), "modes 0-2, and the light-only variant of a later unsplit bounce");
 #ifdef PT_WGCLOCK
     const unsigned long long wg_t0 = wall_clock64();       // 100 MHz: latency of the workgroup's phases (prologue, tile loop, tail)
 #endif
@@ -565,6 +579,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE == 1 ? PT_FAST
         classifyPath<FIRST>(p, iter, part, batched, hit, ps.color, pix, bin, pending);
     };
     int32_t *ccnt = qcnt + 2;                                   // MODE 1: candidates of the tile so far (LDS)
+    int n_last = 0;                                             // LAST: rays of this wave's tiles that entered the intersection (wave-uniform)
     int32_t k1_next = 0;                                        // MODE 2: the next tile's word, requested one tile ahead
     // The ranking pass (MODE 2) has three barriers per tile: counts by wave 0, keys scattered to their slots through LDS.
     // MEASURED AND NOT KEPT, code removed (round 5, -DPT_RANK_ONE_BARRIER; last in commit 77f3d5a): the pass with ONE barrier per tile --
@@ -599,7 +614,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE == 1 ? PT_FAST
         // ranking histogram (read after later barriers).  The ranking pass (MODE 2) has no intersection whose barriers would separate
         // this from the ballots' writes: it zeroes the histogram right after a tile's LAST read of it instead (below), and once before
         // its first tile -- three barriers per tile instead of five for a kernel that is a chain of barriers and little else.
-        if (MODE != 2 && !direct) for (int k = tid; k < 2 * WAVES * nb; k += TILE) lds[k] = 0;
+        if (MODE != 2 && !direct && !LAST) for (int k = tid; k < 2 * WAVES * nb; k += TILE) lds[k] = 0;      // (the light-only bounce ranks nothing)
         ps.o = ps.d = ps.color = V3(0.f, 0.f, 0.f);
         unsigned long long key = KEY_NONE;
         int32_t k1 = 0;
@@ -667,6 +682,27 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE == 1 ? PT_FAST
             }
         }
         STAMP(0);        // load + shade (or ray generation)
+        if (LAST) {
+            n_last += __popcll(__ballot(alive));              // rays that enter this bounce's intersection (rays_per_bounce)
+            if (p.sc.light_bits == 0u) continue;                 // (uniform) nothing in the scene emits: every path ends black
+            Ray ray; ray.o = ps.o; ray.d = ps.d;
+            const bool reach = alive && cullMask<true>(p.sc, ray, p.sc.light_bits) != 0u;
+            Hit none;                                         // (never read: no decode)
+            uint32_t mesh_cand = 0;
+            tileIntersect<false, false, false, false>(p.sc, reach, ray, false, none, rec, tcnt, tq, tid, lane, wave, key, mesh_cand TI_PASS);
+            if (reach && key != KEY_NONE) {
+                // the winner's material; classifyPath with a hit that holds what it reads (t > 0: the key functions accept nothing else)
+                const float *G = reinterpret_cast<const float *>(pt_lds) + p.sc.ntri_lds * 24 + p.sc.nmats * 11 + (int)((key >> 24) & 0xff) * GTAB_WORDS;
+                Hit lh;
+                lh.t = 1.f; lh.n = V3(0.f, 0.f, 0.f); lh.u = lh.v = 0.f; lh.geom = 0; lh.ncode = 0;
+                lh.mat = __float_as_int(G[37]);
+                int lbin = 0;
+                bool lpend = false;
+                classifyRay(lh, ps, pix, lbin, lpend);
+            }
+            STAMP(1);
+            continue;
+        }
         // computeIntersections(b) + the terminal cases of shadeFakeMaterial(b)
         Hit hit;
         hit.t = -1.f; hit.n = V3(0.f, 0.f, 0.f); hit.u = hit.v = 0.f; hit.geom = 0; hit.mat = 0; hit.ncode = 0;
@@ -1024,6 +1060,10 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE == 1 ? PT_FAST
 #ifdef PT_WGCLOCK
     const unsigned long long wg_t2 = wall_clock64();
 #endif
+    if (LAST) {                          // nothing was stored: no tail.  The rays counted, one atomic per wave (every lane holds the wave's sum)
+        if (lane == 0 && n_last) atomicAdd(&totals_all[0], n_last);
+        return;
+    }
     if (MODE == 1) {                     // counts belong to MODE 2; what is left in the LDS queue goes out now
         if (*qcnt > 0) flushQueue(p, seg, qbuf, qcnt, qbase, tid);
         return;
@@ -1296,6 +1336,7 @@ __global__ __launch_bounds__(256) void k_finish(const BounceParams p_in) {
     }
 }
 
+#ifndef PT_KERNELS_LAST_UNIT
 // ---- per-stage kernels for the parity tests (AoS records of the reference in, same out) ----------------------
 __global__ void k_kat_geom(DScene sc, int gi, int n, const float *rays, float *out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1530,3 +1571,24 @@ const KernelSet g_kernels_here = {PT_ARITH, ks_bounce, ks_mesh, ks_finish, ks_ka
 #define PT_ARITH_EXPORT_(n) ptx_arith_kernels_##n
 #define PT_ARITH_EXPORT(n) PT_ARITH_EXPORT_(n)
 extern "C" const void *PT_ARITH_EXPORT(PT_ARITH)(void) { return &g_kernels_here; }
+
+#else   // PT_KERNELS_LAST_UNIT
+// pt_kernels_last.hip: this source again, per level, for ONE thing -- the light-only last bounce (k_bounce<false, MODE_LAST, .>), a code
+// object of its own beside the level's pt_kernels.hip one.  Nothing else is instantiated here (k_mesh, k_finish are templates nobody
+// names; the test kernels and the launcher table are compiled out), and pt_kernels.hip itself does not instantiate this mode: the
+// kernels of that unit are exactly the ones they were.
+void ks_bounce_last(int fast, dim3 grid, size_t lds, hipStream_t stream, const void *params) {
+    const BounceParams &bp = *static_cast<const BounceParams *>(params);
+    // (launched in place of k_bounce<false, 0, fast> where last_violation (pt_engine.hip) allows it, with the same grid and the same LDS)
+    if (fast) hipLaunchKernelGGL((k_bounce<false, MODE_LAST, true>), grid, dim3(TILE), lds - sizeof(int32_t) * (17 - REC_ROWS_FAST0) * TILE, stream, bp);
+    else hipLaunchKernelGGL((k_bounce<false, MODE_LAST, false>), grid, dim3(TILE), lds, stream, bp);
+}
+const LastKernelSet g_last_here = {PT_ARITH, ks_bounce_last};
+
+}  // namespace
+
+// all this translation unit exports: its launcher
+#define PT_LAST_EXPORT_(n) ptx_arith_last_##n
+#define PT_LAST_EXPORT(n) PT_LAST_EXPORT_(n)
+extern "C" const void *PT_LAST_EXPORT(PT_ARITH)(void) { return &g_last_here; }
+#endif

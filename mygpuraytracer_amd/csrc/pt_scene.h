@@ -24,6 +24,7 @@ struct SceneFacts {
     int uses_uv = 0;
     uint32_t cube_bits = 0, sphere_bits = 0, mesh_bits = 0;   // geoms 0..31 by kind, for the candidate masks
     uint32_t bump_bits = 0;
+    uint32_t light_bits = 0;                             // geoms 0..31 whose material emits (emittance > 0): DScene::light_bits
     int tri_lds = 0, ntri_lds = 0, cull = 0;
     bool split_mesh = false;                             // k_bounce as MODE 1 + k_mesh + k_finish + MODE 2 (scenes with BVH meshes)
     unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
@@ -54,5 +55,7 @@ void tile_geom_masks(const DCamera &c, int tile_rows, int tile_rank, int tile_wo
                      bool dof, std::vector<uint32_t> &masks);
 void camera_to_device(const ptx_camera &c, DCamera &d);
 int owned_pixels(int W, int H, int tile_rows, int tile_rank, int tile_world);      // pixels of the row blocks this rank owns
+// bit g (g < 32): geom g's material has emittance > 0 -- classifyPath's test of a hit's material, per geom
+uint32_t light_geom_bits(int nmaterials, const DMaterial *mats, int ngeoms, const int32_t *geom_material);
 
 }  // namespace ptd

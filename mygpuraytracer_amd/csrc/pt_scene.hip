@@ -222,6 +222,18 @@ std::vector<float> triangle_table(const float *faces15, int nfaces) {
     return tri9;
 }
 
+// The geoms a path can end on WITH radiance: bit g = geom g's material emits (emittance > 0, classifyPath's test of the hit's material).
+// The last bounce of a launch set looks only for these (k_bounce's light-only variant).  (A material index outside the table sets no bit; geoms beyond
+// 31 have none -- such scenes do not take the tile path.)
+uint32_t light_geom_bits(int nmaterials, const DMaterial *mats, int ngeoms, const int32_t *geom_material) {
+    uint32_t bits = 0;
+    for (int g = 0; g < ngeoms && g < 32; g++) {
+        const int m = geom_material[g];
+        if (m >= 0 && m < nmaterials && mats[m].emittance > 0.0f) bits |= 1u << g;
+    }
+    return bits;
+}
+
 // scene upload (pathtraceInit, src/pathtrace.cu:111-146) -- flattened, no host struct is mutated
 int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials, const ptx_options &opt, int owned,
                      int nbins, size_t lds_limit, const SceneSwitches &sw, HostScene &hs) {
@@ -348,6 +360,11 @@ int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const pt
     static_assert(sizeof(DMaterial) == sizeof(ptx_material), "material layout");
     if (nmaterials) memcpy(hs.mats.data(), materials, sizeof(DMaterial) * (size_t)nmaterials);
     for (const DMaterial &m : hs.mats) hs.h_spec.push_back(m.hasReflective > 0.0f || m.hasRefractive > 0.0f ? 1 : 0);
+    {
+        std::vector<int32_t> gm((size_t)ngeoms);
+        for (int i = 0; i < ngeoms; i++) gm[i] = hs.geoms[i].materialid;
+        hs.light_bits = light_geom_bits(nmaterials, hs.mats.data(), ngeoms, gm.data());
+    }
     {   // which records carry what (record_masks); off: more than 64 bins, no material, or PTX_DEBUG_NO_DIR_SKIP
         unsigned long long need = ~0ull, cubes = 0ull;
         const bool off = nbins > 64 || nmaterials < 1 || sw.no_dir_skip;
@@ -447,6 +464,14 @@ int ptx_debug_record_masks(int nmaterials, const ptx_material *materials, int ng
     unsigned long long d = 0, n = 0;
     record_masks(nmaterials, reinterpret_cast<const DMaterial *>(materials), ngeoms, geom_type, geom_material, sort_by_material != 0, d, n);
     masks[0] = d; masks[1] = n;
+    return 0;
+}
+
+// CPU-only: ptx_create's light_bits (light_geom_bits) for ngeoms geoms given by their material: bit g = geom g can end a path with radiance.
+int ptx_debug_light_bits(int nmaterials, const ptx_material *materials, int ngeoms, const int32_t *geom_material, uint32_t *bits_out) {
+    if (nmaterials < 0 || (nmaterials && !materials) || ngeoms < 0 || (ngeoms && !geom_material) || !bits_out)
+    { set_error(PTX_ERR_INVALID, "ptx_debug_light_bits: bad argument"); return -1; }
+    *bits_out = light_geom_bits(nmaterials, reinterpret_cast<const DMaterial *>(materials), ngeoms, geom_material);
     return 0;
 }
 

@@ -6,7 +6,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ("pt_kernels.hip", "pt_kernels.h", "pt_engine.hip", "pt_device.h", "pt_bvh.h", "Makefile")
+KERNEL_SOURCES = ("pt_kernels.hip", "pt_kernels_last.hip", "pt_kernels.h", "pt_engine.hip", "pt_device.h", "pt_bvh.h", "Makefile")
 
 
 def source_sha16():
@@ -18,12 +18,14 @@ def source_sha16():
 
 def kernel_label(name):
     """'k_bounce' / 'k_bounce<first>' for the unsplit kernel (MODE 0); the halves of the split bounce apart: 'k_bounce pass1',
-    'k_bounce<first> pass1', '... pass2'; k_mesh / k_mesh<first>; k_gather.  Both spellings rocprofv3 has used (demangled
+    'k_bounce<first> pass1', '... pass2' (the light-only last bounce, mode 3, counts as 'k_bounce'); k_mesh / k_mesh<first>; k_gather.  Both spellings rocprofv3 has used (demangled
     k_bounce<false, 1, true>, mangled k_bounceILb0ELi1ELb1E)."""
     m = re.search(r"k_bounce<\s*(true|false)\s*,\s*(\d)", name) or re.search(r"k_bounceILb([01])ELi(\d)", name)
     if m:
         first = m.group(1) in ("true", "1")
         mode = int(m.group(2))
+        if mode == 3:      # the light-only last bounce (MODE_LAST): one of the depth - 1 later-bounce launches of a launch set
+            mode = 0
         return ("k_bounce<first>" if first else "k_bounce") + ("" if mode == 0 else " pass%d" % mode)
     m = re.search(r"k_mesh<\s*(true|false)", name) or re.search(r"k_meshILb([01])", name)
     if m:
