@@ -383,6 +383,76 @@ int  ptx_denoise_buffers_variance(int device, int w, int h, const float *rgb, co
                                   const uint8_t *hit, const int32_t *ids2, const float *var1, const ptx_denoise_params *dp,
                                   const ptx_variance_params *vp, float *out_rgb, float *out_var1);
 
+/* ---- sample moments by batch means: error estimate, stop rule, measured variance for the filter, csrc/pt_moments.hip ----------------
+ * The per-sample covariance of every pixel's radiance, estimated from the accumulation buffer alone: no rendering kernel is involved.
+ * Whenever the caller says "N samples are in the buffer now" (ptx_moments_add), the difference to the snapshot the handle kept is the
+ * sum of one batch; the batch mean is folded into running moments and the snapshot is replaced.  Batches of iid samples give an
+ * unbiased estimate of the per-sample covariance whatever their sizes.  Definition (tests/moments_ref.py restates it):
+ *   State per pixel (56 B): snap = accumulation rgb at the last add and W, the samples it held; mean = the weighted mean rgb of the
+ *   batch means and the batch count B; M = the upper triangle (rr, gg, bb, rg, rb, gb) of the weighted scatter matrix.  All zero after
+ *   create and reset, so the first add takes everything in the buffer as one batch.
+ *   Add with samples_total = N > W: k = N - W, x = (acc - snap) / k per channel, then West's weighted update
+ *     W' = W + k, d = x - mean, mean' = mean + (k / W') d, M' = M + k d (x - mean')^T, B' = B + 1, snap' = (acc, N).
+ *   (mean = snap / W and x - mean' = (W / W') d, so d = D / (k W) with D = W acc - W' snap and the scatter term is D D^T / (k W W'): the
+ *   device evaluates it in that form, D from exact fp32 products, so that a batch mean close to the running mean costs no precision.)
+ *   B >= 2: the per-sample covariance estimate is C = M / (B - 1), and the variance of the frame's mean of a linear functional g of
+ *   the colour is g^T C g / W.  B < 2: no estimate (ptx_moments_read gives C = 0).
+ *   Summary (ptx_moments_summarize), over the pixels with B >= 2, g = Rec. 709 (l above): q = max(g^T C g, 0), se = sqrt(q / W),
+ *   rel = se / max(l(mean), floor).  Reduced on the device in two stages of fixed order without float atomics: the same bits on
+ *   every run.
+ *   Measured variance for the filter (ptx_denoise_measured): ptx_denoise_variance without a handle, whose v0 on a hit pixel with
+ *   B >= min_batches is max(g^T C g, 0) / W, g_k = l_k / max(albedo_k, 1e-3) when demodulating, else g_k = l_k (l_k the Rec. 709
+ *   weights): the exact variance of the demodulated luminance, which is why the state is a covariance and not a scalar.  Hit pixels
+ *   with B < min_batches take the spatial estimate of ptx_denoise_variance; miss pixels 0.  The colour is rgb / spp as in ptx_denoise;
+ *   W is the handle's, so samples rendered after the last add make v0 conservative, never too small.
+ * Precision: everything is fp32.  acc - snap is exact or correctly rounded, but acc itself carries ulp(acc) / 2 per gather, so a batch
+ * mean carries about ulp(acc) / k = 2^-23 N / k of the pixel's mean in rounding noise, against a sampling noise of sigma / sqrt(k):
+ * negligible (below 1 % of the batch's standard deviation for sigma >= the mean / 10) below about 10^5 samples per pixel with batches
+ * of at least 8.  W and B are held as floats: exact to 2^24.
+ * The handle never looks at what the buffer holds: after ptx_reset_image (or ptx_write_image, or a camera change that restarts the
+ * accumulation) the caller MUST call ptx_moments_reset before the next add, or that add's batch is the difference of two unrelated
+ * frames.  A handle serves one W x H on one device, across tracers and streams, like ptx_temporal: each enqueueing call makes the
+ * tracer's stream wait for the handle's previous work and records an event after its own. */
+typedef struct ptx_moments ptx_moments;            /* opaque */
+typedef struct ptx_moments_params {
+    float floor;               /* > 0: rel = se / max(l(mean), floor); default 0.05 (stated, not tuned) */
+    float threshold;           /* >= 0: pixels with rel > threshold are counted; default 0.05 (stated, not tuned) */
+} ptx_moments_params;
+typedef struct ptx_moments_summary {
+    int64_t pixels;            /* pixels with B >= 2 (0: every other field but samples and batches is 0) */
+    int64_t pixels_over;       /* of those, rel > threshold */
+    int64_t samples;           /* W: samples_total of the last add */
+    double  mean_rel_se;       /* mean, root mean square and maximum of rel */
+    double  rms_rel_se;
+    double  max_rel_se;
+    double  mean_variance;     /* mean of q = g^T C g, the per-sample luminance variance */
+    int32_t batches;           /* B: adds since create / reset */
+    int32_t reserved;
+} ptx_moments_summary;
+void   ptx_default_moments_params(ptx_moments_params *p);
+size_t ptx_sizeof_moments_params(void);
+size_t ptx_sizeof_moments_summary(void);
+int  ptx_moments_create(int device, int width, int height, ptx_moments **out);     /* PTX_ERR_NODEVICE without a device */
+void ptx_moments_destroy(ptx_moments *m);          /* NULL is a no-op; waits for its last use */
+int  ptx_moments_reset(ptx_moments *m);            /* forget everything: required after ptx_reset_image (see above) */
+/* Enqueues one add on t's stream, ordered after every iteration rendered so far (render-ahead included: an iteration is in the buffer
+ * once its ptx_iterate / ptx_render returned, exactly what ptx_denoise reads).  The accumulation buffer, statistics and what later
+ * iterations compute are untouched.  Refused (PTX_ERR_INVALID, nothing enqueued): samples_total <= the last add's, a handle of another
+ * device or size, tile_world > 1. */
+int  ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total);
+/* The same from a host frame (W*H*3 floats, a sum of samples_total samples, e.g. after ptx_multi_read_image), through a staging buffer
+ * the handle owns; synchronous. */
+int  ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samples_total);
+/* mean3: W*H*3 floats; cov6: W*H*6 floats of C (rr, gg, bb, rg, rb, gb), 0 where B < 2; batches1: W*H int32 of B; samples_out: W.
+ * NULLs allowed; waits for the handle's last work. */
+int  ptx_moments_read(ptx_moments *m, float *mean3, float *cov6, int32_t *batches1, int64_t *samples_out);
+int  ptx_moments_summarize(ptx_moments *m, const ptx_moments_params *p, ptx_moments_summary *out);   /* p NULL = defaults; waits */
+/* ptx_denoise_variance(t, NULL, ...) with the measured v0 above; min_batches <= 0 means 4, 1 is refused (C needs B >= 2).  The result
+ * goes into the tracer's denoised frame and ptx_read_variance.  Refused like ptx_denoise_variance and ptx_moments_add, and before the
+ * handle's first add. */
+int  ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params *dp, const ptx_variance_params *vp, int min_batches,
+                          int spp);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);

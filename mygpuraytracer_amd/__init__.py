@@ -15,20 +15,24 @@ from .api import (  # noqa: F401
     DenoiseParams,
     TemporalParams,
     VarianceParams,
+    MomentsParams,
+    MomentsSummary,
     Scene,
     Tracer,
     Temporal,
+    Moments,
     MultiTracer,
     StreamCompaction,
     build_library,
     default_denoise_params,
     default_temporal_params,
     default_variance_params,
+    default_moments_params,
     denoise_buffers,
     denoise_buffers_variance,
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "Scene", "Tracer", "Temporal", "MultiTracer",
-           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "denoise_buffers",
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
+           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "denoise_buffers",
            "denoise_buffers_variance", "load_library"]

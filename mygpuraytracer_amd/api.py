@@ -181,6 +181,85 @@ class Temporal:
         return dict(history=hist, count=count, mix=mix)
 
 
+class MomentsParams(C.Structure):
+    """ptx_moments_params: the error summary's floor and threshold (include/mi355x_pathtracer.h; defaults from
+    ptx_default_moments_params)."""
+    _fields_ = [("floor", C.c_float), ("threshold", C.c_float)]
+
+
+class MomentsSummary(C.Structure):
+    """ptx_moments_summary (include/mi355x_pathtracer.h)."""
+    _fields_ = [("pixels", C.c_int64), ("pixels_over", C.c_int64), ("samples", C.c_int64), ("mean_rel_se", C.c_double),
+                ("rms_rel_se", C.c_double), ("max_rel_se", C.c_double), ("mean_variance", C.c_double), ("batches", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def default_moments_params(**kw):
+    """ptx_default_moments_params with keyword overrides (floor, threshold)."""
+    return _default_params(MomentsParams, "ptx_default_moments_params", (), **kw)
+
+
+class Moments:
+    """Per-pixel sample moments by batch means on one device (opaque ptx_moments): add(tracer, samples) whenever `samples` iterations
+    are in the tracer's accumulation buffer, then summary() for the frame's error estimate, read() for the per-pixel mean and
+    covariance, or Tracer.denoise_measured(moments, spp).  After Tracer.reset_image call reset()."""
+
+    def __init__(self, device, width, height):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_moments_create(int(device), int(width), int(height), C.byref(h)), "ptx_moments_create")
+        self.h = h
+        self.device, self.width, self.height = int(device), int(width), int(height)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ptx_moments_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """forget everything: the next add takes the whole buffer as one batch"""
+        _check(self.lib.ptx_moments_reset(self.h), "ptx_moments_reset")
+
+    def add(self, tracer, samples):
+        """one batch: what the tracer's accumulation buffer gained since the last add; `samples` = the iterations it holds now
+        (enqueued on the tracer's stream)"""
+        _check(self.lib.ptx_moments_add(self.h, tracer.h, int(samples)), "ptx_moments_add")
+
+    def add_host(self, rgb_sum, samples):
+        """the same from a host frame, (H, W, 3) or (H*W, 3) float32 sums of `samples` samples (synchronous)"""
+        rgb = np.ascontiguousarray(rgb_sum, np.float32)
+        if rgb.size != self.width * self.height * 3:
+            raise PathTracerError("Moments.add_host: the frame must hold %d x %d x 3 floats" % (self.width, self.height))
+        _check(self.lib.ptx_moments_add_host(self.h, _ptr(rgb), int(samples)), "ptx_moments_add_host")
+
+    def read(self):
+        """dict of mean (H, W, 3), cov (H, W, 6: rr, gg, bb, rg, rb, gb of the per-sample covariance, 0 where batches < 2), batches
+        (H, W) int32 and samples (int)"""
+        hh, ww = self.height, self.width
+        mean, cov, b = np.zeros((hh, ww, 3), np.float32), np.zeros((hh, ww, 6), np.float32), np.zeros((hh, ww), np.int32)
+        n = C.c_int64(0)
+        _check(self.lib.ptx_moments_read(self.h, _ptr(mean), _ptr(cov), _ptr(b), C.byref(n)), "ptx_moments_read")
+        return dict(mean=mean, cov=cov, batches=b, samples=int(n.value))
+
+    def summary(self, **params):
+        """ptx_moments_summarize as a dict; params: floor, threshold"""
+        p, out = default_moments_params(**params), MomentsSummary()
+        _check(self.lib.ptx_moments_summarize(self.h, C.byref(p), C.byref(out)), "ptx_moments_summarize")
+        return {k: getattr(out, k) for k, _ in MomentsSummary._fields_ if k != "reserved"}
+
+
 def _frame_arrays(fn, rgb, albedo, normal, position, hit):
     """one (H, W) frame as the ptx_denoise_buffers* entry points take it: h, w, rgb (H, W, 3) float32, albedo (or None) / normal /
     position (H*W, 3) float32, hit (H*W) uint8"""
@@ -396,6 +475,19 @@ def load_library():
     L.ptx_read_variance.restype, L.ptx_read_variance.argtypes = i, [vp, vp, vp]
     L.ptx_denoise_buffers_variance.restype = i
     L.ptx_denoise_buffers_variance.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), vp, vp]
+    L.ptx_sizeof_moments_params.restype = L.ptx_sizeof_moments_summary.restype = C.c_size_t
+    if L.ptx_sizeof_moments_params() != C.sizeof(MomentsParams) or L.ptx_sizeof_moments_summary() != C.sizeof(MomentsSummary):
+        raise PathTracerError("ptx_moments_params / ptx_moments_summary layout mismatch")
+    L.ptx_default_moments_params.argtypes = [C.POINTER(MomentsParams)]
+    L.ptx_moments_create.restype, L.ptx_moments_create.argtypes = i, [i, i, i, C.POINTER(vp)]
+    L.ptx_moments_destroy.restype, L.ptx_moments_destroy.argtypes = None, [vp]
+    L.ptx_moments_reset.restype, L.ptx_moments_reset.argtypes = i, [vp]
+    L.ptx_moments_add.restype, L.ptx_moments_add.argtypes = i, [vp, vp, C.c_int64]
+    L.ptx_moments_add_host.restype, L.ptx_moments_add_host.argtypes = i, [vp, vp, C.c_int64]
+    L.ptx_moments_read.restype, L.ptx_moments_read.argtypes = i, [vp, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.ptx_moments_summarize.restype, L.ptx_moments_summarize.argtypes = i, [vp, C.POINTER(MomentsParams), C.POINTER(MomentsSummary)]
+    L.ptx_denoise_measured.restype = i
+    L.ptx_denoise_measured.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), i, i]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -855,6 +947,18 @@ class Tracer:
         dp, tp, vpar = _split_variance_params("denoise_variance", params)
         _check(self.lib.ptx_denoise_variance(self.h, None if temporal is None else temporal.h, C.byref(dp), C.byref(tp), C.byref(vpar),
                                              int(spp)), "ptx_denoise_variance")
+        return self.read_denoised() if read else None
+
+    def denoise_measured(self, moments, spp, min_batches=None, read=True, **params):
+        """denoise_variance() with the variance measured by `moments` (a Moments fed from this tracer's buffer) in place of the spatial
+        estimate, on every hit pixel with at least min_batches batches (None: 4); params: any field of ptx_denoise_params and
+        ptx_variance_params.  variance() gives the v0 it used."""
+        for k in params:
+            if k not in _DENOISE_KEYS + _VARIANCE_KEYS:
+                raise TypeError("denoise_measured: unknown parameter %r" % k)
+        dp, _, vpar = _split_variance_params("denoise_measured", params)
+        _check(self.lib.ptx_denoise_measured(self.h, moments.h, C.byref(dp), C.byref(vpar), 0 if min_batches is None else int(min_batches),
+                                             int(spp)), "ptx_denoise_measured")
         return self.read_denoised() if read else None
 
     def variance(self):

@@ -17,6 +17,11 @@
 //                                  [--temporal]   (with --denoise: GPUdenoise reuses the previous frame's samples, ptx_denoise_temporal)
 //                                  [--variance [--phi-luminance X]]   (with --denoise: the variance-guided filter, ptx_denoise_variance;
 //                                                                      combines with --temporal and --frames)
+//                                  [--until-error E [--error-floor F]]   (render in batches of 16 iterations, one ptx_moments_add after
+//                                                                      each; stop at the first check with mean_rel_se <= E, or at
+//                                                                      --iterations; F = ptx_moments_params.floor)
+//                                  [--measured]   (with --denoise: the variance-guided filter on the variance the run measured,
+//                                                                      ptx_denoise_measured; without --until-error a batch every 16 iterations)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -83,11 +88,14 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured]\n", argv[0]);
         return 1;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
-    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false;
+    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false, measured = false;
+    double until_error = -1.0;
+    ptx_moments_params mparams;
+    ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
     int ckpt_every = 0, frames = 0;
@@ -120,7 +128,17 @@ int main(int argc, char **argv) {
         else if (a == "--temporal") temporal = true;
         else if (a == "--variance") variance = true;
         else if (a == "--phi-luminance") { need(1); varianceParams().phi_luminance = (float)atof(argv[++i]); }
+        else if (a == "--until-error") { need(1); until_error = atof(argv[++i]); }
+        else if (a == "--error-floor") { need(1); mparams.floor = (float)atof(argv[++i]); }
+        else if (a == "--measured") measured = true;
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
+    }
+    const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of 16 iterations, a ptx_moments_add after each
+    if (measured && !denoise) { fprintf(stderr, "--measured needs --denoise\n"); return 1; }
+    if (measured && (temporal || variance)) { fprintf(stderr, "--measured does not combine with --temporal or --variance\n"); return 1; }
+    if (batches && (frames > 0 || per_call || !ckpt_path.empty())) {
+        fprintf(stderr, "--until-error and --measured do not combine with --frames, --per-call or --checkpoint\n");
+        return 1;
     }
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
     if (variance && !denoise) { fprintf(stderr, "--variance needs --denoise\n"); return 1; }
@@ -147,7 +165,7 @@ int main(int argc, char **argv) {
     pathtraceFree();
     pathtraceInit(scene);
     ptx_tracer *t = pathtraceHandle();
-    const int n = (int)scene->state.iterations;
+    int n = (int)scene->state.iterations;
     int done = 0;
     if (!resume_path.empty()) {                 // continue a render: the buffer and the iteration count are all the state
         long long it = 0;
@@ -158,7 +176,7 @@ int main(int argc, char **argv) {
         printf("Resumed %s at %d of %d samples.\n", resume_path.c_str(), done, n);
     }
     const int rendered = std::max(n - done, 0);
-    const int chunk = (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
+    const int chunk = batches ? 16 : (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
     double per_call_ms = 0.0;
     if (per_call) {
         // the reference's own loop (runCuda, src/main.cpp:128-148): one pathtrace(pbo, frame, iteration) per frame, the fp32 frame
@@ -179,6 +197,18 @@ int main(int argc, char **argv) {
         if (!ckpt_path.empty()) {
             if (!ptimg::write_checkpoint(ckpt_path, width, height, done, &scene->state.image[0].x)) { fprintf(stderr, "cannot write %s\n", ckpt_path.c_str()); return 1; }
         }
+        if (batches) pathtraceMomentsAdd(done);
+        if (until_error >= 0.0) {
+            ptx_moments_summary sum;
+            if (ptx_moments_summarize(pathtraceMoments(), &mparams, &sum) != PTX_OK) { fprintf(stderr, "summary failed: %s\n", ptx_last_error()); return 1; }
+            const bool stop = sum.pixels > 0 && sum.mean_rel_se <= until_error;
+            printf("check: %d iterations, %d batches, mean rel se %.6g, rms %.6g, max %.6g, %lld of %lld pixels over %g\n", done, (int)sum.batches,
+                   sum.mean_rel_se, sum.rms_rel_se, sum.max_rel_se, (long long)sum.pixels_over, (long long)sum.pixels, (double)mparams.threshold);
+            if (stop || done >= n) {
+                printf("until-error: %d iterations, mean rel se %.6g %s %g\n", done, sum.mean_rel_se, stop ? "<=" : ">", until_error);
+                n = done;
+            }
+        }
     }
     ptx_stats st;
     ptx_get_stats(t, &st);
@@ -196,7 +226,8 @@ int main(int argc, char **argv) {
     if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", ss.str().c_str()); }
     if (denoise && n > 0) {                     // the denoised frame next to it: mean radiance already, so divided by 1
         std::vector<float> den((size_t)width * height * 3);
-        const int rc = variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);
+        const int rc = measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
+                     : variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);
         if (rc != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         ptimg::to_rgb8_mirrored(width, height, den.data(), 1.0f, rgb8);
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
@@ -209,6 +240,7 @@ int main(int argc, char **argv) {
         if (!ptimg::write_hdr(ss.str() + ".hdr", width, height, mean.data())) { fprintf(stderr, "cannot write %s.hdr\n", ss.str().c_str()); return 1; }
         printf("Saved %s.hdr.\n", ss.str().c_str());
     }
+    GPUdenoiseRelease();
     pathtraceFree();
     delete scene;
     return 0;

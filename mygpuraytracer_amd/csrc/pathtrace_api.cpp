@@ -30,6 +30,9 @@ bool g_variance_params_init = false;
 ptx_temporal *g_temporal = nullptr;  // GPUdenoise's history with denoiseTemporal() on: kept across pathtraceFree / pathtraceInit
 int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
 int g_device = 0;                    // the device of g_tracer
+ptx_moments *g_moments = nullptr;    // pathtrace()'s batch means with momentsBatch() > 0: created on first use
+int g_moments_key[3] = {0, 0, 0};    // its device, width, height
+int g_calls = 0;                     // pathtrace() calls since pathtraceInit
 
 void check(int rc, const char *what) {
     if (rc == PTX_OK) return;
@@ -199,9 +202,44 @@ ptx_variance_params &varianceParams() {
     return g_variance_params;
 }
 
+int &momentsBatch() {
+    static int k = 0;
+    return k;
+}
+
+ptx_moments *pathtraceMoments() { return g_moments; }
+
+bool &denoiseMeasured() {
+    static bool on = false;
+    return on;
+}
+
 void GPUdenoiseRelease() {
     ptx_temporal_destroy(g_temporal);
     g_temporal = nullptr;
+    ptx_moments_destroy(g_moments);
+    g_moments = nullptr;
+}
+
+// one batch: everything the frame gained since the last one
+void pathtraceMomentsAdd(int iter) {
+    if (!g_tracer || !hst_scene) { fprintf(stderr, "pathtraceMomentsAdd called before pathtraceInit\n"); exit(EXIT_FAILURE); }
+    const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+    const int key[3] = {g_device, w, h};
+    if (g_moments && memcmp(key, g_moments_key, sizeof key) != 0) { ptx_moments_destroy(g_moments); g_moments = nullptr; }
+    if (!g_moments) {
+        check(ptx_moments_create(g_device, w, h, &g_moments), "pathtrace moments");
+        memcpy(g_moments_key, key, sizeof key);
+    }
+    if (g_multi) check(ptx_moments_add_host(g_moments, &hst_scene->state.image[0].x, iter), "pathtrace moments");   // the assembled frame
+    else check(ptx_moments_add(g_moments, g_tracer, iter), "pathtrace moments");
+}
+
+// after every momentsBatch()-th call
+static void moments_step(int iter) {
+    const int k = momentsBatch();
+    g_calls++;
+    if (k > 0 && g_calls % k == 0) pathtraceMomentsAdd(iter);
 }
 
 void pathtraceInit(Scene *scene) {
@@ -209,6 +247,8 @@ void pathtraceInit(Scene *scene) {
     g_albedo_read = false;
     g_last_iter = 0;
     g_output_on_device = false;
+    g_calls = 0;
+    if (g_moments) ptx_moments_reset(g_moments);
     const std::vector<int> &devs = pathtraceDevices();
     if (devs.size() > 1) {
         // the C ABI's multi-device layer takes the loaded scene: hand it the caller's camera and depth first
@@ -216,6 +256,7 @@ void pathtraceInit(Scene *scene) {
         ptx_scene_set_trace_depth(scene->handle(), scene->state.traceDepth);
         check(ptx_multi_create(scene->handle(), &pathtraceOptions(), devs.data(), (int)devs.size(), 0, &g_multi), "pathtraceInit");
         g_tracer = ptx_multi_tracer(g_multi, 0);
+        g_device = devs[0];
         check(ptx_multi_set_render_ahead(g_multi, pathtraceRenderAhead() ? 1 : 0), "pathtraceInit");
     } else {
         ptx_options o = pathtraceOptions();
@@ -263,6 +304,7 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
             g_albedo_read = true;
         }
         check(ptx_synchronize(g_tracer), "pathtrace");
+        moments_step(iter);
         return;
     }
     check(ptx_set_camera(g_tracer, hst_scene->state.camera.c_abi(), hst_scene->state.traceDepth), "pathtrace camera");
@@ -272,6 +314,7 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
     if (!apps) check(ptx_write_pbo_device(g_tracer, iter, pbo), "sendImageToPBO");
     check(ptx_read_image(g_tracer, &hst_scene->state.image[0].x), "image readback");     // :555-556
     if (apps) check(ptx_read_albedo(g_tracer, &hst_scene->state.albedo[0].x), "albedo readback");
+    moments_step(iter);
 }
 
 // apps/src/pathtrace.cu:673-685: the denoised frame in state.output -> the pbo, scaled by 255 and clamped, no division by iter
@@ -290,7 +333,11 @@ void GPUdenoise(bool keep_on_device) {
     if (!g_tracer || !hst_scene) { fprintf(stderr, "GPUdenoise called before pathtraceInit\n"); exit(EXIT_FAILURE); }
     if (g_multi) { fprintf(stderr, "GPUdenoise: the denoiser runs on one device; pathtraceDevices() names several\n"); exit(EXIT_FAILURE); }
     if (g_last_iter < 1) { fprintf(stderr, "GPUdenoise called before the first pathtrace\n"); exit(EXIT_FAILURE); }
-    if (denoiseTemporal()) {
+    if (denoiseMeasured()) {
+        if (denoiseTemporal()) { fprintf(stderr, "GPUdenoise: denoiseMeasured() does not combine with denoiseTemporal()\n"); exit(EXIT_FAILURE); }
+        if (!g_moments) { fprintf(stderr, "GPUdenoise: denoiseMeasured() needs momentsBatch() > 0 and at least one batch\n"); exit(EXIT_FAILURE); }
+        check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");
+    } else if (denoiseTemporal()) {
         const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
         const int key[3] = {g_device, w, h};
         if (g_temporal && memcmp(key, g_temporal_key, sizeof key) != 0) GPUdenoiseRelease();     // another device or resolution

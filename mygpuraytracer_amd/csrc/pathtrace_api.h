@@ -270,6 +270,18 @@ ptx_temporal_params &temporalParams();                  // what it reprojects wi
 // the spatial estimate alone.
 bool &denoiseVariance();
 ptx_variance_params &varianceParams();                  // what it filters with (ptx_default_variance_params until changed)
+// Sample moments by batch means (ptx_moments_*): momentsBatch() = k > 0 makes pathtrace() add one batch to a module-level handle after
+// every k-th call since pathtraceInit (which resets it: a new tracer starts a new accumulation); 0, the default, is off.  The handle is
+// created on first use, recreated when the device or the resolution changes, and freed by GPUdenoiseRelease(); pathtraceMoments() hands
+// it out (NULL before the first batch) for ptx_moments_summarize / ptx_moments_read.
+int &momentsBatch();
+ptx_moments *pathtraceMoments();
+// The same batch by hand, for a caller that renders through pathtraceHandle() (ptx_render) instead of pathtrace(): `iteration` = the
+// iterations in the accumulation buffer now.  With several pathtraceDevices() the batch is taken from state.image.
+void pathtraceMomentsAdd(int iteration);
+// Measured variance (ptx_denoise_measured): off by default.  When on, GPUdenoise takes the variance-guided filter's input variance from
+// that handle (momentsBatch() must have collected at least one batch).  Not with denoiseTemporal(): it prints an error and exits.
+bool &denoiseMeasured();
 void GPUdenoiseRelease();
 
 namespace mi355x {

@@ -1,5 +1,6 @@
 // pt_denoise.h -- internal interface between the tracer (pt_engine.hip: G-buffer pass, ptx_denoise / ptx_denoise_temporal /
-// ptx_denoise_variance), the a-trous filter with its variance guidance (pt_denoise.hip) and the temporal reprojection (pt_temporal.hip).
+// ptx_denoise_variance / ptx_denoise_measured, ptx_moments_add), the a-trous filter with its variance guidance (pt_denoise.hip), the
+// temporal reprojection (pt_temporal.hip) and the batch-means moments (pt_moments.hip).
 // Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
 //
 // Device layout of the guide images, one record per pixel, pixelIndex = x + y*W (the frame's own order):
@@ -17,6 +18,14 @@
 //                                                        luminance variance when ptx_denoise_variance wrote the state, else 0)
 //   ids[i] = int2(material id, geom id)
 // 56 B per pixel: a bilinear tap reads one whole record.
+//
+// A moments state (ptx_moments, pt_moments.hip), 56 B per pixel:
+//   snap[i] = float4(accumulation rgb at the last add, W = the samples it held)
+//   mean[i] = float4(weighted mean rgb of the batch means, batch count B)
+//   ma[i]   = float4(M rr, gg, bb, rg)                  (the weighted scatter matrix's upper triangle)
+//   mb      = float4(M rb, gb of pixel (2j, y), M rb, gb of pixel (2j + 1, y)) at [y * pt_moments_pairs(W) + j]: the two floats that
+//             are left share a 16-byte record with the row neighbour's, so that k_moments_add moves whole float4 only (lanes 2j and
+//             2j + 1 of a wave are always that pair: a workgroup's x0 is a multiple of 64).  An odd W pads each row by 8 B.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +57,28 @@ struct ptx_temporal {
     float4 *d_hn = nullptr;               // W*H: the last call's (h rgb, n_h)
     hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
     bool used = false, done = false;      // ev was recorded / d_mix, d_hn hold a result
+};
+
+struct PtMomentsState {
+    float4 *snap = nullptr, *mean = nullptr, *ma = nullptr, *mb = nullptr;
+};
+inline int pt_moments_pairs(int w) { return (w + 1) / 2; }
+
+// one workgroup's (stage one) or the frame's (stage two) share of ptx_moments_summarize
+struct PtMomentsPartial {
+    double sum_rel, sum_rel2, max_rel, sum_q;
+    unsigned long long n, over;
+};
+
+struct ptx_moments {
+    int device = 0, w = 0, h = 0;
+    PtMomentsState st;
+    float *d_stage = nullptr;             // W*H*3: ptx_moments_add_host's upload (first use)
+    PtMomentsPartial *d_part = nullptr;   // one per workgroup of the pixel grid, then the total
+    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
+    bool used = false;                    // ev was recorded
+    long long samples = 0;                // W: samples_total of the last add; 0 = fresh (the buffers are read as zeros)
+    int batches = 0;                      // B
 };
 
 // Rec. 709 luminance, the one every variance of the denoiser is a variance of
@@ -83,6 +114,15 @@ hipError_t pt_variance_spatial_enqueue(hipStream_t st, int w, int h, const ptx_d
 hipError_t pt_atrous_enqueue(hipStream_t st, int w, int h, const float4 *nh, const float4 *xt, const float4 *alb, float4 *tmp0,
                              float4 *tmp1, float *out_rgb, const ptx_denoise_params &dp, const ptx_variance_params *vp = nullptr,
                              float *var_in = nullptr, float *var_out = nullptr);
+
+const char *pt_moments_params_problem(const ptx_moments_params &p);
+// One add on `st`: rgb = the accumulation buffer (W*H*3) holding `total` samples, k = total - the last add's; fresh: the state reads
+// as zeros (first add after create / reset).
+hipError_t pt_moments_add_enqueue(hipStream_t st, int w, int h, const float *rgb, float k, float total, int fresh, const PtMomentsState &s);
+// pt_atrous_prep_enqueue with the measured variance: c = float4(rgb / spp (demodulated on hit pixels), v), v = max(g^T C g, 0) / W on
+// hit pixels with B >= min_batches (>= 2), -1 on the other hit pixels (pt_variance_spatial_enqueue fills those in), 0 on miss pixels.
+hipError_t pt_moments_prep_enqueue(hipStream_t st, int w, int h, const float *rgb, float spp, const float4 *nh, const float4 *alb, int demod,
+                                   const PtMomentsState &s, int min_batches, float4 *c);
 
 // hist's camera -> PtTemporalCam (in double, then rounded); valid = 0 when the system is singular or not finite
 PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist);

@@ -1491,6 +1491,65 @@ int ptx_read_variance(ptx_tracer *t, float *input_var1, float *output_var1) {
     return PTX_OK;
 }
 
+// ---- sample moments by batch means (pt_moments.hip; definition in include/mi355x_pathtracer.h) ---------------------------------------
+// The checks of denoise_begin on a moments handle.  The accumulation buffer is read on the tracer's stream, where every gather runs,
+// those of iterations traced ahead included (ahead_finish_segment): the order ptx_denoise's read of it has.
+static int moments_begin(const std::string &fn, ptx_tracer *t, const ptx_moments *m) {
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (m->device != t->device)
+        return set_error(PTX_ERR_INVALID, fn + ": the moments handle was created on device " + std::to_string(m->device) +
+                                              ", the tracer runs on device " + std::to_string(t->device));
+    if (m->w != t->cam.resx || m->h != t->cam.resy)
+        return set_error(PTX_ERR_INVALID, fn + ": the moments handle's size " + std::to_string(m->w) + " x " + std::to_string(m->h) +
+                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
+    return PTX_OK;
+}
+
+int ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total) {
+    if (samples_total < 1) return set_error(PTX_ERR_INVALID, "ptx_moments_add: samples_total must be >= 1");
+    if (!m || !t) return set_error(PTX_ERR_INVALID, "ptx_moments_add: null moments handle or tracer");
+    if (samples_total <= m->samples)
+        return set_error(PTX_ERR_INVALID, "ptx_moments_add: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
+                                              std::to_string(m->samples));
+    if (const int rc = moments_begin("ptx_moments_add", t, m)) return rc;
+    HIPCHECK(hipSetDevice(t->device));
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));     // the handle's last work, maybe on another tracer's stream
+    HIPCHECK(pt_moments_add_enqueue(t->stream, m->w, m->h, t->d_image, (float)(samples_total - m->samples), (float)samples_total,
+                                    m->samples == 0, m->st));
+    HIPCHECK(hipEventRecord(m->ev, t->stream));
+    m->used = true;
+    m->samples = samples_total;
+    m->batches++;
+    return PTX_OK;
+}
+
+int ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params *dparams, const ptx_variance_params *vparams, int min_batches,
+                         int spp) {
+    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
+    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
+    if (spp < 1) return bad_spp("ptx_denoise_measured");
+    if (min_batches == 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: min_batches must be >= 2 (<= 0: the default, 4)");
+    if (!t || !m) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: null tracer or moments handle");
+    if (m->samples == 0) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: no add on this moments handle yet");
+    if (const int rc = moments_begin("ptx_denoise_measured", t, m)) return rc;
+    if (const int rc = denoise_begin("ptx_denoise_measured", t, nullptr, true)) return rc;
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    const float4 *g = t->d_gbuf;
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
+    HIPCHECK(pt_moments_prep_enqueue(t->stream, W, H, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, m->st,
+                                     min_batches <= 0 ? 4 : min_batches, t->d_dn_tmp));
+    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
+    m->used = true;
+    HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
+    t->dn_done = t->var_done = true;
+    return PTX_OK;
+}
+
 int ptx_read_denoised(ptx_tracer *t, float *host_rgb) {
     if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
     if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_read_denoised: no ptx_denoise on this tracer yet");
