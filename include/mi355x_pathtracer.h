@@ -496,6 +496,19 @@ int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8);
 /* CPU-only: the geoms a path can end on with radiance, as ptx_create works them out: bit g of *bits_out (g < 32) = the material of geom g
  * (geom_material[g]) has emittance > 0.  The last bounce of a path looks only for these geoms.  Returns 0, -1 on a bad argument. */
 int ptx_debug_light_bits(int nmaterials, const ptx_material *materials, int ngeoms, const int32_t *geom_material, uint32_t *bits_out);
+/* Host-only (reads what ptx_create kept on the host, launches nothing): how mesh geom `geom` of a live tracer is searched.
+ * out8 = { root of its BVH (-1: none, the plain loop over its faces), depth of the binary tree, root of its four-wide nodes (-1: none),
+ * stack entries their walk needs, stack entries per lane the tracer's launches provide (bvh_stack), 1 if frames take the split mesh search
+ * (k_mesh + k_finish) else 0, the walk a FRAME takes for this geom, the walk the single-ray search takes when it is handed a stack
+ * (ptx_kat_tile_intersect with split = 1) }, walks as PTX_WALK_*.  A frame of an unsplit scene, k_finish (split: every mesh k_mesh leaves
+ * to it), ptx_kat_geom_test, ptx_kat_compute_intersections and ptx_kat_tile_intersect with split = 0 search without a stack: PTX_WALK_LOOP
+ * without a tree, PTX_WALK_SKIP with one.  Returns PTX_OK, or an error for a null argument or a geom that is not a mesh. */
+#define PTX_WALK_LOOP 0        /* the reference's loop over all faces (fused into the bounce kernel, or in k_finish) */
+#define PTX_WALK_SKIP 1        /* stackless walk over the skip links */
+#define PTX_WALK_ORDERED 2     /* front-to-back walk of the binary tree */
+#define PTX_WALK_WIDE 3        /* four-wide walk, one ray per lane from start to end */
+#define PTX_WALK_WIDE_REFILL 4 /* four-wide walk under k_mesh's refilling schedule */
+int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]);
 /* Debug: workgroups of the specialised later-bounce kernel that fit a CU with lds_bytes of dynamic LDS each (0: what this tracer launches). */
 int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes);
 /* Debug: after waiting for the tracer's streams, the nonzero words left in the per-iteration "lit" bit-planes (out3[0]) and in the

@@ -341,6 +341,9 @@ def debug_light_bits(materials, geom_material):
     return int(out[0])
 
 
+WALK_NAMES = ("loop", "skip", "ordered", "wide", "wide_refill")      # PTX_WALK_* of include/mi355x_pathtracer.h
+
+
 def build_library(force=False):
     """Compiles the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(LIB_PATH):
@@ -508,6 +511,8 @@ def load_library():
         L.ptx_debug_cull_boxes.restype, L.ptx_debug_cull_boxes.argtypes = i, [i, vp, vp]
     if hasattr(L, "ptx_debug_light_bits"):
         L.ptx_debug_light_bits.restype, L.ptx_debug_light_bits.argtypes = i, [i, vp, i, vp, vp]
+    if hasattr(L, "ptx_debug_mesh_plan"):
+        L.ptx_debug_mesh_plan.restype, L.ptx_debug_mesh_plan.argtypes = i, [vp, i, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
         L.ptx_kat_fast_exact.restype, L.ptx_kat_fast_exact.argtypes = i, [vp, vp]
     L.ptx_debug_set_capture.restype, L.ptx_debug_set_capture.argtypes = i, [vp, i]
@@ -1021,6 +1026,16 @@ class Tracer:
 
     def owned_pixels(self):
         return self.lib.ptx_owned_pixels(self.h)
+
+    def mesh_plan(self, gi):
+        """ptx_debug_mesh_plan (host only): how mesh geom gi is searched -- dict(root, depth, wroot, wneed, bvh_stack, split, frame_walk,
+        stack_walk), the walks as WALK_NAMES: what a frame takes for it, and what the single-ray search takes when handed a stack
+        (tile_intersect(split=True)); every other entry point searches without a stack: "loop" without a tree, "skip" with one."""
+        o = np.zeros(8, np.int32)
+        _check(self.lib.ptx_debug_mesh_plan(self.h, int(gi), _ptr(o)), "ptx_debug_mesh_plan")
+        d = dict(zip(("root", "depth", "wroot", "wneed", "bvh_stack", "split"), (int(x) for x in o[:6])))
+        d["frame_walk"], d["stack_walk"] = WALK_NAMES[int(o[6])], WALK_NAMES[int(o[7])]
+        return d
 
     def stats(self):
         s = Stats()

@@ -31,7 +31,8 @@
 //
 //      Below that conditioning the reference's own test decides by rounding noise over a band of width ~64 u D / kappa along
 //      the triangle's edges; the static inflation (2e-3 of the node's diagonal + 1e-5 of the mesh's) still covers most of
-//      it, but equality there is measured (tests/test_bvh.py: grazing rays, needles, far origins up to 10^6 mesh sizes),
+//      it, but equality there is measured (on the host, tests/test_bvh.py: grazing rays, needles, far origins up to 10^6 mesh sizes;
+//      on the device, tests/test_gpu_mesh_walks.py: the same meshes through every walk the kernels take, against the oracle's loop),
 //      not proven.  The slack grows with distance: a ray from 10^4 mesh sizes away prunes little -- as it must, its
 //      triangle tests being accurate to a fraction of the mesh only.
 //

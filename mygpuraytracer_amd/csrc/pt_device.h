@@ -1092,6 +1092,17 @@ PT_HD vec3 mulRows(const float *r, vec3 v, float w) {
 // are cubes, spheres or meshes is a per-scene constant (sc.cube_bits / sphere_bits / mesh_bits).
 // SUBSET: only the geoms whose bit is set in `subset` are tested (a wave-uniform mask: the camera-ray bounce knows per tile which geoms
 // its pixels can see at all, k_bounce's tile_geoms); the others' bits stay 0.
+// FAR ORIGINS.  The slab bounds of the pre-test carry a rounding error of at most u (5 |o| + 4 |c| + 3 h) per plane in world units
+// (u = 2^-24: one rounding each of o * ix and of the two multiply-adds, and the reciprocal's 2 u between axes).  The box's own terms
+// are covered by the 1e-4 |coordinate| of its inflation at any size; the ORIGIN's term is covered by the inflation's absolute 1e-3 only
+// while 5 u |o| <= 1e-3 / 2, i.e. |o| <= 1.6e3 per axis -- beyond that a ray the exact tests accept can miss the inflated box by
+// rounding alone (measured: 9 of 1600 rays from 10^6 mesh sizes away lost their hit, tests/test_gpu_mesh_walks.py).  So a ray whose
+// origin lies beyond CULL_FAR_ORIGIN on some axis is not pre-tested: every geom (of the subset) stays a candidate and the exact tests
+// decide, as in the reference.  Rays start at the camera or on a geom, so only a scene with a world box or a camera beyond
+// CULL_FAR_ORIGIN / 2 can have such rays at all: the host says so with DScene::cull == 2 (pt_prepare_scene, enqueue_batch; the test
+// entry point for arbitrary rays always does), and every other scene (cull == 1) does not even look -- the specialised bounce kernels,
+// which fold cull to 1, are not taken for a far scene (fast_violation).
+constexpr float CULL_FAR_ORIGIN = 1024.0f;
 template <bool SUBSET = false>
 PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffffu) {
     typedef const __attribute__((address_space(4))) float cfloat;
@@ -1111,6 +1122,9 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
     const float ax = __builtin_fabsf(ix), ay = __builtin_fabsf(iy), az = __builtin_fabsf(iz);
     uint32_t mask = 0;
     const int n = sc.ngeoms;
+    auto far_origin = [&]() {
+        return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ray.o.x), __builtin_fabsf(ray.o.y)), __builtin_fabsf(ray.o.z)) > CULL_FAR_ORIGIN;
+    };
     auto slab = [&](const float *bx) {
         const float mx = __builtin_fmaf(bx[0], ix, ox), my = __builtin_fmaf(bx[1], iy, oy), mz = __builtin_fmaf(bx[2], iz, oz);
         const float x0 = __builtin_fmaf(bx[4], -ax, mx), x1 = __builtin_fmaf(bx[4], ax, mx);
@@ -1134,6 +1148,7 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
             mask |= slab(bx[0]) ? (1u << i) : 0u;
             mask |= slab(bx[1]) ? (1u << j) : 0u;
         }
+        if (sc.cull > 1 && far_origin()) mask = n >= 32 ? subset : subset & ((1u << n) - 1u);
         return mask;
     }
     // From the last geom down, two boxes per trip, each verdict shifted in from the right (mask + mask + verdict: ONE add-with-carry
@@ -1157,6 +1172,7 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
             asm("v_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(mask) : "s"(verdict) : "vcc");
         }
     }
+    if (sc.cull > 1 && far_origin()) mask = n >= 32 ? 0xffffffffu : (1u << n) - 1u;
     return mask;
 }
 

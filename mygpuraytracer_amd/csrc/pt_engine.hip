@@ -298,6 +298,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     int32_t *d_super = nullptr;                          // (points into d_totals' allocation)
     DevBuf<float> d_tri9, d_gtab, d_aabb;
     std::vector<float> h_aabb;                           // host copy of the world boxes (update_tile_geoms)
+    std::vector<int32_t> h_geom_type, h_roots, h_depths, h_wroots, h_wneeds;      // host copies of the per-geom tree tables (ptx_debug_mesh_plan)
     DevBuf<uint32_t> d_tile_geoms; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
     DevBuf<BvhQuad> d_bvh_nodes; DevBuf<float> d_bvh_tris; DevBuf<int32_t> d_bvh_root, d_bvh_depth;                          // pt_bvh.h (NULL: no mesh has one)
     DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
@@ -449,6 +450,7 @@ const char *fast_violation(const ptx_tracer *t, int mode, bool first, bool needs
     if (bp.emit_count) return "the cache-filling pass (emit_count != NULL) records bounce-0 light hits";
     if (needs_albedo) return "the launch set contains iteration 1 of the apps variant (albedo AOV)";
     if (!bp.sc.cull || !bp.sc.tri_lds) return "candidate masks or LDS scene tables are off";
+    if (bp.sc.cull != 1) return "rays can start beyond CULL_FAR_ORIGIN (far geometry or camera): the pre-test must look at origins";
     if (mode == 0) {
         if (t->split_mesh) return "the scene takes the split mesh search";
         if (first && bp.dof) return "depth of field on the camera-ray bounce";
@@ -531,7 +533,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
     const bool needs_albedo = t->d_albedo && iter_first == 1;
     // (only the grid size depends on this estimate; what is launched is decided per launch by fast_violation)
     const bool fast_unsplit = !t->split_mesh && !t->no_fast && batched && !t->uses_uv && t->opt.sort_by_material &&
-                              !needs_albedo && t->cull && t->tri_lds && t->bump_bits == 0 && t->ntri_lds == t->ntri &&
+                              !needs_albedo && t->cull == 1 && t->tri_lds && t->bump_bits == 0 && t->ntri_lds == t->ntri &&
                               !t->d_bvh_root;
     // ... the split bounce's kernels are many short ones: 16 workgroups per CU (C5 -2 %); everything else 8 as before
     // (traced ahead of per-call requests: two of the seven slots per CU stay free, so that the caller's own short kernels -- gather,
@@ -640,6 +642,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         }
         BounceParams bp;
         bp.sc = t->scene(); bp.sc.tri_lds = t->tri_lds; bp.sc.ntri_lds = t->split_mesh ? 0 : t->ntri_lds; bp.sc.cull = t->cull; bp.cam = t->cam; bp.tm = t->tm;
+        for (int k = 0; k < 3; k++) if (bp.sc.cull && !(std::fabs(t->cam.position[k]) <= 0.5f * CULL_FAR_ORIGIN)) bp.sc.cull = 2;      // (a camera far out: cullMask, FAR ORIGINS)
         bp.sc.ldsblob = t->d_ldsblob;
         // (split: the mesh search runs in k_mesh from global memory, so the triangle tables need no LDS)
         // bounce b writes its stage into soa[1 - (b & 1)] (bounce 0 of a cache-enabled tracer: into soa[2], kept across
@@ -1032,6 +1035,8 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         if (!hs.ldsblob.empty()) HC(hipMemcpy(t->d_ldsblob, hs.ldsblob.data(), sizeof(float) * hs.ldsblob.size(), hipMemcpyHostToDevice));
     }
     t->h_aabb = std::move(hs.aabb);                       // (the host keeps corners for the camera tile masks)
+    for (const DGeom &g : hs.geoms) t->h_geom_type.push_back(g.type);
+    t->h_roots = hs.roots; t->h_depths = hs.depths; t->h_wroots = hs.wroots; t->h_wneeds = hs.wneeds;
     t->h_spec = std::move(hs.h_spec);
     const size_t npix = (size_t)W * H, nseg = (size_t)t->kmax * t->lanes, nb = (size_t)t->nbins;
     if (external_image) t->d_image = external_image;
@@ -1703,7 +1708,7 @@ int ptx_kat_tile_intersect(ptx_tracer *t, int n, const void *paths44, void *isec
     HIPCHECK(d_i.alloc((size_t)n));
     // the scene as enqueue_batch hands it to k_bounce (tables staged; split: without the triangle tables) and as k_mesh gets it
     DScene sc = t->scene();
-    sc.tri_lds = t->tri_lds; sc.ntri_lds = (split || t->split_mesh) ? 0 : t->ntri_lds; sc.cull = t->cull;
+    sc.tri_lds = t->tri_lds; sc.ntri_lds = (split || t->split_mesh) ? 0 : t->ntri_lds; sc.cull = t->cull ? 2 : 0;      // (the caller's rays can start anywhere: cullMask, FAR ORIGINS)
     sc.ldsblob = (split || t->split_mesh) == t->split_mesh ? t->d_ldsblob : nullptr;      // (the blob is laid out for the tracer's own choice)
     DScene scg = t->scene();
     scg.bvh_stack = t->bvh_stack;
@@ -1828,6 +1833,22 @@ int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes) {
     const int triWords = t->tri_lds ? sceneTableWords(ntri_lds, t->nmats, t->ngeoms) : 0;
     size_t lds = lds_bytes > 0 ? (size_t)lds_bytes : sizeof(int32_t) * (bounceLdsWords(triWords, t->nbins) - (17 - REC_ROWS_FAST0) * TILE);
     return static_cast<const KernelSet *>(ptx_arith_kernels_0())->bounce_occupancy(lds);
+}
+
+// Host-only: what pt_prepare_scene decided for one mesh geom, and which walk each caller of the mesh search takes for it -- the rules of
+// k_mesh's set-up (pt_kernels.hip: wideok), of meshKey (pt_device.h: wideok / ordered) and of ptx_create's bvh_stack, restated on the host copies.
+int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]) {
+    if (!t || !out8) return set_error(PTX_ERR_INVALID, "null argument");
+    if (geom < 0 || geom >= t->ngeoms || (size_t)geom >= t->h_roots.size()) return set_error(PTX_ERR_INVALID, "geom index out of range");
+    if (t->h_geom_type[geom] != G_OBJ) return set_error(PTX_ERR_INVALID, "ptx_debug_mesh_plan: the geom is not a mesh");
+    const int root = t->h_roots[geom], depth = t->h_depths[geom], wroot = t->h_wroots[geom], wneed = t->h_wneeds[geom];
+    // (the four-wide tables reach the device only when some tree has four-wide nodes: ptx_create, step 7)
+    const bool wide = root >= 0 && wroot >= 0 && t->d_bvh_wroot && wneed <= t->bvh_stack;
+    const bool ordered = root >= 0 && depth < t->bvh_stack;
+    out8[0] = root; out8[1] = depth; out8[2] = wroot; out8[3] = wneed; out8[4] = t->bvh_stack; out8[5] = t->split_mesh ? 1 : 0;
+    out8[6] = root < 0 ? PTX_WALK_LOOP : (t->split_mesh && wide) ? PTX_WALK_WIDE_REFILL : PTX_WALK_SKIP;
+    out8[7] = root < 0 ? PTX_WALK_LOOP : wide ? PTX_WALK_WIDE : ordered ? PTX_WALK_ORDERED : PTX_WALK_SKIP;
+    return PTX_OK;
 }
 
 int ptx_debug_aux_nonzero(ptx_tracer *t, int64_t out3[3]) {

@@ -25,7 +25,7 @@ struct SceneFacts {
     uint32_t cube_bits = 0, sphere_bits = 0, mesh_bits = 0;   // geoms 0..31 by kind, for the candidate masks
     uint32_t bump_bits = 0;
     uint32_t light_bits = 0;                             // geoms 0..31 whose material emits (emittance > 0): DScene::light_bits
-    int tri_lds = 0, ntri_lds = 0, cull = 0;
+    int tri_lds = 0, ntri_lds = 0, cull = 0;             // cull: 0 off, 1 candidate masks, 2 candidate masks in a scene where rays can start far out (cullMask)
     bool split_mesh = false;                             // k_bounce as MODE 1 + k_mesh + k_finish + MODE 2 (scenes with BVH meshes)
     unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
     unsigned long long ntab_bins = 0ull;                 // BounceParams::ntab_bins (none: every record carries its normal)

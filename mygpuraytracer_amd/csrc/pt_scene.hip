@@ -326,6 +326,11 @@ int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const pt
     hs.aabb_ch.assign(hs.aabb.size(), 0.f);
     for (int i = 0; i < ngeoms; i++) world_box_centre_half(&hs.aabb[(size_t)i * 8], &hs.aabb_ch[(size_t)i * 8]);
     hs.cull = (hs.tri_lds && ngeoms >= 1 && ngeoms <= 32 && !opt.no_cull) ? 1 : 0;
+    // 2: some world box reaches beyond CULL_FAR_ORIGIN / 2 (or is unbounded: a NaN vertex), so rays can START that far out -- the
+    // candidate pre-test then looks at every ray's origin (cullMask, pt_device.h: FAR ORIGINS)
+    for (int i = 0; i < ngeoms && hs.cull; i++)
+        for (int k = 0; k < 3; k++)
+            if (!(std::fabs(hs.aabb[(size_t)i * 8 + k]) <= 0.5f * CULL_FAR_ORIGIN && std::fabs(hs.aabb[(size_t)i * 8 + 4 + k]) <= 0.5f * CULL_FAR_ORIGIN)) hs.cull = 2;
     // normals that do not depend on the ray, computed once with the device's own functions (compiled for the host with
     // the same flags: no contraction, IEEE divide and square root), so the kernels read what they would have computed
     hs.fnorm.assign((size_t)std::max(hs.ntri, 1) * 3, 0.f); hs.cnorm.assign(ng1 * 18, 0.f);
@@ -450,7 +455,7 @@ int ptx_debug_bvh_check(const float *faces15, int nfaces, const float *rays6, in
     }
     if (stats4) { stats4[0] = (int64_t)(bb.nodes.size() / 2); stats4[1] = (int64_t)(bb.tris.size() / BVH_TRI); stats4[2] = visited; stats4[3] = mismatches; }
     g_bvh_visits[0] = visited; g_bvh_visits[1] = visited_ordered; g_bvh_visits[2] = visited_wide / 4; g_bvh_visits[3] = wneed;
-    g_bvh_visits[4] = sum_group_max; g_bvh_visits[5] = groups; g_bvh_visits[6] = tris_wide;
+    g_bvh_visits[4] = sum_group_max; g_bvh_visits[5] = groups; g_bvh_visits[6] = tris_wide; g_bvh_visits[7] = depth;
     return PTX_OK;
 }
 
@@ -510,7 +515,8 @@ int ptx_debug_tile_geoms(const ptx_camera *camera, int ngeoms, const float *boxe
 }
 
 // node visits of the last ptx_debug_bvh_check: skip-link walk, front-to-back binary walk, four-wide walk (nodes), wide stack need,
-// sum over groups of 64 consecutive rays of the longest four-wide walk in the group, number of groups, triangles the four-wide walk tested
+// sum over groups of 64 consecutive rays of the longest four-wide walk in the group, number of groups, triangles the four-wide walk tested,
+// depth of the binary tree
 int ptx_debug_bvh_visits(int64_t out8[8]) {
     if (!out8) return set_error(PTX_ERR_INVALID, "null argument");
     for (int k = 0; k < 8; k++) out8[k] = g_bvh_visits[k];

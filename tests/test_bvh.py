@@ -3,13 +3,24 @@
 The tree only decides WHICH triangles are looked at; the per-triangle arithmetic and the choice of the winner (nearest
 distance, lowest face index on ties) are the loop's.  ptx_debug_bvh_check runs both on the host with the library's own
 code (the traversal is the function the kernels inline), so face and distance must agree bit for bit -- including
-duplicate triangles (ties), axis-parallel rays (zero direction components), grazing rays and far origins."""
+duplicate triangles (ties), axis-parallel rays (zero direction components), grazing rays and far origins.
+
+What is covered where.  HERE, on the host: the skip-link walk, the front-to-back binary walk (trees shallower than BVH_STACK), the
+single-ray four-wide walk and the four-wide steps under their finest schedule (one node or ONE triangle per turn), each against the
+loop.  ON THE DEVICE, tests/test_gpu_mesh_walks.py: the same meshes (tests/meshcases.py) through every walk the kernels take -- k_mesh's
+refilling four-wide walk, k_finish's fallback (skip links or loop), the single-lane four-wide walk and the ordered walk of meshKey with
+a stack, the skip-link walk of k_kat_geom, the plain loop fused, chunked and from LDS -- against the oracle's loop, bit for bit, with
+ptx_debug_mesh_plan saying which walk ran.  The fixture tests at the end of this file assert, without a GPU, that every case added for
+the device tier agrees with the loop on the host and HAS the property it exists for (a tree deeper than the stacks, ties, NaNs ...), so
+a failure there points at the device and no device case passes vacuously."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from conftest import beq
+import meshcases as mc
+from meshcases import hull, rays_around
 
 
 def run_check(product, faces, rays):
@@ -27,33 +38,6 @@ def run_check(product, faces, rays):
                                fb.ctypes.data, tb.ctypes.data, st.ctypes.data)
     assert rc == 0
     return fl, tl, fb, tb, st
-
-
-def hull(rings, segs, rng=None):
-    """closed UV-mapped ellipsoid-like hull, outward CCW, as 15-float faces"""
-    v = []
-    for r in range(rings + 1):
-        th = np.pi * r / rings
-        for s in range(segs + 1):
-            ph = 2 * np.pi * s / segs
-            b = 1.0 + 0.25 * np.sin(3 * th) * np.cos(2 * ph)
-            v.append((1.6 * np.sin(th) * np.cos(ph) * b, 0.7 * np.cos(th), np.sin(th) * np.sin(ph) * b, s / segs, r / rings))
-    v = np.array(v, np.float32)
-    idx = lambda r, s: r * (segs + 1) + s
-    f = []
-    for r in range(rings):
-        for s in range(segs):
-            a, b, c, d = idx(r, s), idx(r, s + 1), idx(r + 1, s + 1), idx(r + 1, s)
-            f.append(np.concatenate([v[a], v[c], v[d]]))
-            f.append(np.concatenate([v[a], v[b], v[c]]))
-    return np.array(f, np.float32)
-
-
-def rays_around(rng, n, radius, target_scale=1.0):
-    o = rng.normal(size=(n, 3)).astype(np.float32)
-    o *= (radius / np.linalg.norm(o, axis=1, keepdims=True)).astype(np.float32)
-    tgt = (rng.uniform(-1, 1, size=(n, 3)) * target_scale).astype(np.float32)
-    return np.concatenate([o, tgt - o], axis=1).astype(np.float32)
 
 
 def assert_same(res):
@@ -96,12 +80,7 @@ def test_walk_statistics_of_the_last_check(product):
 
 def test_triangle_soup_and_ties(product):
     rng = np.random.default_rng(11)
-    n = 3000
-    c = rng.uniform(-2, 2, size=(n, 1, 3))
-    tri = (c + rng.normal(scale=0.15, size=(n, 3, 3))).astype(np.float32)
-    uv = rng.uniform(0, 1, size=(n, 3, 2)).astype(np.float32)
-    faces = np.concatenate([tri, uv], axis=2).reshape(n, 15)
-    faces = np.concatenate([faces, faces[:500], faces[100:300]])      # exact duplicates: the lower face index must win
+    faces, n = mc.soup(rng, 3000)                                     # + exact duplicates: the lower face index must win
     rays = rays_around(rng, 30000, 5.0, 2.0)
     fl, st = assert_same(run_check(product, faces, rays))
     hit = fl[fl >= 0]
@@ -110,53 +89,19 @@ def test_triangle_soup_and_ties(product):
 
 def test_axis_parallel_and_grazing(product):
     rng = np.random.default_rng(13)
-    # a flat grid in the plane y = 0 (boxes of zero thickness) plus a vertical wall
-    g = 40
-    xs = np.linspace(-2, 2, g + 1, dtype=np.float32)
-    f = []
-    for i in range(g):
-        for j in range(g):
-            a = (xs[i], 0, xs[j], 0, 0); b = (xs[i + 1], 0, xs[j], 1, 0); c = (xs[i + 1], 0, xs[j + 1], 1, 1); d = (xs[i], 0, xs[j + 1], 0, 1)
-            f.append(np.array(a + d + c, np.float32)); f.append(np.array(a + c + b, np.float32))     # facing +y
-    for i in range(g):
-        for j in range(g):
-            a = (xs[i], xs[j] + 2, -1, 0, 0); b = (xs[i + 1], xs[j] + 2, -1, 1, 0); c = (xs[i + 1], xs[j + 1] + 2, -1, 1, 1); d = (xs[i], xs[j + 1] + 2, -1, 0, 1)
-            f.append(np.array(a + b + c, np.float32)); f.append(np.array(a + c + d, np.float32))     # facing +z
-    faces = np.array(f, np.float32)
+    # a flat grid in the plane y = 0 (boxes of zero thickness) plus a vertical wall; rays straight down, along -z, down from the grid
+    # lines, grazing
+    faces, xs = mc.flat_grid(40)
     n = 8000
-    o = rng.uniform(-2, 2, size=(n, 3)).astype(np.float32)
-    o[:, 1] = rng.uniform(0.5, 3, size=n)
-    rays = []
-    down = np.tile(np.array([0, -1, 0], np.float32), (n, 1))                       # two zero components
-    rays.append(np.concatenate([o, down], axis=1))
-    o2 = o.copy(); o2[:, 2] = 3
-    rays.append(np.concatenate([o2, np.tile(np.array([0, 0, -1], np.float32), (n, 1))], axis=1))
-    # origins on the grid lines (edges shared by triangles), axis-parallel: ties between neighbours
-    og = np.stack([xs[rng.integers(0, g + 1, n)], np.full(n, 1.0, np.float32), xs[rng.integers(0, g + 1, n)]], axis=1).astype(np.float32)
-    rays.append(np.concatenate([og, down], axis=1))
-    # grazing: almost inside the plane
-    dg = rng.normal(size=(n, 3)).astype(np.float32); dg[:, 1] = -np.abs(rng.normal(scale=1e-4, size=n)).astype(np.float32)
-    og2 = o.copy(); og2[:, 1] = rng.uniform(1e-4, 1e-2, size=n)
-    rays.append(np.concatenate([og2, dg], axis=1))
-    rays = np.concatenate(rays).astype(np.float32)
+    rays = mc.flat_grid_rays(rng, xs, n)
     fl, st = assert_same(run_check(product, faces, rays))
     assert (fl >= 0).sum() > n
 
 
 def test_needles_tiny_and_far(product):
     rng = np.random.default_rng(17)
-    n = 2000
-    base = rng.uniform(-1, 1, size=(n, 3))
-    dirs = rng.normal(size=(n, 3))
-    tri = np.stack([base, base + dirs * rng.uniform(0.5, 2.0, size=(n, 1)), base + rng.normal(scale=1e-3, size=(n, 3))], axis=1)   # needles
-    tiny = rng.uniform(-1, 1, size=(n, 1, 3)) + rng.normal(scale=1e-4, size=(n, 3, 3))
-    tri = np.concatenate([tri, tiny]).astype(np.float32)
-    faces = np.concatenate([tri, np.zeros((len(tri), 3, 2), np.float32)], axis=2).reshape(len(tri), 15)
-    rays = np.concatenate([rays_around(rng, 20000, 3.0, 1.0), rays_around(rng, 10000, 2000.0, 1.0)])
-    # aim a share of the rays straight at triangle centroids so that tiny ones are hit
-    cent = tri.mean(axis=1)[rng.integers(0, len(tri), 10000)]
-    o = rays_around(rng, 10000, 4.0)[:, :3]
-    rays = np.concatenate([rays, np.concatenate([o, cent - o], axis=1)]).astype(np.float32)
+    faces, tri = mc.needles(rng, 2000)
+    rays = mc.needles_rays(rng, tri)
     fl, st = assert_same(run_check(product, faces, rays))
     assert (fl >= 0).sum() > 3000
 
@@ -173,10 +118,7 @@ def test_far_origin_sweep(product, ratio):
     rays = rays_around(rng, n, 3.0 * ratio, 1.6)
     fl, st = assert_same(run_check(product, faces, rays))
     assert (fl >= 0).sum() > n // 20
-    m = 800
-    base = rng.uniform(-1, 1, size=(m, 3))
-    tri = np.stack([base, base + rng.normal(size=(m, 3)) * rng.uniform(0.3, 1.5, size=(m, 1)), base + rng.normal(scale=2e-2, size=(m, 3))], axis=1).astype(np.float32)
-    soup = np.concatenate([tri, np.zeros((m, 3, 2), np.float32)], axis=2).reshape(m, 15)
+    soup = mc.far_soup(rng, 800)
     assert_same(run_check(product, soup, rays_around(rng, 4000, 2.0 * ratio, 1.0)))
 
 
@@ -188,3 +130,75 @@ def test_near_rays_still_prune(product):
     rays = rays_around(rng, 8000, 8.0, 1.5)
     fl, st = assert_same(run_check(product, faces, rays))
     assert st[2] / len(rays) < 450
+
+
+# ---- the fixtures of the device tier (tests/test_gpu_mesh_walks.py): right on the host, and what they claim to be --------------------
+def bvh_visits(product):
+    L = product.load_library()
+    v = np.zeros(8, np.int64)
+    L.ptx_debug_bvh_visits.restype = C.c_int
+    L.ptx_debug_bvh_visits.argtypes = [C.c_void_p]
+    assert L.ptx_debug_bvh_visits(v.ctypes.data) == 0
+    return dict(wide_need=int(v[3]), depth=int(v[7]))
+
+
+def test_fixture_chain_is_deeper_than_the_wide_stack(product):
+    """chain: the four-wide walk needs more than BVH_STACK entries (k_mesh must refuse it), the binary tree is still shallower than
+    BVH_STACK (the ordered walk fits), and at least 25 distinct triangles are hit."""
+    faces, rays = mc.chain_case(np.random.default_rng(31))
+    assert len(faces) <= 3500 and len(rays) <= 40000
+    fl, st = assert_same(run_check(product, faces, rays))
+    v = bvh_visits(product)
+    print("chain: wide stack need %d, binary depth %d, %d distinct faces hit, %.3f of the rays hit" % (v["wide_need"], v["depth"], len(np.unique(fl[fl >= 0])), (fl >= 0).mean()))
+    assert v["wide_need"] > mc.BVH_STACK
+    assert v["depth"] < mc.BVH_STACK
+    assert len(np.unique(fl[fl >= 0])) >= 25
+
+
+def test_fixture_chain_deep_is_deeper_than_every_stack(product):
+    """chain_deep: a binary depth of at least BVH_STACK -- neither stack walk fits, only the skip links remain -- and still hit."""
+    faces, rays = mc.chain_deep_case(np.random.default_rng(31))
+    assert len(faces) <= 3500 and len(rays) <= 40000
+    fl, st = assert_same(run_check(product, faces, rays))
+    v = bvh_visits(product)
+    print("chain_deep: wide stack need %d, binary depth %d, %d distinct faces hit" % (v["wide_need"], v["depth"], len(np.unique(fl[fl >= 0]))))
+    assert v["wide_need"] > mc.BVH_STACK and v["depth"] >= mc.BVH_STACK
+    assert len(np.unique(fl[fl >= 0])) >= 25
+
+
+def test_fixture_coincident_centroids(product):
+    faces, rays = mc.coincident(np.random.default_rng(41))
+    assert len(faces) == 64
+    cent = faces.reshape(-1, 3, 5)[:, :, :3].astype(np.float64).mean(axis=1)
+    assert np.abs(cent - cent[0]).max() < 1e-6                          # one centroid, to float32 rounding of the vertices
+    fl, st = assert_same(run_check(product, faces, rays))
+    assert (fl >= 0).mean() > 0.10
+    assert len(np.unique(fl[fl >= 0])) > 32
+
+
+def test_fixture_soup_with_nan_and_zero_area_triangles(product):
+    faces, rays, n = mc.soup_nan(np.random.default_rng(43))
+    assert len(faces) <= 3520 and np.isnan(faces).any()
+    tri = faces.reshape(-1, 3, 5)[:, :, :3]
+    assert (np.all(tri[:, 1] == tri[:, 2], axis=1)).sum() == 10        # the zero-area ones
+    fl, st = assert_same(run_check(product, faces, rays))
+    assert (fl >= 0).mean() > 0.10
+    assert fl.max() < n                                                 # neither a duplicate nor a degenerate triangle ever wins
+    # ... and ties exist: some winner has an exact copy further down the list
+    assert np.isin(fl[fl >= 0], np.arange(0, 500)).any()
+
+
+@pytest.mark.parametrize("k", [23, 24, 25])
+def test_fixture_hull_cut_to_the_loop_tree_boundary(product, k):
+    faces = mc.hull_cut(k)
+    assert len(faces) == k and (k >= mc.BVH_MIN_FACES) == (k >= 24)
+    fl, st = assert_same(run_check(product, faces, mc.hull_cut_rays(np.random.default_rng(47 + k))))
+    assert (fl >= 0).mean() > 0.10
+    assert len(np.unique(fl[fl >= 0])) > k // 2
+
+
+def test_mesh_plan_refuses_a_null_tracer(product):
+    """ptx_debug_mesh_plan is host-only and says so with an error code, not a crash, when there is no tracer to ask."""
+    L = product.load_library()
+    out = np.zeros(8, np.int32)
+    assert L.ptx_debug_mesh_plan(None, 0, out.ctypes.data) != 0
