@@ -496,6 +496,16 @@ int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8);
 /* CPU-only: the geoms a path can end on with radiance, as ptx_create works them out: bit g of *bits_out (g < 32) = the material of geom g
  * (geom_material[g]) has emittance > 0.  The last bounce of a path looks only for these geoms.  Returns 0, -1 on a bad argument. */
 int ptx_debug_light_bits(int nmaterials, const ptx_material *materials, int ngeoms, const int32_t *geom_material, uint32_t *bits_out);
+/* CPU-only: the object-space boxes of the small meshes (the meshes of a scene in which no mesh is large enough for a BVH), as ptx_create
+ * builds them for the candidate pre-test: a ray is a candidate of such a mesh when it reaches the box of the mesh's faces in the mesh's own
+ * space, which a rotated mesh fills where it fills a fraction of its world box.  geoms as ptx_create takes them (ngeoms <= 32), no_bvh as
+ * ptx_options.no_bvh (no mesh gets a BVH, so every mesh counts as small); table16 = 16
+ * floats per geom, zeros for a geom without an entry: three rows of (a row of the inverse transform's 3 x 3 part, the world point mapped to
+ * the box's centre), the half extent xyz with its derived margins, the margin per unit of the ray origin's distance from the centre;
+ * bit g of *bits_out = geom g has an entry.  margin = 1: the derived margins, 0: none (the CPU tests show with it that they can fail).
+ * Returns 0, -1 on a bad argument.  The environment variable PTX_DEBUG_NO_OBJCULL, read by ptx_create, leaves every mesh without an entry:
+ * candidates then come from the world boxes alone (A/B timing, tests of both paths; same results either way). */
+int ptx_debug_cull_objboxes(int ngeoms, const ptx_geom *geoms, int no_bvh, float margin, float *table16, uint32_t *bits_out);
 /* Host-only (reads what ptx_create kept on the host, launches nothing): how mesh geom `geom` of a live tracer is searched.
  * out8 = { root of its BVH (-1: none, the plain loop over its faces), depth of the binary tree, root of its four-wide nodes (-1: none),
  * stack entries their walk needs, stack entries per lane the tracer's launches provide (bvh_stack), 1 if frames take the split mesh search

@@ -341,6 +341,29 @@ def debug_light_bits(materials, geom_material):
     return int(out[0])
 
 
+def debug_cull_objboxes(geom_ints, geom_mats, faces, margin=1.0, no_bvh=0):
+    """CPU only: the object-space boxes of a scene's small meshes (ptx_debug_cull_objboxes) for geoms given as Scene.dump() gives them:
+    geom_ints (n, 3) = type, material, faces; geom_mats (n, 48) = transform, inverseTransform, invTranspose; faces = a list of (k, 15)
+    arrays.  Returns ((n, 16) float32 table as the device reads it, objcull_bits).  margin 0: the boxes without their derived margins;
+    no_bvh as the option of that name (every mesh counts as small)."""
+    L = load_library()
+    gi = np.ascontiguousarray(geom_ints, np.int32).reshape(-1, 3)
+    gm = np.ascontiguousarray(geom_mats, np.float32).reshape(-1, 48)
+    keep = [np.ascontiguousarray(f, np.float32).reshape(-1, 15) for f in faces]
+    geoms = (Geom * max(len(gi), 1))()
+    for g in range(len(gi)):
+        geoms[g].type, geoms[g].materialid = int(gi[g][0]), int(gi[g][1])
+        for name, k in (("transform", 0), ("inverseTransform", 16), ("invTranspose", 32)):
+            getattr(geoms[g], name)[:] = gm[g][k:k + 16].tolist()
+        geoms[g].faceSize = len(keep[g])
+        geoms[g].faces = keep[g].ctypes.data_as(C.POINTER(C.c_float)) if len(keep[g]) else None
+    out = np.zeros((len(gi), 16), np.float32)
+    bits = np.zeros(1, np.uint32)
+    if L.ptx_debug_cull_objboxes(len(gi), geoms, int(no_bvh), float(margin), _ptr(out), _ptr(bits)) < 0:
+        raise PathTracerError("ptx_debug_cull_objboxes: bad argument")
+    return out, int(bits[0])
+
+
 WALK_NAMES = ("loop", "skip", "ordered", "wide", "wide_refill")      # PTX_WALK_* of include/mi355x_pathtracer.h
 
 
@@ -511,6 +534,8 @@ def load_library():
         L.ptx_debug_cull_boxes.restype, L.ptx_debug_cull_boxes.argtypes = i, [i, vp, vp]
     if hasattr(L, "ptx_debug_light_bits"):
         L.ptx_debug_light_bits.restype, L.ptx_debug_light_bits.argtypes = i, [i, vp, i, vp, vp]
+    if hasattr(L, "ptx_debug_cull_objboxes"):
+        L.ptx_debug_cull_objboxes.restype, L.ptx_debug_cull_objboxes.argtypes = i, [i, C.POINTER(Geom), i, C.c_float, vp, vp]
     if hasattr(L, "ptx_debug_mesh_plan"):
         L.ptx_debug_mesh_plan.restype, L.ptx_debug_mesh_plan.argtypes = i, [vp, i, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)

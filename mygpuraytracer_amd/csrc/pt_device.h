@@ -372,10 +372,14 @@ struct DScene {
     int32_t mesh_chunks;                // > 1: no mesh has a BVH and the longest has this many groups of MESH_CHUNK faces:
                                         // tileIntersect spreads every (ray, mesh) pair over that many lanes
     int32_t cull;                       // != 0: per-lane candidate lists from the world boxes (needs tri_lds, <= 32 geoms)
+    uint32_t objcull_bits;              // bit g: small mesh g has an entry in `objcull`: its candidates are the rays that reach the faces' OBJECT-space
+                                        // box (cullMask).  (It lies in what was padding behind `cull`: no other field of the block has moved)
     const float *__restrict__ ldsblob;  // the tables below in ONE array, in the order and with the ntri_lds the launch stages them
                                         // (tri9, faces, materials, gtab, fnorm, cnorm): a workgroup copies it to LDS with all its loads in
                                         // flight at once -- one memory round trip, where table after table was six (it matters for the
                                         // short kernels of a small tile, which are chains of such round trips); NULL: table by table
+    const float *__restrict__ objcull;  // OBJCULL_WORDS per geom (zeros where objcull_bits has no bit): see objBoxReach.  Read through the scalar
+                                        // cache like `aabb`, never staged in LDS
 };
 
 // Words of dynamic LDS the staged scene tables take (tri9 + faces + fnorm = 27 per staged triangle, 11 per material, gtab 40 +
@@ -1103,10 +1107,55 @@ PT_HD vec3 mulRows(const float *r, vec3 v, float w) {
 // entry point for arbitrary rays always does), and every other scene (cull == 1) does not even look -- the specialised bounce kernels,
 // which fold cull to 1, are not taken for a far scene (fast_violation).
 constexpr float CULL_FAR_ORIGIN = 1024.0f;
+
+// OBJECT-SPACE BOXES OF THE SMALL MESHES.  A mesh that is rotated against the world axes fills a fraction of its world box (the cube of
+// cornellObj.txt, turned 45 degrees about y: half of it), and every ray that reaches the world box costs the tile one pair-list entry
+// per MESH_CHUNK faces, whole blocks of 64 lanes at a time (tileIntersect).  For the geoms of DScene::objcull_bits the verdict of the
+// pre-test is therefore "the ray reaches the box of the faces in the mesh's OWN space".  Like the world test it is not the reference's
+// arithmetic and only has to be conservative.  Table (objcull_entry in pt_scene.hip builds it and derives its margins), OBJCULL_WORDS
+// scalar words per geom:
+//     [0..11]  three rows of four: the row of the inverse transform's 3 x 3 part and, as fourth word, the WORLD point cw that it maps to
+//              the box's centre (the fourth column of gtab's rows is the translation; with it a row would start as a multiply-add of
+//              two scalar operands, which one instruction cannot read: moving the subtraction in front of the product costs nothing)
+//     [12..14] half extent H of the box, with every margin that does not depend on the ray
+//     [15]     k: the margin per unit of the origin's distance |q|_1 from the centre (the exact tests' own error grows with it: pt_bvh.h)
+// With q = M (o - cw) and e = M d (un-normalised: no test below cares for its length) the ray misses the box h = H + k |q|_1 iff one
+// of six axes separates them: a box axis i when |q_i| > h_i and the ray does not move towards the slab (q_i and e_i of one sign,
+// compared as bits: no rounding, no underflow, and -0 counts as moving towards it), or q x e's component i when
+// |q_j e_k - q_k e_j| > h_j |e_k| + h_k |e_j| (+ 2^-100, which keeps the underflow of the four products on the safe side).  No
+// reciprocal and no special case for a zero direction component; a NaN anywhere fails every comparison: not culled.
+// 12 + 9 vector instructions for q and e, 6 for h, 9 + 15 for the axes: 51 where the world test has 13, paid once per wave and mesh, against
+// a block of about 250 per 64 pair-list entries that never come to be (cornellObj at 1920x1080: 42.9 -> 23.6 mesh pairs per tile of the
+// later bounces, 1.262e8 -> 1.205e8 vector instructions per launch; profiles/objbox_cull_ab.txt).
+constexpr int OBJCULL_WORDS = 16;
+PT_DEV bool objBoxReach(const __attribute__((address_space(4))) float *T, Ray ray) {
+    const float px = ray.o.x - T[3], py = ray.o.y - T[7], pz = ray.o.z - T[11];
+    const float qx = __builtin_fmaf(T[2], pz, __builtin_fmaf(T[1], py, T[0] * px));
+    const float qy = __builtin_fmaf(T[6], pz, __builtin_fmaf(T[5], py, T[4] * px));
+    const float qz = __builtin_fmaf(T[10], pz, __builtin_fmaf(T[9], py, T[8] * px));
+    const float ex = __builtin_fmaf(T[2], ray.d.z, __builtin_fmaf(T[1], ray.d.y, T[0] * ray.d.x));
+    const float ey = __builtin_fmaf(T[6], ray.d.z, __builtin_fmaf(T[5], ray.d.y, T[4] * ray.d.x));
+    const float ez = __builtin_fmaf(T[10], ray.d.z, __builtin_fmaf(T[9], ray.d.y, T[8] * ray.d.x));
+    const float ax = __builtin_fabsf(qx), ay = __builtin_fabsf(qy), az = __builtin_fabsf(qz);
+    const float s = T[15] * ((ax + ay) + az);
+    const float hx = T[12] + s, hy = T[13] + s, hz = T[14] + s;
+    const float fx = __builtin_fabsf(ex), fy = __builtin_fabsf(ey), fz = __builtin_fabsf(ez);
+    const float floor_ = 0x1p-100f;
+    bool out = (ax > hx) & ((__float_as_int(qx) ^ __float_as_int(ex)) >= 0);
+    out |= (ay > hy) & ((__float_as_int(qy) ^ __float_as_int(ey)) >= 0);
+    out |= (az > hz) & ((__float_as_int(qz) ^ __float_as_int(ez)) >= 0);
+    out |= __builtin_fabsf(__builtin_fmaf(qy, ez, -(qz * ey))) > __builtin_fmaf(hy, fz, __builtin_fmaf(hz, fy, floor_));
+    out |= __builtin_fabsf(__builtin_fmaf(qz, ex, -(qx * ez))) > __builtin_fmaf(hz, fx, __builtin_fmaf(hx, fz, floor_));
+    out |= __builtin_fabsf(__builtin_fmaf(qx, ey, -(qy * ex))) > __builtin_fmaf(hx, fy, __builtin_fmaf(hy, fx, floor_));
+    return !out;
+}
+
 template <bool SUBSET = false>
 PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffffu) {
     typedef const __attribute__((address_space(4))) float cfloat;
     cfloat *ab = (cfloat *)sc.aabb;
+    cfloat *oc = (cfloat *)sc.objcull;
+    const uint32_t ocb = sc.objcull_bits;        // (wave-uniform, and only bits below ngeoms)
     const float tiny = 1e-20f;
     const float ddx = __builtin_fabsf(ray.d.x) < tiny ? __builtin_copysignf(tiny, ray.d.x) : ray.d.x;
     const float ddy = __builtin_fabsf(ray.d.y) < tiny ? __builtin_copysignf(tiny, ray.d.y) : ray.d.y;
@@ -1134,9 +1183,18 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
         const float tf = __builtin_fminf(__builtin_fminf(x1, y1), z1);
         return !((tf < tn) || (tf < 0.0f));      // any NaN => not culled
     };
+    // The small meshes that have an object-space box come first (usually there is one): ONE copy of that test in the kernel, its verdicts in
+    // `om`; the loops below leave those geoms' bits 0 -- a scalar branch per geom, no vector instruction -- and `om` is or-ed in at the end.
+    // (In place of the world test, not behind a "some lane passed the world test" branch: measured on cornellObj at 1920x1080,
+    // 1.210e8 against 1.222e8 vector instructions per later-bounce launch, profiles/objbox_cull_ab.txt.)
+    uint32_t om = 0;
+    for (uint32_t todo = __builtin_amdgcn_readfirstlane(SUBSET ? ocb & subset : ocb); todo; todo &= todo - 1) {
+        const int g = __builtin_ctz(todo);
+        om |= objBoxReach(oc + g * OBJCULL_WORDS, ray) ? (1u << g) : 0u;
+    }
     if (SUBSET) {
         // (a scalar loop over the set bits, two boxes per trip like the plain loop; n <= 32 wherever the masks are in use)
-        uint32_t todo = __builtin_amdgcn_readfirstlane(n >= 32 ? subset : subset & ((1u << n) - 1u));
+        uint32_t todo = __builtin_amdgcn_readfirstlane((n >= 32 ? subset : subset & ((1u << n) - 1u)) & ~ocb);
         while (todo) {
             const int i = __builtin_ctz(todo);
             todo &= todo - 1;
@@ -1148,6 +1206,7 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
             mask |= slab(bx[0]) ? (1u << i) : 0u;
             mask |= slab(bx[1]) ? (1u << j) : 0u;
         }
+        mask |= om;
         if (sc.cull > 1 && far_origin()) mask = n >= 32 ? subset : subset & ((1u << n) - 1u);
         return mask;
     }
@@ -1158,7 +1217,7 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
         float bx[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) bx[k] = ab[i * 8 + k];
-        mask = slab(bx) ? 1u : 0u;
+        mask = (!((ocb >> i) & 1u) && slab(bx)) ? 1u : 0u;
         i--;
     }
     for (; i > 0; i -= 2) {
@@ -1167,11 +1226,12 @@ PT_DEV uint32_t cullMask(const DScene &sc, Ray ray, uint32_t subset = 0xffffffff
         for (int k = 0; k < 8; k++) { bx[0][k] = ab[i * 8 + k]; bx[1][k] = ab[(i - 1) * 8 + k]; }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const unsigned long long verdict = __builtin_amdgcn_ballot_w64(slab(bx[h]));
+            const unsigned long long verdict = ((ocb >> (i - h)) & 1u) ? 0ull : __builtin_amdgcn_ballot_w64(slab(bx[h]));
             // (written out: the compiler turns `mask + mask + verdict` back into a shift, a select and an or)
             asm("v_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(mask) : "s"(verdict) : "vcc");
         }
     }
+    mask |= om;
     if (sc.cull > 1 && far_origin()) mask = n >= 32 ? 0xffffffffu : (1u << n) - 1u;
     return mask;
 }

@@ -296,7 +296,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     int cache_gx = 0;                                    // workgroups per segment of the launch that filled the cache (its run tables' width)
     DevBuf<int32_t> d_totals;                            // [maxBounces][2][nbins] then [maxBounces][2][nbins][nsuper]
     int32_t *d_super = nullptr;                          // (points into d_totals' allocation)
-    DevBuf<float> d_tri9, d_gtab, d_aabb;
+    DevBuf<float> d_tri9, d_gtab, d_aabb, d_objcull;
     std::vector<float> h_aabb;                           // host copy of the world boxes (update_tile_geoms)
     std::vector<int32_t> h_geom_type, h_roots, h_depths, h_wroots, h_wneeds;      // host copies of the per-geom tree tables (ptx_debug_mesh_plan)
     DevBuf<uint32_t> d_tile_geoms; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
@@ -371,6 +371,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DScene scene() const {
         DScene s; s.geoms = d_geoms; s.mats = d_mats; s.faces = d_faces; s.tri9 = d_tri9; s.texels = d_texels; s.ngeoms = ngeoms; s.nmats = nmats;
         s.gtab = d_gtab; s.aabb = d_aabb; s.cull = 0; s.cube_bits = cube_bits; s.sphere_bits = sphere_bits; s.mesh_bits = mesh_bits; s.light_bits = light_bits;
+        s.objcull = d_objcull; s.objcull_bits = objcull_bits;
         s.bvh_nodes = d_bvh_nodes; s.bvh_tris = d_bvh_tris; s.bvh_root = d_bvh_root; s.bvh_depth = d_bvh_depth; s.bvh_wide = d_bvh_wide; s.bvh_wroot = d_bvh_wroot; s.bvh_wneed = d_bvh_wneed; s.bvh_stack = 0; s.ntri_lds = 0; s.mesh_chunks = mesh_chunks;
         s.fnorm = d_fnorm; s.cnorm = d_cnorm; s.bump_bits = bump_bits;
         s.tri_lds = 0; s.ntri = ntri;      // tri_lds is switched on only by launches that stage the table (k_bounce)
@@ -965,7 +966,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     SceneSwitches sw;
     sw.no_wide_bvh = getenv("PTX_DEBUG_NO_WIDE_BVH") != nullptr; sw.no_chunks = getenv("PTX_DEBUG_NO_CHUNKS") != nullptr;
     sw.no_dir_skip = getenv("PTX_DEBUG_NO_DIR_SKIP") != nullptr; sw.no_normal_codes = getenv("PTX_DEBUG_NO_NORMAL_CODES") != nullptr;
-    sw.force_split = getenv("PTX_DEBUG_FORCE_SPLIT") != nullptr;
+    sw.force_split = getenv("PTX_DEBUG_FORCE_SPLIT") != nullptr; sw.no_objcull = getenv("PTX_DEBUG_NO_OBJCULL") != nullptr;
     if (const int rc = pt_prepare_scene(ngeoms, geoms, nmaterials, materials, opt, t->tm.owned, t->nbins, prop.sharedMemPerBlock, sw, hs)) return fail(rc);
     static_cast<SceneFacts &>(*t) = hs;
     // ---- 5. iterations per launch set, launch sets in flight
@@ -1021,7 +1022,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     }
     // ---- 7. upload the scene, allocate the streams' buffers
     HC(t->d_geoms.upload(hs.geoms)); HC(t->d_mats.upload(hs.mats)); HC(t->d_faces.upload(hs.faces)); HC(t->d_texels.upload(hs.texels));
-    HC(t->d_tri9.upload(hs.tri9)); HC(t->d_gtab.upload(hs.gtab)); HC(t->d_aabb.upload(hs.aabb_ch));
+    HC(t->d_tri9.upload(hs.tri9)); HC(t->d_gtab.upload(hs.gtab)); HC(t->d_aabb.upload(hs.aabb_ch)); HC(t->d_objcull.upload(hs.objcull));
     HC(t->d_fnorm.upload(hs.fnorm)); HC(t->d_cnorm.upload(hs.cnorm));
     if (t->bvh_meshes) {
         HC(t->d_bvh_nodes.upload(hs.bvh.nodes)); HC(t->d_bvh_tris.upload(hs.bvh.tris));

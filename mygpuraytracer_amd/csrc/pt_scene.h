@@ -15,6 +15,7 @@ struct SceneSwitches {
     bool no_dir_skip = false;          // PTX_DEBUG_NO_DIR_SKIP: every record carries direction and normal
     bool no_normal_codes = false;      // PTX_DEBUG_NO_NORMAL_CODES: every record carries its normal
     bool force_split = false;          // PTX_DEBUG_FORCE_SPLIT: the split mesh search for any scene with a mesh (timing experiments only)
+    bool no_objcull = false;           // PTX_DEBUG_NO_OBJCULL: no small mesh gets an object-space box, its candidates come from the world box (A/B timing, tests of both)
 };
 
 // What the scene decides about how it is traced: the tracer (ptx_tracer) keeps these by the same names.
@@ -25,6 +26,7 @@ struct SceneFacts {
     uint32_t cube_bits = 0, sphere_bits = 0, mesh_bits = 0;   // geoms 0..31 by kind, for the candidate masks
     uint32_t bump_bits = 0;
     uint32_t light_bits = 0;                             // geoms 0..31 whose material emits (emittance > 0): DScene::light_bits
+    uint32_t objcull_bits = 0;                           // small meshes 0..31 with an entry in HostScene::objcull: DScene::objcull_bits
     int tri_lds = 0, ntri_lds = 0, cull = 0;             // cull: 0 off, 1 candidate masks, 2 candidate masks in a scene where rays can start far out (cullMask)
     bool split_mesh = false;                             // k_bounce as MODE 1 + k_mesh + k_finish + MODE 2 (scenes with BVH meshes)
     unsigned long long dir_bins = ~0ull;                 // BounceParams::dir_bins (all ones: every record carries its direction)
@@ -37,6 +39,7 @@ struct HostScene : SceneFacts {
     std::vector<float> faces, tri9, gtab, fnorm, cnorm;
     std::vector<uint8_t> texels;
     std::vector<float> aabb, aabb_ch;                    // world boxes, 8 floats per geom: corners (lo xyz, 0, hi xyz, 0) / centre and half extent
+    std::vector<float> objcull;                          // DScene::objcull: OBJCULL_WORDS per geom, zeros where objcull_bits has no bit
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
     BvhBuild bvh;                                        // pt_bvh.h: binary nodes, leaf triangles, four-wide nodes of every mesh that has a tree
     std::vector<int32_t> roots, depths, wroots, wneeds;  // per geom (-1 / 0: no tree)
@@ -57,5 +60,9 @@ void camera_to_device(const ptx_camera &c, DCamera &d);
 int owned_pixels(int W, int H, int tile_rows, int tile_rank, int tile_world);      // pixels of the row blocks this rank owns
 // bit g (g < 32): geom g's material has emittance > 0 -- classifyPath's test of a hit's material, per geom
 uint32_t light_geom_bits(int nmaterials, const DMaterial *mats, int ngeoms, const int32_t *geom_material);
+// The object-space box of one small mesh as cullMask's objBoxReach reads it (OBJCULL_WORDS floats), from the geom's inverse transform
+// (16 floats, columns) and its faces.  margin = 1: the derived margins (pt_scene.hip); 0: the bare box, which the CPU tests use to show that
+// they can fail.  false (out16 zeroed): no entry -- no faces, a singular or non-finite matrix, numbers out of the derivation's range.
+bool objcull_entry(const float *inverse16, const float *faces15, int nfaces, double margin, float out16[OBJCULL_WORDS]);
 
 }  // namespace ptd

@@ -234,6 +234,88 @@ uint32_t light_geom_bits(int nmaterials, const DMaterial *mats, int ngeoms, cons
     return bits;
 }
 
+// The object-space box of a small mesh for the candidate pre-test (cullMask / objBoxReach in pt_device.h, which describes the table).
+// M, tau: the 3 x 3 part and the translation of the geom's inverse transform (the matrix the exact test maps the ray with), c, half: centre
+// and half extent of the faces' vertices in that space, R = |half|_2, cw = fl(M^-1 (c - tau)) the world point stored for the centre,
+// rho = (c - tau) - M cw what its rounding leaves (computed here, in binary64).  u = 2^-24.
+//
+// THE MARGINS, DERIVED.  For a world ray (o, d), |d| = 1, write q* = M o + tau - c and e* = M d for its exact image relative to the
+// centre.  A ray the exact test accepts a face for must pass objBoxReach.  Four things stand between the two:
+//  (1) the reference's triangle test in binary32 accepts rays that pass within 64 u (D + L) / kappa of the triangle or start that far
+//      beyond it (pt_bvh.h derives this; D <= |q*| + R the origin's distance, L <= 2R the longest edge, kappa the triangle's conditioning)
+//      = 2^11 u (|q*| + 3R) for kappa >= 2^-5 -- bvhSlack's constant, with the same caveat: below that conditioning the reference
+//      decides by rounding noise, and equality is measured (tests/test_cull_objboxes.py, tests/test_gpu_objbox_cull.py), not proven;
+//  (2) the reference maps the ray itself in binary32 (mulRows, three roundings deep; normalize): its origin is off by
+//      3.1 u (|M||o| + |tau|)_i <= 3.1 u (KA (|q*| + |rho|) + (|M||cw|)_i + |tau_i|) and its direction by an angle of (3.1 KB + 3) u, which
+//      moves a point of the box by that times its distance from the origin, at most |q*| + 2R;
+//      KA = || |M| |M^-1| ||_inf and KB = max_i |row_i(M)|_2 |M^-1|_F are the two condition numbers that occur (a rotation with a uniform
+//      scale: KA <= 3, KB <= 1.8);
+//  (3) the pre-test's own q and e: p = fl(o - cw), then a product and two fused multiply-adds per component:
+//      |q - q*|_i <= 4.1 u KA (|q*| + |rho|) + |rho_i|,  |e - e*|_i <= 3.1 u |row_i|_2.  The computed pair is the exact image of a ray moved
+//      by that much; a point of the box at parameter t <= (|q*| + 2R) / |e*| moves by |q - q*| + t |e - e*| <= ... + 3.2 u KB (|q*| + 2R);
+//  (4) the six comparisons.  The box axes compare without rounding.  A cross axis rounds two products and two multiply-adds on each
+//      side: |L| <= |l| (1 + u) + 1.01 u |q_k e_j| + 2 eta and R >= r (1 - 2u) - 2 eta + 2^-100 (eta <= 2^-126: underflow), so a half extent
+//      larger by 8 u (h_i + |q|_inf) per axis decides every |l| <= r as not separated; h = H + k |q|_1 itself loses 4 u of its value
+//      to its three additions and one product, inside the 8.
+// Sum, per axis i, with |q*|_inf <= |q*|_2 <= |q*|_1 <= (1 + 13 u KA) |q|_1 + 3 |rho|:
+//      margin_i <= u (2^11 + 7.2 KA + 6.3 KB + 11) |q|_1  +  u (3 * 2^11 + 13 KB + 14) R  +  3.1 u ((|M||cw|)_i + |tau_i|) + (1 + 8 u KA) |rho|_inf.
+// The table holds  k = u W / (1 - 32 u (KA + KB)),  W = 2^11 + 8 KA + 7 KB + 12  (the divisor pays for the second-order terms: the margins'
+// own contribution to "2R", |q*| against the computed |q|), and  H_i = half_i + 4 k R + 4 u ((|M||cw|)_i + |tau_i|) + 2 |rho|_inf,  rounded
+// up: the form of bvhSlack (2^11 u (|o - c| + 4R)) with the matrix's conditioning added.  A FLAT mesh has half_i = 0 on an axis and still
+// H_i >= 4 k R > 0.  There is no term for the origin's size: o enters through o - cw only, so CULL_FAR_ORIGIN does not occur; rays
+// from beyond it keep every candidate as before (cull == 2).  No entry (the world box goes on deciding) for a geom without faces, a
+// matrix that is singular, not finite or conditioned worse than 2^16, or a box outside [2^-60, 2^60]: the derivation assumes none of them.
+bool objcull_entry(const float *inverse16, const float *faces15, int nfaces, double margin, float out16[OBJCULL_WORDS]) {
+    for (int k = 0; k < OBJCULL_WORDS; k++) out16[k] = 0.f;
+    if (!inverse16 || !faces15 || nfaces < 1) return false;
+    double M[3][3], tau[3], lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) M[r][c] = inverse16[c * 4 + r]; tau[r] = inverse16[12 + r]; }
+    for (int j = 0; j < nfaces; j++)
+        for (int v = 0; v < 3; v++)
+            for (int r = 0; r < 3; r++) {
+                const double x = faces15[(size_t)j * 15 + v * 5 + r];
+                if (!std::isfinite(x)) return false;
+                lo[r] = std::min(lo[r], x); hi[r] = std::max(hi[r], x);
+            }
+    double I[3][3];                                  // M^-1 by cofactors
+    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    if (!std::isfinite(det) || det == 0.0) return false;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+            I[r][c] = (M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]) / det;
+        }
+    double KA = 0.0, KB = 0.0, fro = 0.0;
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) fro += I[r][c] * I[r][c];
+    fro = std::sqrt(fro);
+    for (int r = 0; r < 3; r++) {
+        double sum = 0.0;
+        for (int c = 0; c < 3; c++) for (int m = 0; m < 3; m++) sum += std::fabs(M[r][m]) * std::fabs(I[m][c]);
+        KA = std::max(KA, sum);
+        KB = std::max(KB, std::sqrt(M[r][0] * M[r][0] + M[r][1] * M[r][1] + M[r][2] * M[r][2]) * fro);
+    }
+    if (!(KA <= 65536.0 && KB <= 65536.0)) return false;
+    const double u = 1.0 / 16777216.0;
+    double c[3], half[3], R = 0.0, rho = 0.0;
+    float cw[3];
+    for (int r = 0; r < 3; r++) { c[r] = 0.5 * (lo[r] + hi[r]); half[r] = std::max(hi[r] - c[r], c[r] - lo[r]); R += half[r] * half[r]; }
+    R = std::sqrt(R);
+    for (int r = 0; r < 3; r++) cw[r] = (float)(I[r][0] * (c[0] - tau[0]) + I[r][1] * (c[1] - tau[1]) + I[r][2] * (c[2] - tau[2]));
+    for (int r = 0; r < 3; r++) rho = std::max(rho, std::fabs((c[r] - tau[r]) - (M[r][0] * cw[0] + M[r][1] * cw[1] + M[r][2] * cw[2])));
+    const double k = margin * u * (2048.0 + 8.0 * KA + 7.0 * KB + 12.0) / (1.0 - 32.0 * u * (KA + KB));
+    for (int r = 0; r < 3; r++) {
+        const double mcw = std::fabs(M[r][0] * cw[0]) + std::fabs(M[r][1] * cw[1]) + std::fabs(M[r][2] * cw[2]);
+        // (rho is kept at any margin: it is where the stored centre IS, not a bound on rounding; 1e-300 instead of 0 for margin = 0 on a flat axis
+        // would be a margin too, so there H_i may be 0)
+        const double H = half[r] + 4.0 * k * R + margin * 4.0 * u * (mcw + std::fabs(tau[r])) + 2.0 * rho;
+        if (!std::isfinite(H) || H > 0x1p60 || (margin > 0.0 && H < 0x1p-60) || !(std::fabs((double)cw[r]) <= 0x1p60)) { for (int q = 0; q < OBJCULL_WORDS; q++) out16[q] = 0.f; return false; }
+        out16[r * 4 + 0] = (float)M[r][0]; out16[r * 4 + 1] = (float)M[r][1]; out16[r * 4 + 2] = (float)M[r][2]; out16[r * 4 + 3] = cw[r];
+        out16[12 + r] = margin > 0.0 ? nextafterf((float)H, INFINITY) : (float)H;
+    }
+    out16[15] = margin > 0.0 ? nextafterf((float)k, INFINITY) : 0.f;
+    return true;
+}
+
 // scene upload (pathtraceInit, src/pathtrace.cu:111-146) -- flattened, no host struct is mutated
 int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials, const ptx_options &opt, int owned,
                      int nbins, size_t lds_limit, const SceneSwitches &sw, HostScene &hs) {
@@ -331,6 +413,12 @@ int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const pt
     for (int i = 0; i < ngeoms && hs.cull; i++)
         for (int k = 0; k < 3; k++)
             if (!(std::fabs(hs.aabb[(size_t)i * 8 + k]) <= 0.5f * CULL_FAR_ORIGIN && std::fabs(hs.aabb[(size_t)i * 8 + 4 + k]) <= 0.5f * CULL_FAR_ORIGIN)) hs.cull = 2;
+    // object-space boxes for the small meshes that tileIntersect works off as pair-list entries (the scenes mesh_chunks counts: no mesh has a BVH)
+    hs.objcull.assign(ng1 * OBJCULL_WORDS, 0.f);
+    if (hs.cull && !hs.bvh_meshes && !sw.no_chunks && !sw.no_objcull)
+        for (int i = 0; i < ngeoms; i++)
+            if (hs.geoms[i].type == G_OBJ && objcull_entry(hs.geoms[i].inv, hs.faces.data() + (size_t)hs.geoms[i].faceStart * 15, hs.geoms[i].faceCount, 1.0, &hs.objcull[(size_t)i * OBJCULL_WORDS]))
+                hs.objcull_bits |= 1u << i;
     // normals that do not depend on the ray, computed once with the device's own functions (compiled for the host with
     // the same flags: no contraction, IEEE divide and square root), so the kernels read what they would have computed
     hs.fnorm.assign((size_t)std::max(hs.ntri, 1) * 3, 0.f); hs.cnorm.assign(ng1 * 18, 0.f);
@@ -489,6 +577,26 @@ int ptx_debug_cull_boxes(int n, const float *boxes6, float *centre_half8) {
         world_box_centre_half(lohi, centre_half8 + (size_t)g * 8);
     }
     return n;
+}
+
+// CPU-only: ptx_create's object-space boxes of the small meshes (objcull_entry, the rule of pt_prepare_scene: candidate masks on, no mesh
+// with a BVH; no_bvh = ptx_options.no_bvh: no mesh gets one) for ngeoms <= 32 geoms given as ptx_create takes them: table16 = OBJCULL_WORDS
+// floats per geom as cullMask reads them on the device, *bits_out = DScene::objcull_bits.  margin 1 = the derived margins, 0 = none (tests only).
+int ptx_debug_cull_objboxes(int ngeoms, const ptx_geom *geoms, int no_bvh, float margin, float *table16, uint32_t *bits_out) {
+    if (ngeoms < 0 || ngeoms > 32 || (ngeoms && (!geoms || !table16)) || !bits_out || !(margin >= 0.f))
+    { set_error(PTX_ERR_INVALID, "ptx_debug_cull_objboxes: bad argument"); return -1; }
+    bool bvh = false;
+    for (int g = 0; g < ngeoms; g++) {
+        if (geoms[g].faceSize < 0 || (geoms[g].faceSize && !geoms[g].faces)) { set_error(PTX_ERR_INVALID, "ptx_debug_cull_objboxes: bad argument"); return -1; }
+        bvh = bvh || (!no_bvh && geoms[g].type == G_OBJ && geoms[g].faceSize >= BVH_MIN_FACES);
+    }
+    *bits_out = 0;
+    for (int g = 0; g < ngeoms; g++) {
+        for (int k = 0; k < OBJCULL_WORDS; k++) table16[(size_t)g * OBJCULL_WORDS + k] = 0.f;
+        if (!bvh && geoms[g].type == G_OBJ && objcull_entry(geoms[g].inverseTransform, geoms[g].faces, geoms[g].faceSize, margin, table16 + (size_t)g * OBJCULL_WORDS))
+            *bits_out |= 1u << g;
+    }
+    return 0;
 }
 
 // CPU-only: the per-tile geom masks of the camera-ray bounce (update_tile_geoms) for a camera, a tile split and a list of world boxes
