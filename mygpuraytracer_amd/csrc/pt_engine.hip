@@ -306,6 +306,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
     bool no_fast = false;                                // PTX_DEBUG_NO_FAST: always the general k_bounce (A/B timing, tests of both variants)
     bool no_last = false;                                // PTX_DEBUG_NO_LAST: the last bounce runs the full k_bounce like every other (A/B timing, tests of both)
+    bool last_inplace = false;                           // PTX_DEBUG_LAST_INPLACE: the light-only last bounce without the pool of survivors over tiles (A/B timing, tests of both)
     bool force_fast = false;                             // PTX_DEBUG_FORCE_FAST: ask for the specialised variant at every launch (refused
                                                          // with PTX_ERR_INVALID where its preconditions do not hold; tests only)
     DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_items; DevBuf<int32_t> d_item_count;
@@ -578,7 +579,10 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         return g < 1 ? 1 : g;
     };
     const int gx_first = gx_of(true), gx_later = gx_of(false);
-    const int gx_last = gx_of(false, true);      // (the light-only last bounce: the later bounces' grid -- 4 / 8 / 16 workgroups per CU measured alike, profiles/last_bounce_ab.txt)
+    int gx_last = gx_of(false, true);      // (the light-only last bounce: the later bounces' grid -- 4 / 8 / 16 workgroups per CU measured alike, profiles/last_bounce_ab.txt)
+    // (PTX_DEBUG_GX_LAST, tests only: fewer workgroups per segment there, so that a small frame gives a workgroup many tiles -- its pool of
+    // light-box survivors fills and drains as it does at 1080p)
+    if (const char *e = getenv("PTX_DEBUG_GX_LAST")) gx_last = std::max(1, std::min(atoi(e), gx_last));
     const int grid = t->cus * (t->dbg_total_wg_per_cu > 0 ? t->dbg_total_wg_per_cu : per_cu(false));      // (k_finish's grid-stride launch)
     const int gx = gx_later;
     const int nsuper = (gx + 63) / 64;
@@ -682,6 +686,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         bp.emit_count = (first && fill_cache) ? t->d_emit_count : nullptr;
         bp.emit_pix = t->d_emit_pix; bp.emit_rgb = t->d_emit_rgb;
         bp.fenced = reinterpret_cast<unsigned long long *>(t->d_stats + 65); bp.fence_slots = t->fence_slots; bp.fence_slots_cap = (uint32_t)t->cap;
+        bp.last_inplace = t->last_inplace ? 1 : 0;
         bp.tile_geoms = (first && t->tile_geoms_valid) ? t->d_tile_geoms : nullptr;
         if (t->split_mesh) {
             bp.keys = t->d_keys + seg0 * (size_t)t->cap; bp.seg_keys = (size_t)t->cap;
@@ -981,6 +986,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     }
     t->no_fast = getenv("PTX_DEBUG_NO_FAST") != nullptr;
     t->no_last = getenv("PTX_DEBUG_NO_LAST") != nullptr;
+    t->last_inplace = getenv("PTX_DEBUG_LAST_INPLACE") != nullptr;
     t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
     if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
     if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));

@@ -24,6 +24,12 @@ namespace {
 #ifndef PT_PARK_STATE
 #define PT_PARK_STATE 1       // specialised unsplit k_bounce: state that is idle during the pair tests waits in LDS, not in registers
 #endif
+#ifndef PT_PACKED_SLOTS
+#define PT_PACKED_SLOTS 1
+#endif
+#ifndef PT_WAVE_UNIFORM
+#define PT_WAVE_UNIFORM 1     // camera bounce: pair-list slots and ranks in closed form for a wave whose 64 lanes agree (0: A/B builds)
+#endif
 #ifndef PT_FAST_WAVES
 #define PT_FAST_WAVES 8       // waves per SIMD the specialised k_bounce variants are compiled for (<= 64 registers; 8 workgroups'
                               // LDS is also what a CU holds with the Cornell tables since the record buffer lost a row and the window half its runs)
@@ -237,6 +243,8 @@ struct BounceParams {
     const int32_t *in_super;               // [2][nbins][nsuper]: the same per 64 consecutive workgroups
     const int32_t *in_chunk;               // [3][chunk_cap]: per run -- survivors, stored paths, start of the run in the local index
     int32_t in_gx;
+    int32_t last_inplace;                  // the light-only last bounce tests each tile's rays where they are, no pool over tiles (in the
+                                           // padding behind in_gx: no other member moves; PTX_DEBUG_LAST_INPLACE: A/B, tests of both)
     size_t seg_in_totals, seg_in_chunk;    // per-segment strides of those (0: the cached bounce 0, shared by all segments)
     float *image;
     int32_t iter, traceDepth, bounce;      // bounce = index b of the intersect stage done by this launch

@@ -89,6 +89,7 @@ constexpr int ITEMS_PER_PASS = 4;                      // pairs a ray may contri
 // DEFER: the mesh pairs are not worked off here; the caller gets the best key over cubes and spheres and the ray's
 // mesh candidates (split mesh search, see k_mesh), and `hit` is left alone.
 // !DECODE: the caller wants the winning key only (the light-only last bounce: its geom's material is all that matters); `hit` is left alone.
+__device__ __forceinline__ int waveInclusiveScan(int v, int lane);      // (below)
 template <bool DEFER, bool PARK = false, bool SUBSET = false, bool DECODE = true>
 __device__ __forceinline__ void tileIntersect(const DScene &sc, bool alive, Ray ray, bool need_uv, Hit &hit, int32_t *scratch,
                                               int32_t *tcnt, int &q, int tid, int lane, int wave, unsigned long long &key_out,
@@ -99,34 +100,58 @@ __device__ __forceinline__ void tileIntersect(const DScene &sc, bool alive, Ray 
     uint16_t *list = reinterpret_cast<uint16_t *>(scratch + 8 * TILE);             // [CAP] ray | geom << RANK_BITS: cubes from the front,
     uint16_t *listM = list + ITEMS_PER_PASS * TILE;                                // spheres from the back; [CAP] meshes
     constexpr int CAP = ITEMS_PER_PASS * TILE;
-    uint32_t cube_mask = 0, sph_mask = 0, mesh_mask = 0;
+    uint32_t cube_mask = 0, sph_mask = 0, mesh_mask = 0, m_all = 0;
     if (alive) {
-        const uint32_t m = cullMask<SUBSET>(sc, ray, subset);
-        cube_mask = m & sc.cube_bits; sph_mask = m & sc.sphere_bits; mesh_mask = m & sc.mesh_bits;
+        m_all = cullMask<SUBSET>(sc, ray, subset);
+        cube_mask = m_all & sc.cube_bits; sph_mask = m_all & sc.sphere_bits; mesh_mask = m_all & sc.mesh_bits;
     }
     mesh_out = mesh_mask;
     if (DEFER) mesh_mask = 0;
+    // Camera rays (SUBSET): the 64 rays of a wave are neighbouring pixels of a row and very often reach the same boxes -- the back wall
+    // alone, say.  Such a wave (every lane alive, every mask lane 0's, at most ITEMS_PER_PASS candidates: one pass) needs no prefix: with n
+    // entries of a kind per lane, lane l's start at l * n and the wave has 64 * n.  (All threads of the workgroup are here: exec is full.)
+    bool uniform_wave = false;
+    if (SUBSET && PT_WAVE_UNIFORM) {
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)m_all);
+        uniform_wave = __ballot(alive && m_all == m0) == ~0ull && __popc(m0 & (DEFER ? ~sc.mesh_bits : 0xffffffffu)) <= ITEMS_PER_PASS;
+    }
     rayb[0 * TILE + tid] = ray.o.x; rayb[1 * TILE + tid] = ray.o.y; rayb[2 * TILE + tid] = ray.o.z;
     rayb[3 * TILE + tid] = ray.d.x; rayb[4 * TILE + tid] = ray.d.y; rayb[5 * TILE + tid] = ray.d.z;
     best[tid] = KEY_NONE;
     for (;;) {
         // this pass: up to ITEMS_PER_PASS pairs per ray -- cubes, then spheres, then meshes, each kind in a run of
-        // its own so that the waves working the list off run one kind of test.  Slots: prefix inside the wave from
-        // ballots of the 3-bit counts, one LDS atomic per wave and kind for its base (tcnt[4q..]: cube, sphere and
+        // its own so that the waves working the list off run one kind of test.  Slots: prefix inside the wave from ONE scan of
+        // the three capped counts (<= ITEMS_PER_PASS each, a wave's total <= 256: 10-bit fields of one word), one LDS atomic per wave
+        // and kind for its base (tcnt[4q..]: cube, sphere and
         // mesh pairs, "some ray has more"; the other parity's counters are cleared meanwhile for the next pass).
         const int cc = (int)__popc(cube_mask), cs = (int)__popc(sph_mask), cm = (int)__popc(mesh_mask);
         const int nc = cc < ITEMS_PER_PASS ? cc : ITEMS_PER_PASS;
         const int ns = cs < ITEMS_PER_PASS - nc ? cs : ITEMS_PER_PASS - nc;
         const int nm = cm < ITEMS_PER_PASS - nc - ns ? cm : ITEMS_PER_PASS - nc - ns;
         int base[3], tot[3];
-        const int cnt3[3] = {nc, ns, nm};
+        unsigned long long left = 0ull;
+        if (SUBSET && PT_WAVE_UNIFORM && uniform_wave) {                 // (wave-uniform branch; one pass, nothing is left over)
+            const int u0 = __builtin_amdgcn_readfirstlane(nc), u1 = __builtin_amdgcn_readfirstlane(ns), u2 = __builtin_amdgcn_readfirstlane(nm);
+            base[0] = lane * u0; base[1] = lane * u1; base[2] = lane * u2;
+            tot[0] = 64 * u0; tot[1] = 64 * u1; tot[2] = 64 * u2;
+        } else {
+#if PT_PACKED_SLOTS
+            const int packed = nc | (ns << 10) | (nm << 20);
+            const int inc = waveInclusiveScan(packed, lane), exc = inc - packed;
+            const int all = __builtin_amdgcn_readlane(inc, 63);
+            base[0] = exc & 1023; base[1] = (exc >> 10) & 1023; base[2] = exc >> 20;
+            tot[0] = all & 1023; tot[1] = (all >> 10) & 1023; tot[2] = all >> 20;
+#else
+            const int cnt3[3] = {nc, ns, nm};
 #pragma unroll
-        for (int kind = 0; kind < 3; kind++) {
-            const unsigned long long b0 = __ballot(cnt3[kind] & 1), b1 = __ballot(cnt3[kind] & 2), b2 = __ballot(cnt3[kind] & 4);
-            base[kind] = wavePrefix(b0, lane) + 2 * wavePrefix(b1, lane) + 4 * wavePrefix(b2, lane);
-            tot[kind] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+            for (int kind = 0; kind < 3; kind++) {
+                const unsigned long long b0 = __ballot(cnt3[kind] & 1), b1 = __ballot(cnt3[kind] & 2), b2 = __ballot(cnt3[kind] & 4);
+                base[kind] = wavePrefix(b0, lane) + 2 * wavePrefix(b1, lane) + 4 * wavePrefix(b2, lane);
+                tot[kind] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+            }
+#endif
+            left = __ballot(cc + cs + cm > nc + ns + nm);
         }
-        const unsigned long long left = __ballot(cc + cs + cm > nc + ns + nm);
         int wb0 = 0, wb1 = 0, wb2 = 0;
         if (lane == 0) {
             if (tot[0]) wb0 = atomicAdd(&tcnt[4 * q + 0], tot[0]);
@@ -357,6 +382,7 @@ __device__ __forceinline__ void flushQueue(const BounceParams &p, int seg, const
 // slab test as the candidate masks, so a miss there is a miss of the geom in the full test too) go on, to the pair tests against ALL
 // their candidates -- an occluder must win -- and the winner's material alone decides: emissive => the deposit classifyPath makes,
 // otherwise nothing.  No normal, no ranking, no epilogue, no tail; the bounce's ray count, which k_stats sums over the bins, goes to bin 0.
+// The specialised variant pools those rays over the workgroup's tiles and tests them a full tile at a time (see the LAST branch of the tile loop).
 // It is MODE_ 3 of this template (MODE_LAST) and MODE 0 in everything but the above: the other instantiations do not see it.  It is
 // instantiated by pt_kernels_last.hip alone (this source with PT_KERNELS_LAST_UNIT, see the end of the file), one more code object per level.
 constexpr int MODE_LAST = 3;
@@ -397,6 +423,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
     if (MODE == 1 && tid == 0) *qcnt = 0;
     for (int k = tid; k < 2 * nb; k += TILE) run_all[k] = 0;
     if (tid < 8) tcnt[tid] = 0;
+    if (LAST && tid == 0) tcs[0] = 0;                               // (the pool of the light-only bounce, see there)
     __syncthreads();
     const int seg = blockIdx.y;
     const int iter = p.iter + seg * p.iter_stride;
@@ -580,6 +607,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
     };
     int32_t *ccnt = qcnt + 2;                                   // MODE 1: candidates of the tile so far (LDS)
     int n_last = 0;                                             // LAST: rays of this wave's tiles that entered the intersection (wave-uniform)
+    int32_t *pool_n = tcs;                                      // LAST: rays in the pool of light-box survivors (LDS; the per-bin tile counts are not in use there)
     int32_t k1_next = 0;                                        // MODE 2: the next tile's word, requested one tile ahead
     // The ranking pass (MODE 2) has three barriers per tile: counts by wave 0, keys scattered to their slots through LDS.
     // MEASURED AND NOT KEPT, code removed (round 5, -DPT_RANK_ONE_BARRIER; last in commit 77f3d5a): the pass with ONE barrier per tile --
@@ -687,18 +715,64 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
             if (p.sc.light_bits == 0u) continue;                 // (uniform) nothing in the scene emits: every path ends black
             Ray ray; ray.o = ps.o; ray.d = ps.d;
             const bool reach = alive && cullMask<true>(p.sc, ray, p.sc.light_bits) != 0u;
-            Hit none;                                         // (never read: no decode)
-            uint32_t mesh_cand = 0;
-            tileIntersect<false, false, false, false>(p.sc, reach, ray, false, none, rec, tcnt, tq, tid, lane, wave, key, mesh_cand TI_PASS);
-            if (reach && key != KEY_NONE) {
-                // the winner's material; classifyPath with a hit that holds what it reads (t > 0: the key functions accept nothing else)
-                const float *G = reinterpret_cast<const float *>(pt_lds) + p.sc.ntri_lds * 24 + p.sc.nmats * 11 + (int)((key >> 24) & 0xff) * GTAB_WORDS;
-                Hit lh;
-                lh.t = 1.f; lh.n = V3(0.f, 0.f, 0.f); lh.u = lh.v = 0.f; lh.geom = 0; lh.ncode = 0;
-                lh.mat = __float_as_int(G[37]);
-                int lbin = 0;
-                bool lpend = false;
-                classifyRay(lh, ps, pix, lbin, lpend);
+            // The few rays that reach a light's box (a 3 x 3 lamp on a 10 x 10 ceiling: a few per cent of a tile) are not tested where they
+            // are -- the pair machinery would run on every tile for a handful of lanes per wave -- but POOLED over the workgroup's tiles in
+            // the record buffer (this launch stores no record): origin and direction in the rows tileIntersect keeps its copy of the rays in
+            // (0-5), throughput colour and pixel slot behind its scratch (rows 12-15).  A slot = the pool's count + the ray's place among the
+            // tile's survivors (ballot prefix, one LDS atomic per wave, as MODE 1's `ccnt`); the slot index is computed by ALL lanes, in
+            // front of the branch (a readfirstlane inside a divergent branch reads the first ACTIVE lane).  When TILE rays are pooled, or
+            // after the workgroup's last tile, the pool is DRAINED: thread t takes pooled ray t through tileIntersect, once, and the winner's
+            // material decides the deposit with the POOLED colour and pixel slot.  Rays of the tile that found the pool full wait in their
+            // registers and go in behind the drain.  Which lane makes a deposit changes no sum: a pixel has one path per iteration and
+            // segment, and a path deposits once.  p.last_inplace (debug): every tile is drained by itself, ray t in slot t -- the in-place form.
+            // The general kernel (!FAST) keeps that form: the rays that wait across a drain cost it seven registers, 92 -> 99, one wave of five.
+            const bool inplace = !FAST || p.last_inplace != 0;
+            const unsigned long long rb = __ballot(reach);
+            int pbase = 0;
+            if (!inplace && lane == 0 && rb) pbase = atomicAdd(pool_n, __popcll(rb));
+            int slot = inplace ? tid : __builtin_amdgcn_readfirstlane(pbase) + wavePrefix(rb, lane);
+            float *poolf = reinterpret_cast<float *>(rec);
+            auto pool_put = [&](int s) {                                      // (s < TILE: the caller's test)
+                poolf[0 * TILE + s] = ray.o.x; poolf[1 * TILE + s] = ray.o.y; poolf[2 * TILE + s] = ray.o.z;
+                poolf[3 * TILE + s] = ray.d.x; poolf[4 * TILE + s] = ray.d.y; poolf[5 * TILE + s] = ray.d.z;
+                poolf[12 * TILE + s] = ps.color.x; poolf[13 * TILE + s] = ps.color.y; poolf[14 * TILE + s] = ps.color.z;
+                rec[15 * TILE + s] = pix;
+            };
+            if (reach && (uint32_t)slot < (uint32_t)TILE) pool_put(slot);
+            __syncthreads();
+            int total = inplace ? TILE : *pool_n;                      // (uniform; every count since the last drain)
+            while (total >= TILE || (tile == tile1 - 1 && total > 0)) {
+                const int n = min(max(total, 0), TILE);                        // (a bad count costs pixels, never an address)
+                const bool pa = tid < n && (!inplace || reach);
+                Ray pr;
+                pr.o = V3(poolf[0 * TILE + tid], poolf[1 * TILE + tid], poolf[2 * TILE + tid]);
+                pr.d = V3(poolf[3 * TILE + tid], poolf[4 * TILE + tid], poolf[5 * TILE + tid]);
+                Hit none;                                         // (never read: no decode)
+                uint32_t mesh_cand = 0;
+                tileIntersect<false, false, false, false>(p.sc, pa, pr, false, none, rec, tcnt, tq, tid, lane, wave, key, mesh_cand TI_PASS);
+                if (tid == 0) *pool_n = total - n;                // (everybody read the count before tileIntersect's barriers)
+                if (pa && key != KEY_NONE) {
+                    // the winner's material; classifyPath with a hit that holds what it reads (t > 0: the key functions accept nothing else)
+                    const float *G = reinterpret_cast<const float *>(pt_lds) + p.sc.ntri_lds * 24 + p.sc.nmats * 11 + (int)((key >> 24) & 0xff) * GTAB_WORDS;
+                    Hit lh;
+                    lh.t = 1.f; lh.n = V3(0.f, 0.f, 0.f); lh.u = lh.v = 0.f; lh.geom = 0; lh.ncode = 0;
+                    lh.mat = __float_as_int(G[37]);
+                    PathState pps;
+                    pps.o = pr.o; pps.d = pr.d;
+                    pps.color = V3(poolf[12 * TILE + tid], poolf[13 * TILE + tid], poolf[14 * TILE + tid]);
+                    const int ppix = rec[15 * TILE + tid];
+                    int lbin = 0;
+                    bool lpend = false;
+                    // (the pooled slot went through LDS: checked again before it becomes the address of a deposit)
+                    if ((uint32_t)ppix < (uint32_t)p.tm.owned) classifyRay(lh, pps, ppix, lbin, lpend);
+                    else fence_report(p);
+                }
+                total -= n;
+                if (!FAST) break;                                 // (in place, known at compile time: no ray waits)
+                __syncthreads();                                  // the pool's rows are free: the rays that waited go in
+                slot -= TILE;
+                if (reach && (uint32_t)slot < (uint32_t)TILE) pool_put(slot);
+                __syncthreads();
             }
             STAMP(1);
             continue;
@@ -863,6 +937,19 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
                         w_all[wave * nb + bin] = __popc(alo) + __popc(ahi);
                         w_scat[wave * nb + bin] = __popc(plo) + __popc(phi);
                     }
+                }
+            } else if (PT_WAVE_UNIFORM && FIRST && MODE != 2 && __builtin_amdgcn_uicmp((uint32_t)abin, (uint32_t)__builtin_amdgcn_readfirstlane(abin), 32) == ~0ull &&
+                       __builtin_amdgcn_readfirstlane(abin) >= 0) {
+                // Camera rays: a wave of 64 neighbouring pixels that all hit the same material (every lane alive, one bin) -- most waves of a
+                // Cornell frame.  The rank among all is the lane, the wave's count 64; among the stored ones the same if all are stored, nothing
+                // if none is, and one prefix otherwise: the loop below with its single turn spelt out, minus what is known.
+                const int b = __builtin_amdgcn_readfirstlane(abin);
+                const unsigned long long m_scat = __builtin_amdgcn_uicmp((uint32_t)pbin, (uint32_t)b, 32);
+                r_all = lane;
+                r_scat = m_scat == ~0ull ? lane : m_scat == 0ull ? 0 : wavePrefix(m_scat, lane);
+                if (lane == 0) {
+                    w_all[wave * nb + b] = 64;
+                    w_scat[wave * nb + b] = __popcll(m_scat);
                 }
             } else {
                 unsigned long long remaining = __builtin_amdgcn_uicmp((uint32_t)abin, 0xffffffffu, 33);       // (alive lanes)
