@@ -15,6 +15,7 @@
  *   thrust::sort_by_key(.., sortByMaterial())   src/pathtrace.cu:418-422,518     sc_sort_records_by_key_device
  *   thrust::stable_partition(.., isTerminate()) src/pathtrace.cu:424-428,541     sc_partition_records_device
  *   (the kept half of that partition alone)                                      sc_compact_records_device
+ *   thrust::sort_by_key(keys, keys + n, values)  with keys of any value          sc_radix_sort_records_device
  *
  * Same argument meaning as the reference: n elements, host pointers in and out (the GPU variants allocate and
  * copy internally, exactly like the reference's), exclusive prefix sum, compaction keeps non-zero elements in
@@ -96,6 +97,42 @@ int sc_sort_records_by_key(int n, int nkeys, int descending, const int *keys,
         int *perm, int *key_totals);
 int sc_partition_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count);
 int sc_compact_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count);
+
+/* ---- records by full 32-bit keys: thrust::sort_by_key for keys of ANY value ---------------------------------------------------
+ * A stable least-significant-digit radix sort of n records, 8 bits per pass.  The 32 key bits of element i are read at
+ * d_keys + i * key_stride_bytes (a field of a record serves, as above) and mapped to an unsigned u whose order is the key type's:
+ *     SC_KEY_INT32    u = bits ^ 0x80000000
+ *     SC_KEY_UINT32   u = bits
+ *     SC_KEY_FLOAT32  u = (bits >> 31) ? ~bits : bits | 0x80000000
+ * and, with descending != 0, complemented afterwards.  sc_radix_map_key is that map (host code, no device).  The float order is total:
+ * negative NaNs < -inf < ... < -0 < +0 < ... < +inf < positive NaNs, NaNs by payload -- a NaN key gives a defined order and never an
+ * address.  The result is the stable sort by the field (u >> begin_bit) & (2^(end_bit - begin_bit) - 1), 0 <= begin_bit <= end_bit <= 32:
+ * equal fields keep input order, ascending or descending; begin_bit == end_bit copies the input.  ceil((end_bit - begin_bit) / 8)
+ * passes move (u, source index) pairs inside the workspace; the records themselves move once, in a gather behind the last pass.
+ * d_perm[p], if given, receives the source index of output row p; d_keys_out[p], if given, the caller's original 32 key bits of
+ * that row (what thrust::sort_by_key leaves in the key array).
+ * Limits, refusals and side effects are sc_sort_records_by_key_device's: record_bytes a multiple of 4 in 4..256, stride a multiple of
+ * 4 and >= 4, 4-byte aligned pointers (16-byte moves where the size and both pointers allow), no output equal to or overlapping an
+ * input, the keys or another output; anything else returns PTX_ERR_INVALID with the offending value in ptx_last_error(), enqueues
+ * nothing and is checked before the device (PTX_ERR_NODEVICE).  Workspace: sc_radix_workspace_bytes(n) bytes of device memory (about
+ * 16 n), 8-byte aligned, contents arbitrary, reusable by any later call of the library it is large enough for.  No allocation, no
+ * host synchronisation, no copy; the same bytes on every run; n == 0 writes nothing. */
+enum { SC_KEY_INT32 = 0, SC_KEY_UINT32 = 1, SC_KEY_FLOAT32 = 2 };
+
+unsigned long long sc_radix_workspace_bytes(int n);                    /* 0 for n < 0 */
+unsigned int sc_radix_map_key(int key_type, int descending, unsigned int bits);
+
+int sc_radix_sort_records_device(int n, int key_type, int descending, int begin_bit, int end_bit,
+        const void *d_keys, int key_stride_bytes,
+        void *d_out_a, const void *d_in_a, int record_bytes_a,
+        void *d_out_b, const void *d_in_b, int record_bytes_b,         /* NULL, NULL, 0 = one array */
+        int *d_perm, void *d_keys_out,                                  /* both optional */
+        void *d_workspace, void *stream);
+
+/* host pointers (keys: n 32-bit words); allocates, copies, synchronises and sets sc_last_gpu_ms; perm and keys_out may be NULL */
+int sc_radix_sort_records(int n, int key_type, int descending, int begin_bit, int end_bit, const void *keys,
+        void *out_a, const void *in_a, int record_bytes_a, void *out_b, const void *in_b, int record_bytes_b,
+        int *perm, void *keys_out);
 
 float sc_last_gpu_ms(void);      /* device time of the kernels of the previous GPU call (hipEvent), ms */
 float sc_last_cpu_ms(void);      /* wall time of the previous sc_cpu_* call, ms */

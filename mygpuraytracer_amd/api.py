@@ -577,6 +577,10 @@ def load_library():
     L.sc_sort_records_by_key.restype, L.sc_sort_records_by_key.argtypes = i, [i, i, i, vp, vp, vp, i, vp, vp, i, vp, vp]
     for n in ("sc_partition_records", "sc_compact_records"):
         getattr(L, n).restype, getattr(L, n).argtypes = i, [i, i, vp, vp, vp, vp]
+    L.sc_radix_workspace_bytes.restype, L.sc_radix_workspace_bytes.argtypes = C.c_ulonglong, [i]
+    L.sc_radix_map_key.restype, L.sc_radix_map_key.argtypes = C.c_uint, [i, i, C.c_uint]
+    L.sc_radix_sort_records_device.restype, L.sc_radix_sort_records_device.argtypes = i, [i, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp]
+    L.sc_radix_sort_records.restype, L.sc_radix_sort_records.argtypes = i, [i, i, i, i, i, vp, vp, vp, i, vp, vp, i, vp, vp]
     L.sc_last_gpu_ms.restype = f
     L.sc_last_cpu_ms.restype = f
     L.sc_ilog2.restype, L.sc_ilog2.argtypes = i, [i]
@@ -1279,6 +1283,45 @@ class StreamCompaction:
         """The rows with flag != 0, in order."""
         out, count = self._split_records(self.lib.sc_compact_records, "sc_compact_records", records, flags)
         return out[:count].copy()
+
+    # records by full 32-bit keys: thrust::sort_by_key for keys of any value (an 8-bit LSD radix sort; the records move once)
+    KEY_INT32, KEY_UINT32, KEY_FLOAT32 = 0, 1, 2
+
+    def radix_workspace_bytes(self, n):
+        return int(self.lib.sc_radix_workspace_bytes(int(n)))
+
+    def radix_map_key(self, key_type, descending, bits):
+        """the order-preserving map of 32 key bits to the unsigned value the sort compares"""
+        return int(self.lib.sc_radix_map_key(int(key_type), int(bool(descending)), int(bits) & 0xffffffff))
+
+    def radix_sort_records_device(self, n, key_type, descending, begin_bit, end_bit, d_keys, key_stride_bytes, d_out_a, d_in_a, record_bytes_a,
+                                  d_out_b, d_in_b, record_bytes_b, d_perm, d_keys_out, d_workspace, stream=0):
+        _check(self.lib.sc_radix_sort_records_device(int(n), int(key_type), int(bool(descending)), int(begin_bit), int(end_bit), d_keys,
+                                                     int(key_stride_bytes), d_out_a, d_in_a, int(record_bytes_a), d_out_b, d_in_b, int(record_bytes_b),
+                                                     d_perm, d_keys_out, d_workspace, stream), "sc_radix_sort_records_device")
+
+    def radix_sort_records(self, keys, *arrays, key_type=None, descending=False, begin_bit=0, end_bit=32):
+        """Stable sort of one or two host record arrays by bits [begin_bit, end_bit) of 32-bit keys: int32, uint32 or float32 (taken
+        from keys.dtype when key_type is None; floats in the total order -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN).
+        Returns (the permuted arrays as a list, perm = source index of every output row, keys_out = the keys in output order)."""
+        keys = np.ascontiguousarray(keys)
+        if key_type is None:
+            types = {np.dtype(np.int32): self.KEY_INT32, np.dtype(np.uint32): self.KEY_UINT32, np.dtype(np.float32): self.KEY_FLOAT32}
+            if keys.dtype not in types:
+                raise PathTracerError("radix_sort_records: keys are int32, uint32 or float32, got %s" % keys.dtype)
+            key_type = types[keys.dtype]
+        if keys.dtype.itemsize != 4 or keys.ndim != 1:
+            raise PathTracerError("radix_sort_records: keys are one 32-bit word per row, got %s %r" % (keys.dtype, keys.shape))
+        if not 1 <= len(arrays) <= 2:
+            raise PathTracerError("radix_sort_records: one or two record arrays, got %d" % len(arrays))
+        n = len(keys)
+        recs = [self._records(a, n) for a in arrays]
+        outs = [np.empty_like(a) for a, _ in recs]
+        perm, keys_out = np.empty(n, np.int32), np.empty_like(keys)
+        b = (_ptr(outs[1]), _ptr(recs[1][0]), recs[1][1]) if len(recs) == 2 else (None, None, 0)
+        _check(self.lib.sc_radix_sort_records(n, int(key_type), int(bool(descending)), int(begin_bit), int(end_bit), _ptr(keys), _ptr(outs[0]),
+                                              _ptr(recs[0][0]), recs[0][1], b[0], b[1], b[2], _ptr(perm), _ptr(keys_out)), "sc_radix_sort_records")
+        return outs, perm, keys_out
 
     def last_gpu_ms(self):
         return float(self.lib.sc_last_gpu_ms())

@@ -521,6 +521,282 @@ int records_host(const char *what, int n, int nkeys, int descending, bool flags,
     return PTX_OK;
 }
 
+
+// ---- records by full 32-bit keys: an LSD radix sort on top of the counting pass (sc_radix_sort_records_device) ------------------------
+// thrust::sort_by_key sorts by any int; the counting sort above takes 256 distinct keys.  This is the general case: the caller's 32 key
+// bits are mapped to an unsigned u whose order is the key type's (rx_map), and the field (u >> begin_bit) & (2^(end_bit - begin_bit) - 1)
+// is sorted 8 bits at a time, least significant digit first, every pass stable.  What the passes move is (u, source index) pairs, held
+// structure-of-arrays in the workspace; the wide records move ONCE, in a gather behind the last pass.
+//   pass  : count -> scan -> move over the same SR_TILE tiles and the same key-major table[digit][tile] as the counting sort, the scan
+//           being the library's own k_onepass.  The first pass reads the caller's strided keys and maps them (the source index is the
+//           position); later passes read one pair buffer and write the other.  The last pass writes the indices alone.
+//   rank  : inside a wave, by a constant eight ballots -- one per digit bit, ANDed (or AND-NOTed) into the lane's peer mask -- and
+//           mbcnt below the lane, where k_records_move takes one trip per distinct key (up to 64 with random digits).  Groups and digits
+//           are then combined through the same [32 groups][256] uint16 LDS counts.
+//   move  : every pair is put at its sorted position of the tile in LDS and the tile is stored in that order: a digit's run of a tile is
+//           one contiguous store stream.  The destination of position p is recomputed from its digit (table start + p - the digit's
+//           start in the tile), so no destination array is kept.
+//   gather: out[p] = in[index[p]] for one or two arrays, a record's dwords (or quads) on consecutive lanes as sr_copy has them; the
+//           same kernel writes d_perm and d_keys_out (the caller's original bits, fetched through the index).
+// As above no atomic decides a rank (they add up the count kernel's LDS histogram and nothing else), so a destination is a function of
+// the keys alone.  Whatever comes out of the workspace and becomes an address -- a table entry, a source index -- is clamped below n
+// first: a workspace that something else scribbled on between the kernels gives a wrong order, never an address outside the arrays.
+constexpr int RX_BITS = 8, RX_DIGITS = 1 << RX_BITS;
+static_assert(RX_DIGITS == SR_MAXKEYS, "the radix passes share the counting sort's table and LDS count layout");
+
+__host__ __device__ inline unsigned rx_map(int key_type, int descending, unsigned bits) {
+    unsigned u = bits;
+    if (key_type == SC_KEY_INT32) u = bits ^ 0x80000000u;
+    else if (key_type == SC_KEY_FLOAT32) u = (bits >> 31) ? ~bits : bits | 0x80000000u;
+    return descending ? ~u : u;
+}
+
+struct RxKeys {
+    const char *keys;                                          // the caller's: first pass and gather
+    int stride, key_type, descending;
+    const unsigned *u_in, *i_in;                               // later passes: the pair buffer to read (u_in == nullptr: first pass)
+    int shift, bits;                                           // this pass's digit = (u >> shift) & ((1 << bits) - 1)
+};
+
+__device__ __forceinline__ unsigned rx_u(const RxKeys &K, long long i) {
+    if (K.u_in) return K.u_in[i];
+    return rx_map(K.key_type, K.descending, *reinterpret_cast<const unsigned *>(K.keys + i * K.stride));
+}
+__device__ __forceinline__ int rx_digit(const RxKeys &K, unsigned u) { return (int)((u >> K.shift) & ((1u << K.bits) - 1u)); }
+
+__global__ __launch_bounds__(SR_THREADS) void k_radix_count(int n, int tiles, RxKeys K, int *__restrict__ table) {
+    __shared__ int s_hist[SR_WAVES][RX_DIGITS];                // a row per wave; the atomics only count
+    const int tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x, nd = 1 << K.bits;
+    const long long tbase = (long long)tile * SR_TILE;
+    for (int k = tid; k < SR_WAVES * RX_DIGITS; k += SR_THREADS) (&s_hist[0][0])[k] = 0;
+    unsigned u[SR_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        const long long i = tbase + r * SR_THREADS + tid;
+        u[r] = i < n ? rx_u(K, i) : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++)
+        if (tbase + r * SR_THREADS + tid < n) atomicAdd(&s_hist[wave][rx_digit(K, u[r])], 1);
+    __syncthreads();
+    for (int k = tid; k < nd; k += SR_THREADS) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < SR_WAVES; w++) c += s_hist[w][k];
+        table[(size_t)k * tiles + tile] = c;
+    }
+}
+
+__global__ __launch_bounds__(SR_THREADS) void k_radix_move(int n, int tiles, RxKeys K, const int *__restrict__ table,
+                                                          unsigned *__restrict__ u_out, unsigned *__restrict__ i_out) {
+    __shared__ alignas(8) uint16_t s_cnt[SR_RW * RX_DIGITS];   // [group][digit] counts (<= 64), then per digit their exclusive prefixes (< 2048)
+    __shared__ int s_kstart[RX_DIGITS], s_gbase[RX_DIGITS];    // where a digit's run starts: in the tile's sorted order, and in the output
+    __shared__ unsigned s_u[SR_TILE], s_i[SR_TILE];            // the tile's pairs in sorted order
+    static_assert(sizeof(s_cnt) % 8 == 0 && __alignof__(s_cnt) >= 8, "s_cnt is zeroed in words: aligned and a whole number of them");
+    const int tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x, nd = 1 << K.bits;
+    const long long tbase = (long long)tile * SR_TILE;
+    const int cnt = (int)min((long long)SR_TILE, n - tbase);
+
+    for (int q = tid; q < SR_RW * nd / 2; q += SR_THREADS) reinterpret_cast<uint32_t *>(s_cnt)[q] = 0u;      // (SR_RW is even)
+    unsigned u[SR_ROUNDS], src[SR_ROUNDS];
+    int rk[SR_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        const int slot = r * SR_THREADS + tid;
+        u[r] = slot < cnt ? rx_u(K, tbase + slot) : 0u;
+        src[r] = slot < cnt ? (K.i_in ? K.i_in[tbase + slot] : (unsigned)(tbase + slot)) : 0u;
+    }
+    // (fence: a table entry becomes the base of store addresses)
+    for (int k = tid; k < nd; k += SR_THREADS) s_gbase[k] = (int)min((unsigned)table[(size_t)k * tiles + tile], (unsigned)n);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++) {
+        const bool valid = r * SR_THREADS + tid < cnt;
+        const int d = rx_digit(K, u[r]);
+        unsigned long long peers = __ballot(valid);            // the lanes with this lane's digit: one ballot per digit bit
+#pragma unroll
+        for (int b = 0; b < RX_BITS; b++) {
+            const bool bit = (d >> b) & 1;
+            const unsigned long long set = __ballot(valid && bit);
+            peers &= bit ? set : ~set;
+        }
+        rk[r] = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
+        if (valid && rk[r] == 0) s_cnt[(r * SR_WAVES + wave) * nd + d] = (uint16_t)__popcll(peers);
+    }
+    __syncthreads();
+    for (int k = tid; k < nd; k += SR_THREADS) {               // per digit: exclusive prefix over the groups, in tile order
+        int run = 0;
+        for (int g = 0; g < SR_RW; g++) {
+            const int c = s_cnt[g * nd + k];
+            s_cnt[g * nd + k] = (uint16_t)run;
+            run += c;
+        }
+        s_kstart[k] = run;
+    }
+    __syncthreads();
+    if (wave == 0) {                                           // exclusive prefix over the digits' totals, four digits per lane
+        const int lane = tid;
+        int t[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { t[j] = 4 * lane + j < nd ? s_kstart[4 * lane + j] : 0; sum += t[j]; }
+        int run = wave_inclusive_scan(sum, lane) - sum;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { if (4 * lane + j < nd) s_kstart[4 * lane + j] = run; run += t[j]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SR_ROUNDS; r++)
+        if (r * SR_THREADS + tid < cnt) {
+            const int d = rx_digit(K, u[r]);
+            const int p = s_kstart[d] + s_cnt[(r * SR_WAVES + wave) * nd + d] + rk[r];
+            s_u[p] = u[r];
+            s_i[p] = src[r];
+        }
+    __syncthreads();
+    for (int p = tid; p < cnt; p += SR_THREADS) {
+        const unsigned v = s_u[p];
+        const int d = rx_digit(K, v);
+        // (fence: table start + place in the run, below n whatever the table held)
+        const unsigned dst = min((unsigned)s_gbase[d] + (unsigned)(p - s_kstart[d]), (unsigned)(n - 1));
+        if (u_out) u_out[dst] = v;
+        i_out[dst] = s_i[p];
+    }
+}
+
+template <typename V>
+__device__ __forceinline__ void rx_gather_copy(const SrArray &A, long long tbase, int cnt, const int *s_idx, int tid) {
+    const V *__restrict__ src = reinterpret_cast<const V *>(A.in);
+    V *__restrict__ dst = reinterpret_cast<V *>(A.out) + tbase * A.units;
+    const unsigned units = (unsigned)A.units, total = (unsigned)cnt * units;
+#pragma unroll 4
+    for (unsigned idx = tid; idx < total; idx += SR_THREADS) {
+        const unsigned p = units == 1 ? idx : __umulhi(idx, A.magic), w = idx - p * units;
+        dst[idx] = src[(long long)s_idx[p] * units + w];
+    }
+}
+
+// out[p] = in[index[p]] (index == nullptr: the identity, a copy); d_perm[p] = index[p]; d_keys_out[p] = the caller's key bits of that row
+__global__ __launch_bounds__(SR_THREADS) void k_radix_gather(int n, RxKeys K, const unsigned *__restrict__ index, SrArray A, SrArray B,
+                                                            int *__restrict__ perm, unsigned *__restrict__ keys_out) {
+    __shared__ int s_idx[SR_TILE];
+    const int tid = threadIdx.x;
+    const long long tbase = (long long)blockIdx.x * SR_TILE;
+    const int cnt = (int)min((long long)SR_TILE, n - tbase);
+    for (int p = tid; p < cnt; p += SR_THREADS) {
+        // (fence: a source index becomes a load address)
+        const int s = index ? (int)min(index[tbase + p], (unsigned)(n - 1)) : (int)(tbase + p);
+        s_idx[p] = s;
+        if (perm) perm[tbase + p] = s;
+        if (keys_out) keys_out[tbase + p] = *reinterpret_cast<const unsigned *>(K.keys + (long long)s * K.stride);
+    }
+    __syncthreads();
+    if (A.vec16) rx_gather_copy<v4i>(A, tbase, cnt, s_idx, tid); else rx_gather_copy<int>(A, tbase, cnt, s_idx, tid);
+    if (B.in) { if (B.vec16) rx_gather_copy<v4i>(B, tbase, cnt, s_idx, tid); else rx_gather_copy<int>(B, tbase, cnt, s_idx, tid); }
+}
+
+// workspace: [the scan's own, for 256 * tiles ints][the table, 256 * tiles ints][u0][i0][u1][i1], n words each, every part 8-byte aligned
+struct RxLayout { unsigned long long table, pair[4], total; };
+RxLayout rx_layout(int n) {
+    RxLayout L;
+    const unsigned long long m = (unsigned long long)RX_DIGITS * sr_tiles(n), words = ((unsigned long long)n * 4 + 7) & ~7ull;
+    L.table = (sc_scan_workspace_bytes((int)m) + 7) & ~7ull;
+    L.pair[0] = L.table + ((m * 4 + 7) & ~7ull);
+    for (int k = 1; k < 4; k++) L.pair[k] = L.pair[k - 1] + words;
+    L.total = L.pair[3] + words;
+    return L;
+}
+
+int rx_check(const char *what, int n, int key_type, int begin_bit, int end_bit, int stride, int bytes_a, int bytes_b, bool has_b) {
+    if (key_type != SC_KEY_INT32 && key_type != SC_KEY_UINT32 && key_type != SC_KEY_FLOAT32) return sr_invalid(what, "key_type", key_type, "is none of SC_KEY_INT32, SC_KEY_UINT32, SC_KEY_FLOAT32");
+    if (begin_bit < 0 || begin_bit > 32) return sr_invalid(what, "begin_bit", begin_bit, "is outside 0..32");
+    if (end_bit < 0 || end_bit > 32) return sr_invalid(what, "end_bit", end_bit, "is outside 0..32");
+    if (begin_bit > end_bit) return sr_invalid(what, "begin_bit", begin_bit, "is above end_bit");
+    return sr_check_sizes(what, n, RX_DIGITS, stride, bytes_a, bytes_b, has_b);
+}
+
+int radix_device(const char *what, int n, int key_type, int descending, int begin_bit, int end_bit, const void *d_keys, int stride,
+                 void *d_out_a, const void *d_in_a, int bytes_a, void *d_out_b, const void *d_in_b, int bytes_b,
+                 int *d_perm, void *d_keys_out, void *d_ws, hipStream_t st) {
+    const bool has_b = d_out_b || d_in_b || bytes_b;
+    if (int rc = rx_check(what, n, key_type, begin_bit, end_bit, stride, bytes_a, bytes_b, has_b)) return rc;
+    if (n > 0) {
+        if (!d_keys || !d_out_a || !d_in_a || !d_ws || (has_b && (!d_out_b || !d_in_b))) return sr_invalid(what, "a device pointer", 0, "is null");
+        if (((uintptr_t)d_ws) & 7) return sr_invalid(what, "d_workspace", (long long)(uintptr_t)d_ws, "must be 8-byte aligned");
+        if ((((uintptr_t)d_keys | (uintptr_t)d_out_a | (uintptr_t)d_in_a | (uintptr_t)d_out_b | (uintptr_t)d_in_b | (uintptr_t)d_perm | (uintptr_t)d_keys_out) & 3))
+            return sr_invalid(what, "a device pointer", 0, "is not 4-byte aligned");
+        if (d_out_a == d_in_a || d_out_a == d_keys || (has_b && (d_out_b == d_in_b || d_out_b == d_in_a || d_out_a == d_in_b || d_out_a == d_out_b || d_out_b == d_keys)))
+            return sr_invalid(what, "d_out", (long long)(uintptr_t)d_out_a, "is an input or the other output: there is no in-place form");
+        if (d_keys_out && (d_keys_out == d_keys || d_keys_out == d_in_a || d_keys_out == d_in_b || d_keys_out == d_out_a || d_keys_out == d_out_b || d_keys_out == (void *)d_perm))
+            return sr_invalid(what, "d_keys_out", (long long)(uintptr_t)d_keys_out, "is an input or another output: there is no in-place form");
+        if (d_perm && ((void *)d_perm == d_keys || (void *)d_perm == d_in_a || (void *)d_perm == d_in_b || (void *)d_perm == d_out_a || (void *)d_perm == d_out_b))
+            return sr_invalid(what, "d_perm", (long long)(uintptr_t)d_perm, "is an input or another output");
+    }
+    if (int rc = sr_no_device(what)) return rc;
+    if (n == 0) return PTX_OK;
+    const int tiles = sr_tiles(n);
+    const RxLayout L = rx_layout(n);
+    int *table = (int *)((char *)d_ws + L.table);
+    unsigned *buf[4];
+    for (int k = 0; k < 4; k++) buf[k] = (unsigned *)((char *)d_ws + L.pair[k]);
+    RxKeys K;
+    K.keys = (const char *)d_keys; K.stride = stride; K.key_type = key_type; K.descending = descending != 0;
+    K.u_in = nullptr; K.i_in = nullptr; K.shift = 0; K.bits = 0;
+    const int passes = (end_bit - begin_bit + RX_BITS - 1) / RX_BITS;
+    for (int p = 0; p < passes; p++) {
+        K.shift = begin_bit + RX_BITS * p;
+        K.bits = std::min(RX_BITS, end_bit - K.shift);
+        const bool last = p + 1 == passes;
+        unsigned *u_out = last ? nullptr : buf[2 * (p & 1)], *i_out = buf[2 * (p & 1) + 1];
+        hipLaunchKernelGGL(k_radix_count, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, table);
+        SC_CHECK(hipGetLastError());
+        if (int rc = onepass_device((1 << K.bits) * tiles, table, table, nullptr, d_ws, st, false)) return rc;
+        hipLaunchKernelGGL(k_radix_move, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, (const int *)table, u_out, i_out);
+        SC_CHECK(hipGetLastError());
+        K.u_in = u_out; K.i_in = i_out;
+    }
+    hipLaunchKernelGGL(k_radix_gather, dim3(tiles), dim3(SR_THREADS), 0, st, n, K, (const unsigned *)K.i_in, sr_array(d_out_a, d_in_a, bytes_a),
+                       sr_array(has_b ? d_out_b : nullptr, has_b ? d_in_b : nullptr, has_b ? bytes_b : 4), d_perm, (unsigned *)d_keys_out);
+    SC_CHECK(hipGetLastError());
+    return PTX_OK;
+}
+
+int radix_host(const char *what, int n, int key_type, int descending, int begin_bit, int end_bit, const void *keys,
+               void *out_a, const void *in_a, int bytes_a, void *out_b, const void *in_b, int bytes_b, int *perm, void *keys_out) {
+    const bool has_b = out_b || in_b || bytes_b;
+    if (int rc = rx_check(what, n, key_type, begin_bit, end_bit, 4, bytes_a, bytes_b, has_b)) return rc;
+    if (n > 0 && (!keys || !out_a || !in_a || (has_b && (!out_b || !in_b)))) return sr_invalid(what, "a host pointer", 0, "is null");
+    if (int rc = sr_no_device(what)) return rc;
+    if (n == 0) return PTX_OK;
+    SrDeviceBuffers dev;
+    void *d_keys = nullptr, *d_in_a = nullptr, *d_out_a = nullptr, *d_in_b = nullptr, *d_out_b = nullptr, *d_perm = nullptr, *d_kout = nullptr, *d_ws = nullptr;
+    const size_t na = (size_t)n * bytes_a, nb = has_b ? (size_t)n * bytes_b : 0, nk = sizeof(int) * (size_t)n;
+    SC_CHECK(dev.get(&d_keys, nk));
+    SC_CHECK(dev.get(&d_in_a, na)); SC_CHECK(dev.get(&d_out_a, na));
+    if (has_b) { SC_CHECK(dev.get(&d_in_b, nb)); SC_CHECK(dev.get(&d_out_b, nb)); }
+    if (perm) SC_CHECK(dev.get(&d_perm, nk));
+    if (keys_out) SC_CHECK(dev.get(&d_kout, nk));
+    SC_CHECK(dev.get(&d_ws, sc_radix_workspace_bytes(n)));
+    SC_CHECK(hipMemcpy(d_keys, keys, nk, hipMemcpyHostToDevice));
+    SC_CHECK(hipMemcpy(d_in_a, in_a, na, hipMemcpyHostToDevice));
+    if (has_b) SC_CHECK(hipMemcpy(d_in_b, in_b, nb, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1;
+    SC_CHECK(hipEventCreate(&e0)); SC_CHECK(hipEventCreate(&e1));
+    SC_CHECK(hipEventRecord(e0, 0));
+    const int rc = radix_device(what, n, key_type, descending, begin_bit, end_bit, d_keys, 4, d_out_a, d_in_a, bytes_a, d_out_b, d_in_b, bytes_b,
+                                (int *)d_perm, d_kout, d_ws, 0);
+    SC_CHECK(hipEventRecord(e1, 0));
+    SC_CHECK(hipEventSynchronize(e1));
+    SC_CHECK(hipEventElapsedTime(&g_gpu_ms, e0, e1));
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (rc != PTX_OK) return rc;
+    SC_CHECK(hipMemcpy(out_a, d_out_a, na, hipMemcpyDeviceToHost));
+    if (has_b) SC_CHECK(hipMemcpy(out_b, d_out_b, nb, hipMemcpyDeviceToHost));
+    if (perm) SC_CHECK(hipMemcpy(perm, d_perm, nk, hipMemcpyDeviceToHost));
+    if (keys_out) SC_CHECK(hipMemcpy(keys_out, d_kout, nk, hipMemcpyDeviceToHost));
+    return PTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -689,6 +965,25 @@ int sc_partition_records(int n, int record_bytes, void *out, const void *in, con
 int sc_compact_records(int n, int record_bytes, void *out, const void *in, const int *flags, int *count) {
     if (!count) { ptx_internal_set_error("sc_compact_records: count is null"); return PTX_ERR_INVALID; }
     return records_host("sc_compact_records", n, 2, 0, true, true, flags, out, in, record_bytes, nullptr, nullptr, 0, nullptr, count, 1);
+}
+
+// ---- records by full 32-bit keys (kernels and limits: k_radix_count / k_radix_move / k_radix_gather above) -------------------------
+unsigned long long sc_radix_workspace_bytes(int n) { return n < 0 ? 0 : rx_layout(n).total; }
+
+unsigned int sc_radix_map_key(int key_type, int descending, unsigned int bits) { return rx_map(key_type, descending != 0, bits); }
+
+// thrust::sort_by_key with keys of any value: int, unsigned or float, a bit range of them, ascending or descending
+int sc_radix_sort_records_device(int n, int key_type, int descending, int begin_bit, int end_bit, const void *d_keys, int key_stride_bytes,
+                                 void *d_out_a, const void *d_in_a, int record_bytes_a, void *d_out_b, const void *d_in_b, int record_bytes_b,
+                                 int *d_perm, void *d_keys_out, void *d_workspace, void *stream) {
+    return radix_device("sc_radix_sort_records_device", n, key_type, descending, begin_bit, end_bit, d_keys, key_stride_bytes, d_out_a, d_in_a, record_bytes_a,
+                        d_out_b, d_in_b, record_bytes_b, d_perm, d_keys_out, d_workspace, (hipStream_t)stream);
+}
+
+int sc_radix_sort_records(int n, int key_type, int descending, int begin_bit, int end_bit, const void *keys, void *out_a, const void *in_a, int record_bytes_a,
+                          void *out_b, const void *in_b, int record_bytes_b, int *perm, void *keys_out) {
+    return radix_host("sc_radix_sort_records", n, key_type, descending, begin_bit, end_bit, keys, out_a, in_a, record_bytes_a, out_b, in_b, record_bytes_b,
+                      perm, keys_out);
 }
 
 float sc_last_gpu_ms(void) { return g_gpu_ms; }

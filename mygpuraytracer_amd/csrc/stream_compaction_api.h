@@ -19,6 +19,8 @@
 //     Records::sortByKey(num_paths, nmaterials, 1, &dev_isects->materialId, sizeof(ShadeableIntersection), out_isects, dev_isects,
 //                        out_paths, dev_paths);                                           // was thrust::sort_by_key(.., sortByMaterial())
 //     int live = Records::stablePartition(num_paths, out_paths, dev_paths, &dev_paths->remainingBounces, sizeof(PathSegment));
+// and, for keys of any value (int, unsigned or float; pixel index, Morton code, hit distance), thrust::sort_by_key proper:
+//     Records::radixSortByKey(num_paths, 0, 0, 32, &dev_paths->pixelIndex, sizeof(PathSegment), out_paths, dev_paths);
 // It allocates its workspace with hipMalloc, so it exists only in translation units compiled for HIP (hipcc, or
 // -D__HIP_PLATFORM_AMD__ with the HIP headers on the include path).
 // Not carried over: startGpuTimer/endGpuTimer and their CPU twins (the library times its operations itself).
@@ -156,6 +158,32 @@ inline void sortByKey(int n, int nkeys, int descending, const int *firstKey, int
     void *ws = mi355x_borrow(n, nkeys, &count);
     Common::mi355x_check(sc_sort_records_by_key_device(n, nkeys, descending, firstKey, keyStride, outA, inA, (int)sizeof(T), outB, inB, (int)sizeof(U),
                                                        nullptr, nullptr, ws, stream), "Records::sortByKey");
+}
+
+// thrust::sort_by_key for keys of any value: K = int, unsigned or float, bits [beginBit, endBit) of the key's order-preserving map
+// (include/mi355x_stream_compaction.h), ascending or descending, stable.  perm (source index per output row) and keysOut (the keys in
+// output order) are optional device arrays of n.
+template <typename K> struct mi355x_key_type;
+template <> struct mi355x_key_type<int> { static constexpr int value = SC_KEY_INT32; };
+template <> struct mi355x_key_type<unsigned> { static constexpr int value = SC_KEY_UINT32; };
+template <> struct mi355x_key_type<float> { static constexpr int value = SC_KEY_FLOAT32; };
+
+template <typename K, typename T>
+inline void radixSortByKey(int n, int descending, int beginBit, int endBit, const K *firstKey, int keyStride, T *outA, const T *inA,
+                           int *perm = nullptr, K *keysOut = nullptr, void *stream = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    void *ws = mi355x_workspace(sc_radix_workspace_bytes(n));
+    Common::mi355x_check(sc_radix_sort_records_device(n, mi355x_key_type<K>::value, descending, beginBit, endBit, firstKey, keyStride, outA, inA, (int)sizeof(T),
+                                                      nullptr, nullptr, 0, perm, keysOut, ws, stream), "Records::radixSortByKey");
+}
+template <typename K, typename T, typename U>
+inline void radixSortByKey(int n, int descending, int beginBit, int endBit, const K *firstKey, int keyStride, T *outA, const T *inA, U *outB, const U *inB,
+                           int *perm = nullptr, K *keysOut = nullptr, void *stream = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    static_assert(std::is_trivially_copyable<U>::value && sizeof(U) % 4 == 0, "records are trivially copyable, a multiple of 4 bytes");
+    void *ws = mi355x_workspace(sc_radix_workspace_bytes(n));
+    Common::mi355x_check(sc_radix_sort_records_device(n, mi355x_key_type<K>::value, descending, beginBit, endBit, firstKey, keyStride, outA, inA, (int)sizeof(T),
+                                                      outB, inB, (int)sizeof(U), perm, keysOut, ws, stream), "Records::radixSortByKey");
 }
 
 template <typename T>
