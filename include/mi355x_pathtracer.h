@@ -506,6 +506,14 @@ int ptx_debug_light_bits(int nmaterials, const ptx_material *materials, int ngeo
  * Returns 0, -1 on a bad argument.  The environment variable PTX_DEBUG_NO_OBJCULL, read by ptx_create, leaves every mesh without an entry:
  * candidates then come from the world boxes alone (A/B timing, tests of both paths; same results either way). */
 int ptx_debug_cull_objboxes(int ngeoms, const ptx_geom *geoms, int no_bvh, float margin, float *table16, uint32_t *bits_out);
+/* CPU-only: the tangent frames of the cubes' faces, as ptx_create tabulates them for the diffuse sampler.  A stored hit on a cube of a
+ * material that only cubes have names one of the cube's six face normals by a code; the two vectors the sampler builds from a normal
+ * (perp1, perp2 of calculateRandomDirectionInHemisphere) depend on that normal alone, so the bounce reads them from this table instead of
+ * computing them per ray.  geoms as ptx_create takes them; out36_per_geom = 36 floats per geom: side (axis * 2 + (sign > 0)) at side * 6 =
+ * perp1 xyz, perp2 xyz, computed from that side's tabulated normal with the sampler's own arithmetic (same bits); zeros for a geom that is
+ * not a cube.  Returns 0, -1 on a bad argument.  The environment variable PTX_DEBUG_NO_TANGENTS, read by ptx_create, makes every ray
+ * compute its frame (A/B timing, tests of both paths; same results either way). */
+int ptx_debug_cube_tangents(int ngeoms, const ptx_geom *geoms, float *out36_per_geom);
 /* Host-only (reads what ptx_create kept on the host, launches nothing): how mesh geom `geom` of a live tracer is searched.
  * out8 = { root of its BVH (-1: none, the plain loop over its faces), depth of the binary tree, root of its four-wide nodes (-1: none),
  * stack entries their walk needs, stack entries per lane the tracer's launches provide (bvh_stack), 1 if frames take the split mesh search

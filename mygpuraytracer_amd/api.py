@@ -364,6 +364,24 @@ def debug_cull_objboxes(geom_ints, geom_mats, faces, margin=1.0, no_bvh=0):
     return out, int(bits[0])
 
 
+def debug_cube_tangents(geom_ints, geom_mats):
+    """CPU only: the tangent frames of the cubes' tabulated face normals (ptx_debug_cube_tangents) for geoms given as Scene.dump() gives
+    them: geom_ints (n, 3) = type, material, faces; geom_mats (n, 48) = transform, inverseTransform, invTranspose.  Returns an (n, 6, 6)
+    float32 array: per geom and side (axis * 2 + (sign > 0)) perp1 xyz, perp2 xyz; zeros for a geom that is not a cube."""
+    L = load_library()
+    gi = np.ascontiguousarray(geom_ints, np.int32).reshape(-1, 3)
+    gm = np.ascontiguousarray(geom_mats, np.float32).reshape(-1, 48)
+    geoms = (Geom * max(len(gi), 1))()
+    for g in range(len(gi)):
+        geoms[g].type, geoms[g].materialid = int(gi[g][0]), int(gi[g][1])
+        for name, k in (("transform", 0), ("inverseTransform", 16), ("invTranspose", 32)):
+            getattr(geoms[g], name)[:] = gm[g][k:k + 16].tolist()
+    out = np.zeros((len(gi), 6, 6), np.float32)
+    if L.ptx_debug_cube_tangents(len(gi), geoms, _ptr(out)) < 0:
+        raise PathTracerError("ptx_debug_cube_tangents: bad argument")
+    return out
+
+
 WALK_NAMES = ("loop", "skip", "ordered", "wide", "wide_refill")      # PTX_WALK_* of include/mi355x_pathtracer.h
 
 
@@ -536,6 +554,8 @@ def load_library():
         L.ptx_debug_light_bits.restype, L.ptx_debug_light_bits.argtypes = i, [i, vp, i, vp, vp]
     if hasattr(L, "ptx_debug_cull_objboxes"):
         L.ptx_debug_cull_objboxes.restype, L.ptx_debug_cull_objboxes.argtypes = i, [i, C.POINTER(Geom), i, C.c_float, vp, vp]
+    if hasattr(L, "ptx_debug_cube_tangents"):
+        L.ptx_debug_cube_tangents.restype, L.ptx_debug_cube_tangents.argtypes = i, [i, C.POINTER(Geom), vp]
     if hasattr(L, "ptx_debug_mesh_plan"):
         L.ptx_debug_mesh_plan.restype, L.ptx_debug_mesh_plan.argtypes = i, [vp, i, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)

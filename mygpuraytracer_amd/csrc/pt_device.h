@@ -380,7 +380,12 @@ struct DScene {
                                         // short kernels of a small tile, which are chains of such round trips); NULL: table by table
     const float *__restrict__ objcull;  // OBJCULL_WORDS per geom (zeros where objcull_bits has no bit): see objBoxReach.  Read through the scalar
                                         // cache like `aabb`, never staged in LDS
+    const float *__restrict__ ctan;     // CTAN_WORDS per geom: the tangent frames (tangentFrame: perp1 xyz, perp2 xyz) of a cube's six tabulated
+                                        // normals, side by side as in cnorm; zeros for other geoms.  Read per lane from global memory by the
+                                        // bounces that read coded records (k_bounce's fetch), never staged in LDS; NULL (PTX_DEBUG_NO_TANGENTS):
+                                        // every lane computes its frame
 };
+constexpr int CTAN_WORDS = 36;
 
 // Words of dynamic LDS the staged scene tables take (tri9 + faces + fnorm = 27 per staged triangle, 11 per material, gtab 40 +
 // cnorm 18 per geom), rounded to 16 bytes.  ONE definition for the kernels and for the host that sizes their launches: what
@@ -1511,23 +1516,49 @@ PT_DEV float meshIntersectionTest(const DScene &sc, const DGeom &g, Ray r, vec3 
 #define PT_TWO_PI 6.2831853071795864769252867665590057683943f            // src/utilities.h:13
 #define PT_SQRT_OF_ONE_THIRD 0.5773502691896257645091487805019574556476f // src/utilities.h:14
 
-// calculateRandomDirectionInHemisphere, src/interactions.h:11-43
-PT_DEV vec3 randomDirectionInHemisphere(vec3 normal, Rng &rng) {
-    float up = pt_sqrt(rng.uniform(0.f, 1.f));
-    float over = pt_sqrt(1 - up * up);
-    float around = rng.uniform(0.f, 1.f) * PT_TWO_PI;
+// The tangent frame calculateRandomDirectionInHemisphere builds from a normal (src/interactions.h:24-41): it depends on the normal alone.
+// ONE definition for the sampler below and for the host, which tabulates it per cube face at upload (DScene::ctan, pt_scene.hip).
+PT_HD void tangentFrame(vec3 normal, vec3 &perp1, vec3 &perp2) {
     vec3 notNormal;
     if (__builtin_fabsf(normal.x) < PT_SQRT_OF_ONE_THIRD) notNormal = V3(1, 0, 0);
     else if (__builtin_fabsf(normal.y) < PT_SQRT_OF_ONE_THIRD) notNormal = V3(0, 1, 0);
     else notNormal = V3(0, 0, 1);
-    vec3 perp1 = normalize(cross(normal, notNormal));
-    vec3 perp2 = normalize(cross(normal, perp1));
+    perp1 = normalize(cross(normal, notNormal));
+    perp2 = normalize(cross(normal, perp1));
+}
+
+// A hit's tangent frame when it is known before the sampler runs: has != 0 on the lanes whose record named a tabulated cube face
+// (k_bounce's fetch); every other lane computes its frame.
+struct TanFrame {
+    vec3 perp1, perp2;
+    int32_t has;
+};
+
+// calculateRandomDirectionInHemisphere, src/interactions.h:11-43.  TAB (k_bounce's readers of coded records): lanes with tf.has bring
+// their frame and the computation sits behind a branch, so a wave whose lanes all bring one skips it as a whole; !TAB: every lane computes.
+template <bool TAB>
+PT_DEV vec3 randomDirectionInHemisphereT(vec3 normal, Rng &rng, const TanFrame &tf) {
+    float up = pt_sqrt(rng.uniform(0.f, 1.f));
+    float over = pt_sqrt(1 - up * up);
+    float around = rng.uniform(0.f, 1.f) * PT_TWO_PI;
+    vec3 perp1 = tf.perp1, perp2 = tf.perp2;
+    if (!TAB) tangentFrame(normal, perp1, perp2);      // (where the reference has it)
     float sn, cs;
     sincos_pt(around, &sn, &cs);
+    if (TAB) {      // the frame behind the sin/cos, which does not depend on it: a tabulated one is first read here, as late as the sampler allows
+        int32_t has = tf.has;
+        asm volatile("" : "+v"(has));      // (opaque: no second copy of the sin/cos for the path on which it is a constant)
+        if (!has) tangentFrame(normal, perp1, perp2);
+    }
     vec3 a = scale(normal, up);
     vec3 b = scale(perp1, cs * over);
     vec3 c = scale(perp2, sn * over);
     return add(add(a, b), c);
+}
+PT_DEV vec3 randomDirectionInHemisphere(vec3 normal, Rng &rng) {
+    TanFrame tf;
+    tf.perp1 = tf.perp2 = V3(0.f, 0.f, 0.f); tf.has = 0;
+    return randomDirectionInHemisphereT<false>(normal, rng, tf);
 }
 
 // calculateJitteredDirectionHemisphere, src/interactions.h:46-85 -- DEAD CODE in the reference (JITTERED_SAMPLING 0; its call site does
@@ -1581,8 +1612,9 @@ struct PathState {
 // TEX = false: the scene has no texture at all (every DTex::ch is 0), so the texel branches and the loads that decide them are
 // left out.  The two diffuse cases -- an OBJ geom's and everything else's -- share one copy of the hemisphere sampler: a wave
 // that holds both kinds of hit runs it once, and the kernel holds its binary64 sin/cos once.
-template <bool TEX = true>
-PT_DEV bool scatterRay(const DScene &sc, PathState &ps, vec3 intersect, const Hit &hit, const DMaterial &m, Rng &rng) {
+// tf: the hit's tangent frame where the caller has it (TanFrame; TAB: it may): only the diffuse sampler reads it.
+template <bool TEX, bool TAB>
+PT_DEV bool scatterRayT(const DScene &sc, PathState &ps, vec3 intersect, const Hit &hit, const DMaterial &m, Rng &rng, const TanFrame &tf) {
     vec3 n = hit.n;
     if (m.hasReflective > 0) {
         vec3 reflectDir = reflect(ps.d, n);
@@ -1657,11 +1689,18 @@ PT_DEV bool scatterRay(const DScene &sc, PathState &ps, vec3 intersect, const Hi
             }
         }
         ps.color = mul(ps.color, diffuseColor);
-        vec3 nd = randomDirectionInHemisphere(n, rng);
+        vec3 nd = randomDirectionInHemisphereT<TAB>(n, rng, tf);
         ps.d = nd;
         ps.o = add(intersect, scale(nd, 0.01f));
     }
     return false;
+}
+
+template <bool TEX = true>
+PT_DEV bool scatterRay(const DScene &sc, PathState &ps, vec3 intersect, const Hit &hit, const DMaterial &m, Rng &rng) {
+    TanFrame tf;
+    tf.perp1 = tf.perp2 = V3(0.f, 0.f, 0.f); tf.has = 0;
+    return scatterRayT<TEX, false>(sc, ps, intersect, hit, m, rng, tf);
 }
 
 // ConcentricSampleDisk, src/pathtrace.cu:183-197

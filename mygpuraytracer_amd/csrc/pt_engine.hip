@@ -303,6 +303,8 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DevBuf<BvhQuad> d_bvh_nodes; DevBuf<float> d_bvh_tris; DevBuf<int32_t> d_bvh_root, d_bvh_depth;                          // pt_bvh.h (NULL: no mesh has one)
     DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
     DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
+    DevBuf<float> d_ctan;                                // tangent frames of the cubes' tabulated normals (DScene::ctan)
+    bool no_tangents = false;                            // PTX_DEBUG_NO_TANGENTS: DScene::ctan is NULL, every lane computes its frame (A/B timing, tests of both)
     DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
     bool no_fast = false;                                // PTX_DEBUG_NO_FAST: always the general k_bounce (A/B timing, tests of both variants)
     bool no_last = false;                                // PTX_DEBUG_NO_LAST: the last bounce runs the full k_bounce like every other (A/B timing, tests of both)
@@ -375,6 +377,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
         s.objcull = d_objcull; s.objcull_bits = objcull_bits;
         s.bvh_nodes = d_bvh_nodes; s.bvh_tris = d_bvh_tris; s.bvh_root = d_bvh_root; s.bvh_depth = d_bvh_depth; s.bvh_wide = d_bvh_wide; s.bvh_wroot = d_bvh_wroot; s.bvh_wneed = d_bvh_wneed; s.bvh_stack = 0; s.ntri_lds = 0; s.mesh_chunks = mesh_chunks;
         s.fnorm = d_fnorm; s.cnorm = d_cnorm; s.bump_bits = bump_bits;
+        s.ctan = no_tangents ? nullptr : d_ctan.p;
         s.tri_lds = 0; s.ntri = ntri;      // tri_lds is switched on only by launches that stage the table (k_bounce)
         s.ldsblob = nullptr;               // (set by enqueue_batch together with tri_lds / ntri_lds: the blob is laid out for those)
         return s;
@@ -988,6 +991,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     t->no_last = getenv("PTX_DEBUG_NO_LAST") != nullptr;
     t->last_inplace = getenv("PTX_DEBUG_LAST_INPLACE") != nullptr;
     t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
+    t->no_tangents = getenv("PTX_DEBUG_NO_TANGENTS") != nullptr;
     if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
     if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));
     if (const char *e = getenv("PTX_DEBUG_EXTRA_LDS")) t->dbg_extra_lds = std::max(0, std::min(atoi(e), 32768)) & ~15;
@@ -1029,7 +1033,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     // ---- 7. upload the scene, allocate the streams' buffers
     HC(t->d_geoms.upload(hs.geoms)); HC(t->d_mats.upload(hs.mats)); HC(t->d_faces.upload(hs.faces)); HC(t->d_texels.upload(hs.texels));
     HC(t->d_tri9.upload(hs.tri9)); HC(t->d_gtab.upload(hs.gtab)); HC(t->d_aabb.upload(hs.aabb_ch)); HC(t->d_objcull.upload(hs.objcull));
-    HC(t->d_fnorm.upload(hs.fnorm)); HC(t->d_cnorm.upload(hs.cnorm));
+    HC(t->d_fnorm.upload(hs.fnorm)); HC(t->d_cnorm.upload(hs.cnorm)); HC(t->d_ctan.upload(hs.ctan));
     if (t->bvh_meshes) {
         HC(t->d_bvh_nodes.upload(hs.bvh.nodes)); HC(t->d_bvh_tris.upload(hs.bvh.tris));
         HC(t->d_bvh_root.upload(hs.roots)); HC(t->d_bvh_depth.upload(hs.depths));

@@ -541,7 +541,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
 #ifdef PT_WGCLOCK
     const unsigned long long wg_t1 = wall_clock64();
 #endif
-    struct InRec { float f[14]; int32_t pix, mg, idx; };
+    struct InRec { float f[14]; int32_t pix, mg, idx; float tf[6]; int32_t has_tf; uint32_t tf4; };      // (tf: the hit's tangent frame where has_tf, at byte tf4 of the table: fetch, fetchFrame)
     // sorted position -> (entry of the local index, RNG stream index of its run's first survivor).  Uniform call: the window
     // moves on (barriers) when the tile's last position lies beyond it -- a few times per workgroup at most.
     auto locate = [&](int tile_, uint32_t &li4, int &idx_base) {
@@ -586,6 +586,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
         r.f[0] = A.x; r.f[1] = A.y; r.f[2] = A.z; r.pix = __float_as_int(A.w);
         r.f[6] = B.x; r.f[7] = B.y; r.f[8] = B.z; r.mg = __float_as_int(B.w);
         r.f[3] = r.f[4] = r.f[5] = 0.f; r.f[9] = r.f[10] = r.f[11] = 0.f; r.f[12] = r.f[13] = 0.f;
+        r.tf[0] = r.tf[1] = r.tf[2] = r.tf[3] = r.tf[4] = r.tf[5] = 0.f; r.has_tf = 0; r.tf4 = 0u;
         // (texcoords matter on OBJ geoms only, whose records have both a normal and a direction: where a part is not read they are the 0 it would hold)
         if (with_dir) { const quad D = ld_u(reinterpret_cast<const quad *>(in.quadD()), j16); r.f[3] = D.x; r.f[4] = D.y; r.f[5] = D.z; if (p.uses_uv) r.f[13] = D.w; }
         if (!coded_n) { const quad C = ld_u(reinterpret_cast<const quad *>(in.quadC()), j16); r.f[9] = C.x; r.f[10] = C.y; r.f[11] = C.z; if (p.uses_uv) r.f[12] = C.w; }
@@ -594,6 +595,14 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
             const int g = (int)min((uint32_t)(r.mg >> 16), (uint32_t)(p.sc.ngeoms - 1));
             const vec3 n = cubeNormalByCode(p.sc, reinterpret_cast<const float *>(pt_lds) + p.sc.ntri_lds * 24 + p.sc.nmats * 11, g, (r.pix >> 28) & 7);
             r.f[9] = n.x; r.f[10] = n.y; r.f[11] = n.z;
+            // ... and, where the code names a face, the place of the tangent frame the diffuse sampler would build from that normal (DScene::ctan,
+            // computed at upload by the sampler's own tangentFrame; requested by fetchFrame below).  The address is made of the clamped geom and
+            // a side 0-5, nothing else.
+            const int code = (r.pix >> 28) & 7;
+            if (p.sc.ctan && (code & 3)) {
+                r.tf4 = (uint32_t)(g * CTAN_WORDS + (((code & 3) - 1) * 2 + ((code & 4) ? 1 : 0)) * 6) << 2;
+                r.has_tf = 1;
+            }
             r.pix &= 0x0fffffff;
         }
         // (fence: the pixel slot becomes the address of the path's radiance when it ends -- found by a record read with other masks than
@@ -601,6 +610,18 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
         // it is counted, and it neither scatters nor adds light to a pixel that is not its own)
         if (__builtin_expect((uint32_t)r.pix >= (uint32_t)p.tm.owned, 0)) { fence_report(p); r.pix = 0; return false; }
         return true;
+    };
+    // The request of a tabulated frame, the tail of fetch: issued once the record's quads have arrived (`mat` comes out of quad B), so that the
+    // three loads do not sit in front of the wait for every load in flight where coded and uncoded records join; read at the end of the sampler.
+    auto fetchFrame = [&](InRec &r, int mat) {
+        int32_t has = r.has_tf;
+        asm volatile("" : "+v"(has) : "v"(mat));      // (opaque, and behind the material index: the block below stays where it is written)
+        if (has) {
+            typedef float pair __attribute__((ext_vector_type(2)));
+            const pair T0 = ld_u(reinterpret_cast<const pair *>(p.sc.ctan), r.tf4), T1 = ld_u(reinterpret_cast<const pair *>(p.sc.ctan), r.tf4 + 8u),
+                       T2 = ld_u(reinterpret_cast<const pair *>(p.sc.ctan), r.tf4 + 16u);
+            r.tf[0] = T0.x; r.tf[1] = T0.y; r.tf[2] = T1.x; r.tf[3] = T1.y; r.tf[4] = T2.x; r.tf[5] = T2.y;
+        }
     };
     auto classifyRay = [&](const Hit &hit, const PathState &ps, int pix, int &bin, bool &pending) {
         classifyPath<FIRST>(p, iter, part, batched, hit, ps.color, pix, bin, pending);
@@ -698,13 +719,16 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
                 const int mg = cur.mg;
                 h.mat = mg & 0xffff; h.geom = mg >> 16;
                 const int sidx = cur.idx;
+                fetchFrame(cur, h.mat);
 #ifdef PT_STAMPS
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 STAMP(11);
 #endif
                 Rng rng; rng.seed(iter, sidx, 0);
-                bool ended = (FAST && MODE == 0) ? scatterRay<false>(p.sc, ps, intersect, h, getMaterial(p.sc, h.mat), rng)
-                                                 : scatterRay<true>(p.sc, ps, intersect, h, getMaterial(p.sc, h.mat), rng);
+                TanFrame tf;
+                tf.perp1 = V3(cur.tf[0], cur.tf[1], cur.tf[2]); tf.perp2 = V3(cur.tf[3], cur.tf[4], cur.tf[5]); tf.has = cur.has_tf;
+                bool ended = (FAST && MODE == 0) ? scatterRayT<false, true>(p.sc, ps, intersect, h, getMaterial(p.sc, h.mat), rng, tf)
+                                                 : scatterRayT<true, true>(p.sc, ps, intersect, h, getMaterial(p.sc, h.mat), rng, tf);
                 if (ended && rec_ok) deposit(p.tm, p.image, part, batched, pix, ps.color, p.apps, p.fence_slots_cap);      // emissive texel: remainingBounces 1 -> 0, colour goes to the image
                 if (ended || !rec_ok) alive = false;
             }

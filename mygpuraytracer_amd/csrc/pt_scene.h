@@ -37,6 +37,7 @@ struct HostScene : SceneFacts {
     std::vector<DGeom> geoms;
     std::vector<DMaterial> mats;
     std::vector<float> faces, tri9, gtab, fnorm, cnorm;
+    std::vector<float> ctan;                             // DScene::ctan: CTAN_WORDS per geom, the tangent frames of the six normals in cnorm (zeros: not a cube)
     std::vector<uint8_t> texels;
     std::vector<float> aabb, aabb_ch;                    // world boxes, 8 floats per geom: corners (lo xyz, 0, hi xyz, 0) / centre and half extent
     std::vector<float> objcull;                          // DScene::objcull: OBJCULL_WORDS per geom, zeros where objcull_bits has no bit
@@ -64,5 +65,9 @@ uint32_t light_geom_bits(int nmaterials, const DMaterial *mats, int ngeoms, cons
 // (16 floats, columns) and its faces.  margin = 1: the derived margins (pt_scene.hip); 0: the bare box, which the CPU tests use to show that
 // they can fail.  false (out16 zeroed): no entry -- no faces, a singular or non-finite matrix, numbers out of the derivation's range.
 bool objcull_entry(const float *inverse16, const float *faces15, int nfaces, double margin, float out16[OBJCULL_WORDS]);
+// A cube's six face normals (cnorm18, index (axis * 2 + (sign > 0)) * 3: boxIntersectionTest's normalize(invTranspose * +-e_axis)) and the
+// tangent frame of each (ctan36: perp1 xyz, perp2 xyz per side, the diffuse sampler's tangentFrame of the very floats written to cnorm18),
+// from rows 0-2 of the cube's invTranspose as gtab holds them (12 floats).
+void cube_face_tables(const float *invT_rows12, float *cnorm18, float *ctan36);
 
 }  // namespace ptd

@@ -316,6 +316,21 @@ bool objcull_entry(const float *inverse16, const float *faces15, int nfaces, dou
     return true;
 }
 
+void cube_face_tables(const float *invT_rows12, float *cnorm18, float *ctan36) {
+    for (int side = 0; side < 6; side++) {
+        const int axis = side >> 1;
+        const float sgn = (side & 1) ? 1.f : -1.f;
+        const vec3 e = V3(axis == 0 ? sgn : 0.f, axis == 1 ? sgn : 0.f, axis == 2 ? sgn : 0.f);
+        const vec3 n = normalize(mulRows(invT_rows12, e, 0.0f));
+        float *o = cnorm18 + side * 3;
+        o[0] = n.x; o[1] = n.y; o[2] = n.z;
+        vec3 perp1, perp2;
+        tangentFrame(V3(o[0], o[1], o[2]), perp1, perp2);      // (of the floats the kernels read back as the normal)
+        float *t = ctan36 + side * 6;
+        t[0] = perp1.x; t[1] = perp1.y; t[2] = perp1.z; t[3] = perp2.x; t[4] = perp2.y; t[5] = perp2.z;
+    }
+}
+
 // scene upload (pathtraceInit, src/pathtrace.cu:111-146) -- flattened, no host struct is mutated
 int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials, const ptx_options &opt, int owned,
                      int nbins, size_t lds_limit, const SceneSwitches &sw, HostScene &hs) {
@@ -422,6 +437,7 @@ int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const pt
     // normals that do not depend on the ray, computed once with the device's own functions (compiled for the host with
     // the same flags: no contraction, IEEE divide and square root), so the kernels read what they would have computed
     hs.fnorm.assign((size_t)std::max(hs.ntri, 1) * 3, 0.f); hs.cnorm.assign(ng1 * 18, 0.f);
+    hs.ctan.assign(ng1 * CTAN_WORDS, 0.f);
     for (int i = 0; i < ngeoms; i++) {
         const DGeom &d = hs.geoms[i];
         if (d.type == G_OBJ) {
@@ -435,15 +451,7 @@ int pt_prepare_scene(int ngeoms, const ptx_geom *geoms, int nmaterials, const pt
                 o[0] = n.x; o[1] = n.y; o[2] = n.z;
             }
         } else if (d.type == G_CUBE) {                       // boxIntersectionTest, src/intersections.h:86
-            const float *invT = &hs.gtab[(size_t)i * GTAB_WORDS + 24];
-            for (int side = 0; side < 6; side++) {
-                const int axis = side >> 1;
-                const float sgn = (side & 1) ? 1.f : -1.f;
-                const vec3 e = V3(axis == 0 ? sgn : 0.f, axis == 1 ? sgn : 0.f, axis == 2 ? sgn : 0.f);
-                const vec3 n = normalize(mulRows(invT, e, 0.0f));
-                float *o = &hs.cnorm[(size_t)i * 18 + side * 3];
-                o[0] = n.x; o[1] = n.y; o[2] = n.z;
-            }
+            cube_face_tables(&hs.gtab[(size_t)i * GTAB_WORDS + 24], &hs.cnorm[(size_t)i * 18], &hs.ctan[(size_t)i * CTAN_WORDS]);
         }
     }
     if (ngeoms > 32) hs.bump_bits = 0xffffffffu;          // (no per-geom bit beyond 32 geoms: such scenes do not take the tile path)
@@ -595,6 +603,23 @@ int ptx_debug_cull_objboxes(int ngeoms, const ptx_geom *geoms, int no_bvh, float
         for (int k = 0; k < OBJCULL_WORDS; k++) table16[(size_t)g * OBJCULL_WORDS + k] = 0.f;
         if (!bvh && geoms[g].type == G_OBJ && objcull_entry(geoms[g].inverseTransform, geoms[g].faces, geoms[g].faceSize, margin, table16 + (size_t)g * OBJCULL_WORDS))
             *bits_out |= 1u << g;
+    }
+    return 0;
+}
+
+// CPU-only: ptx_create's table of tangent frames (DScene::ctan, cube_face_tables) for ngeoms geoms given as ptx_create takes them:
+// out36_per_geom = CTAN_WORDS floats per geom -- side (axis * 2 + (sign > 0)) at side * 6: perp1 xyz, perp2 xyz of that face's tabulated
+// normal, as the diffuse sampler would compute them -- zeros for a geom that is not a cube.
+int ptx_debug_cube_tangents(int ngeoms, const ptx_geom *geoms, float *out36_per_geom) {
+    if (ngeoms < 0 || (ngeoms && (!geoms || !out36_per_geom))) { set_error(PTX_ERR_INVALID, "ptx_debug_cube_tangents: bad argument"); return -1; }
+    for (int g = 0; g < ngeoms; g++) {
+        float *o = out36_per_geom + (size_t)g * CTAN_WORDS;
+        for (int k = 0; k < CTAN_WORDS; k++) o[k] = 0.f;
+        if (geoms[g].type != G_CUBE) continue;
+        float rows[12], cnorm18[18];
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) rows[r * 4 + c] = geoms[g].invTranspose[c * 4 + r];      // (as pt_prepare_scene fills gtab)
+        cube_face_tables(rows, cnorm18, o);
     }
     return 0;
 }
