@@ -1,6 +1,7 @@
 // pt_engine.hip -- the host unit of the MI355X (gfx950) path-tracing engine behind include/mi355x_pathtracer.h: the ptx_tracer struct, scene
-// upload, buffers, launch plans, every ptx_* entry point that needs a device, and the kernels that are the same at every arithmetic
+// upload, buffers, every ptx_* entry point that needs a device, and the kernels that are the same at every arithmetic
 // level (debug capture, cache replay, gather, statistics, preview, G-buffer, k_kat_fast_exact, k_hold).  Scene preparation: pt_scene.hip.
+// The debug switches and the launch plans (iterations per set, grids, LDS bytes, the cut of a short run): pt_plan.hip.
 //
 // What belongs here: everything that is level 0 by nature.  This file is compiled ONCE, at the exact level; the kernels whose results
 // depend on the arithmetic level (k_bounce, k_mesh, k_finish, the per-stage test kernels) are pt_kernels.hip's, one code object per
@@ -19,6 +20,7 @@
 #include "../../include/mi355x_pathtracer.h"
 #include "pt_kernels.h"
 #include "pt_scene.h"
+#include "pt_plan.h"
 #include "pt_denoise.h"
 
 namespace {
@@ -32,8 +34,6 @@ int set_error(int code, const std::string &msg) { g_last_error = msg; return cod
         if (e_ != hipSuccess)                                                                            \
             return set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
-
-constexpr int MAX_LANES = 8;     // launch sets in flight at most (ptx_options.lanes)
 
 // debug capture: the sorted stream materialised -- what the next k_bounce would read, resolved the slow, obvious way from the same
 // tables (run prefixes by one thread, a binary search per position), so that the parity tests see the order the kernels define
@@ -268,7 +268,7 @@ template <class T> struct DevBuf {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it is traced, pt_scene.h: ntri, cull, tri_lds, split_mesh, the masks ...)
+struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on and the debug switches `dbg`, pt_plan.h; what the scene decides, pt_scene.h)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -278,11 +278,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DCamera cam{};
     int traceDepth = 0;
     TileMap tm{};
-    int nbins = 1, nmats = 0, ngeoms = 0, maxTiles = 0, grid = 0, grid_seg = 0, cap = 0, cus = 0;
-    bool grid_forced = false;                  // PTX_DEBUG_WG_PER_CU given: the grid is what it says for every kernel
-    int dbg_mesh_wg_per_cu = 0;                 // PTX_DEBUG_MESH_WG_PER_CU: workgroups per CU of k_mesh's grid (tuning experiments)
-    int dbg_extra_lds = 0;
-    int dbg_total_wg_per_cu = 0, dbg_nsets = 0; // PTX_DEBUG_TOTAL_WG_PER_CU / PTX_DEBUG_NSETS: tuning experiments (grid of a whole launch; sets of a short run)
+    int cap = 0;                               // slots of one segment: maxTiles x TILE
     // device memory
     DevBuf<DGeom> d_geoms; DevBuf<DMaterial> d_mats; DevBuf<float> d_faces; DevBuf<uint8_t> d_texels;
     float *d_image = nullptr; DevBuf<float> d_image_own; // d_image: the caller's buffer, or d_image_own
@@ -304,22 +300,14 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
     DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
     DevBuf<float> d_ctan;                                // tangent frames of the cubes' tabulated normals (DScene::ctan)
-    bool no_tangents = false;                            // PTX_DEBUG_NO_TANGENTS: DScene::ctan is NULL, every lane computes its frame (A/B timing, tests of both)
     DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
-    bool no_fast = false;                                // PTX_DEBUG_NO_FAST: always the general k_bounce (A/B timing, tests of both variants)
-    bool no_last = false;                                // PTX_DEBUG_NO_LAST: the last bounce runs the full k_bounce like every other (A/B timing, tests of both)
-    bool last_inplace = false;                           // PTX_DEBUG_LAST_INPLACE: the light-only last bounce without the pool of survivors over tiles (A/B timing, tests of both)
-    bool force_fast = false;                             // PTX_DEBUG_FORCE_FAST: ask for the specialised variant at every launch (refused
-                                                         // with PTX_ERR_INVALID where its preconditions do not hold; tests only)
     DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_items; DevBuf<int32_t> d_item_count;
     DevBuf<int32_t> d_tile_done;                         // split first bounce: [segments][maxTiles], see BounceParams::tile_done
     size_t seg_items = 0;
     int nsuper = 1;
     size_t totals_bytes = 0, seg_totals = 0, field_stride = 0, seg_part = 0;
     int kmax = 1;                                        // iterations per launch set (segments)
-    long long split_min_paths = 1LL << 20;               // ptx_render_strided: smallest launch set a short run is cut into
-    int lanes = 1;                                       // launch sets in flight at once, each on a stream of its own with its own
-                                                         // kmax segments of every per-iteration buffer (lane 0 = `stream`)
+    // (lanes, pt_plan.h: each launch set in flight runs on a stream of its own with its own kmax segments of every per-iteration buffer)
     hipStream_t lane_stream[MAX_LANES] = {};      // [0] = `stream`, the others are the tracer's own
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {}, ev_chain[MAX_LANES] = {};
     // Render-ahead for the one-iteration-per-call shape (ptx_iterate = the reference's pathtrace(iter)): lanes 1 and 2 take
@@ -356,7 +344,6 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
     DevBuf<int32_t> d_cache_totals;                      // [2][nbins] of bounce 0 (cache)
     DevBuf<int32_t> d_emit_count, d_emit_pix; DevBuf<float> d_emit_rgb;
     DevBuf<int64_t> d_stats;                             // [64] last iteration, [64] = running total, [65] = fenced indices (BounceParams::fenced), [66..68] = stored paths: all, with direction, with normal code
-    uint32_t fence_slots = 0;                            // = cap; PTX_DEBUG_FENCE_SLOTS lowers it (test of the counter: entries beyond it are fenced)
     int maxBounces = 0;
     bool cache_valid = false;
     int64_t iterations = 0;
@@ -377,7 +364,7 @@ struct ptx_tracer : SceneFacts {      // (+ what the scene decides about how it 
         s.objcull = d_objcull; s.objcull_bits = objcull_bits;
         s.bvh_nodes = d_bvh_nodes; s.bvh_tris = d_bvh_tris; s.bvh_root = d_bvh_root; s.bvh_depth = d_bvh_depth; s.bvh_wide = d_bvh_wide; s.bvh_wroot = d_bvh_wroot; s.bvh_wneed = d_bvh_wneed; s.bvh_stack = 0; s.ntri_lds = 0; s.mesh_chunks = mesh_chunks;
         s.fnorm = d_fnorm; s.cnorm = d_cnorm; s.bump_bits = bump_bits;
-        s.ctan = no_tangents ? nullptr : d_ctan.p;
+        s.ctan = dbg.no_tangents ? nullptr : d_ctan.p;
         s.tri_lds = 0; s.ntri = ntri;      // tri_lds is switched on only by launches that stage the table (k_bounce)
         s.ldsblob = nullptr;               // (set by enqueue_batch together with tri_lds / ntri_lds: the blob is laid out for those)
         return s;
@@ -410,9 +397,9 @@ void fastdiv_magic(uint32_t d, uint32_t &mul, uint32_t &sh) {
 
 int update_tile_geoms(ptx_tracer *t) {
     t->tile_geoms_valid = false;
-    if (!t->cull || t->ngeoms > 32 || t->ngeoms < 1 || getenv("PTX_DEBUG_NO_TILE_GEOMS")) return PTX_OK;
+    if (!t->cull || t->ngeoms > 32 || t->ngeoms < 1 || t->dbg.no_tile_geoms) return PTX_OK;
     const bool dof = t->opt.depth_of_field != 0;
-    if (dof && getenv("PTX_DEBUG_NO_TILE_GEOMS_DOF")) return PTX_OK;
+    if (dof && t->dbg.no_tile_geoms_dof) return PTX_OK;
     std::vector<uint32_t> masks;
     tile_geom_masks(t->cam, t->tm.tile_rows, t->tm.tile_rank, t->tm.tile_world, t->tm.owned, t->maxTiles, t->ngeoms, t->h_aabb.data(), dof, masks);
     HIPCHECK(hipMemcpyAsync(t->d_tile_geoms, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, t->stream));
@@ -485,12 +472,12 @@ const char *last_violation(const ptx_tracer *t, int mode, bool first, const Boun
 // light-only variant, where it is taken (it reads the previous launch's run tables and writes none: any grid will do).
 int launch_bounce(const ptx_tracer *t, bool first, int mode, bool needs_albedo, dim3 grid, size_t lds, hipStream_t stream, const BounceParams &bp, int gx_last = 0) {
     const char *why = fast_violation(t, mode, first, needs_albedo, bp);
-    bool fast = !t->no_fast && !why;
-    if (t->force_fast) {
+    bool fast = !t->dbg.no_fast && !why;
+    if (t->dbg.force_fast) {
         if (why) return set_error(PTX_ERR_INVALID, std::string("specialised k_bounce requested outside its preconditions: ") + why);
         fast = true;
     }
-    if (!t->no_last && !last_violation(t, mode, first, bp)) {
+    if (!t->dbg.no_last && !last_violation(t, mode, first, bp)) {
         if (gx_last > 0) grid.x = (unsigned)gx_last;
         t->ksl->bounce_last(fast ? 1 : 0, grid, lds, stream, &bp);
         return PTX_OK;
@@ -512,102 +499,25 @@ int enqueue_batch(ptx_tracer *t, int iter_first, int K, int stride = 1, int lane
     return rc;
 }
 
-// k_stats over the nseg segments from segment seg, which leaves their totals zero behind it
-void launch_stats(ptx_tracer *t, hipStream_t stream, size_t seg, int nseg, bool skip_first, unsigned long long dir_bins, unsigned long long ntab_bins) {
+// The tail of a launch set, or of one segment of a traced-ahead one: the nseg segments from segment seg into the image (k_gather, where
+// ending paths stored into per-iteration buffers) and their statistics (k_stats).  Both leave what they read -- the lit planes, the
+// totals -- zero behind them.
+void launch_gather_stats(ptx_tracer *t, hipStream_t stream, size_t seg, int nseg, bool use_cache, unsigned long long dir_bins, unsigned long long ntab_bins) {
+    if (nseg > 1 || t->lanes > 1)
+        hipLaunchKernelGGL(k_gather, dim3(std::min(2048, (t->tm.owned + 255) / 256)), dim3(256), 0, stream, t->tm, t->cam.resx, nseg,
+                           t->seg_part, t->d_part + seg * t->seg_part, t->d_image, (uint32_t)t->cap);
     const size_t super_off = 2 * (size_t)t->nbins * t->maxBounces;              // (t->d_super's offset in every segment)
     const int super_words = t->traceDepth * 2 * t->nbins * t->nsuper;
     const int nclear = (int)std::min<size_t>(128, ((size_t)nseg * super_words + 255) / 256);
     hipLaunchKernelGGL(k_stats, dim3(1 + nclear), dim3(64), 0, stream, t->d_totals + seg * t->seg_totals, t->nbins, t->traceDepth, 2 * t->nbins,
-                       skip_first ? 1 : 0, nseg, t->seg_totals, super_off, super_words, t->d_stats, t->d_stats + 64, dir_bins, ntab_bins, t->d_stats + 66);
+                       use_cache ? 1 : 0, nseg, t->seg_totals, super_off, super_words, t->d_stats, t->d_stats + 64, dir_bins, ntab_bins, t->d_stats + 66);
 }
 
-int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lane, int prev_lane, bool defer) {
-    hipStream_t stream = lane == 0 ? t->stream : t->lane_stream[lane];
-    const size_t seg0 = (size_t)lane * t->kmax;
-    const int nb = t->nbins;
-    const int ntri_lds = t->split_mesh ? 0 : t->ntri_lds;
-    const int triWords = t->tri_lds ? sceneTableWords(ntri_lds, t->nmats, t->ngeoms) : 0;
-    const size_t lds_bounce = sizeof(int32_t) * (bounceLdsWords(triWords, nb) + (t->split_mesh ? QUEUE_WORDS : 0)) + (size_t)t->dbg_extra_lds;      // (+ PTX_DEBUG_EXTRA_LDS bytes: occupancy experiments)
-    const bool cache_on = t->cache_active();
-    const bool use_cache = cache_on && t->cache_valid && iter_first != 1;
-    const bool fill_cache = cache_on && !use_cache;
-    const bool batched = K > 1 || t->lanes > 1;      // ending paths store into per-iteration buffers, k_gather sums them
-    // the specialised unsplit kernel runs 5 workgroups per CU at a time: a grid of 8 per CU would be 1.6 rounds of them (C4 -1.3 %)
-    // (the apps variant's x PI at the deposit stays a run-time value in every kernel; its albedo AOV is written by iteration 1 alone,
-    // so only a launch set that contains iteration 1 needs the general kernel for it)
-    const bool needs_albedo = t->d_albedo && iter_first == 1;
-    // (only the grid size depends on this estimate; what is launched is decided per launch by fast_violation)
-    const bool fast_unsplit = !t->split_mesh && !t->no_fast && batched && !t->uses_uv && t->opt.sort_by_material &&
-                              !needs_albedo && t->cull == 1 && t->tri_lds && t->bump_bits == 0 && t->ntri_lds == t->ntri &&
-                              !t->d_bvh_root;
-    // ... the split bounce's kernels are many short ones: 16 workgroups per CU (C5 -2 %); everything else 8 as before
-    // (traced ahead of per-call requests: two of the seven slots per CU stay free, so that the caller's own short kernels -- gather,
-    // preview -- start at once instead of waiting for one of these long-running workgroups to end: 0.53 -> 0.50 ms per call)
-    // The launch's workgroups: one round of the kernel's occupancy over the whole chip, WHATEVER one segment holds (round 3: until
-    // then the total was capped by one segment's tile count, so the K = 10 segments of a 1/8 tile ran as 1010 workgroups of ten
-    // tiles -- 4 per CU -- instead of 1790 of six: 20 steps of such a tile 0.636 -> 0.585 ms, tools/gpu_tile_grid_sweep.py)
-    // Round 4: MORE workgroups than one round of the occupancy.  A workgroup owns a contiguous chunk of tiles, and chunks are unequal --
-    // the camera-ray bounce's tiles cost anything from nothing (a tile that sees no geom) to a full tile, the later bounces' tiles
-    // differ by material mix -- so with one chunk per resident workgroup a kernel ends when its heaviest chunk does; and the other launch
-    // sets' short kernels (k_finish, the ranking pass) get a slot only when a workgroup of the long one retires.  Measured on one box
-    // each (gpurun_out/r4_c4wg*.log, r4_bouncewg*.log): C4 camera bounce alone 0.0365 (7 per CU) / 0.0338 (14) / 0.0320 (21) / 0.0300 ms
-    // (28), later bounces 0.163 / 0.161 / 0.160 / 0.160 / 0.173 (42), wall of the 20-step run 0.176 / 0.172 / 0.173 / 0.173 / 0.179;
-    // C5 (split bounce) 16 per CU 1.06-1.10, 32 1.03-1.07, 48 1.04-1.07 ms per iteration.
-    // End of round 4, after the records' diet (32 B instead of 56 for a wall hit, 16-byte quads) and with eight workgroups' LDS per CU: the
-    // later bounces as ONE round of the occupancy again (8 per CU) and the camera bounce 20 -- C4's 20-step run 0.147 -> 0.1425 ms per
-    // step, its long run 0.1415 -> 0.138 (three runs each of six plans on one box, gpurun_out/r4grid2.log; 28 / 14 was the choice while
-    // the kernels moved 40 % more bytes and a chunk's tail of index traffic was worth spreading).
-    // (traced ahead of per-call requests: five per CU, so that two slots stay free for the caller's own short kernels)
-    auto per_cu = [&](bool first_bounce, bool last_bounce = false) {
-        if (fast_unsplit && !defer && last_bounce) { if (const char *e = getenv("PTX_DEBUG_WG_LAST")) return std::max(1, atoi(e)); }      // tuning experiments
-        if (fast_unsplit && !defer) { if (const char *e = getenv(first_bounce ? "PTX_DEBUG_WG_FIRST" : "PTX_DEBUG_WG_LATER")) return std::max(1, atoi(e)); }      // tuning experiments
-        if (fast_unsplit) return defer ? PT_FAST_WAVES - 2 : first_bounce ? 20 : PT_FAST_WAVES;
-        return t->split_mesh ? 32 : 8;
-    };
-    auto gx_of = [&](bool first_bounce, bool last_bounce = false) {
-        int grid = t->grid_forced ? t->grid : t->cus * per_cu(first_bounce, last_bounce);
-        if (t->dbg_total_wg_per_cu > 0) grid = t->cus * t->dbg_total_wg_per_cu;      // tuning experiments
-        int g = grid / K;                            // workgroups per segment
-        if (!t->grid_forced && t->dbg_total_wg_per_cu <= 0) {
-            // ... but only where a workgroup keeps at least ~8 tiles of the camera bounce: a rank's 1/8 tile is a chain of dependent round
-            // trips per workgroup life, and more workgroups are more prologues there -- 20 steps of such a tile 0.54 -> 0.60 ms
-            // with the larger grids.  Below that the grid is one round of the occupancy, as before.
-            const int base = t->cus * (fast_unsplit ? (defer ? PT_FAST_WAVES - 2 : PT_FAST_WAVES) : t->split_mesh ? 16 : 8) / K;
-            g = std::min(g, std::max(base, t->maxTiles / 8));
-        }
-        if (g < 64 && t->dbg_total_wg_per_cu <= 0) g = 64;
-        if (g > t->maxTiles) g = t->maxTiles;
-        if (g > t->grid_seg) g = t->grid_seg;
-        if (g > grid) g = grid;
-        return g < 1 ? 1 : g;
-    };
-    const int gx_first = gx_of(true), gx_later = gx_of(false);
-    int gx_last = gx_of(false, true);      // (the light-only last bounce: the later bounces' grid -- 4 / 8 / 16 workgroups per CU measured alike, profiles/last_bounce_ab.txt)
-    // (PTX_DEBUG_GX_LAST, tests only: fewer workgroups per segment there, so that a small frame gives a workgroup many tiles -- its pool of
-    // light-box survivors fills and drains as it does at 1080p)
-    if (const char *e = getenv("PTX_DEBUG_GX_LAST")) gx_last = std::max(1, std::min(atoi(e), gx_last));
-    const int grid = t->cus * (t->dbg_total_wg_per_cu > 0 ? t->dbg_total_wg_per_cu : per_cu(false));      // (k_finish's grid-stride launch)
-    const int gx = gx_later;
-    const int nsuper = (gx + 63) / 64;
-    const size_t chunk_cap = (size_t)nb * t->grid_seg;                 // runs per table at most
-    const size_t seg_counts = (2 * (size_t)nb + 1) * t->maxTiles, seg_chunk = 2 * 3 * chunk_cap, seg_totals = t->seg_totals;      // (two prefix tables + stored paths per tile)
-    int32_t *counts_all = t->d_counts + seg0 * seg_counts, *counts_scat = counts_all + (size_t)nb * t->maxTiles;
-    // run tables of bounce b: parity b & 1 of the segment's pair (bounce b + 1 reads them while it writes its own)
-    auto chunks = [&](int bounce) { return t->d_chunk + seg0 * seg_chunk + (size_t)(bounce & 1) * 3 * chunk_cap; };
-    auto totals = [&](int bounce, int which) { return t->d_totals + seg0 * seg_totals + ((size_t)bounce * 2 + which) * nb; };
-    auto supers = [&](int bounce, int which) { return t->d_super + seg0 * seg_totals + ((size_t)bounce * 2 + which) * nb * t->nsuper; };
-    // per-bounce totals and group totals are accumulated with atomics, and the lit planes are set bit by bit: the lane's previous set
-    // left them zero (k_stats, k_gather) -- unless the lane is marked, then all of its segments are cleared here, once
-    if (t->aux_dirty[lane]) {
-        HIPCHECK(hipMemsetAsync(t->d_totals + seg0 * seg_totals, 0, sizeof(int32_t) * seg_totals * (size_t)t->kmax, stream));
-        if (t->d_part)                               // (the planes: behind each segment's radiance, cap / 32 words per segment)
-            HIPCHECK(hipMemset2DAsync(t->d_part + seg0 * t->seg_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
-                                      (size_t)t->cap / 8, (size_t)t->kmax, stream));
-        t->aux_dirty[lane] = false;
-    }
-
-    // per-kernel timing brackets (only when switched on; costs two event records per launch)
-    auto kt_begin = [&](int kind) -> int {
+// per-kernel timing (ptx_set_kernel_timing; costs two event records per launch): begin(kind) in front of a launch, end() behind it
+struct KernelTimer {
+    ptx_tracer *t;
+    hipStream_t stream;
+    int begin(int kind) const {
         if (!t->ktiming) return PTX_OK;
         if (t->kev_used + 2 > t->kev.size()) {
             hipEvent_t a, b2;
@@ -618,135 +528,180 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         t->kev_kind[t->kev_used / 2] = kind;
         HIPCHECK(hipEventRecord(t->kev[t->kev_used], stream));
         return PTX_OK;
-    };
-    auto kt_end = [&]() -> int {
+    }
+    int end() const {
         if (!t->ktiming) return PTX_OK;
         HIPCHECK(hipEventRecord(t->kev[t->kev_used + 1], stream));
         t->kev_used += 2;
         return PTX_OK;
-    };
-#define KT(kind, launch) do { int rc_ = kt_begin(kind); if (rc_ != PTX_OK) return rc_; launch; rc_ = kt_end(); if (rc_ != PTX_OK) return rc_; } while (0)
-    if (fill_cache) HIPCHECK(hipMemsetAsync(t->d_emit_count, 0, sizeof(int32_t), stream));
-    // what this batch's launches WRITE their records with (a debug capture switches the masks off for its own launches); k_stats weighs
-    // the batch's stored paths by these, not by the tracer's
-    const bool masks_off = t->capture_bounce >= 0 && !getenv("PTX_DEBUG_KEEP_DIR_SKIP");
-    const unsigned long long batch_dir_bins = masks_off ? ~0ull : t->dir_bins, batch_ntab_bins = masks_off ? 0ull : t->ntab_bins;
+    }
+};
+
+// a lane's segments of the per-iteration tables (seg0 = its first segment)
+struct SegmentViews {
+    int32_t *counts_all, *counts_scat, *chunk, *total, *super;
+    size_t chunk_cap, nb, nsuper;
+    SegmentViews(const ptx_tracer *t, const BatchPlan &p, size_t seg0)
+        : counts_all(t->d_counts + seg0 * p.seg_counts), counts_scat(counts_all + (size_t)t->nbins * t->maxTiles), chunk(t->d_chunk + seg0 * p.seg_chunk),
+          total(t->d_totals + seg0 * t->seg_totals), super(t->d_super + seg0 * t->seg_totals), chunk_cap(p.chunk_cap), nb(t->nbins), nsuper(t->nsuper) {}
+    // run tables of bounce b: parity b & 1 of the segment's pair (bounce b + 1 reads them while it writes its own)
+    int32_t *chunks(int bounce) const { return chunk + (size_t)(bounce & 1) * 3 * chunk_cap; }
+    int32_t *totals(int bounce, int which) const { return total + ((size_t)bounce * 2 + which) * nb; }
+    int32_t *supers(int bounce, int which) const { return super + ((size_t)bounce * 2 + which) * nb * nsuper; }
+};
+
+// what every bounce of one launch set has in common
+struct BatchSet {
+    int iter_first, K, stride;
+    size_t seg0;                                  // the lane's first segment
+    bool cache_on, use_cache, fill_cache;         // the first-bounce cache: in use at all / replayed by this set / filled by it
+    bool batched;                                 // ending paths store into per-iteration buffers, k_gather sums them
+    // what this set's launches WRITE their records with (a debug capture switches the masks off for its own launches); k_stats weighs
+    // the set's stored paths by these, not by the tracer's
+    unsigned long long dir_bins, ntab_bins;
+};
+
+// the parameters of bounce b's launches (the split bounce's three kernels share them)
+BounceParams fill_bounce_params(const ptx_tracer *t, const BatchSet &s, const BatchPlan &p, const SegmentViews &v, int b) {
+    const bool first = b == 0;
+    const size_t seg0 = s.seg0;
+    BounceParams bp;
+    bp.sc = t->scene(); bp.sc.tri_lds = t->tri_lds; bp.sc.ntri_lds = t->split_mesh ? 0 : t->ntri_lds; bp.sc.cull = t->cull; bp.cam = t->cam; bp.tm = t->tm;
+    for (int k = 0; k < 3; k++) if (bp.sc.cull && !(std::fabs(t->cam.position[k]) <= 0.5f * CULL_FAR_ORIGIN)) bp.sc.cull = 2;      // (a camera far out: cullMask, FAR ORIGINS)
+    bp.sc.ldsblob = t->d_ldsblob;
+    // bounce b writes its stage into soa[1 - (b & 1)] (bounce 0 of a cache-enabled tracer: into soa[2], kept across
+    // iterations) and reads the previous bounce's through that bounce's local index and run tables
+    const bool from_cache = (b == 1 && s.cache_on), to_cache = (first && s.cache_on);
+    bp.in = from_cache ? t->soa[2] : soa_shift(t->soa[b & 1], seg0 * t->cap);
+    bp.stage = to_cache ? t->soa[2] : soa_shift(t->soa[1 - (b & 1)], seg0 * t->cap);
+    bp.in_totals = first ? nullptr : from_cache ? t->d_cache_totals : v.totals(b - 1, 0);
+    bp.in_super = first ? nullptr : from_cache ? t->d_cache_super : v.supers(b - 1, 0);
+    bp.in_chunk = first ? nullptr : from_cache ? t->d_cache_chunk : v.chunks(b - 1);
+    bp.in_gx = from_cache ? t->cache_gx : (b == 1 ? p.gx_first : p.gx_later);      // workgroups per segment of the launch whose run tables it reads
+    bp.seg_in_totals = from_cache ? 0 : t->seg_totals; bp.seg_in_chunk = from_cache ? 0 : p.seg_chunk;
+    bp.image = t->d_image;
+    bp.iter = s.iter_first; bp.iter_stride = s.stride; bp.traceDepth = t->traceDepth; bp.bounce = b;
+    bp.aa = t->opt.antialiasing; bp.dof = t->opt.depth_of_field; bp.sort = t->opt.sort_by_material; bp.uses_uv = t->uses_uv; bp.dir_bins = s.dir_bins;
+    bp.ntab_bins = s.ntab_bins; bp.apps = t->opt.apps_variant; bp.albedo = t->d_albedo;
+    // (the masks tell the READER of a stage what its records hold; a launch that WRITES with other masks than it reads with -- a cached
+    // camera bounce replayed while a debug capture has switched them off, or the other way round -- gets both: in_* for what it reads)
+    bp.in_dir_bins = from_cache ? t->cache_dir_bins : bp.dir_bins; bp.in_ntab_bins = from_cache ? t->cache_ntab_bins : bp.ntab_bins;
+    // (the local index's form: this launch's, and that of the launch whose stage it reads)
+    bp.idx16 = first ? p.idx16_first : p.idx16_later;
+    bp.in_idx16 = first ? 0 : from_cache ? t->cache_idx16 : (b == 1 ? p.idx16_first : p.idx16_later);
+    bp.nbins = t->nbins; bp.maxTiles = t->maxTiles;
+    bp.counts_all = v.counts_all; bp.counts_scat = v.counts_scat;
+    bp.chunk = to_cache ? t->d_cache_chunk : v.chunks(b); bp.chunk_cap = (int32_t)p.chunk_cap;
+    bp.super_all = v.supers(b, 0); bp.super_scat = v.supers(b, 1);
+    bp.totals_all = v.totals(b, 0); bp.totals_scat = v.totals(b, 1);
+    bp.nsuper = t->nsuper;
+    bp.seg_in = from_cache ? 0 : (size_t)t->cap; bp.seg_stage = to_cache ? 0 : (size_t)t->cap;
+    bp.seg_counts = p.seg_counts; bp.seg_chunk = to_cache ? 0 : p.seg_chunk; bp.seg_totals = t->seg_totals;
+    bp.stamps = t->d_stamps;
+    bp.seg_part = t->seg_part;
+    bp.part = s.batched ? t->d_part + seg0 * bp.seg_part : nullptr;
+    bp.emit_count = (first && s.fill_cache) ? t->d_emit_count : nullptr;
+    bp.emit_pix = t->d_emit_pix; bp.emit_rgb = t->d_emit_rgb;
+    bp.fenced = reinterpret_cast<unsigned long long *>(t->d_stats + 65); bp.fence_slots_cap = (uint32_t)t->cap;
+    bp.fence_slots = t->dbg.fence_slots > 0 ? (uint32_t)std::min<long long>(t->cap, t->dbg.fence_slots) : (uint32_t)t->cap;
+    bp.last_inplace = t->dbg.last_inplace ? 1 : 0;
+    bp.tile_geoms = (first && t->tile_geoms_valid) ? t->d_tile_geoms : nullptr;
+    if (t->split_mesh) {
+        bp.keys = t->d_keys + seg0 * (size_t)t->cap; bp.seg_keys = (size_t)t->cap;
+        bp.items = t->d_items + seg0 * t->seg_items; bp.seg_items = t->seg_items;
+        bp.item_count = t->d_item_count + 2 * seg0;          // (a launch set's K counts, then its K cursors: one memset)
+        bp.item_cursor = bp.item_count + s.K;
+        bp.tile_done = (first && t->d_tile_done) ? t->d_tile_done + seg0 * (size_t)t->maxTiles : nullptr;
+    } else {
+        bp.keys = nullptr; bp.items = nullptr; bp.item_count = nullptr; bp.item_cursor = nullptr; bp.seg_keys = bp.seg_items = 0; bp.tile_done = nullptr;
+    }
+    return bp;
+}
+
+int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lane, int prev_lane, bool defer) {
+    hipStream_t stream = lane == 0 ? t->stream : t->lane_stream[lane];
+    const int nb = t->nbins;
+    // (the apps variant's albedo AOV is written by iteration 1 alone: only a launch set that contains it needs the general kernel for it)
+    const bool needs_albedo = t->d_albedo && iter_first == 1;
+    const BatchPlan p = plan_batch(*t, K, defer, needs_albedo);
+    BatchSet s;
+    s.iter_first = iter_first; s.K = K; s.stride = stride; s.seg0 = (size_t)lane * t->kmax;
+    s.cache_on = t->cache_active(); s.use_cache = s.cache_on && t->cache_valid && iter_first != 1; s.fill_cache = s.cache_on && !s.use_cache;
+    s.batched = K > 1 || t->lanes > 1;
+    const bool masks_off = t->capture_bounce >= 0 && !t->dbg.keep_dir_skip;
+    s.dir_bins = masks_off ? ~0ull : t->dir_bins; s.ntab_bins = masks_off ? 0ull : t->ntab_bins;
+    const SegmentViews v(t, p, s.seg0);
+    const KernelTimer kt{t, stream};
+    // per-bounce totals and group totals are accumulated with atomics, and the lit planes are set bit by bit: the lane's previous set
+    // left them zero (k_stats, k_gather) -- unless the lane is marked, then all of its segments are cleared here, once
+    if (t->aux_dirty[lane]) {
+        HIPCHECK(hipMemsetAsync(v.total, 0, sizeof(int32_t) * t->seg_totals * (size_t)t->kmax, stream));
+        if (t->d_part)                               // (the planes: behind each segment's radiance, cap / 32 words per segment)
+            HIPCHECK(hipMemset2DAsync(t->d_part + s.seg0 * t->seg_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
+                                      (size_t)t->cap / 8, (size_t)t->kmax, stream));
+        t->aux_dirty[lane] = false;
+    }
+    if (s.fill_cache) HIPCHECK(hipMemsetAsync(t->d_emit_count, 0, sizeof(int32_t), stream));
     for (int b = 0; b < t->traceDepth; b++) {
         const bool first = b == 0;
-        if (first && use_cache) {
+        if (first && s.use_cache) {
             // first-bounce cache: the sorted bounce-0 stream and its light hits are identical every iteration
             // when primary rays are not jittered, so bounce 0 is skipped (intent of src/pathtrace.cu:492-499,514)
-            hipLaunchKernelGGL(k_seed_totals, dim3(1), dim3(256), 0, stream, totals(0, 0), seg_totals, K, t->d_cache_totals, 2 * nb);
-            if (batched) {
-                // (the cached bounce-0 misses need nothing: their flags were cleared with the batch's)
-                const size_t seg_part = t->seg_part;
+            // (the cached bounce-0 misses need nothing: their flags were cleared with the batch's)
+            hipLaunchKernelGGL(k_seed_totals, dim3(1), dim3(256), 0, stream, v.totals(0, 0), t->seg_totals, K, t->d_cache_totals, 2 * nb);
+            if (s.batched)
                 hipLaunchKernelGGL(k_replay_emission, dim3(64), dim3(256), 0, stream, t->tm, t->d_emit_count, t->d_emit_pix, t->d_emit_rgb,
-                                   t->d_part + seg0 * seg_part, seg_part, K, 0, (uint32_t)t->cap);
-            } else {
+                                   t->d_part + s.seg0 * t->seg_part, t->seg_part, K, 0, (uint32_t)t->cap);
+            else
                 hipLaunchKernelGGL(k_replay_emission, dim3(64), dim3(256), 0, stream, t->tm, t->d_emit_count, t->d_emit_pix, t->d_emit_rgb,
                                    t->d_image, (size_t)0, 1, 1, (uint32_t)t->cap);
-            }
             continue;
         }
-        BounceParams bp;
-        bp.sc = t->scene(); bp.sc.tri_lds = t->tri_lds; bp.sc.ntri_lds = t->split_mesh ? 0 : t->ntri_lds; bp.sc.cull = t->cull; bp.cam = t->cam; bp.tm = t->tm;
-        for (int k = 0; k < 3; k++) if (bp.sc.cull && !(std::fabs(t->cam.position[k]) <= 0.5f * CULL_FAR_ORIGIN)) bp.sc.cull = 2;      // (a camera far out: cullMask, FAR ORIGINS)
-        bp.sc.ldsblob = t->d_ldsblob;
-        // (split: the mesh search runs in k_mesh from global memory, so the triangle tables need no LDS)
-        // bounce b writes its stage into soa[1 - (b & 1)] (bounce 0 of a cache-enabled tracer: into soa[2], kept across
-        // iterations) and reads the previous bounce's through that bounce's local index and run tables
-        const bool from_cache = (b == 1 && cache_on), to_cache = (first && cache_on);
-        bp.in = from_cache ? t->soa[2] : soa_shift(t->soa[b & 1], seg0 * t->cap);
-        bp.stage = to_cache ? t->soa[2] : soa_shift(t->soa[1 - (b & 1)], seg0 * t->cap);
-        bp.in_totals = first ? nullptr : from_cache ? t->d_cache_totals : totals(b - 1, 0);
-        bp.in_super = first ? nullptr : from_cache ? t->d_cache_super : supers(b - 1, 0);
-        bp.in_chunk = first ? nullptr : from_cache ? t->d_cache_chunk : chunks(b - 1);
-        const int gx_b = first ? gx_first : gx_later;                       // this launch's workgroups per segment
-        bp.in_gx = from_cache ? t->cache_gx : (b == 1 ? gx_first : gx_later);      // ... and those of the launch whose run tables it reads
-        bp.seg_in_totals = from_cache ? 0 : seg_totals; bp.seg_in_chunk = from_cache ? 0 : seg_chunk;
-        bp.image = t->d_image;
-        bp.iter = iter_first; bp.iter_stride = stride; bp.traceDepth = t->traceDepth; bp.bounce = b;
-        bp.aa = t->opt.antialiasing; bp.dof = t->opt.depth_of_field; bp.sort = t->opt.sort_by_material; bp.uses_uv = t->uses_uv; bp.dir_bins = batch_dir_bins;
-        bp.ntab_bins = batch_ntab_bins; bp.apps = t->opt.apps_variant; bp.albedo = t->d_albedo;
-        // (the masks tell the READER of a stage what its records hold; a launch that WRITES with other masks than it reads with -- a cached
-        // camera bounce replayed while a debug capture has switched them off, or the other way round -- gets both: in_* for what it reads)
-        bp.in_dir_bins = from_cache ? t->cache_dir_bins : bp.dir_bins; bp.in_ntab_bins = from_cache ? t->cache_ntab_bins : bp.ntab_bins;
-        // (one-word local index where no workgroup's chunk can pass 128 tiles: this launch's, and that of the launch whose stage it reads)
-        auto idx16_of = [&](int gxw) { return (!getenv("PTX_DEBUG_NO_IDX16") && (t->maxTiles + gxw - 1) / std::max(gxw, 1) <= 128) ? 1 : 0; };
-        bp.idx16 = idx16_of(first ? gx_first : gx_later);
-        bp.in_idx16 = first ? 0 : from_cache ? t->cache_idx16 : idx16_of(b == 1 ? gx_first : gx_later);
-        bp.nbins = nb; bp.maxTiles = t->maxTiles;
-        bp.counts_all = counts_all; bp.counts_scat = counts_scat;
-        bp.chunk = to_cache ? t->d_cache_chunk : chunks(b); bp.chunk_cap = (int32_t)chunk_cap;
-        bp.super_all = supers(b, 0); bp.super_scat = supers(b, 1);
-        bp.totals_all = totals(b, 0); bp.totals_scat = totals(b, 1);
-        bp.nsuper = t->nsuper;
-        bp.seg_in = from_cache ? 0 : (size_t)t->cap; bp.seg_stage = to_cache ? 0 : (size_t)t->cap;
-        bp.seg_counts = seg_counts; bp.seg_chunk = to_cache ? 0 : seg_chunk; bp.seg_totals = seg_totals;
-        bp.stamps = t->d_stamps;
-        bp.seg_part = t->seg_part;
-        bp.part = batched ? t->d_part + seg0 * bp.seg_part : nullptr;
-        bp.emit_count = (first && fill_cache) ? t->d_emit_count : nullptr;
-        bp.emit_pix = t->d_emit_pix; bp.emit_rgb = t->d_emit_rgb;
-        bp.fenced = reinterpret_cast<unsigned long long *>(t->d_stats + 65); bp.fence_slots = t->fence_slots; bp.fence_slots_cap = (uint32_t)t->cap;
-        bp.last_inplace = t->last_inplace ? 1 : 0;
-        bp.tile_geoms = (first && t->tile_geoms_valid) ? t->d_tile_geoms : nullptr;
-        if (t->split_mesh) {
-            bp.keys = t->d_keys + seg0 * (size_t)t->cap; bp.seg_keys = (size_t)t->cap;
-            bp.items = t->d_items + seg0 * t->seg_items; bp.seg_items = t->seg_items;
-            bp.item_count = t->d_item_count + 2 * seg0;          // (a launch set's K counts, then its K cursors: one memset)
-            bp.item_cursor = bp.item_count + K;
-            bp.tile_done = (first && t->d_tile_done) ? t->d_tile_done + seg0 * (size_t)t->maxTiles : nullptr;
+        const BounceParams bp = fill_bounce_params(t, s, p, v, b);
+        const int gx_b = first ? p.gx_first : p.gx_later;                       // this launch's workgroups per segment
+        int rc;
+        if (t->split_mesh) {       // pass 1 parks the mesh candidates, k_mesh searches them, k_finish shades what it found, pass 2 ranks
             HIPCHECK(hipMemsetAsync(bp.item_count, 0, sizeof(int32_t) * 2 * (size_t)K, stream));
-            KT(first ? 0 : 1, { int rcl = launch_bounce(t, first, 1, needs_albedo, dim3(gx_b, K), lds_bounce, stream, bp); if (rcl != PTX_OK) return rcl; });
-            // the per-lane traversal stack lives in LDS and is what limits k_mesh's occupancy: as many entries as the longest walk needs
-            // (k_mesh's waves draw from the segment's queue until it is empty: one round of the kernel's occupancy is all the grid needs)
-            // Three workgroups per CU, not the five its LDS would admit: a workgroup holds 31 KB (the walks' stacks), five of them nearly all
-            // of a CU's 160 KB -- while k_mesh runs, the OTHER launch sets' kernels then find no LDS to start in and the overlap of the three
-            // sets stops.  With three, k_mesh alone is 4 % slower and C5's wall time 2 % shorter (1.066 -> 1.045 ms per iteration; 4: 1.054,
-            // 2: 1.059; nine runs each on one box); a wave also draws from 460 rays instead of 270.
-            const int mesh_gx = std::max(1, t->cus * (t->dbg_mesh_wg_per_cu > 0 ? t->dbg_mesh_wg_per_cu : PT_MESH_WG_PER_CU) / K);
-            KT(2, { t->ks->mesh(first ? 1 : 0, dim3(mesh_gx, K), sizeof(int32_t) * ((size_t)t->bvh_stack * 256 + 32 * MESH_GEOM_WORDS), stream, &bp, t->bvh_stack);
-                    t->ks->finish(first ? 1 : 0, dim3(std::max(1, grid / K), K), stream, &bp); });
-            const size_t lds_pass2 = sizeof(int32_t) * ((size_t)ldsHeadWords(nb) + TILE);      // (ranking head + one key per slot)
-            KT(3, { int rcl = launch_bounce(t, first, 2, needs_albedo, dim3(gx_b, K), lds_pass2, stream, bp); if (rcl != PTX_OK) return rcl; });
+            if ((rc = kt.begin(first ? 0 : 1)) != PTX_OK) return rc;
+            if ((rc = launch_bounce(t, first, 1, needs_albedo, dim3(gx_b, K), p.lds_bounce, stream, bp)) != PTX_OK) return rc;
+            if ((rc = kt.end()) != PTX_OK || (rc = kt.begin(2)) != PTX_OK) return rc;
+            t->ks->mesh(first ? 1 : 0, dim3(p.mesh_gx, K), p.lds_mesh, stream, &bp, t->bvh_stack);
+            t->ks->finish(first ? 1 : 0, dim3(p.finish_gx, K), stream, &bp);
+            if ((rc = kt.end()) != PTX_OK || (rc = kt.begin(3)) != PTX_OK) return rc;
+            if ((rc = launch_bounce(t, first, 2, needs_albedo, dim3(gx_b, K), p.lds_pass2, stream, bp)) != PTX_OK) return rc;
+            if ((rc = kt.end()) != PTX_OK) return rc;
         } else {
-            bp.keys = nullptr; bp.items = nullptr; bp.item_count = nullptr; bp.item_cursor = nullptr; bp.seg_keys = bp.seg_items = 0; bp.tile_done = nullptr;
-            KT(first ? 0 : 1, { int rcl = launch_bounce(t, first, 0, needs_albedo, dim3(gx_b, K), lds_bounce, stream, bp, gx_last); if (rcl != PTX_OK) return rcl; });
+            if ((rc = kt.begin(first ? 0 : 1)) != PTX_OK) return rc;
+            if ((rc = launch_bounce(t, first, 0, needs_albedo, dim3(gx_b, K), p.lds_bounce, stream, bp, p.gx_last)) != PTX_OK) return rc;
+            if ((rc = kt.end()) != PTX_OK) return rc;
         }
-
-        if (first && fill_cache) {
-            HIPCHECK(hipMemcpyAsync(t->d_cache_totals, totals(0, 0), sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToDevice, stream));
-            HIPCHECK(hipMemcpyAsync(t->d_cache_super, supers(0, 0), sizeof(int32_t) * 2 * nb * t->nsuper, hipMemcpyDeviceToDevice, stream));
+        if (first && s.fill_cache) {
+            HIPCHECK(hipMemcpyAsync(t->d_cache_totals, v.totals(0, 0), sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToDevice, stream));
+            HIPCHECK(hipMemcpyAsync(t->d_cache_super, v.supers(0, 0), sizeof(int32_t) * 2 * nb * t->nsuper, hipMemcpyDeviceToDevice, stream));
             t->cache_gx = gx_b;
             t->cache_dir_bins = bp.dir_bins; t->cache_ntab_bins = bp.ntab_bins; t->cache_idx16 = bp.idx16;
             t->cache_valid = true;
         }
-        if (t->capture_bounce == b && t->d_cap && b + 1 < t->traceDepth) {       // K == 1 here (see ptx_render)
-            // (K == 1, lane 0: segment 0 of the buffers)
-            int32_t *gs = t->d_cap + 3 * (size_t)t->cap + nb, *ga = gs + chunk_cap + 1;
-            hipLaunchKernelGGL(k_capture_prefix, dim3(1), dim3(64), 0, stream, bp.chunk, (int)chunk_cap, nb * gx_b, gs, ga);
-            hipLaunchKernelGGL(k_capture, dim3(std::min(1024, (t->cap + 255) / 256)), dim3(256), 0, stream, bp.stage, bp.chunk, (int)chunk_cap,
+        if (t->capture_bounce == b && t->d_cap && b + 1 < t->traceDepth) {       // (K == 1, lane 0 -- see ptx_render: segment 0 of the buffers)
+            int32_t *gs = t->d_cap + 3 * (size_t)t->cap + nb, *ga = gs + p.chunk_cap + 1;
+            hipLaunchKernelGGL(k_capture_prefix, dim3(1), dim3(64), 0, stream, bp.chunk, (int)p.chunk_cap, nb * gx_b, gs, ga);
+            hipLaunchKernelGGL(k_capture, dim3(std::min(1024, (t->cap + 255) / 256)), dim3(256), 0, stream, bp.stage, bp.chunk, (int)p.chunk_cap,
                                nb * gx_b, gs, ga, t->cap, t->d_cap, t->d_cap_f, bp.idx16);
-            HIPCHECK(hipMemcpyAsync(t->d_cap + 3 * (size_t)t->cap, totals(b, 1), sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, stream));
+            HIPCHECK(hipMemcpyAsync(t->d_cap + 3 * (size_t)t->cap, v.totals(b, 1), sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, stream));
             t->cap_filled = true;
         }
     }
-    if (defer) {                                     // render-ahead: gather and statistics follow per iteration (finish_segment)
-        t->ahead[lane].use_cache = use_cache;
-        t->ahead[lane].dir_bins = batch_dir_bins; t->ahead[lane].ntab_bins = batch_ntab_bins;
+    if (defer) {                                     // render-ahead: gather and statistics follow per iteration (ahead_finish_segment)
+        t->ahead[lane].use_cache = s.use_cache;
+        t->ahead[lane].dir_bins = s.dir_bins; t->ahead[lane].ntab_bins = s.ntab_bins;
         HIPCHECK(hipGetLastError());
         return PTX_OK;
     }
     if (prev_lane >= 0 && prev_lane != lane) HIPCHECK(hipStreamWaitEvent(stream, t->ev_chain[prev_lane], 0));      // the previous batch's gather + stats
-    if (batched)
-        hipLaunchKernelGGL(k_gather, dim3(std::min(2048, (t->tm.owned + 255) / 256)), dim3(256), 0, stream, t->tm, t->cam.resx, K,
-                           t->seg_part, t->d_part + seg0 * t->seg_part, t->d_image, (uint32_t)t->cap);
-    launch_stats(t, stream, seg0, K, use_cache, batch_dir_bins, batch_ntab_bins);
+    launch_gather_stats(t, stream, s.seg0, K, s.use_cache, s.dir_bins, s.ntab_bins);
     if (t->lanes > 1) HIPCHECK(hipEventRecord(t->ev_chain[lane], stream));
     HIPCHECK(hipGetLastError());
     t->iterations += K;
-    (void)nsuper;
     return PTX_OK;
 }
 
@@ -797,13 +752,10 @@ int ahead_start(ptx_tracer *t, int lane, int first) {
 // (its k_gather and k_stats leave the segment's plane and totals zero, as the tail of a whole batch does)
 int ahead_finish_segment(ptx_tracer *t, int lane, int seg) {
     const ptx_tracer::Ahead &a = t->ahead[lane];
-    const size_t sg = (size_t)lane * t->kmax + seg, seg_part = t->seg_part;
     const bool was_dirty = t->aux_dirty[lane];
     t->aux_dirty[lane] = true;                           // (until both are enqueued)
     HIPCHECK(hipStreamWaitEvent(t->stream, t->ev_ahead1[lane], 0));
-    hipLaunchKernelGGL(k_gather, dim3(std::min(2048, (t->tm.owned + 255) / 256)), dim3(256), 0, t->stream, t->tm, t->cam.resx, 1,
-                       seg_part, t->d_part + sg * seg_part, t->d_image, (uint32_t)t->cap);
-    launch_stats(t, t->stream, sg, 1, a.use_cache, a.dir_bins, a.ntab_bins);
+    launch_gather_stats(t, t->stream, (size_t)lane * t->kmax + seg, 1, a.use_cache, a.dir_bins, a.ntab_bins);
     HIPCHECK(hipGetLastError());
     t->aux_dirty[lane] = was_dirty;
     t->iterations += 1;
@@ -849,52 +801,6 @@ int ptx_create(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_mate
         (void)hipGetLastError();
         cap = used / 2;
     }
-}
-
-// Iterations per launch set and launch sets in flight, from sizes alone: the explicit option, or the rule below (about 24 M paths per
-// set, within a quarter of the device's memory: mem_free / mem_total, 0 = unknown; budget_mb > 0 = PTX_DEBUG_MEM_BUDGET_MB, tests only),
-// then the cap of the out-of-memory retry (kmax_cap > 0), 64, and the 4 GiB of the prefix tables.  refusal: non-empty = nothing fits.
-struct LaunchPlan { int kmax = 1, lanes = 1; std::string refusal; };
-static LaunchPlan plan_launch_sets(int owned_pixels, int nbins, int maxTiles, const ptx_options &opt, int kmax_cap, size_t mem_free, size_t mem_total,
-                                   long long budget_mb) {
-    LaunchPlan p;
-    // three launch sets in flight (one per stream) unless told otherwise: kernels of different sets overlap and
-    // kernel tails are filled (C4, iterations per set x sets: 8 x 1 0.41, 8 x 2 0.30, 12 x 3 0.276, 12 x 4 0.31 ms per
-    // iteration); also with one iteration per launch set, i.e. frames so large that only one fits the memory rule below
-    // (7680 x 4320: 6.2 -> 4.75 ms per iteration); needs the per-iteration radiance buffers
-    p.lanes = opt.lanes >= 1 ? std::min(opt.lanes, MAX_LANES) : 3;
-    // With the first-bounce cache the iterations of a batch all start from the one cached bounce-0 stream
-    int kmax = opt.batch;
-    if (kmax <= 0) {
-        // about 24 M paths per launch set, at least 12 iterations: 12 of a 1080p frame, up to 32 of a small frame or of one rank's tile
-        // (1/8 of 1080p: 0.058 -> 0.048 ms per iteration with 32 instead of 8), fewer only where the streams of all launch sets in
-        // flight (two stages of 19 words + radiance + the split search's keys and queue = 176 B per path and iteration) would pass
-        // 64 GB of the 288.  Round 4: 12 instead of 5 at 3840x2160 (the rule was 16 GB with a guessed 400 B per path): every kernel of the
-        // split bounce gets 2.4x the work per launch -- C5 1.23 -> 1.17 ms per iteration with round 3's kernels, and what the refilling
-        // k_mesh needs: 1.4 M parked rays per launch instead of 0.6 M for the chip's 330 k lanes.
-        // Round 5: the 64 GB are a ceiling, not a constant -- a quarter of what the device (a CPX / NPS partition, a GPU shared by
-        // several ranks) has free or in total, whichever is less; and an allocation that still fails is retried with half the
-        // iterations per set (ptx_create) before the caller is told.
-        const long long owned = std::max(owned_pixels, 1);
-        long long want = ((24LL << 20) + owned / 2) / owned;
-        want = std::min<long long>(32, std::max<long long>(12, want));
-        long long budget = 64LL << 30;
-        if (mem_total > 0) budget = std::min<long long>(budget, (long long)(std::min(mem_free, mem_total) / 4));
-        if (budget_mb > 0) budget = budget_mb << 20;
-        kmax = (int)std::min<long long>(want, std::max<long long>(1, budget / (176LL * p.lanes * owned)));
-    }
-    if (kmax_cap > 0 && kmax > kmax_cap) kmax = kmax_cap;      // (the retry after an allocation failed)
-    if (kmax > 64) kmax = 64;
-    // the per-tile prefix tables grow with bins x tiles x iterations in flight: keep them under 4 GiB by putting fewer
-    // iterations into a launch set, then fewer launch sets in flight
-    auto counts_bytes = [&](int k, int l) { return sizeof(int32_t) * (2 * (size_t)nbins + 1) * maxTiles * (size_t)k * l; };
-    while (counts_bytes(kmax, p.lanes) > (4ULL << 30) && kmax > 1) kmax /= 2;
-    if (counts_bytes(kmax, p.lanes) > (4ULL << 30)) p.lanes = 1;
-    if (counts_bytes(kmax, 1) > (4ULL << 30))
-        p.refusal = "material sort over " + std::to_string(nbins) + " materials on " + std::to_string(maxTiles) +
-                    " tiles needs more than 4 GiB of prefix tables: render with sort_by_material = 0";
-    p.kmax = kmax;
-    return p;
 }
 
 static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, const ptx_material *materials,
@@ -946,6 +852,8 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
 #define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(PTX_ERR_HIP); } } while (0)
     t->ks = ks; t->ksl = ksl;
     t->device = dev; t->opt = opt; t->traceDepth = t->maxBounces = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
+    t->dbg = read_debug_switches();                      // (once: nothing below, and no later call, looks at the environment again)
+    t->sort_by_material = opt.sort_by_material != 0;
     hipDeviceProp_t prop;
     HC(hipGetDeviceProperties(&prop, dev));
     // ---- 3. tile split: rows owned by this device, and the grid its tiles can use
@@ -959,44 +867,22 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     t->maxTiles = (std::max(t->tm.owned, 1) + TILE - 1) / TILE;
     t->cap = t->maxTiles * TILE;                          // whole tiles: the stage is written tile by tile
     t->nbins = opt.sort_by_material ? (nmaterials > 0 ? nmaterials : 1) : 1;
-    {
-        int per_cu = 16;                      // upper bound (sizes the per-workgroup tables); enqueue_batch picks 7, 8 or 16 per CU
-        if (const char *e = getenv("PTX_DEBUG_WG_PER_CU")) { per_cu = std::max(1, atoi(e)); t->grid_forced = true; }      // tuning experiments only
-        t->cus = prop.multiProcessorCount;
-        // (also for K segments in one launch: a 1/8 tile's ten iterations as 10 x 101 workgroups of 10 tiles run 6 % FASTER than as
-        // 10 x 128 of 8 -- a grid that does not quite fill the chip leaves room for the other launch set's kernel to start)
-        t->grid = std::max(1, std::min(t->maxTiles, prop.multiProcessorCount * per_cu));
-    }
-    t->grid_seg = std::max(1, std::min(t->grid, t->maxTiles));      // what one segment (iteration) can use: sizes its tables
+    t->cus = prop.multiProcessorCount;
+    plan_grids(*t);
     t->nsuper = (t->grid_seg + 63) / 64;
     // ---- 4. the scene's tables, on the host (pt_scene.hip)
     HostScene hs;
-    SceneSwitches sw;
-    sw.no_wide_bvh = getenv("PTX_DEBUG_NO_WIDE_BVH") != nullptr; sw.no_chunks = getenv("PTX_DEBUG_NO_CHUNKS") != nullptr;
-    sw.no_dir_skip = getenv("PTX_DEBUG_NO_DIR_SKIP") != nullptr; sw.no_normal_codes = getenv("PTX_DEBUG_NO_NORMAL_CODES") != nullptr;
-    sw.force_split = getenv("PTX_DEBUG_FORCE_SPLIT") != nullptr; sw.no_objcull = getenv("PTX_DEBUG_NO_OBJCULL") != nullptr;
-    if (const int rc = pt_prepare_scene(ngeoms, geoms, nmaterials, materials, opt, t->tm.owned, t->nbins, prop.sharedMemPerBlock, sw, hs)) return fail(rc);
+    if (const int rc = pt_prepare_scene(ngeoms, geoms, nmaterials, materials, opt, t->tm.owned, t->nbins, prop.sharedMemPerBlock, t->dbg.scene, hs)) return fail(rc);
     static_cast<SceneFacts &>(*t) = hs;
     // ---- 5. iterations per launch set, launch sets in flight
     {
         size_t mem_free = 0, mem_total = 0;
         if (opt.batch <= 0 && hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { mem_free = mem_total = 0; (void)hipGetLastError(); }
-        const char *e = getenv("PTX_DEBUG_MEM_BUDGET_MB");      // tests only
-        const LaunchPlan plan = plan_launch_sets(t->tm.owned, t->nbins, t->maxTiles, opt, kmax_cap, mem_free, mem_total, e ? std::max(1LL, atoll(e)) : 0);
+        const LaunchPlan plan = plan_launch_sets(t->tm.owned, t->nbins, t->maxTiles, opt, kmax_cap, mem_free, mem_total, t->dbg.mem_budget_mb);
         if (!plan.refusal.empty()) { set_error(PTX_ERR_UNSUPPORTED, plan.refusal); return fail(PTX_ERR_UNSUPPORTED); }
         t->kmax = *kmax_used = plan.kmax;
         t->lanes = plan.lanes;
     }
-    t->no_fast = getenv("PTX_DEBUG_NO_FAST") != nullptr;
-    t->no_last = getenv("PTX_DEBUG_NO_LAST") != nullptr;
-    t->last_inplace = getenv("PTX_DEBUG_LAST_INPLACE") != nullptr;
-    t->force_fast = getenv("PTX_DEBUG_FORCE_FAST") != nullptr;
-    t->no_tangents = getenv("PTX_DEBUG_NO_TANGENTS") != nullptr;
-    if (const char *e = getenv("PTX_DEBUG_TOTAL_WG_PER_CU")) t->dbg_total_wg_per_cu = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_NSETS")) t->dbg_nsets = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_EXTRA_LDS")) t->dbg_extra_lds = std::max(0, std::min(atoi(e), 32768)) & ~15;
-    if (const char *e = getenv("PTX_DEBUG_MESH_WG_PER_CU")) t->dbg_mesh_wg_per_cu = std::max(0, atoi(e));
-    if (const char *e = getenv("PTX_DEBUG_SPLIT_MIN")) t->split_min_paths = std::max(1LL, atoll(e));      // tuning experiments only
     // ---- 6. streams and events
     if (stream) { t->stream = (hipStream_t)stream; t->own_stream = false; }
     else {
@@ -1005,7 +891,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         // the bounce kernels' workgroups
         int prio_lo = 0, prio_hi = 0;
         if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) { prio_lo = prio_hi = 0; (void)hipGetLastError(); }
-        if (getenv("PTX_DEBUG_NO_PRIORITY")) prio_hi = prio_lo;
+        if (t->dbg.no_priority) prio_hi = prio_lo;
         HC(hipStreamCreateWithPriority(&t->stream, hipStreamNonBlocking, prio_hi));
         t->own_stream = true;
     }
@@ -1018,11 +904,8 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
                 // priority at that level dispatch 2 % faster than at the default level (C4 wall 0.216 -> 0.211 ms), any
                 // mix of levels lies in between, the veneer's per-call loop does not care
                 int prio_lo = 0, prio = 0;
-                if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio) != hipSuccess || getenv("PTX_DEBUG_NO_PRIORITY")) { prio = 0; (void)hipGetLastError(); }
-                if (const char *e = getenv("PTX_DEBUG_LANE_PRIO")) {          // tuning experiments only: p1,p2,... (HIP priority values)
-                    const char *q = e;
-                    for (int k = 1; k <= l && q; k++) { prio = atoi(q); q = strchr(q, ','); if (q) q++; }
-                }
+                if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio) != hipSuccess || t->dbg.no_priority) { prio = 0; (void)hipGetLastError(); }
+                if (t->dbg.has_lane_prio) prio = t->dbg.lane_prio[l];
                 HC(hipStreamCreateWithPriority(&t->lane_stream[l], hipStreamNonBlocking, prio));
             }
             HC(hipEventCreateWithFlags(&t->ev_join[l], hipEventDisableTiming));
@@ -1047,6 +930,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     }
     t->h_aabb = std::move(hs.aabb);                       // (the host keeps corners for the camera tile masks)
     for (const DGeom &g : hs.geoms) t->h_geom_type.push_back(g.type);
+    t->has_bvh = t->d_bvh_root != nullptr;
     t->h_roots = hs.roots; t->h_depths = hs.depths; t->h_wroots = hs.wroots; t->h_wneeds = hs.wneeds;
     t->h_spec = std::move(hs.h_spec);
     const size_t npix = (size_t)W * H, nseg = (size_t)t->kmax * t->lanes, nb = (size_t)t->nbins;
@@ -1069,7 +953,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         HC(t->d_keys.alloc((size_t)t->cap * nseg));
         HC(t->d_items.alloc(t->seg_items * nseg));
         HC(t->d_item_count.alloc(2 * nseg));              // [nseg] counts (pass 1), [nseg] cursors (k_mesh)
-        if (!getenv("PTX_DEBUG_NO_FIRST_FUSION")) { HC(t->d_tile_done.alloc((size_t)t->maxTiles * nseg)); HC(t->d_tile_done.zero()); }
+        if (!t->dbg.no_first_fusion) { HC(t->d_tile_done.alloc((size_t)t->maxTiles * nseg)); HC(t->d_tile_done.zero()); }
     }
     HC(t->d_counts.alloc((2 * nb + 1) * t->maxTiles * nseg));
     HC(t->d_chunk.alloc(2 * 3 * nb * t->grid_seg * nseg)); HC(t->d_chunk.zero());
@@ -1089,8 +973,6 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     HC(t->d_tile_geoms.alloc((size_t)std::max(t->maxTiles, 1)));
     if (update_tile_geoms(t) != PTX_OK) return fail(PTX_ERR_HIP);
     HC(t->d_stats.alloc(69)); HC(t->d_stats.zero());
-    t->fence_slots = (uint32_t)t->cap;
-    if (const char *e = getenv("PTX_DEBUG_FENCE_SLOTS")) t->fence_slots = (uint32_t)std::min<long long>(t->cap, std::max<long long>(1, atoll(e)));      // tests only
 #undef HC
     *out = t;
     return PTX_OK;
@@ -1160,22 +1042,11 @@ int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
     HIPCHECK(hipSetDevice(t->device));
     ahead_discard(t);
     if (const int rc = fold_render_time(t)) return rc;      // (before the events are reused)
+    // (the one switch read per call, not at create: tools/gpu_prequeue.py toggles it on a live tracer)
     if (const char *e = getenv("PTX_DEBUG_PREQUEUE_US")) hipLaunchKernelGGL(k_hold, dim3(1), dim3(64), 0, t->stream, (long long)atoi(e) * 100);      // (100 MHz)
     HIPCHECK(hipEventRecord(t->ev_start, t->stream));
     // per-kernel timing and the debug capture look at one launch set at a time
-    // A run shorter than lanes x kmax iterations is cut into equal launch sets, one per lane, as long as each keeps at
-    // least split_min_paths primary rays (below that the launches no longer fill the chip and overlap buys nothing).
-    int kb = t->kmax;
-    if (t->lanes > 1 && count < t->lanes * t->kmax) {
-        const long long owned = std::max(t->tm.owned, 1);
-        const int kmin = (int)std::min<long long>(t->kmax, (t->split_min_paths + owned - 1) / owned);
-        // ... and into TWO sets rather than three while two can hold the call: a one-shot of three sets starts its third
-        // late (the host issues the sets one after the other) and makes all of them smaller -- 20 iterations as 10 + 10
-        // instead of 7 + 7 + 6: full frame equal, 1/2 tile -2 %, 1/4 and 1/8 tile -7 % (round 3's sweep; tools/gpu_tile_grid_sweep.py is its successor)
-        int nsets = count <= 2 * t->kmax ? std::min(2, t->lanes) : t->lanes;
-        if (t->dbg_nsets > 0) nsets = std::min(t->dbg_nsets, t->lanes);
-        kb = std::min(t->kmax, std::max(kmin, (count + nsets - 1) / nsets));
-    }
+    const int kb = sets_per_call(count, t->kmax, t->lanes, t->tm.owned, t->dbg.split_min_paths, t->dbg.nsets);
     const int nl = (t->lanes > 1 && !t->ktiming && t->capture_bounce < 0 && count > kb) ? t->lanes : 1;
     auto fork = [&]() -> int {                           // the other lanes start after what is on the main stream so far
         HIPCHECK(hipEventRecord(t->ev_fork, t->stream));
@@ -1185,8 +1056,7 @@ int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
     if (nl > 1) { int rc = fork(); if (rc != PTX_OK) return rc; }
     int batch = 0, prev_lane = -1;
     bool used[MAX_LANES] = {};
-    int first_set = 0;
-    if (const char *e = getenv("PTX_DEBUG_FIRST_SET")) first_set = atoi(e);      // tuning experiments only
+    const int first_set = t->dbg.first_set;
     for (int k = 0; k < count; batch++) {
         int K = std::min(nl > 1 ? kb : t->kmax, count - k);
         if (nl > 1 && first_set > 0 && count <= 2 * t->kmax) K = std::min(batch == 0 ? std::min(first_set, t->kmax) : t->kmax, count - k);
