@@ -452,6 +452,30 @@ int  ptx_moments_summarize(ptx_moments *m, const ptx_moments_params *p, ptx_mome
  * handle's first add. */
 int  ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params *dp, const ptx_variance_params *vp, int min_batches,
                           int spp);
+/* ---- the temporal history and the measured variance together, csrc/pt_temporal.hip (k_reproject_measured) ---------------------------
+ * ptx_denoise_variance(t, h, dp, tp, vp, spp) with one change: the V written into the state for a hit pixel.  Taps, acceptance tests,
+ * n_h, h, mix, n, the segment rule, the state layout, the filter and the outputs (ptx_read_denoised, ptx_read_variance,
+ * ptx_temporal_read) are that call's.  Definition (tests/temporal_measured_ref.py restates it):
+ *   B = the moments handle's batch count (one number per handle: every add touches every pixel), min_batches <= 0 means 4, 1 is refused.
+ *   B < min_batches: the call IS ptx_denoise_variance(t, h, ...), decided on the host: the same kernels, the same bits; the moments
+ *   state is not read.
+ *   B >= min_batches: q = max(g^T M g / (B - 1), 0), g_k = l_k / max(albedo_k, 1e-3): the per-sample variance of the demodulated
+ *   luminance as ptx_denoise_measured takes it, an estimate with B - 1 degrees of freedom.
+ *     A pixel that inherits a V (hist valid, hist carries V, n_h > 0), with e, V_h, mu_h of ptx_denoise_variance (their bilinear
+ *     weights, and only theirs, from the projection evaluated in double: a measured V differs so much between neighbouring pixels that
+ *     an fp32 ulp of u is up to 2 % of V_h; taps, n_h, h and mix keep the fp32 weights and that call's bits): e estimates the same
+ *     per-sample variance with one degree of freedom, so the current view's share is the two pooled by degrees of freedom,
+ *       V_c = ((B - 1) q + e) / B,   V = (n_h V_h + spp V_c) / (n_h + spp)       (ptx_denoise_variance: V_c = e).
+ *     Every other hit pixel (no hist, a hist without V, n_h == 0, a specular pixel with specular_history == 0): V = q, where
+ *     ptx_denoise_variance writes -1 for its spatial estimate; so no spatial estimate is taken anywhere.  Miss pixels: 0.
+ *   v0 = V / n as there, and the state is marked as carrying V: ptx_denoise_variance and this call share a handle in any order.
+ * Refused, with nothing enqueued: everything ptx_denoise_variance refuses with a handle (demodulate == 0 included) and everything
+ * ptx_denoise_measured refuses (a NULL handle, no add yet, another device or size, tile_world > 1, min_batches == 1).  Both handles'
+ * events are waited for and recorded.  The moments handle's W is not compared with spp (as in ptx_denoise_measured: q is per sample).
+ * The caller resets the moments handle (ptx_moments_reset) whenever the accumulation restarts -- at every camera change in particular,
+ * so that q describes the current view's samples alone -- exactly as for ptx_denoise_measured; the temporal handle is NOT reset there. */
+int  ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m, const ptx_denoise_params *dp,
+                                   const ptx_temporal_params *tp, const ptx_variance_params *vp, int min_batches, int spp);
 
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */

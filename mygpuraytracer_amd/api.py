@@ -532,6 +532,8 @@ def load_library():
     L.ptx_moments_summarize.restype, L.ptx_moments_summarize.argtypes = i, [vp, C.POINTER(MomentsParams), C.POINTER(MomentsSummary)]
     L.ptx_denoise_measured.restype = i
     L.ptx_denoise_measured.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), i, i]
+    L.ptx_denoise_temporal_measured.restype = i
+    L.ptx_denoise_temporal_measured.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams), i, i]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -1003,16 +1005,23 @@ class Tracer:
                                              int(spp)), "ptx_denoise_variance")
         return self.read_denoised() if read else None
 
-    def denoise_measured(self, moments, spp, min_batches=None, read=True, **params):
+    def denoise_measured(self, moments, spp, min_batches=None, read=True, temporal=None, **params):
         """denoise_variance() with the variance measured by `moments` (a Moments fed from this tracer's buffer) in place of the spatial
         estimate, on every hit pixel with at least min_batches batches (None: 4); params: any field of ptx_denoise_params and
-        ptx_variance_params.  variance() gives the v0 it used."""
+        ptx_variance_params.  variance() gives the v0 it used.
+        temporal: a Temporal: denoise_variance(spp, temporal) whose per-sample variance pools the measured one with the history's
+        (ptx_denoise_temporal_measured); params may then name ptx_temporal_params' fields too.  Reset `moments` at every camera step."""
+        mb = 0 if min_batches is None else int(min_batches)
+        if temporal is not None:
+            dp, tp, vpar = _split_variance_params("denoise_measured", params)
+            _check(self.lib.ptx_denoise_temporal_measured(self.h, temporal.h, moments.h, C.byref(dp), C.byref(tp), C.byref(vpar), mb,
+                                                          int(spp)), "ptx_denoise_temporal_measured")
+            return self.read_denoised() if read else None
         for k in params:
             if k not in _DENOISE_KEYS + _VARIANCE_KEYS:
                 raise TypeError("denoise_measured: unknown parameter %r" % k)
         dp, _, vpar = _split_variance_params("denoise_measured", params)
-        _check(self.lib.ptx_denoise_measured(self.h, moments.h, C.byref(dp), C.byref(vpar), 0 if min_batches is None else int(min_batches),
-                                             int(spp)), "ptx_denoise_measured")
+        _check(self.lib.ptx_denoise_measured(self.h, moments.h, C.byref(dp), C.byref(vpar), mb, int(spp)), "ptx_denoise_measured")
         return self.read_denoised() if read else None
 
     def variance(self):

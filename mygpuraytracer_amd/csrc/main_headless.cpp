@@ -19,9 +19,14 @@
 //                                                                      combines with --temporal and --frames)
 //                                  [--until-error E [--error-floor F]]   (render in batches of 16 iterations, one ptx_moments_add after
 //                                                                      each; stop at the first check with mean_rel_se <= E, or at
-//                                                                      --iterations; F = ptx_moments_params.floor)
-//                                  [--measured]   (with --denoise: the variance-guided filter on the variance the run measured,
-//                                                                      ptx_denoise_measured; without --until-error a batch every 16 iterations)
+//                                                                      --iterations; F = ptx_moments_params.floor; not with --frames)
+//                                  [--measured [--measure-every K]]   (with --denoise: the variance-guided filter on the variance the
+//                                                                      run measured, ptx_denoise_measured: a batch every K iterations,
+//                                                                      16 unless given.  Implies --variance.  With --frames the moments
+//                                                                      start again at every view; with --temporal as well the history's
+//                                                                      variance is pooled with them, ptx_denoise_temporal_measured.  A view
+//                                                                      that ends with fewer than 4 batches falls back to the unmeasured
+//                                                                      estimate and says so.)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -46,11 +51,13 @@ static std::string currentTimeString() {          // src/preview.cpp:13-19
 }
 
 // --frames: the camera-change loop of apps/src/main.cpp:221-271 over an orbit, one tracer per frame, the denoiser's history (with
-// --temporal) kept across them by the veneer
+// --temporal) kept across them by the veneer.  measured: one batch of moments after every measure_every-th pathtrace() of a view
+// (pathtraceInit starts them again), and GPUdenoise filters with them.
 static int run_frames(Scene *scene, int frames, const std::string &orbit_script, const std::string &frame_step, const std::string &out_prefix,
-                      bool denoise, bool temporal, bool variance, bool pfm) {
+                      bool denoise, bool temporal, bool variance, bool measured, int measure_every, bool pfm) {
     denoiseTemporal() = temporal;
-    denoiseVariance() = variance;
+    denoiseVariance() = variance || measured;
+    if (measured) momentsBatch() = measure_every;
     const Camera base = scene->state.camera;
     const int width = base.resolution[0], height = base.resolution[1], n = (int)scene->state.iterations;
     if (n < 1) { fprintf(stderr, "--frames needs --iterations N >= 1\n"); return 1; }
@@ -72,6 +79,11 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
         printf("Saved %s.png.\n", name.c_str());
         if (pfm) { ptimg::write_pfm(name + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", name.c_str()); }
         if (denoise) {
+            const int nbatches = measured ? n / measure_every : 0;
+            if (measured && nbatches < 4)
+                printf("frame %d: %d batch(es) of %d iterations, fewer than 4: fell back to the unmeasured variance estimate\n", f, nbatches,
+                       measure_every);
+            denoiseMeasured() = nbatches > 0;    // (no batch at all: there is no moments handle to hand over)
             GPUdenoise();                        // state.output = the denoised mean radiance
             ptimg::to_rgb8_mirrored(width, height, &scene->state.output[0].x, 1.0f, rgb8);
             if (!ptimg::write_png_rgb8(name + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", name.c_str()); return 1; }
@@ -88,7 +100,7 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]]\n", argv[0]);
         return 1;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
@@ -98,7 +110,7 @@ int main(int argc, char **argv) {
     ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
-    int ckpt_every = 0, frames = 0;
+    int ckpt_every = 0, frames = 0, measure_every = 16;
     ptx_options &opt = pathtraceOptions();
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
@@ -131,13 +143,15 @@ int main(int argc, char **argv) {
         else if (a == "--until-error") { need(1); until_error = atof(argv[++i]); }
         else if (a == "--error-floor") { need(1); mparams.floor = (float)atof(argv[++i]); }
         else if (a == "--measured") measured = true;
+        else if (a == "--measure-every") { need(1); measure_every = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
     }
-    const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of 16 iterations, a ptx_moments_add after each
+    const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of measure_every iterations, a ptx_moments_add after each
     if (measured && !denoise) { fprintf(stderr, "--measured needs --denoise\n"); return 1; }
-    if (measured && (temporal || variance)) { fprintf(stderr, "--measured does not combine with --temporal or --variance\n"); return 1; }
-    if (batches && (frames > 0 || per_call || !ckpt_path.empty())) {
-        fprintf(stderr, "--until-error and --measured do not combine with --frames, --per-call or --checkpoint\n");
+    if (measure_every < 1) { fprintf(stderr, "--measure-every needs K >= 1\n"); return 1; }
+    if (until_error >= 0.0 && frames > 0) { fprintf(stderr, "--until-error does not combine with --frames\n"); return 1; }
+    if (batches && (per_call || !ckpt_path.empty())) {
+        fprintf(stderr, "--until-error and --measured do not combine with --per-call or --checkpoint\n");
         return 1;
     }
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
@@ -157,7 +171,7 @@ int main(int argc, char **argv) {
     if (resw > 0 && resh > 0) scene->setResolution(resw, resh);
     if (depth > 0) scene->state.traceDepth = depth;
     if (iterations > 0) scene->state.iterations = (unsigned)iterations;
-    if (frames > 0) return run_frames(scene, frames, orbit_script, frame_step, out_prefix, denoise, temporal, variance, pfm);
+    if (frames > 0) return run_frames(scene, frames, orbit_script, frame_step, out_prefix, denoise, temporal, variance, measured, measure_every, pfm);
     if (orbit_script.empty()) scene->applyRunCudaCamera();
     else if (!scene->runOrbitScript(orbit_script)) { fprintf(stderr, "bad --orbit script: %s\n", orbit_script.c_str()); return 1; }
     const int width = scene->state.camera.resolution[0], height = scene->state.camera.resolution[1];
@@ -176,7 +190,7 @@ int main(int argc, char **argv) {
         printf("Resumed %s at %d of %d samples.\n", resume_path.c_str(), done, n);
     }
     const int rendered = std::max(n - done, 0);
-    const int chunk = batches ? 16 : (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
+    const int chunk = batches ? measure_every : (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
     double per_call_ms = 0.0;
     if (per_call) {
         // the reference's own loop (runCuda, src/main.cpp:128-148): one pathtrace(pbo, frame, iteration) per frame, the fp32 frame

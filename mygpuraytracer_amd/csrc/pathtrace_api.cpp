@@ -333,19 +333,27 @@ void GPUdenoise(bool keep_on_device) {
     if (!g_tracer || !hst_scene) { fprintf(stderr, "GPUdenoise called before pathtraceInit\n"); exit(EXIT_FAILURE); }
     if (g_multi) { fprintf(stderr, "GPUdenoise: the denoiser runs on one device; pathtraceDevices() names several\n"); exit(EXIT_FAILURE); }
     if (g_last_iter < 1) { fprintf(stderr, "GPUdenoise called before the first pathtrace\n"); exit(EXIT_FAILURE); }
-    if (denoiseMeasured()) {
-        if (denoiseTemporal()) { fprintf(stderr, "GPUdenoise: denoiseMeasured() does not combine with denoiseTemporal()\n"); exit(EXIT_FAILURE); }
-        if (!g_moments) { fprintf(stderr, "GPUdenoise: denoiseMeasured() needs momentsBatch() > 0 and at least one batch\n"); exit(EXIT_FAILURE); }
+    if (denoiseMeasured() && !g_moments) {
+        fprintf(stderr, "GPUdenoise: denoiseMeasured() needs momentsBatch() > 0 and at least one batch\n");
+        exit(EXIT_FAILURE);
+    }
+    if (denoiseMeasured() && !denoiseTemporal()) {
         check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");
     } else if (denoiseTemporal()) {
         const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
         const int key[3] = {g_device, w, h};
-        if (g_temporal && memcmp(key, g_temporal_key, sizeof key) != 0) GPUdenoiseRelease();     // another device or resolution
+        if (g_temporal && memcmp(key, g_temporal_key, sizeof key) != 0) {     // another device or resolution (g_moments looks after itself)
+            ptx_temporal_destroy(g_temporal);
+            g_temporal = nullptr;
+        }
         if (!g_temporal) {
             check(ptx_temporal_create(g_device, w, h, &g_temporal), "GPUdenoise");
             memcpy(g_temporal_key, key, sizeof key);
         }
-        if (denoiseVariance())
+        if (denoiseMeasured())       // (pathtraceInit reset g_moments with the accumulation: its batches are this view's alone)
+            check(ptx_denoise_temporal_measured(g_tracer, g_temporal, g_moments, &denoiseParams(), &temporalParams(), &varianceParams(), 0,
+                                                g_last_iter), "GPUdenoise");
+        else if (denoiseVariance())
             check(ptx_denoise_variance(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), &varianceParams(), g_last_iter), "GPUdenoise");
         else
             check(ptx_denoise_temporal(g_tracer, g_temporal, &denoiseParams(), &temporalParams(), g_last_iter), "GPUdenoise");

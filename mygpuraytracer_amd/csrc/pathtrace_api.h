@@ -280,7 +280,9 @@ ptx_moments *pathtraceMoments();
 // iterations in the accumulation buffer now.  With several pathtraceDevices() the batch is taken from state.image.
 void pathtraceMomentsAdd(int iteration);
 // Measured variance (ptx_denoise_measured): off by default.  When on, GPUdenoise takes the variance-guided filter's input variance from
-// that handle (momentsBatch() must have collected at least one batch).  Not with denoiseTemporal(): it prints an error and exits.
+// that handle (momentsBatch() must have collected at least one batch).  With denoiseTemporal() on as well it is
+// ptx_denoise_temporal_measured: the history's variance pooled with the measured one of the current view (pathtraceInit resets the
+// moments handle at every camera change, so its batches are that view's; fewer than 4 of them and the call is ptx_denoise_variance).
 bool &denoiseMeasured();
 void GPUdenoiseRelease();
 

@@ -1,6 +1,6 @@
 // pt_denoise.h -- internal interface between the tracer (pt_engine.hip: G-buffer pass, ptx_denoise / ptx_denoise_temporal /
-// ptx_denoise_variance / ptx_denoise_measured, ptx_moments_add), the a-trous filter with its variance guidance (pt_denoise.hip), the
-// temporal reprojection (pt_temporal.hip) and the batch-means moments (pt_moments.hip).
+// ptx_denoise_variance / ptx_denoise_measured / ptx_denoise_temporal_measured, ptx_moments_add), the a-trous filter with its variance
+// guidance (pt_denoise.hip), the temporal reprojection (pt_temporal.hip) and the batch-means moments (pt_moments.hip).
 // Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
 //
 // Device layout of the guide images, one record per pixel, pixelIndex = x + y*W (the frame's own order):
@@ -15,7 +15,8 @@
 //   nh[i]  = float4(normal xyz, hit ? 1 : 0)          (copied from the tracer's G-buffer)
 //   xn[i]  = float4(world position xyz, sample count n)
 //   dd[i]  = float4(D rgb, V)                          (D = mix / max(albedo, 1e-3) on hit pixels, mix on miss pixels; V = the per-sample
-//                                                        luminance variance when ptx_denoise_variance wrote the state, else 0)
+//                                                        luminance variance when ptx_denoise_variance or
+//                                                        ptx_denoise_temporal_measured wrote the state, else 0)
 //   ids[i] = int2(material id, geom id)
 // 56 B per pixel: a bilinear tap reads one whole record.
 //
@@ -46,13 +47,19 @@ struct PtTemporalCam {
     int32_t valid;
 };
 
+// The same inverse and position in double, for k_reproject_measured's weights of V_h and mu_h alone (pt_temporal.hip)
+struct PtTemporalCamD {
+    double pos[3] = {0.0, 0.0, 0.0};
+    double minv[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+};
+
 struct ptx_temporal {
     int device = 0, w = 0, h = 0;
     PtTemporalState st[2];
     int cur = 0;                          // st[cur] is cur, st[cur ^ 1] is hist
     ptx_camera cam[2];                    // the camera of each state
     bool cur_valid = false, hist_valid = false;
-    bool has_v[2] = {false, false};       // st[i].dd.w holds a V (written by ptx_denoise_variance, not by ptx_denoise_temporal)
+    bool has_v[2] = {false, false};       // st[i].dd.w holds a V (not after ptx_denoise_temporal, which writes 0 there)
     float *d_mix = nullptr;               // W*H*3: the last call's mix (the filter's input)
     float4 *d_hn = nullptr;               // W*H: the last call's (h rgb, n_h)
     hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
@@ -83,6 +90,14 @@ struct ptx_moments {
 
 // Rec. 709 luminance, the one every variance of the denoiser is a variance of
 __host__ __device__ inline float pt_luminance(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
+// g^T M g / (B - 1) for the weights g of a linear functional of the colour, M a moments state's scatter matrix (ma, and rb, gb of mb):
+// the one definition pt_moments.hip's summary and prep and pt_temporal.hip's k_reproject_measured evaluate
+__device__ __forceinline__ float quad_form(float g0, float g1, float g2, const float4 A, float rb, float gb, float B) {
+    const float diag = g0 * g0 * A.x + g1 * g1 * A.y + g2 * g2 * A.z;
+    const float off = g0 * g1 * A.w + g0 * g2 * rb + g1 * g2 * gb;
+    return (diag + 2.f * off) / (B - 1.f);
+}
 
 // What pt_denoise.hip and pt_temporal.hip share: the pixel kernels' workgroup of 64 x 4 pixels (a wave is one 64-pixel row segment)
 // and its grid, the ptx_last_error of a failed call, and the checked HIP call of their entry points.
@@ -125,13 +140,19 @@ hipError_t pt_moments_prep_enqueue(hipStream_t st, int w, int h, const float *rg
                                    const PtMomentsState &s, int min_batches, float4 *c);
 
 // hist's camera -> PtTemporalCam (in double, then rounded); valid = 0 when the system is singular or not finite
-PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist);
+// (precise: the unrounded inverse too)
+PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist, PtTemporalCamD *precise = nullptr);
 
 // Enqueues the reprojection + mix on `st`: reads the tracer's G-buffer (gnh, gxt, galb, gids) and accumulation rgb / spp, writes
 // st_cur, mix (W*H*3) and hn (W*H).  spec: one byte per material (!= 0: reflective or refractive).
 // variance != 0: cur.dd.w = V where hist supplies one (hist_has_v != 0 and n_h > 0), -1 on the other hit pixels
 // (pt_variance_spatial_enqueue fills those in); variance == 0: dd.w = 0.
+// moments != NULL (with variance != 0; batches = its B >= 2): ptx_denoise_temporal_measured's V.  q = max(g^T M g / (B - 1), 0) with
+// g_k = l_k / max(albedo_k, 1e-3); where hist supplies a V the current view's share is ((B - 1) q + e) / B in place of e, and the
+// other hit pixels get q, so nothing is left for the spatial estimate; camd: hist's camera from pt_temporal_camera's `precise`.
+// NULL / 0: the kernels above, as they were.
 hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
                                float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
                                const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
-                               float4 *hn, int variance = 0, int hist_has_v = 0);
+                               float4 *hn, int variance = 0, int hist_has_v = 0, const PtMomentsState *moments = nullptr, int batches = 0,
+                               const PtTemporalCamD *camd = nullptr);

@@ -1269,8 +1269,10 @@ static int denoise_begin(const std::string &fn, ptx_tracer *t, const ptx_tempora
 }
 
 // The handle's step on the tracer's stream: wait for the handle's last work, start a new segment when the camera changed (cur becomes
-// hist), then reproject hist into the current view and mix (with V when variance).
-static int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_params &tp, int spp, bool variance) {
+// hist), then reproject hist into the current view and mix (with V when variance; moments: ptx_denoise_temporal_measured's V, from that
+// state with its `batches`).
+static int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_params &tp, int spp, bool variance,
+                         const PtMomentsState *moments = nullptr, int batches = 0) {
     if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));     // the handle's last work, maybe on another tracer's stream
     ptx_camera cam;
     memcpy(&cam, &t->cam, sizeof cam);
@@ -1282,10 +1284,12 @@ static int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_para
     const int hi = h->cur ^ 1;
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     const float4 *g = t->d_gbuf;
-    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, pt_temporal_camera(h->cam[hi], h->hist_valid), tp, t->d_image,
+    PtTemporalCamD camd;
+    const PtTemporalCam hcam = pt_temporal_camera(h->cam[hi], h->hist_valid, &camd);
+    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, hcam, tp, t->d_image,
                                  (float)spp, g, g + n, g + 2 * n, reinterpret_cast<const int2 *>(g + 3 * n), t->d_spec,
                                  (int)t->h_spec.size(), h->st[h->cur], h->st[hi], h->d_mix, h->d_hn, variance ? 1 : 0,
-                                 variance && h->hist_valid && h->has_v[hi] ? 1 : 0));
+                                 variance && h->hist_valid && h->has_v[hi] ? 1 : 0, moments, batches, &camd));
     return PTX_OK;
 }
 
@@ -1432,6 +1436,43 @@ int ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params
     m->used = true;
     HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
     HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
+    t->dn_done = t->var_done = true;
+    return PTX_OK;
+}
+
+// ---- the two together: the temporal history's V pooled with the measured variance (definition in include/mi355x_pathtracer.h) --------
+int ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m, const ptx_denoise_params *dparams,
+                                  const ptx_temporal_params *tparams, const ptx_variance_params *vparams, int min_batches, int spp) {
+    const std::string fn = "ptx_denoise_temporal_measured";
+    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
+    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
+    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
+    if (spp < 1) return bad_spp(fn);
+    if (min_batches == 1) return set_error(PTX_ERR_INVALID, fn + ": min_batches must be >= 2 (<= 0: the default, 4)");
+    if (!dp.demodulate)
+        return set_error(PTX_ERR_INVALID, fn + ": ptx_denoise_params.demodulate must be != 0 (the state's moments are in demodulated space)");
+    if (!t || !h || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, temporal handle or moments handle");
+    if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on this moments handle yet");
+    if (const int rc = moments_begin(fn, t, m)) return rc;
+    // too few batches for the measured variance: ptx_denoise_variance itself, so the same bits (the moments state is not read)
+    if (m->batches < (min_batches <= 0 ? 4 : min_batches)) return ptx_denoise_variance(t, h, &dp, &tp, &vp, spp);
+    if (const int rc = denoise_begin(fn, t, h, true)) return rc;
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    const float4 *g = t->d_gbuf;
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
+    if (const int rc = temporal_step(t, h, tp, spp, true, &m->st, m->batches)) return rc;
+    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
+    m->used = true;
+    const PtTemporalState &cur = h->st[h->cur];
+    // (no spatial pass: every hit pixel's dd.w is a V already, nothing is marked -1)
+    HIPCHECK(pt_variance_prep_state_enqueue(t->stream, (int)n, cur, t->d_dn_tmp));
+    h->has_v[h->cur] = true;
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
+    if (const int rc = temporal_done(t, h)) return rc;
     t->dn_done = t->var_done = true;
     return PTX_OK;
 }

@@ -79,13 +79,6 @@ __global__ __launch_bounds__(NT) void k_moments_add(int w, int h, int pairs, flo
     if (even) mb[pb] = make_float4(rb, gb, nrb, ngb);
 }
 
-// g^T M g / (B - 1) for the weights g of a linear functional of the colour
-__device__ __forceinline__ float quad_form(float g0, float g1, float g2, const float4 A, float rb, float gb, float B) {
-    const float diag = g0 * g0 * A.x + g1 * g1 * A.y + g2 * g2 * A.z;
-    const float off = g0 * g1 * A.w + g0 * g2 * rb + g1 * g2 * gb;
-    return (diag + 2.f * off) / (B - 1.f);
-}
-
 __device__ __forceinline__ void partial_add(PtMomentsPartial &a, const PtMomentsPartial &b) {
     a.sum_rel += b.sum_rel; a.sum_rel2 += b.sum_rel2; a.sum_q += b.sum_q;
     a.max_rel = fmax(a.max_rel, b.max_rel);

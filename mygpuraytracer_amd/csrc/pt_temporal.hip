@@ -8,6 +8,14 @@
 // (h, n_h).  It copies what the next segment needs out of the G-buffer, which ensure_gbuffer rewrites in place on the next view.
 // k_reproject_variance (ptx_denoise_variance) is the same pixel function, reproject_pixel<true>: the same arithmetic plus the per-sample luminance variance V in dd.w: inherited
 // and updated where the history carries one, -1 (= "pt_denoise.hip's spatial estimate fills this in") on the other hit pixels.
+// k_reproject_measured (ptx_denoise_temporal_measured) is reproject_pixel<true, true>: it also reads the pixel's share of a moments state
+// (ma as one float4, its (rb, gb) of mb as one float2: 24 B more per pixel) and takes from it q, the measured per-sample variance of
+// the demodulated luminance with B - 1 degrees of freedom.  Where V is inherited, q is pooled with the between-view term e (one degree
+// of freedom) by degrees of freedom; the other hit pixels get q in place of -1.  A measured V is per pixel and as spiky as the samples
+// (0 beside 3 where one of eight samples found the light), so V_h and mu_h are ill-conditioned in the bilinear weights where the
+// spatial estimate's windowed V was not: u near 100 carries an fp32 ulp of 8e-6 of a pixel, 2 % of a weight of 5e-4.  This kernel
+// therefore takes the weights of those two sums -- and of nothing else: taps, n_h, h and mix are the other kernels', bit for bit --
+// from the projection redone in double (PtTemporalCamD; fp64 is full rate on CDNA).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -21,7 +29,7 @@ namespace {
 
 constexpr int BX = PT_BX, BY = PT_BY;
 
-template <bool VAR>
+template <bool VAR, bool MEASURED = false>
 __device__ __forceinline__ void reproject_pixel(
         int w, int h, const PtTemporalCam cam, float max_history, int specular_history, float normal_cos, float plane_tolerance,
         int hist_has_v,
@@ -29,7 +37,9 @@ __device__ __forceinline__ void reproject_pixel(
         const float4 *__restrict__ galb, const int2 *__restrict__ gids, const uint8_t *__restrict__ spec, int nmats,
         float4 *__restrict__ cnh, float4 *__restrict__ cxn, float4 *__restrict__ cdd, int2 *__restrict__ cids,
         const float4 *__restrict__ hnh, const float4 *__restrict__ hxn, const float4 *__restrict__ hdd, const int2 *__restrict__ hids,
-        float *__restrict__ mix, float4 *__restrict__ hn) {
+        float *__restrict__ mix, float4 *__restrict__ hn,
+        const float4 *__restrict__ ma = nullptr, const float2 *__restrict__ mb2 = nullptr, int pairs = 0, float batches = 0.f,
+        const PtTemporalCamD camd = PtTemporalCamD()) {
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= w || y >= h) return;
     const int p = y * w + x;
@@ -40,9 +50,15 @@ __device__ __forceinline__ void reproject_pixel(
     float4 a = make_float4(1.f, 1.f, 1.f, 0.f);
     float h0 = 0.f, h1 = 0.f, h2 = 0.f, nhist = 0.f;
     float var = hit ? -1.f : 0.f;                        // VAR only: V, or -1 where the spatial estimate has to supply it
+    float q = 0.f;                                       // MEASURED only: max(g^T M g / (B - 1), 0), g = the demodulated luminance's weights
     if (hit) {
         const float4 al = galb[p];
         a = make_float4(fmaxf(al.x, 1e-3f), fmaxf(al.y, 1e-3f), fmaxf(al.z, 1e-3f), 0.f);
+        if (MEASURED) {                                  // = k_moments_prep's v * W when demodulating
+            const float2 m2 = mb2[(size_t)y * pairs * 2 + x];
+            q = fmaxf(quad_form(0.2126f / a.x, 0.7152f / a.y, 0.0722f / a.z, ma[p], m2.x, m2.y, batches), 0.f);
+            var = q;                                     // nothing inherited: the measured variance alone
+        }
         const bool specular = id.x >= 0 && id.x < nmats && spec[id.x] != 0;
         if (cam.valid && (specular_history || !specular)) {
             const float dx = xp.x - cam.pos[0], dy = xp.y - cam.pos[1], dz = xp.z - cam.pos[2];
@@ -57,6 +73,15 @@ __device__ __forceinline__ void reproject_pixel(
                 const float fu = u - uf, fv = v - vf;
                 const float lim = plane_tolerance * sqrtf(dx * dx + dy * dy + dz * dz);
                 float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f, sv = 0.f;
+                float pfu = 0.f, pfv = 0.f, pr = 0.f, pg = 0.f, pb = 0.f, pw = 0.f, pv = 0.f;     // MEASURED only: the precise weights' sums
+                if (MEASURED) {                          // the same taps' fractions from (u, v) in double, clamped to their cell
+                    const double ex = (double)xp.x - camd.pos[0], ey = (double)xp.y - camd.pos[1], ez = (double)xp.z - camd.pos[2];
+                    const double ds = camd.minv[0] * ex + camd.minv[1] * ey + camd.minv[2] * ez;
+                    const double du = (camd.minv[3] * ex + camd.minv[4] * ey + camd.minv[5] * ez) / ds;
+                    const double dv = (camd.minv[6] * ex + camd.minv[7] * ey + camd.minv[8] * ez) / ds;
+                    pfu = (float)fmin(fmax(du - (double)uf, 0.0), 1.0);
+                    pfv = (float)fmin(fmax(dv - (double)vf, 0.0), 1.0);
+                }
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
 #pragma unroll
@@ -76,6 +101,10 @@ __device__ __forceinline__ void reproject_pixel(
                         const float4 dq = hdd[q];
                         sr += wt * dq.x; sg += wt * dq.y; sb += wt * dq.z; sn += wt * xq.w; sw += wt;
                         if (VAR) sv += wt * dq.w;
+                        if (MEASURED) {
+                            const float pt = (i ? pfu : 1.f - pfu) * (j ? pfv : 1.f - pfv);
+                            pr += pt * dq.x; pg += pt * dq.y; pb += pt * dq.z; pv += pt * dq.w; pw += pt;
+                        }
                     }
                 }
                 if (sw > 0.f) {
@@ -84,9 +113,12 @@ __device__ __forceinline__ void reproject_pixel(
                     else nhist = 0.f;
                     if (VAR && hist_has_v && nhist > 0.f) {
                         // the pairwise update of a per-sample variance: between-batch term e, then the mean by sample counts
-                        const float mu = pt_luminance(sr / sw, sg / sw, sb / sw), lc = pt_luminance(c0 / a.x, c1 / a.y, c2 / a.z);
+                        const bool precise = MEASURED && pw > 0.f;          // (pw == 0: every accepted tap sits on a clamped edge)
+                        const float mu = precise ? pt_luminance(pr / pw, pg / pw, pb / pw) : pt_luminance(sr / sw, sg / sw, sb / sw);
+                        const float lc = pt_luminance(c0 / a.x, c1 / a.y, c2 / a.z);
                         const float d = lc - mu, tot = nhist + spp, e = d * d * nhist * spp / tot;
-                        var = (nhist * (sv / sw) + spp * e) / tot;
+                        if (MEASURED) var = (nhist * (precise ? pv / pw : sv / sw) + spp * (((batches - 1.f) * q + e) / batches)) / tot;
+                        else var = (nhist * (sv / sw) + spp * e) / tot;
                     }
                 }
             }
@@ -120,6 +152,12 @@ __device__ __forceinline__ void reproject_pixel(
 __global__ __launch_bounds__(BX * BY) void k_temporal_reproject(REPROJECT_PARAMS) { reproject_pixel<false>(REPROJECT_ARGS); }
 // ptx_denoise_variance's: the same pixel function with V
 __global__ __launch_bounds__(BX * BY) void k_reproject_variance(REPROJECT_PARAMS) { reproject_pixel<true>(REPROJECT_ARGS); }
+// ptx_denoise_temporal_measured's: V from the moments state too (batches = B >= 2, one number per handle)
+__global__ __launch_bounds__(BX * BY) void k_reproject_measured(REPROJECT_PARAMS, const float4 *__restrict__ ma,
+                                                                const float2 *__restrict__ mb2, int pairs, float batches,
+                                                                const PtTemporalCamD camd) {
+    reproject_pixel<true, true>(REPROJECT_ARGS, ma, mb2, pairs, batches, camd);
+}
 
 }  // namespace
 
@@ -130,7 +168,7 @@ const char *pt_temporal_params_problem(const ptx_temporal_params &p) {
     return nullptr;
 }
 
-PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist) {
+PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist, PtTemporalCamD *precise) {
     PtTemporalCam k;
     memset(&k, 0, sizeof k);
     const double W = c.resolution[0], H = c.resolution[1];
@@ -159,6 +197,10 @@ PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist) {
         ok = ok && std::isfinite(k.minv[i]);
     }
     for (int i = 0; i < 3; i++) k.pos[i] = c.position[i];
+    if (precise) {
+        for (int i = 0; i < 9; i++) precise->minv[i] = inv[i];
+        for (int i = 0; i < 3; i++) precise->pos[i] = c.position[i];
+    }
     k.valid = ok ? 1 : 0;
     return k;
 }
@@ -166,7 +208,16 @@ PtTemporalCam pt_temporal_camera(const ptx_camera &c, bool have_hist) {
 hipError_t pt_temporal_enqueue(hipStream_t st, int w, int h, const PtTemporalCam &cam, const ptx_temporal_params &p, const float *rgb,
                                float spp, const float4 *gnh, const float4 *gxt, const float4 *galb, const int2 *gids,
                                const uint8_t *spec, int nmats, const PtTemporalState &cur, const PtTemporalState &hist, float *mix,
-                               float4 *hn, int variance, int hist_has_v) {
+                               float4 *hn, int variance, int hist_has_v, const PtMomentsState *moments, int batches,
+                               const PtTemporalCamD *camd) {
+    if (variance && moments && camd && batches >= 2) {
+        hipLaunchKernelGGL(k_reproject_measured, pt_pixel_grid(w, h), dim3(BX, BY), 0, st, w, h, cam, (float)p.max_history,
+                           p.specular_history ? 1 : 0, p.normal_cos, p.plane_tolerance, hist_has_v, rgb, spp, gnh, gxt, galb, gids, spec,
+                           nmats, cur.nh, cur.xn, cur.dd, cur.ids, (const float4 *)hist.nh, (const float4 *)hist.xn, (const float4 *)hist.dd,
+                           (const int2 *)hist.ids, mix, hn, (const float4 *)moments->ma, reinterpret_cast<const float2 *>(moments->mb),
+                           pt_moments_pairs(w), (float)batches, *camd);
+        return hipGetLastError();
+    }
     const auto kernel = variance ? k_reproject_variance : k_temporal_reproject;
     hipLaunchKernelGGL(kernel, pt_pixel_grid(w, h), dim3(BX, BY), 0, st, w, h, cam, (float)p.max_history, p.specular_history ? 1 : 0,
                        p.normal_cos, p.plane_tolerance, hist_has_v, rgb, spp, gnh, gxt, galb, gids, spec, nmats, cur.nh, cur.xn, cur.dd,
