@@ -502,6 +502,13 @@ int ptx_kat_libm(ptx_tracer *t, int n, const float *x, float *sin_out, float *co
  * expansions of sqrtf(x), 1 / sqrtf(x) and 1 / a, on ALL 2^32 operand bit patterns: mismatches[3] = how many patterns differ
  * bitwise (two NaNs count as equal).  0, 0, 0 is the only acceptable answer. */
 int ptx_kat_fast_exact(ptx_tracer *t, int64_t mismatches[3]);
+/* Two more routines of pt_device.h against what they stand for, on the device.  counts[0]: bit patterns, of ALL 2^32, on which pt_rsqrt_unit
+ * (1 / sqrt of an operand next to 1) differs from pt_rsqrt_glm; counts[1]: patterns inside its window (2 W + 1).  counts[2]: quotients of
+ * pt_div_pairs3 (a cube's six slab quotients, one reciprocal per axis) that differ from the divisions a / d, over every pair of exponents for
+ * numerator and denominator with exponent_reps random mantissas each, every triple of the special values (zeros, infinities, NaNs, subnormals,
+ * the guard's bounds) and random_sets random sets from the slab test's range; counts[3]: sets that took the shared reciprocal.  Two NaNs
+ * count as equal.  counts[0] == counts[2] == 0 is the only acceptable answer. */
+int ptx_kat_unit_rsqrt(ptx_tracer *t, int exponent_reps, int64_t random_sets, int64_t counts[4]);
 /* CPU-only (no device, no tracer): the per-tile geom masks the camera-ray bounce uses (bit g of masks_out[tile] clear = no camera ray of
  * that tile of 256 owned pixels can reach box g; boxes6 = lo xyz, hi xyz per geom, <= 32 geoms), for a camera, depth of field on / off and a
  * row-tile split.  Returns the number of tiles, -1 on a bad argument.  The CPU tests check the superset property ray by ray. */

@@ -562,6 +562,8 @@ def load_library():
         L.ptx_debug_mesh_plan.restype, L.ptx_debug_mesh_plan.argtypes = i, [vp, i, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
         L.ptx_kat_fast_exact.restype, L.ptx_kat_fast_exact.argtypes = i, [vp, vp]
+    if hasattr(L, "ptx_kat_unit_rsqrt"):
+        L.ptx_kat_unit_rsqrt.restype, L.ptx_kat_unit_rsqrt.argtypes = i, [vp, i, C.c_int64, vp]
     L.ptx_debug_set_capture.restype, L.ptx_debug_set_capture.argtypes = i, [vp, i]
     L.ptx_debug_read_stream.restype, L.ptx_debug_read_stream.argtypes = i, [vp, C.POINTER(i), vp, vp, vp, vp, i]
     # several devices behind one handle (csrc/pt_multi.cpp)
@@ -1080,6 +1082,12 @@ class Tracer:
         """mismatches of the device's guarded core sqrt / 1/sqrt / 1/a against the compiler's IEEE expansions over all 2^32 operands"""
         m = np.zeros(3, np.int64)
         _check(self.lib.ptx_kat_fast_exact(self.h, _ptr(m)), "ptx_kat_fast_exact")
+        return m.tolist()
+
+    def kat_unit_rsqrt(self, exponent_reps=64, random_sets=1 << 26):
+        """[pt_rsqrt_unit != pt_rsqrt_glm over all 2^32 operands, operands in the window, slab quotients != a / d, sets through the shared reciprocal]"""
+        m = np.zeros(4, np.int64)
+        _check(self.lib.ptx_kat_unit_rsqrt(self.h, int(exponent_reps), int(random_sets), _ptr(m)), "ptx_kat_unit_rsqrt")
         return m.tolist()
 
     def owned_pixels(self):

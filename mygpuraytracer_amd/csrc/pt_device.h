@@ -100,8 +100,100 @@ PT_HD float pt_sqrt(float x) { return __builtin_sqrtf(x); }
 PT_HD float pt_rsqrt_glm(float x) { return 1.0f / __builtin_sqrtf(x); }
 PT_HD float pt_rcp_pos(float a) { return 1.0f / a; }
 #endif
+// ---- 1 / sqrt(s) for s next to 1: the second normalize of a unit vector ------------------------------------------------------------
+// getPointOnRay normalizes a direction its callers have normalized already (the reference does, src/intersections.h:28), and the second
+// normalize is not the identity in binary32: s = dot(v, v) of a normalized v is a few ulps off 1 and 1 / sqrt(s) one of a handful of
+// values next to 1.  For s = 1 + d ulps (d the signed distance of the bit patterns; an ulp is 2^-23 above 1 and 2^-24 below) the two
+// correctly rounded operations give
+//     d >= 0:  sqrt -> 1 + (d >> 1) ulps (an odd d lies just below the tie),   1 / that -> 1 - 2 (d >> 1) ulps of 2^-24
+//     d <  0:  sqrt -> 1 - ceil(-d / 2) ulps of 2^-24 (again just below the tie), 1 / that -> 1 + ceil(-d / 4) ulps of 2^-23
+// i.e. bits(result) = bits(1) - (d < 0 ? d >> 2 : d & ~1) with an arithmetic shift: the quadratic terms stay below a quarter ulp for
+// -8190 <= d <= 2897, and tests/unit_rsqrt_check.cpp compares the mapping with 1.0f / sqrtf(s) on every operand of the window.  The window:
+// the largest |d| that program finds over v = normalize(u), 10^8 random u and the adversarial ones (axis vectors, equal components,
+// components 2^+-20 apart; the dot product separate or fused), is PT_UNIT_DMAX; the window is twice that, PT_UNIT_W.  One unsigned
+// compare decides; every other operand takes pt_rsqrt_glm as before, so the result is that function's for every operand
+// (`ptx_kat_unit_rsqrt`, tests/test_gpu_unit_rsqrt.py).  -DPT_UNIT_RSQRT=0 builds the code without it (A/B timing and tests).
+#ifndef PT_UNIT_RSQRT
+#define PT_UNIT_RSQRT 1
+#endif
+constexpr uint32_t PT_UNIT_DMAX = 7, PT_UNIT_W = 2 * PT_UNIT_DMAX;
+PT_HD bool pt_in_unit_window(uint32_t sbits) { return sbits - (0x3f800000u - PT_UNIT_W) <= 2u * PT_UNIT_W; }
+PT_HD uint32_t pt_unit_rsqrt_bits(uint32_t sbits) {                                 // for pt_in_unit_window(sbits) only
+    const int32_t d = (int32_t)(sbits - 0x3f800000u);
+    return 0x3f800000u - (uint32_t)(d < 0 ? d >> 2 : d & ~1);
+}
+#if defined(__HIP_DEVICE_COMPILE__) && PT_ARITH < 2 && PT_FAST_EXACT && PT_UNIT_RSQRT
+__device__ __forceinline__ float pt_rsqrt_unit(float s) {
+    const uint32_t sbits = __float_as_uint(s);
+    if (__builtin_expect(pt_in_unit_window(sbits), 1)) return __uint_as_float(pt_unit_rsqrt_bits(sbits));
+    return pt_rsqrt_glm(s);
+}
+#else
+PT_HD float pt_rsqrt_unit(float s) { return pt_rsqrt_glm(s); }
+#endif
+// ---- two quotients with one denominator: a1 / d and a2 / d (the two slabs of a cube's axis) -----------------------------------------
+// The compiler expands an IEEE a / d into (gfx950, f32 denormals on)
+//     ds = v_div_scale(d, d, a)   ns = v_div_scale(a, d, a)   r = v_rcp(ds)   e = fma(-ds, r, 1)   r = fma(e, r, r)
+//     q = ns * r   e = fma(-ds, q, ns)   q = fma(e, r, q)   e = fma(-ds, q, ns)   v_div_fmas(e, r, q)   v_div_fixup(., d, a)
+// The first line's seed and Newton step depend on d alone.  v_div_scale hands its operand back unscaled, and leaves VCC clear so that
+// v_div_fmas is a plain fma, unless (ISA, V_DIV_SCALE_F32): an operand is zero or NaN; d is subnormal; 1 / d is (|d| > 2^126); the
+// exponents of a and d differ by 96 or more; a / d is subnormal (they differ by -126 or less); a's biased exponent is <= 23.
+// v_div_fixup returns its first operand unchanged (its sign is already the quotient's) unless an operand is zero, infinite or NaN or
+// the exponents differ by less than -150 or 128 or more.  With 2^-42 <= |a1|, |a2|, |d| <= 2^42 none of these holds -- the exponents
+// differ by 84 at most -- and the expansion IS the core below, instruction for instruction, with r shared by the two quotients:
+// 13 instructions for 22, behind a guard of five: v_min3, v_max3, two compares, and one ordered compare of the numerators.  (The
+// minimum and maximum drop a quiet NaN -- harmless, the quotient is a NaN either way -- but a signalling NaN in one of their first two
+// operands comes out of the first stage quiet and is dropped by the second together with the operand beside it, which then goes
+// unchecked; in the third place it reaches the result.  So d stands third and the numerators are compared with each other.)
+// Every other operand takes a / d.  `ptx_kat_unit_rsqrt` compares the pair with the two divisions on the device.
+// -DPT_SHARED_RCP=0 builds the code without it.
+#ifndef PT_SHARED_RCP
+#define PT_SHARED_RCP 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && PT_ARITH < 2 && PT_FAST_EXACT && PT_SHARED_RCP
+#define PT_SLAB_SHARED 1               // (primKey's slab loop is written for either: without it the loop is the one it was, to the instruction)
+#else
+#define PT_SLAB_SHARED 0
+#endif
+#if PT_SLAB_SHARED
+// 2^-42 <= |a1|, |a2|, |d| <= 2^42
+__device__ __forceinline__ bool pt_div_pair_in_range(float a1, float a2, float d) {
+    const float f1 = __builtin_fabsf(a1), f2 = __builtin_fabsf(a2), fd = __builtin_fabsf(d);
+    const float lo = __builtin_fminf(__builtin_fminf(f1, f2), fd), hi = __builtin_fmaxf(__builtin_fmaxf(f1, f2), fd);
+    return lo >= 0x1p-42f && hi <= 0x1p42f && !__builtin_isunordered(a1, a2);
+}
+__device__ __forceinline__ void pt_div_pair_core(float a1, float a2, float d, float &q1, float &q2) {
+    float r = __builtin_amdgcn_rcpf(d);
+    const float e = __builtin_fmaf(-d, r, 1.0f);
+    r = __builtin_fmaf(e, r, r);
+    float p1 = a1 * r, p2 = a2 * r;
+    p1 = __builtin_fmaf(__builtin_fmaf(-d, p1, a1), r, p1);
+    p2 = __builtin_fmaf(__builtin_fmaf(-d, p2, a2), r, p2);
+    q1 = __builtin_fmaf(__builtin_fmaf(-d, p1, a1), r, p1);
+    q2 = __builtin_fmaf(__builtin_fmaf(-d, p2, a2), r, p2);
+}
+#else
+PT_HD bool pt_div_pair_in_range(float, float, float) { return false; }
+PT_HD void pt_div_pair_core(float a1, float a2, float d, float &q1, float &q2) { q1 = a1 / d; q2 = a2 / d; }
+#endif
+// the three axes of a cube's slab test: t1[k] = a1[k] / d[k], t2[k] = a2[k] / d[k].  One branch for the three guards: a ray with an
+// operand out of range on any axis takes the divisions on all of them.
+PT_HD void pt_div_pairs3(const float a1[3], const float a2[3], const float d[3], float t1[3], float t2[3]) {
+    bool core = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++) core = core & pt_div_pair_in_range(a1[k], a2[k], d[k]);
+    if (__builtin_expect(core, 1)) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) pt_div_pair_core(a1[k], a2[k], d[k], t1[k], t2[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { t1[k] = a1[k] / d[k]; t2[k] = a2[k] / d[k]; }
+    }
+}
 // glm normalize = x * (1 / sqrt(dot(x,x)))  (func_geometric.inl:154-159, func_exponential.inl:62-68)
 PT_HD vec3 normalize(vec3 a) { return scale(a, pt_rsqrt_glm(dot(a, a))); }
+// the same for an operand that is a normalize result (same bits for every operand: only the fast case differs)
+PT_HD vec3 normalize_unit(vec3 a) { return scale(a, pt_rsqrt_unit(dot(a, a))); }
 PT_HD float length(vec3 a) { return pt_sqrt(dot(a, a)); }
 PT_HD float fmin_glm(float x, float y) { return x < y ? x : y; }   // glm min: x < y ? x : y
 PT_HD float fmax_glm(float x, float y) { return x > y ? x : y; }   // glm max: x > y ? x : y
@@ -475,8 +567,9 @@ enum { G_SPHERE = 0, G_CUBE = 1, G_TRIANGLE = 2, G_OBJ = 3 };
 struct Ray { vec3 o, d; };
 
 // getPointOnRay, src/intersections.h:27-29
+// (every caller hands in a ray whose direction it has normalized: the reference's second normalize sees dot(d, d) next to 1)
 PT_DEV vec3 getPointOnRay(Ray r, float t) {
-    vec3 nd = normalize(r.d);
+    vec3 nd = normalize_unit(r.d);
     float tt = t - .0001f;
     return add(r.o, V3(tt * nd.x, tt * nd.y, tt * nd.z));
 }
@@ -1269,10 +1362,19 @@ PT_DEV unsigned long long primKey(const float *gtab, int g, Ray ray) {
         float tmin_s = 0.f, tmax_s = 0.f;
         const float qo[3] = {q.o.x, q.o.y, q.o.z};
         const float qd[3] = {q.d.x, q.d.y, q.d.z};
+#if PT_SLAB_SHARED
+        const float a1[3] = {-0.5f - qo[0], -0.5f - qo[1], -0.5f - qo[2]}, a2[3] = {+0.5f - qo[0], +0.5f - qo[1], +0.5f - qo[2]};
+        float q1[3], q2[3];                    // (-0.5f - qo) / qd and (+0.5f - qo) / qd: one reciprocal per axis
+        pt_div_pairs3(a1, a2, qd, q1, q2);
+#endif
 #pragma unroll
         for (int xyz = 0; xyz < 3; ++xyz) {
+#if PT_SLAB_SHARED
+            float t1 = q1[xyz], t2 = q2[xyz];
+#else
             float t1 = (-0.5f - qo[xyz]) / qd[xyz];
             float t2 = (+0.5f - qo[xyz]) / qd[xyz];
+#endif
             float ta = fmin_glm(t1, t2);
             float tb = fmax_glm(t1, t2);
             float ns = t2 < t1 ? +1.f : -1.f;

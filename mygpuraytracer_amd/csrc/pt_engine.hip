@@ -250,6 +250,14 @@ extern "C" const void *ptx_arith_kernels_2(void) __attribute__((weak));
 extern "C" const void *ptx_arith_last_0(void);      // (pt_kernels_last.hip: the light-only last bounce of each level)
 extern "C" const void *ptx_arith_last_1(void) __attribute__((weak));
 extern "C" const void *ptx_arith_last_2(void) __attribute__((weak));
+// the exact and the contracted level once more, compiled with -DPT_UNIT_RSQRT=0 -DPT_SHARED_RCP=0 (pt_device.h): the plain second normalize
+// and six divisions per cube pair, for PTX_DEBUG_NO_UNIT_RSQRT -- a switch inside the kernels would cost them a scalar register
+extern "C" const void *ptx_arith_kernels_0p(void) __attribute__((weak));
+extern "C" const void *ptx_arith_kernels_1p(void) __attribute__((weak));
+extern "C" const void *ptx_arith_last_0p(void) __attribute__((weak));
+extern "C" const void *ptx_arith_last_1p(void) __attribute__((weak));
+// pt_kat_unit.hip: the known-answer kernels of pt_rsqrt_unit and pt_div_pairs3 (ptx_kat_unit_rsqrt)
+namespace ptd { void launch_kat_unit_rsqrt(int cus, hipStream_t stream, unsigned long long *out, int exponent_reps, unsigned long long random_sets); }
 
 // An owned device array -- every device buffer of the tracer, the scratch of the per-stage entry points -- freed when its owner goes, on
 // every way out (a HIPCHECK that fails returns from the middle).  Each step hands back the hipError_t: ptx_create looks for out-of-memory.
@@ -853,6 +861,13 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     t->ks = ks; t->ksl = ksl;
     t->device = dev; t->opt = opt; t->traceDepth = t->maxBounces = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
     t->dbg = read_debug_switches();                      // (once: nothing below, and no later call, looks at the environment again)
+    if (t->dbg.no_unit_rsqrt && opt.arith < 2) {         // (level 2 takes the hardware's seeds either way)
+        const void *tab = opt.arith == 1 ? (ptx_arith_kernels_1p ? ptx_arith_kernels_1p() : nullptr) : (ptx_arith_kernels_0p ? ptx_arith_kernels_0p() : nullptr);
+        const void *last = opt.arith == 1 ? (ptx_arith_last_1p ? ptx_arith_last_1p() : nullptr) : (ptx_arith_last_0p ? ptx_arith_last_0p() : nullptr);
+        if (!tab || !last) { set_error(PTX_ERR_UNSUPPORTED, "PTX_DEBUG_NO_UNIT_RSQRT: this library was built without the plain code objects of arithmetic level " + std::to_string(opt.arith)); return fail(PTX_ERR_UNSUPPORTED); }
+        t->ks = static_cast<const KernelSet *>(tab); t->ksl = static_cast<const LastKernelSet *>(last);
+        if (t->ks->arith != opt.arith || t->ksl->arith != opt.arith) { set_error(PTX_ERR_HIP, "arithmetic code object mismatch (plain)"); return fail(PTX_ERR_HIP); }
+    }
     t->sort_by_material = opt.sort_by_material != 0;
     hipDeviceProp_t prop;
     HC(hipGetDeviceProperties(&prop, dev));
@@ -1699,6 +1714,21 @@ int ptx_kat_fast_exact(ptx_tracer *t, int64_t mismatches[3]) {
     unsigned long long h[3];
     HIPCHECK(d.download(h));
     for (int k = 0; k < 3; k++) mismatches[k] = (int64_t)h[k];
+    return PTX_OK;
+}
+
+int ptx_kat_unit_rsqrt(ptx_tracer *t, int exponent_reps, int64_t random_sets, int64_t counts[4]) {
+    KAT_PROLOGUE
+    if (!counts || exponent_reps < 0 || random_sets < 0) return set_error(PTX_ERR_INVALID, "bad argument");
+    DevBuf<unsigned long long> d;
+    HIPCHECK(d.alloc(4));
+    HIPCHECK(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), t->stream));
+    launch_kat_unit_rsqrt(t->cus, t->stream, d.p, exponent_reps, (unsigned long long)random_sets);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    unsigned long long h[4];
+    HIPCHECK(d.download(h));
+    for (int k = 0; k < 4; k++) counts[k] = (int64_t)h[k];
     return PTX_OK;
 }
 

@@ -47,12 +47,28 @@
 // `ptd` is renamed for the translation units of levels 1 and 2, before pt_device.h is seen: every inline function of pt_device.h /
 // pt_bvh.h compiled with those flags gets a symbol of its own, so the linker can never hand an exact translation unit a contracted
 // copy (or the other way round).
-#if PT_ARITH == 1
+// PT_PLAIN (Makefile: with -DPT_UNIT_RSQRT=0 -DPT_SHARED_RCP=0, levels 0 and 1): the same once more without those two routines of
+// pt_device.h, exported as ptx_arith_kernels_<level>p / ptx_arith_last_<level>p (PTX_DEBUG_NO_UNIT_RSQRT).
+#if defined(PT_PLAIN) && PT_PLAIN && !defined(PT_ARITH)
+#error "PT_PLAIN needs PT_ARITH"
+#endif
+#if defined(PT_PLAIN) && PT_PLAIN && PT_ARITH == 0
+#define ptd ptd_plain0
+#define PT_ARITH_TAG 0p
+#elif defined(PT_PLAIN) && PT_PLAIN && PT_ARITH == 1
+#define ptd ptd_plain1
+#define PT_ARITH_TAG 1p
+#elif defined(PT_PLAIN) && PT_PLAIN
+#error "PT_PLAIN: levels 0 and 1 only"
+#elif PT_ARITH == 1
 #define ptd ptd_arith1
 #elif PT_ARITH == 2
 #define ptd ptd_arith2
 #elif defined(PT_ARITH) && PT_ARITH != 0
 #error "PT_ARITH must be 0, 1 or 2"
+#endif
+#ifndef PT_ARITH_TAG
+#define PT_ARITH_TAG PT_ARITH
 #endif
 #include <string.h>
 
@@ -1681,7 +1697,7 @@ const KernelSet g_kernels_here = {PT_ARITH, ks_bounce, ks_mesh, ks_finish, ks_ka
 // all this translation unit exports: its table
 #define PT_ARITH_EXPORT_(n) ptx_arith_kernels_##n
 #define PT_ARITH_EXPORT(n) PT_ARITH_EXPORT_(n)
-extern "C" const void *PT_ARITH_EXPORT(PT_ARITH)(void) { return &g_kernels_here; }
+extern "C" const void *PT_ARITH_EXPORT(PT_ARITH_TAG)(void) { return &g_kernels_here; }
 
 #else   // PT_KERNELS_LAST_UNIT
 // pt_kernels_last.hip: this source again, per level, for ONE thing -- the light-only last bounce (k_bounce<false, MODE_LAST, .>), a code
@@ -1701,5 +1717,5 @@ const LastKernelSet g_last_here = {PT_ARITH, ks_bounce_last};
 // all this translation unit exports: its launcher
 #define PT_LAST_EXPORT_(n) ptx_arith_last_##n
 #define PT_LAST_EXPORT(n) PT_LAST_EXPORT_(n)
-extern "C" const void *PT_LAST_EXPORT(PT_ARITH)(void) { return &g_last_here; }
+extern "C" const void *PT_LAST_EXPORT(PT_ARITH_TAG)(void) { return &g_last_here; }
 #endif

@@ -22,6 +22,8 @@ struct DebugSwitches {
     bool force_fast = false;           // PTX_DEBUG_FORCE_FAST: ask for the specialised variant at every launch (refused with PTX_ERR_INVALID
                                        // where its preconditions do not hold; tests only)
     bool no_tangents = false;          // PTX_DEBUG_NO_TANGENTS: DScene::ctan is NULL, every lane computes its frame (A/B timing, tests of both)
+    bool no_unit_rsqrt = false;        // PTX_DEBUG_NO_UNIT_RSQRT: levels 0 and 1 from the code objects built without pt_rsqrt_unit and the shared reciprocal
+                                       // of the slab test (pt_device.h; A/B timing, tests of both)
     bool keep_dir_skip = false;        // PTX_DEBUG_KEEP_DIR_SKIP: a debug capture leaves the record masks on (tests only)
     bool no_idx16 = false;             // PTX_DEBUG_NO_IDX16: the two-word local index everywhere (tests of both forms)
     bool no_priority = false;          // PTX_DEBUG_NO_PRIORITY: every stream at the default priority (tuning experiments)

@@ -22,6 +22,7 @@ DebugSwitches read_debug_switches() {
     d.no_tile_geoms = on("PTX_DEBUG_NO_TILE_GEOMS"); d.no_tile_geoms_dof = on("PTX_DEBUG_NO_TILE_GEOMS_DOF");
     d.no_fast = on("PTX_DEBUG_NO_FAST"); d.no_last = on("PTX_DEBUG_NO_LAST"); d.last_inplace = on("PTX_DEBUG_LAST_INPLACE");
     d.force_fast = on("PTX_DEBUG_FORCE_FAST"); d.no_tangents = on("PTX_DEBUG_NO_TANGENTS"); d.keep_dir_skip = on("PTX_DEBUG_KEEP_DIR_SKIP");
+    d.no_unit_rsqrt = on("PTX_DEBUG_NO_UNIT_RSQRT");
     d.no_idx16 = on("PTX_DEBUG_NO_IDX16"); d.no_priority = on("PTX_DEBUG_NO_PRIORITY"); d.no_first_fusion = on("PTX_DEBUG_NO_FIRST_FUSION");
     d.wg_per_cu = count("PTX_DEBUG_WG_PER_CU", 1);
     d.total_wg_per_cu = count("PTX_DEBUG_TOTAL_WG_PER_CU", 0);
