@@ -560,6 +560,11 @@ int ptx_debug_cube_tangents(int ngeoms, const ptx_geom *geoms, float *out36_per_
 int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]);
 /* Debug: workgroups of the specialised later-bounce kernel that fit a CU with lds_bytes of dynamic LDS each (0: what this tracer launches). */
 int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes);
+/* Host-only: the layout of the local index (the sort's output) this tracer's launches use.  out8 = { 1: bin-major, written in k_bounce's
+ * tile loop / 0: chunk-compact, written by its tail; log2 N2; words allocated per entry; nbins * N2 (the bound an entry is checked
+ * against); words of one segment's index; bytes per path and iteration the memory rule counted; the stage's slots; why not bin-major
+ * (0: it is; 1 PTX_DEBUG_TAIL_INDEX, 2 split bounce, 3 more than 64 bins, 4 no direct epilogue, 5 offsets pass 32 bits, 6 memory rule) }. */
+int ptx_debug_index_plan(ptx_tracer *t, int64_t out8[8]);
 /* Debug: after waiting for the tracer's streams, the nonzero words left in the per-iteration "lit" bit-planes (out3[0]) and in the
  * per-bounce and group totals (out3[1]) of every lane's segments -- both 0 between launch sets, which clear what they read.  Segments
  * of a traced-ahead batch not yet gathered are not counted, nor are the lanes marked for a full clear before their next set (out3[2]). */

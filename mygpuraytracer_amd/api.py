@@ -560,6 +560,8 @@ def load_library():
         L.ptx_debug_cube_tangents.restype, L.ptx_debug_cube_tangents.argtypes = i, [i, C.POINTER(Geom), vp]
     if hasattr(L, "ptx_debug_mesh_plan"):
         L.ptx_debug_mesh_plan.restype, L.ptx_debug_mesh_plan.argtypes = i, [vp, i, vp]
+    if hasattr(L, "ptx_debug_index_plan"):      # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
+        L.ptx_debug_index_plan.restype, L.ptx_debug_index_plan.argtypes = i, [vp, vp]
     if hasattr(L, "ptx_kat_fast_exact"):        # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
         L.ptx_kat_fast_exact.restype, L.ptx_kat_fast_exact.argtypes = i, [vp, vp]
     if hasattr(L, "ptx_kat_unit_rsqrt"):
@@ -1101,6 +1103,16 @@ class Tracer:
         _check(self.lib.ptx_debug_mesh_plan(self.h, int(gi), _ptr(o)), "ptx_debug_mesh_plan")
         d = dict(zip(("root", "depth", "wroot", "wneed", "bvh_stack", "split"), (int(x) for x in o[:6])))
         d["frame_walk"], d["stack_walk"] = WALK_NAMES[int(o[6])], WALK_NAMES[int(o[7])]
+        return d
+
+    def index_plan(self):
+        """ptx_debug_index_plan (host only): the layout of the local index this tracer's launches use -- dict(loop, n2_log2, words, entries,
+        seg_words, bytes_per_path, slots, why); loop = bin-major and written in k_bounce's tile loop, why = 0 or the term of the plan's
+        predicate that sent the tracer back to the tail's chunk-compact index."""
+        o = np.zeros(8, np.int64)
+        _check(self.lib.ptx_debug_index_plan(self.h, _ptr(o)), "ptx_debug_index_plan")
+        d = dict(zip(("loop", "n2_log2", "words", "entries", "seg_words", "bytes_per_path", "slots", "why"), (int(x) for x in o)))
+        d["loop"] = bool(d["loop"])
         return d
 
     def stats(self):

@@ -45,7 +45,11 @@ __global__ void k_capture_prefix(const int32_t *chunk, int chunk_cap, int nruns,
     gs[nruns] = s; ga[nruns] = a;
 }
 __global__ void k_capture(PathSoA stage, const int32_t *chunk, int chunk_cap, int nruns, const int32_t *gs, const int32_t *ga, int cap,
-                          int32_t *out_i, float *out_f, int idx16) {
+                          int32_t *out_i, float *out_f, int idx16, int loop_idx, int nbins) {
+    // (bin-major index, BounceParams::loop_idx: stage.i is the index itself, the place inside the chunk the entry's low bits)
+    const bool loop = (loop_idx & 1) != 0;
+    const int n2s = (loop_idx >> 8) & 31;
+    const size_t entries = (size_t)nbins << n2s;
     const int n = min(gs[nruns], cap);
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         int lo = 0, hi = nruns - 1;                              // last run that starts at or before k
@@ -53,10 +57,11 @@ __global__ void k_capture(PathSoA stage, const int32_t *chunk, int chunk_cap, in
             const int mid = (lo + hi + 1) >> 1;
             if (gs[mid] <= k) lo = mid; else hi = mid - 1;
         }
-        const int li = chunk[2 * chunk_cap + lo] + (k - gs[lo]);
-        const uint32_t w = (uint32_t)stage.lsrc()[li];
-        int j = idx16 ? li + (int)(int16_t)(w & 0xffffu) : (int)w;
-        const int rank = idx16 ? (int)(w >> 16) : stage.lidx()[li];
+        int li = chunk[2 * chunk_cap + lo] + (k - gs[lo]);
+        if (loop) li = li < 0 ? 0 : ((size_t)li >= entries ? (int)entries - 1 : li);
+        const uint32_t w = (uint32_t)(loop ? stage.i[li] : stage.lsrc()[li]);
+        int j = idx16 ? (loop ? li & ((1 << n2s) - 1) : li) + (int)(int16_t)(w & 0xffffu) : (int)w;
+        const int rank = idx16 ? (int)(w >> 16) : loop ? stage.i[entries + li] : stage.lidx()[li];
         j = j < 0 ? 0 : (j >= cap ? cap - 1 : j);
         out_i[k] = stage.pix()[j]; out_i[(size_t)cap + k] = ga[lo] + rank; out_i[2 * (size_t)cap + k] = stage.mg()[j];
         for (int f = 0; f < SOA_LOGICAL_FLOATS; f++) out_f[(size_t)f * cap + k] = stage.fieldAt(f, (size_t)j);
@@ -335,6 +340,8 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     bool aux_dirty[MAX_LANES] = {};
     unsigned long long cache_dir_bins = ~0ull, cache_ntab_bins = 0ull;      // ... as the cached camera bounce was written
     int cache_idx16 = 0;                                                    // ... and its local index (BounceParams::idx16)
+    bool cache_loop = false;                                                // ... and that index's layout (bit 0 of BounceParams::loop_idx)
+    IndexPlan ix;                                                           // the local index's layout, for every launch of this tracer
     DevBuf<uchar4> d_pbo;                                // ptx_write_pbo's device staging (allocated on first use)
     DevBuf<float> d_denoised;                            // ptx_write_denoised_pbo_device's copy of the host frame (first use)
     DevBuf<float> d_albedo;                              // apps variant only: W*H*3
@@ -597,6 +604,13 @@ BounceParams fill_bounce_params(const ptx_tracer *t, const BatchSet &s, const Ba
     // (the local index's form: this launch's, and that of the launch whose stage it reads)
     bp.idx16 = first ? p.idx16_first : p.idx16_later;
     bp.in_idx16 = first ? 0 : from_cache ? t->cache_idx16 : (b == 1 ? p.idx16_first : p.idx16_later);
+    // ... and its layout.  Bin-major: the stages' int pointers are the lane's first segment of the index itself (a cached stage's: its one)
+    const bool in_loop = first ? false : from_cache ? t->cache_loop : t->ix.loop;
+    bp.loop_idx = (t->ix.loop ? 1 : 0) | (in_loop ? 2 : 0) | (t->ix.words == 2 ? 4 : 0) | (t->ix.n2_log2 << 8);
+    if (t->ix.loop) {
+        bp.in.i = from_cache ? t->d_ibuf[2].p : t->d_ibuf[b & 1] + seg0 * t->ix.seg_words;
+        bp.stage.i = to_cache ? t->d_ibuf[2].p : t->d_ibuf[1 - (b & 1)] + seg0 * t->ix.seg_words;
+    }
     bp.nbins = t->nbins; bp.maxTiles = t->maxTiles;
     bp.counts_all = v.counts_all; bp.counts_scat = v.counts_scat;
     bp.chunk = to_cache ? t->d_cache_chunk : v.chunks(b); bp.chunk_cap = (int32_t)p.chunk_cap;
@@ -687,14 +701,14 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
             HIPCHECK(hipMemcpyAsync(t->d_cache_totals, v.totals(0, 0), sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToDevice, stream));
             HIPCHECK(hipMemcpyAsync(t->d_cache_super, v.supers(0, 0), sizeof(int32_t) * 2 * nb * t->nsuper, hipMemcpyDeviceToDevice, stream));
             t->cache_gx = gx_b;
-            t->cache_dir_bins = bp.dir_bins; t->cache_ntab_bins = bp.ntab_bins; t->cache_idx16 = bp.idx16;
+            t->cache_dir_bins = bp.dir_bins; t->cache_ntab_bins = bp.ntab_bins; t->cache_idx16 = bp.idx16; t->cache_loop = (bp.loop_idx & 1) != 0;
             t->cache_valid = true;
         }
         if (t->capture_bounce == b && t->d_cap && b + 1 < t->traceDepth) {       // (K == 1, lane 0 -- see ptx_render: segment 0 of the buffers)
             int32_t *gs = t->d_cap + 3 * (size_t)t->cap + nb, *ga = gs + p.chunk_cap + 1;
             hipLaunchKernelGGL(k_capture_prefix, dim3(1), dim3(64), 0, stream, bp.chunk, (int)p.chunk_cap, nb * gx_b, gs, ga);
             hipLaunchKernelGGL(k_capture, dim3(std::min(1024, (t->cap + 255) / 256)), dim3(256), 0, stream, bp.stage, bp.chunk, (int)p.chunk_cap,
-                               nb * gx_b, gs, ga, t->cap, t->d_cap, t->d_cap_f, bp.idx16);
+                               nb * gx_b, gs, ga, t->cap, t->d_cap, t->d_cap_f, bp.idx16, bp.loop_idx, nb);
             HIPCHECK(hipMemcpyAsync(t->d_cap + 3 * (size_t)t->cap, v.totals(b, 1), sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, stream));
             t->cap_filled = true;
         }
@@ -890,6 +904,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     if (const int rc = pt_prepare_scene(ngeoms, geoms, nmaterials, materials, opt, t->tm.owned, t->nbins, prop.sharedMemPerBlock, t->dbg.scene, hs)) return fail(rc);
     static_cast<SceneFacts &>(*t) = hs;
     // ---- 5. iterations per launch set, launch sets in flight
+    long long ix_budget = 0;
     {
         size_t mem_free = 0, mem_total = 0;
         if (opt.batch <= 0 && hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { mem_free = mem_total = 0; (void)hipGetLastError(); }
@@ -897,6 +912,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         if (!plan.refusal.empty()) { set_error(PTX_ERR_UNSUPPORTED, plan.refusal); return fail(PTX_ERR_UNSUPPORTED); }
         t->kmax = *kmax_used = plan.kmax;
         t->lanes = plan.lanes;
+        ix_budget = launch_budget_bytes(mem_free, mem_total, t->dbg.mem_budget_mb);
     }
     // ---- 6. streams and events
     if (stream) { t->stream = (hipStream_t)stream; t->own_stream = false; }
@@ -946,6 +962,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     t->h_aabb = std::move(hs.aabb);                       // (the host keeps corners for the camera tile masks)
     for (const DGeom &g : hs.geoms) t->h_geom_type.push_back(g.type);
     t->has_bvh = t->d_bvh_root != nullptr;
+    t->ix = plan_local_index(*t, t->cap, t->tm.owned, t->kmax, ix_budget);      // (behind has_bvh: it asks plan_batch for every set's grids)
     t->h_roots = hs.roots; t->h_depths = hs.depths; t->h_wroots = hs.wroots; t->h_wneeds = hs.wneeds;
     t->h_spec = std::move(hs.h_spec);
     const size_t npix = (size_t)W * H, nseg = (size_t)t->kmax * t->lanes, nb = (size_t)t->nbins;
@@ -956,7 +973,8 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
     for (int k = 0; k < (t->cache_active() ? 3 : 2); k++) {
         const size_t stride = k == 2 ? (size_t)t->cap : t->field_stride;
         HC(t->d_fbuf[k].alloc(SOA_FLOATS * stride));
-        HC(t->d_ibuf[k].alloc(SOA_INTS * stride));
+        // (bin-major index: the ints of a stage are its index alone, nbins x N2 entries per segment)
+        HC(t->d_ibuf[k].alloc(t->ix.loop ? t->ix.seg_words * (k == 2 ? 1 : nseg) : SOA_INTS * stride));
         carve(t->soa[k], t->d_fbuf[k], t->d_ibuf[k], stride);
     }
     t->seg_part = 3 * (size_t)t->cap + (size_t)t->cap / 32;     // per-iteration radiance of the OWNED pixels (slot-indexed), whole tiles, then the
@@ -1800,6 +1818,16 @@ int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]) {
     out8[0] = root; out8[1] = depth; out8[2] = wroot; out8[3] = wneed; out8[4] = t->bvh_stack; out8[5] = t->split_mesh ? 1 : 0;
     out8[6] = root < 0 ? PTX_WALK_LOOP : (t->split_mesh && wide) ? PTX_WALK_WIDE_REFILL : PTX_WALK_SKIP;
     out8[7] = root < 0 ? PTX_WALK_LOOP : wide ? PTX_WALK_WIDE : ordered ? PTX_WALK_ORDERED : PTX_WALK_SKIP;
+    return PTX_OK;
+}
+
+// Host-only: the layout of the local index this tracer's launches use (pt_plan.h, IndexPlan) -- what the tests of both forms assert the
+// code path by.
+int ptx_debug_index_plan(ptx_tracer *t, int64_t out8[8]) {
+    if (!t || !out8) return set_error(PTX_ERR_INVALID, "null argument");
+    const IndexPlan &x = t->ix;
+    out8[0] = x.loop ? 1 : 0; out8[1] = x.n2_log2; out8[2] = x.words; out8[3] = (int64_t)x.entries; out8[4] = (int64_t)x.seg_words;
+    out8[5] = x.bytes_per_path; out8[6] = t->cap; out8[7] = x.why_code;
     return PTX_OK;
 }
 

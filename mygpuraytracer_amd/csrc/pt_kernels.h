@@ -121,7 +121,7 @@ struct PathSoA {
     // segments x capacity; a segment's part of an array starts seg * capacity slots further).  Kept as bases + stride rather than a pointer
     // per field: a kernel that holds two of these in scalar registers for its whole tile loop has none left for anything else.
     float *q;          // [4][stride] quads
-    int32_t *i;        // [3][stride]: idx, lsrc, lidx
+    int32_t *i;        // [3][stride]: idx, lsrc, lidx -- or, where the local index is bin-major (BounceParams::loop_idx), that index and nothing else
     uint32_t stride;
     struct F4 { float *b; __host__ __device__ float &operator[](size_t s) const { return b[s * 4]; } };      // one component of a quad array
     struct I4 { int32_t *b; __host__ __device__ int32_t &operator[](size_t s) const { return b[s * 4]; } };
@@ -269,6 +269,16 @@ struct BounceParams {
     unsigned long long ntab_bins;          // bit b: every hit of material bin b is a cube hit (no sphere or OBJ geom has the material): its records
                                            // carry the 3-bit code of the cube's tabulated normal in pix's bits 28-30 instead of the normal
     int32_t apps;                          // apps/src variant: radiance * PI at gather, albedo AOV on iteration 1
+    // The local index written INSIDE the tile loop (pt_plan.h, IndexPlan; in the padding behind apps: no other member moves).  Bin-major:
+    // a segment's index is [nbins][N2] entries, N2 = the stage's slots rounded up to a power of two, and the entry of a stored path is
+    // bin * N2 + S + q -- S the first slot of the writing workgroup's chunk, q the bin's stored paths in the chunk's earlier tiles + the
+    // path's rank among the tile's -- all of which a lane of the direct epilogue holds.  The word(s) are today's: (slot - (S + q)) as 16
+    // signed bits | rank << 16, or slot and rank in two words (the second [nbins][N2] behind the first).  A run starts at bin * N2 + S,
+    // known at kernel start; the reader's position inside the chunk is (entry & (N2 - 1)).  In this form stage.i / in.i point at the
+    // index of the launch's first segment (segments nbins * N2 * words apart), and the stage key, the per-tile prefix tables and the
+    // tail's pass over the keys do not exist.  Bit 0: THIS launch writes the form; bit 1: the launch that wrote `in` did; bit 2: two
+    // words per entry are allocated (some launch set of the tracer keeps the two-word form); bits 8-15: log2 N2.
+    int32_t loop_idx;
     float *albedo;
     int32_t nbins, maxTiles;
     int32_t *counts_all, *counts_scat;     // [nbins][maxTiles]: prefix of the tile inside its workgroup's chunk

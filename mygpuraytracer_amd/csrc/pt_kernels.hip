@@ -458,6 +458,14 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
     // of the pair test and the ranking's one.  The histogram rows a wave zeroes are now its OWN, after the pair test's barriers (every
     // wave has then left the previous tile): no other wave can still be reading them.
     const bool direct = PT_DIRECT_STORE && MODE != 2 && (FAST || nb <= 64);      // (the specialised variants are only launched with <= 64 bins: fast_violation)
+    // The local index in its bin-major form (BounceParams::loop_idx), unsplit bounce only.  loop_w: a pending lane of the direct epilogue
+    // stores its index word beside its quads -- no stage key, no per-tile prefix tables, no stored count per tile, and no pass over the
+    // keys in the tail.  in_loop: `in` was written that way.  Both are compile-time false in the split bounce's kernels.
+    const bool loop_w = MODE == 0 && !LAST && direct && (p.loop_idx & 1), in_loop = MODE == 0 && !FIRST && (p.loop_idx & 2);
+    const uint32_t n2s = (uint32_t)(p.loop_idx >> 8) & 31u;                                   // log2 N2
+    const size_t ix_seg = ((size_t)nb << n2s) << ((p.loop_idx >> 2) & 1);                       // words of one segment's index
+    int32_t *ix_out = p.stage.i + (p.seg_stage ? ix_seg * seg : 0);
+    const int32_t *ix_in = p.in.i + (p.seg_in ? ix_seg * seg : 0);
     int32_t *chunk_out = p.chunk + p.seg_chunk * seg;
     int32_t *super_all = p.super_all + p.seg_totals * seg, *super_scat = p.super_scat + p.seg_totals * seg;
     int32_t *totals_all = p.totals_all + p.seg_totals * seg, *totals_scat = p.totals_scat + p.seg_totals * seg;
@@ -571,8 +579,10 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
                 for (int st = WIN / 2; st; st >>= 1) k += win[k + st] <= jp ? st : 0;      // last run that starts at or before jp
                 // (the clamp cannot bite while the tables are consistent: it is there so that no gather address depends on that)
                 const uint32_t li = (uint32_t)(win[2 * (WIN + 1) + k] + (jp - win[k]));
-                if (__builtin_expect(li >= p.fence_slots, 0)) fence_report(p);
-                li4 = min(li, p.fence_slots - 1u) << 2;
+                // (an entry of the bin-major index is checked against ITS words, nbins * N2; the slot it names against fence_slots, in fetch)
+                const uint32_t li_lim = in_loop ? (uint32_t)nb << n2s : p.fence_slots;
+                if (__builtin_expect(li >= li_lim, 0)) fence_report(p);
+                li4 = min(li, li_lim - 1u) << 2;
                 idx_base = win[WIN + 1 + k];
                 done = true;
             }
@@ -588,10 +598,11 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
         const PathSoA in = soa_fresh(in_k);
         // the sorted stream is not materialised: its position is entry li of the previous bounce's local index, which names the
         // slot of that bounce's stage and the path's rank inside its run
-        const uint32_t w = (uint32_t)ld_u(in.lsrc(), li4);
+        // (bin-major form: the entry's place in its bin's row is the position inside the writer's chunk the distance counts from)
+        const uint32_t w = (uint32_t)ld_u(in_loop ? ix_in : in.lsrc(), li4);
         uint32_t j;
-        if (p.in_idx16) { j = (li4 >> 2) + (uint32_t)(int32_t)(int16_t)(w & 0xffffu); r.idx = idx_base + (int)(w >> 16); }
-        else { j = w; r.idx = idx_base + ld_u(in.lidx(), li4); }
+        if (p.in_idx16) { j = (in_loop ? (li4 >> 2) & ((1u << n2s) - 1u) : li4 >> 2) + (uint32_t)(int32_t)(int16_t)(w & 0xffffu); r.idx = idx_base + (int)(w >> 16); }
+        else { j = w; r.idx = idx_base + ld_u(in_loop ? ix_in + ((p.loop_idx & 4) ? (size_t)nb << n2s : 0) : in.lidx(), li4); }
         if (__builtin_expect(j >= p.fence_slots, 0)) fence_report(p);
         const uint32_t j4 = min(j, p.fence_slots - 1u) << 2;
         const bool with_dir = (uint32_t)(jp - dir_lo0) < (uint32_t)dir_len0 || (uint32_t)(jp - dir_lo1) < (uint32_t)dir_len1;
@@ -829,7 +840,7 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
             int mbin = 0;
             bool mpend = false;
             if (alive) classifyRay(hit, ps, pix, mbin, mpend);
-            if (tid == 0) tile_np[tile] = 0;
+            if (!loop_w && tid == 0) tile_np[tile] = 0;
             if (tid == 0) run_all[p.sort ? p.sc.nmats - 1 : 0] += min(TILE, n_in - tile * TILE);
             continue;
         }
@@ -943,6 +954,15 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
         // is still summing the previous tile's)
         if (MODE != 2 && direct && lane < nb) { w_all[wave * nb + lane] = 0; w_scat[wave * nb + lane] = 0; }
         if (MODE != 2 && alive) classifyRay(hit, ps, pix, bin, pending);
+        // Bin-major index: the chunk's survivors / stored paths of this path's bin BEFORE this tile -- what the tail used to gather back from
+        // counts_all / counts_scat.  Ordering: run_all / run_scat are written (a) by wave 0 in the epilogue of a tile, behind that tile's
+        // ranking barrier below, and (b) by thread 0 in the camera bounce's empty-tile shortcut, which has no barrier of its own but which
+        // thread 0 can only reach behind the ranking barrier of the tile before it.  Every path to here has passed a barrier of THIS tile
+        // (the pair test's, or the one in its place), which every write of an earlier tile precedes in its writer's program order; and this
+        // tile's write (a) lies behind the ranking barrier, which no wave passes before every wave has made this read.  So the read sees
+        // exactly the earlier tiles' sums, in every wave.
+        int pre_all = 0, pre_scat = 0;
+        if (loop_w && pending) { pre_all = run_all[bin]; pre_scat = run_scat[bin]; }
         STAMP(2);        // classify + deposit
         // stable rank of this path inside its tile, per material bin: among all alive paths (-> RNG stream
         // index) and among the stored ones (-> storage position)
@@ -1020,8 +1040,10 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
             int ca = 0, cs = 0;
             if (ln < nb) for (int w = 0; w < WAVES; w++) { ca += w_all[w * nb + ln]; cs += w_scat[w * nb + ln]; }
             if (wave == 0 && ln < nb) {      // the tile's place in the chunk: one wave's business, as before
-                counts_all[(size_t)ln * p.maxTiles + tile] = MODE == 1 ? ca : run_all[ln];
-                counts_scat[(size_t)ln * p.maxTiles + tile] = MODE == 1 ? cs : run_scat[ln];
+                if (!loop_w) {               // (bin-major index: nobody reads the tables, every pending lane took its prefix from LDS above)
+                    counts_all[(size_t)ln * p.maxTiles + tile] = MODE == 1 ? ca : run_all[ln];
+                    counts_scat[(size_t)ln * p.maxTiles + tile] = MODE == 1 ? cs : run_scat[ln];
+                }
                 run_all[ln] += ca;
                 run_scat[ln] += cs;
             }
@@ -1111,13 +1133,26 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
                     C.x = hit.n.x; C.y = hit.n.y; C.z = hit.n.z; C.w = p.uses_uv ? hit.u : 0.f;
                     st_u(reinterpret_cast<quad *>(stage.quadC()), g16, C);
                 }
-                if (!partial) st_u(stage.idx(), g4, stage_key(bin, r_all, r_scat));
+                if (loop_w) {
+                    // the path's word of the local index, at bin * N2 + (its position in the chunk): both operands of the distance lie in
+                    // the chunk's slot range (pos <= slot: a bin's stored paths of the earlier tiles are at most those tiles' slots), so
+                    // it fits wherever idx16 holds today, and so does the rank.  The entry is checked against the index's words before it
+                    // is an address.
+                    const uint32_t pos = (uint32_t)(tile0 * TILE + pre_scat + r_scat), e = ((uint32_t)bin << n2s) + pos, slot = g4 >> 2;
+                    const uint32_t rank = (uint32_t)(pre_all + r_all);
+                    if (__builtin_expect(e >= (uint32_t)nb << n2s, 0)) fence_report(p);
+                    else if (p.idx16) st_u(ix_out, e << 2, (int32_t)(((slot - pos) & 0xffffu) | (rank << 16)));
+                    else if (p.loop_idx & 4) {      // (the second table exists: the host's plan, not this launch, says so)
+                        st_u(ix_out, e << 2, (int32_t)slot);
+                        st_u(ix_out + ((size_t)nb << n2s), e << 2, (int32_t)rank);
+                    } else fence_report(p);
+                } else if (!partial) st_u(stage.idx(), g4, stage_key(bin, r_all, r_scat));
             }
             // stored paths of the tile: pass 1's own lie in slots [0, n); a partial tile's parked rays in the top *ccnt slots.  (The top
             // count is vestigial: only the removed one-barrier ranking pass let the tail read it -- the ranking pass that is left writes a key for
             // every slot and overwrites this word with TILE, or the tail takes TILE as known, so the tail's top-of-tile test never bites.  It
             // stays so that the kernels' instruction streams are the ones measured.)
-            if (tid == 0) tile_np[tile] = npend_r | (partial ? *ccnt << 16 : 0);
+            if (!loop_w && tid == 0) tile_np[tile] = npend_r | (partial ? *ccnt << 16 : 0);
             STAMP(4);
             if (MODE == 1 && *qcnt > QCAP - TILE) flushQueue(p, seg, qbuf, qcnt, qbase, tid);      // (uniform: the tile's last atomic on it lies before the ranking's barrier)
             continue;
@@ -1201,14 +1236,17 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
     // index go the path's stage slot and its rank among all survivors of its bin in the chunk.  Nothing of another workgroup is
     // needed, so there is no wait; what IS global (the position of a run in the whole stream) the next launch derives from the
     // run table below.
+    // Bin-major index (loop_w): the words were written in the tile loop; a run starts at bin * N2 + the chunk's first slot, so neither the
+    // scan over the bins nor the pass over the keys is left -- only the run table and the totals.  (The barrier stays: thread b reads
+    // what wave 0 and, in the camera bounce's empty tiles, thread 0 added.)
     int32_t *cbb = toff;                                              // (free after the tile loop)
-    if (nb <= 64) {
+    if (!loop_w && nb <= 64) {
         if (wave == 0) {
             const int v = lane < nb ? run_scat[lane] : 0;
             const int inc = waveInclusiveScan(v, lane);
             if (lane < nb) cbb[lane] = inc - v;
         }
-    } else if (tid == 0) {
+    } else if (!loop_w && tid == 0) {
         int o = 0;
         for (int b = 0; b < nb; b++) { cbb[b] = o; o += run_scat[b]; }
     }
@@ -1218,11 +1256,11 @@ __global__ __launch_bounds__(TILE, !FAST ? PT_BOUNCE_WAVES : MODE_ == 1 ? PT_FAS
         const size_t r = (size_t)b * gridDim.x + blockIdx.x;
         chunk_out[r] = ca;
         chunk_out[(size_t)p.chunk_cap + r] = cs;
-        chunk_out[2 * (size_t)p.chunk_cap + r] = tile0 * TILE + cbb[b];
+        chunk_out[2 * (size_t)p.chunk_cap + r] = loop_w ? (int32_t)(((uint32_t)b << n2s) + (uint32_t)(tile0 * TILE)) : tile0 * TILE + cbb[b];
         if (ca) { atomicAdd(&super_all[b * p.nsuper + (blockIdx.x >> 6)], ca); atomicAdd(&totals_all[b], ca); }
         if (cs) { atomicAdd(&super_scat[b * p.nsuper + (blockIdx.x >> 6)], cs); atomicAdd(&totals_scat[b], cs); }
     }
-    {
+    if (!loop_w) {
         const PathSoA stage = soa_fresh(stage_k);
         const int32_t *keys = stage.idx();
         constexpr int MOVE_U = 4;                                     // tiles per step: their keys are requested before the first is used

@@ -26,6 +26,7 @@ struct DebugSwitches {
                                        // of the slab test (pt_device.h; A/B timing, tests of both)
     bool keep_dir_skip = false;        // PTX_DEBUG_KEEP_DIR_SKIP: a debug capture leaves the record masks on (tests only)
     bool no_idx16 = false;             // PTX_DEBUG_NO_IDX16: the two-word local index everywhere (tests of both forms)
+    bool tail_index = false;           // PTX_DEBUG_TAIL_INDEX: the chunk-compact local index written by k_bounce's tail everywhere (A/B timing, tests of both)
     bool no_priority = false;          // PTX_DEBUG_NO_PRIORITY: every stream at the default priority (tuning experiments)
     bool no_first_fusion = false;      // PTX_DEBUG_NO_FIRST_FUSION: the split camera bounce without BounceParams::tile_done (tuning experiments)
     int wg_per_cu = 0;                 // PTX_DEBUG_WG_PER_CU (>= 1): the grid is what it says for every kernel (tuning experiments only)
@@ -53,6 +54,9 @@ struct LaunchPlan { int kmax = 1, lanes = 1; std::string refusal; };
 LaunchPlan plan_launch_sets(int owned_pixels, int nbins, int maxTiles, const ptx_options &opt, int kmax_cap, size_t mem_free, size_t mem_total,
                             long long budget_mb);
 
+// plan_launch_sets' ceiling on what the streams of all launch sets in flight may take, in bytes
+long long launch_budget_bytes(size_t mem_free, size_t mem_total, long long budget_mb);
+
 // The plain numbers a launch set's plan depends on, all fixed at create: the tracer (ptx_tracer) is one of these.
 struct PlanFacts : SceneFacts {      // (+ what the scene decides about how it is traced, pt_scene.h: ntri, cull, tri_lds, split_mesh, the masks ...)
     int nbins = 1, nmats = 0, ngeoms = 0, maxTiles = 0, cus = 0;
@@ -78,6 +82,26 @@ struct BatchPlan {
 };
 // defer: traced ahead of per-call requests; needs_albedo: the set contains iteration 1 of the apps variant
 BatchPlan plan_batch(const PlanFacts &f, int K, bool defer, bool needs_albedo);
+
+// The form of the local index (BounceParams::loop_idx), fixed at create for all of a tracer's launches.  loop: bin-major, written in
+// k_bounce's tile loop -- only where ALL of these hold: the switch PTX_DEBUG_TAIL_INDEX is not set; the bounce is unsplit (MODE 0: no
+// k_mesh / k_finish, whose ranking pass writes keys for the tail); at most 64 bins; the direct epilogue is compiled in; an entry's byte
+// offset fits 32 bits (nbins * N2 <= 2^30); and the streams with the nbins-fold index still fit the memory rule at the kmax chosen:
+// bytes_per_path x lanes x owned x kmax <= the budget, where bytes_per_path = plan_launch_sets' 176 - the three int words of two stages
+// (24) + the index of two stages, 2 x 4 x words x nbins x N2 / slots rounded up.  Otherwise today's tail and layout, and `why` says which
+// term failed.  words: 1 where every launch set the tracer can plan (K = 1 .. kmax, traced ahead or not, with or without the albedo
+// AOV) has the one-word form, else 2.
+struct IndexPlan {
+    bool loop = false;
+    int n2_log2 = 0;                   // N2 = 1 << n2_log2: the smallest power of two >= slots
+    int words = 1;                     // words allocated per entry
+    size_t entries = 0;                // nbins * N2: the bound an entry is checked against, and the words of one table
+    size_t seg_words = 0;              // entries * words: what one segment's index takes (the allocation is that per segment)
+    long long bytes_per_path = 176;    // per path and iteration of a launch set, all streams
+    const char *why = "";              // loop == false: the term that failed ...
+    int why_code = 0;                  // ... as a number, in the order of the list above (1 = the switch ... 6 = the memory rule)
+};
+IndexPlan plan_local_index(const PlanFacts &f, int slots, int owned_pixels, int kmax, long long budget_bytes);
 
 // Iterations per launch set of a ptx_render call of `count` iterations: kmax, or the equal cut of a short run over the lanes
 int sets_per_call(int count, int kmax, int lanes, int owned_pixels, long long split_min_paths, int dbg_nsets);

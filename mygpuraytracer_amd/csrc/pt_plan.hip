@@ -23,6 +23,7 @@ DebugSwitches read_debug_switches() {
     d.no_fast = on("PTX_DEBUG_NO_FAST"); d.no_last = on("PTX_DEBUG_NO_LAST"); d.last_inplace = on("PTX_DEBUG_LAST_INPLACE");
     d.force_fast = on("PTX_DEBUG_FORCE_FAST"); d.no_tangents = on("PTX_DEBUG_NO_TANGENTS"); d.keep_dir_skip = on("PTX_DEBUG_KEEP_DIR_SKIP");
     d.no_unit_rsqrt = on("PTX_DEBUG_NO_UNIT_RSQRT");
+    d.tail_index = on("PTX_DEBUG_TAIL_INDEX");
     d.no_idx16 = on("PTX_DEBUG_NO_IDX16"); d.no_priority = on("PTX_DEBUG_NO_PRIORITY"); d.no_first_fusion = on("PTX_DEBUG_NO_FIRST_FUSION");
     d.wg_per_cu = count("PTX_DEBUG_WG_PER_CU", 1);
     d.total_wg_per_cu = count("PTX_DEBUG_TOTAL_WG_PER_CU", 0);
@@ -43,6 +44,13 @@ DebugSwitches read_debug_switches() {
         }
     }
     return d;
+}
+
+long long launch_budget_bytes(size_t mem_free, size_t mem_total, long long budget_mb) {
+    long long budget = 64LL << 30;
+    if (mem_total > 0) budget = std::min<long long>(budget, (long long)(std::min(mem_free, mem_total) / 4));
+    if (budget_mb > 0) budget = budget_mb << 20;
+    return budget;
 }
 
 LaunchPlan plan_launch_sets(int owned_pixels, int nbins, int maxTiles, const ptx_options &opt, int kmax_cap, size_t mem_free, size_t mem_total,
@@ -68,9 +76,9 @@ LaunchPlan plan_launch_sets(int owned_pixels, int nbins, int maxTiles, const ptx
         const long long owned = std::max(owned_pixels, 1);
         long long want = ((24LL << 20) + owned / 2) / owned;
         want = std::min<long long>(32, std::max<long long>(12, want));
-        long long budget = 64LL << 30;
-        if (mem_total > 0) budget = std::min<long long>(budget, (long long)(std::min(mem_free, mem_total) / 4));
-        if (budget_mb > 0) budget = budget_mb << 20;
+        // (176 B is the chunk-compact index's figure; where the bin-major index is wider, plan_local_index takes that form only if the
+        // kmax chosen here still fits with ITS bytes per path, so the plans below do not move)
+        const long long budget = launch_budget_bytes(mem_free, mem_total, budget_mb);
         kmax = (int)std::min<long long>(want, std::max<long long>(1, budget / (176LL * p.lanes * owned)));
     }
     if (kmax_cap > 0 && kmax > kmax_cap) kmax = kmax_cap;      // (the retry after an allocation failed)
@@ -173,6 +181,32 @@ BatchPlan plan_batch(const PlanFacts &f, int K, bool defer, bool needs_albedo) {
     p.chunk_cap = (size_t)f.nbins * f.grid_seg;
     p.seg_counts = (2 * (size_t)f.nbins + 1) * f.maxTiles; p.seg_chunk = 2 * 3 * p.chunk_cap;
     return p;
+}
+
+IndexPlan plan_local_index(const PlanFacts &f, int slots, int owned_pixels, int kmax, long long budget_bytes) {
+    IndexPlan x;
+    slots = std::max(slots, 1);
+    while (((size_t)1 << x.n2_log2) < (size_t)slots) x.n2_log2++;
+    const size_t n2 = (size_t)1 << x.n2_log2;
+    x.entries = (size_t)std::max(f.nbins, 1) * n2;
+    for (int K = 1; K <= std::max(kmax, 1) && x.words == 1; K++)
+        for (int v = 0; v < 4 && x.words == 1; v++) {
+            const BatchPlan p = plan_batch(f, K, (v & 1) != 0, (v & 2) != 0);
+            if (!p.idx16_first || !p.idx16_later) x.words = 2;
+        }
+    x.seg_words = x.entries * x.words;
+    const long long wide = 176 - 24 + (long long)((2 * sizeof(int32_t) * x.seg_words + slots - 1) / slots);
+    const long long lanes = std::max(f.lanes, 1), owned = std::max(owned_pixels, 1);
+    auto no = [&](int code, const char *why) { x.why_code = code; x.why = why; };
+    if (f.dbg.tail_index) no(1, "PTX_DEBUG_TAIL_INDEX");
+    else if (f.split_mesh) no(2, "split bounce");
+    else if (f.nbins > 64) no(3, "more than 64 bins");
+    else if (!PT_DIRECT_STORE) no(4, "no direct epilogue");
+    else if (x.entries > ((size_t)1 << 30)) no(5, "index offsets pass 32 bits");
+    else if (wide * lanes * owned * std::max(kmax, 1) > budget_bytes) no(6, "memory rule");
+    else { x.loop = true; x.bytes_per_path = wide; }
+    if (!x.loop) { x.words = 1; x.entries = x.seg_words = 0; }
+    return x;
 }
 
 int sets_per_call(int count, int kmax, int lanes, int owned_pixels, long long split_min_paths, int dbg_nsets) {
