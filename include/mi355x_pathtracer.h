@@ -189,6 +189,29 @@ void ptx_destroy(ptx_tracer *t);                        /* pathtraceFree; NULL i
 int ptx_set_camera(ptx_tracer *t, const ptx_camera *camera, int trace_depth);  /* camera edits without re-init */
 int ptx_reset_image(ptx_tracer *t);
 
+/* ---- active tiles: switch parts of the frame off ------------------------------------------------------------------
+ * A tile is ptx_tile_pixels() consecutive owned pixels, tile = (y * W + x) / ptx_tile_pixels() -- one workgroup pass of the
+ * camera bounce; a tracer has ptx_num_tiles(t) of them, the last one maybe partial.  While a mask is set, the camera bounce
+ * of an inactive tile generates no rays, tests nothing and stores nothing: its paths end black and deposit nothing, so its
+ * pixels of the accumulation buffer keep their bits, and no later bounce sees them.  The path kernels are the same: the mask
+ * is ANDed into the per-tile table of visible geoms they read anyway (a tile that sees no geom takes the same way out).
+ *   Iteration numbers go on counting for the whole frame (they seed the RNG).  The shading RNG is also seeded by a path's place
+ *   in the material-sorted stream, which the missing paths shift: an active pixel receives another sample of the same
+ *   distribution than it would without a mask, not the same bits (a mask that switches off only tiles that see no geom shifts
+ *   nothing: the same bits).  ptx_stats.rays_per_bounce[0] still counts every owned pixel (a masked tile's paths are
+ *   survivors in the miss bin of the camera bounce); ptx_write_pbo divides by the iteration it is given and ptx_read_image
+ *   returns the raw sums, whatever the tiles received -- ptx_adaptive_resolve normalises tile by tile.
+ *   Setting or clearing is ordered like a camera change: it waits for the tracer's stream and drops what was traced ahead
+ *   (ptx_set_render_ahead), then writes the table with a launch on that stream.  A camera change (ptx_set_camera) keeps the mask.
+ * host_active: ntiles bytes, != 0 = active.  Refused: PTX_ERR_INVALID for tile_world > 1 or ntiles != ptx_num_tiles(t);
+ * PTX_ERR_UNSUPPORTED for a tracer without that table (no_cull, more than 32 geoms) or with the first-bounce cache in use
+ * (cache_first_bounce without antialiasing and depth of field: it replays a camera bounce of the whole frame).  The tracer
+ * stays usable, without a mask or with the one it had.  Without a mask every launch is what it is without these calls. */
+int ptx_tile_pixels(void);
+int ptx_num_tiles(const ptx_tracer *t);
+int ptx_set_active_tiles(ptx_tracer *t, const uint8_t *host_active, int ntiles);
+int ptx_clear_active_tiles(ptx_tracer *t);              /* no mask set: a no-op */
+
 /* One iteration of pathtrace() (iter is 1-based and seeds the RNG).  Enqueues on the tracer's stream and
  * returns without waiting; any read entry point below synchronises. */
 int ptx_iterate(ptx_tracer *t, int iter);
@@ -443,6 +466,17 @@ int  ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total);
 /* The same from a host frame (W*H*3 floats, a sum of samples_total samples, e.g. after ptx_multi_read_image), through a staging buffer
  * the handle owns; synchronous. */
 int  ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samples_total);
+/* The add in which tiles advance by different amounts (adaptive sampling below; multi-device callers): tile_samples_total[tile] = the
+ * samples tile's pixels hold now, tile = (y * W + x) / ptx_tile_pixels(), ntiles = ceil(W * H / ptx_tile_pixels()).  The same update
+ * per pixel with its tile's k and W'.  A tile whose total equals its last one is idle: its pixels keep their state bit for bit (zeros
+ * on a fresh handle), W and B included, so ptx_moments_read and ptx_moments_summarize, which use the per-pixel W and B, need nothing
+ * new.  Refused (PTX_ERR_INVALID): a total below the tile's last one, a wrong ntiles.  From its first tiled add until ptx_moments_reset
+ * the handle's `samples` and `batches` are the maxima over the tiles, ptx_moments_add and ptx_moments_add_host are refused, and so are
+ * ptx_denoise_measured and ptx_denoise_temporal_measured, which assume one spp and one B for the frame: the filter on an adaptive
+ * frame is not done.  Synchronous. */
+int  ptx_moments_add_host_tiled(ptx_moments *m, const float *host_rgb_sum, const int64_t *tile_samples_total, int ntiles);
+/* samples1: W*H int32 of the per-pixel W (one number per frame until a tiled add); waits for the handle's last work. */
+int  ptx_moments_read_samples(ptx_moments *m, int32_t *samples1);
 /* mean3: W*H*3 floats; cov6: W*H*6 floats of C (rr, gg, bb, rg, rb, gb), 0 where B < 2; batches1: W*H int32 of B; samples_out: W.
  * NULLs allowed; waits for the handle's last work. */
 int  ptx_moments_read(ptx_moments *m, float *mean3, float *cov6, int32_t *batches1, int64_t *samples_out);
@@ -476,6 +510,56 @@ int  ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_param
  * so that q describes the current view's samples alone -- exactly as for ptx_denoise_measured; the temporal handle is NOT reset there. */
 int  ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m, const ptx_denoise_params *dp,
                                    const ptx_temporal_params *tp, const ptx_variance_params *vp, int min_batches, int spp);
+
+/* ---- adaptive sampling by tiles: stop tracing the tiles whose measured error is low, csrc/pt_adaptive.hip ---------------------------
+ * The loop is render k iterations -> ptx_adaptive_add -> ptx_adaptive_select, until no tile is active; ptx_adaptive_resolve then
+ * gives the frame.  The handle holds, per tile (ptx_tile_pixels() pixels, as the active-tile mask above), the samples its pixels
+ * hold, its batches, whether it is active, and its last error; and one W x H x 3 frame.  After create and reset every tile is active
+ * with 0 samples.  Definition (tests/adaptive_ref.py restates it):
+ *   ptx_adaptive_add(a, m, t, k) = "the last k iterations were rendered under the current mask": every active tile's samples += k and
+ *   batches += 1, then the tiled moments add (ptx_moments_add_host_tiled's update) on t's accumulation buffer with these totals,
+ *   ordered as ptx_moments_add is.  The first call finds every tile active, so it is exact for a frame rendered without a mask.
+ *   ptx_adaptive_select: per pixel with B >= 2, rel = sqrt(max(g^T C g, 0) / W) / max(l(mean), floor) -- ptx_moments_summarize's, g =
+ *   Rec. 709.  Tile error e_T = sqrt(sum rel^2 / n_T), n_T = the tile's pixels inside the frame; sums in double through a tree of fixed
+ *   shape, no float atomics: the same bits on every run.  A tile none of whose pixels has B >= 2 has no estimate (e_T reads 0).
+ *     active_T = samples_T < max_samples && (batches_T < min_batches || e_T > target)
+ *   The flags then become t's mask without leaving the device (ptx_set_active_tiles' ordering and refusals), and the status comes back
+ *   with them in one small read.  Counts are reduced in integers: exact.  A stopped tile receives no samples, so its error does not
+ *   change: it stays stopped under the same parameters.
+ *   ptx_adaptive_resolve: frame[p] = acc[p] / samples[tile(p)] in fp32, the mean radiance; 0 where the tile has no sample.
+ * The handle and the moments handle count the same samples: reset both together (and ptx_clear_active_tiles the tracer) whenever the
+ * accumulation restarts; an add that finds them out of step is refused.  Refused like ptx_moments_add: a handle of another device or
+ * size, tile_world > 1.  Each enqueueing call makes t's stream wait for both handles' previous work and records after its own.
+ * Not done: reactivating a stopped tile on purpose, masks finer than a tile, multi-device tracers, the denoiser on such a frame. */
+typedef struct ptx_adaptive ptx_adaptive;          /* opaque */
+typedef struct ptx_adaptive_params {
+    float   target;            /* > 0: a tile stops when its error <= target; default 0.02 (stated, not tuned) */
+    float   floor;             /* as ptx_moments_params.floor; default 0.05 */
+    int32_t min_batches;       /* >= 2: a tile stays active until it has this many batches; default 4 */
+    int32_t max_samples;       /* > 0: a tile stops at this many samples whatever its error; default 1 << 20 */
+} ptx_adaptive_params;
+typedef struct ptx_adaptive_status {
+    int64_t samples_total;     /* sum over tiles of samples_T * n_T: the pixel-samples the frame holds */
+    int64_t pixels_active;     /* pixels of the active tiles */
+    int32_t tiles, tiles_active;
+    int32_t samples_min, samples_max;      /* over all tiles */
+    float   worst_error;       /* largest e_T over the tiles with an estimate (0: none has one) */
+    int32_t rounds;            /* selects since create / reset, this one included */
+} ptx_adaptive_status;
+void   ptx_default_adaptive_params(ptx_adaptive_params *p);
+size_t ptx_sizeof_adaptive_params(void);
+size_t ptx_sizeof_adaptive_status(void);
+int  ptx_adaptive_create(int device, int width, int height, ptx_adaptive **out);   /* PTX_ERR_NODEVICE without a device */
+void ptx_adaptive_destroy(ptx_adaptive *a);        /* NULL is a no-op; waits for its last use */
+int  ptx_adaptive_reset(ptx_adaptive *a);          /* as after create; waits */
+int  ptx_adaptive_num_tiles(const ptx_adaptive *a);
+int  ptx_adaptive_add(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, int k);
+int  ptx_adaptive_select(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, const ptx_adaptive_params *p, ptx_adaptive_status *status);   /* p NULL = defaults; waits */
+int  ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t);
+/* mean_rgb: W*H*3 floats, the last resolve's frame (zeros before one); samples_per_pixel: W*H int32; tile_error, tile_active: one per
+ * tile.  NULLs allowed; waits for the handle's last work. */
+int  ptx_adaptive_read(ptx_adaptive *a, float *mean_rgb, int32_t *samples_per_pixel, float *tile_error, uint8_t *tile_active);
+float *ptx_adaptive_device_frame(ptx_adaptive *a); /* the resolved frame on the device, W*H*3 floats */
 
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */

@@ -17,6 +17,9 @@ from .api import (  # noqa: F401
     VarianceParams,
     MomentsParams,
     MomentsSummary,
+    AdaptiveParams,
+    AdaptiveStatus,
+    Adaptive,
     Scene,
     Tracer,
     Temporal,
@@ -28,11 +31,13 @@ from .api import (  # noqa: F401
     default_temporal_params,
     default_variance_params,
     default_moments_params,
+    default_adaptive_params,
+    tile_pixels,
     denoise_buffers,
     denoise_buffers_variance,
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
-           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "denoise_buffers",
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
+           "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "default_adaptive_params", "tile_pixels", "denoise_buffers",
            "denoise_buffers_variance", "load_library"]

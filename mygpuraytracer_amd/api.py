@@ -244,6 +244,15 @@ class Moments:
             raise PathTracerError("Moments.add_host: the frame must hold %d x %d x 3 floats" % (self.width, self.height))
         _check(self.lib.ptx_moments_add_host(self.h, _ptr(rgb), int(samples)), "ptx_moments_add_host")
 
+    def add_host_tiled(self, rgb_sum, tile_samples):
+        """add_host in which every tile of tile_pixels() pixels advances by its own amount (ptx_moments_add_host_tiled): tile_samples[tile]
+        = the samples its pixels hold now; a tile whose total did not move keeps its state bit for bit (synchronous)"""
+        rgb = np.ascontiguousarray(rgb_sum, np.float32)
+        if rgb.size != self.width * self.height * 3:
+            raise PathTracerError("Moments.add_host_tiled: the frame must hold %d x %d x 3 floats" % (self.width, self.height))
+        ts = np.ascontiguousarray(tile_samples, np.int64).reshape(-1)
+        _check(self.lib.ptx_moments_add_host_tiled(self.h, _ptr(rgb), _ptr(ts), len(ts)), "ptx_moments_add_host_tiled")
+
     def read(self):
         """dict of mean (H, W, 3), cov (H, W, 6: rr, gg, bb, rg, rb, gb of the per-sample covariance, 0 where batches < 2), batches
         (H, W) int32 and samples (int)"""
@@ -253,11 +262,118 @@ class Moments:
         _check(self.lib.ptx_moments_read(self.h, _ptr(mean), _ptr(cov), _ptr(b), C.byref(n)), "ptx_moments_read")
         return dict(mean=mean, cov=cov, batches=b, samples=int(n.value))
 
+    def read_samples(self):
+        """(H, W) int32: the samples every pixel's moments hold (they differ between tiles after add_host_tiled / Adaptive.add)"""
+        out = np.zeros((self.height, self.width), np.int32)
+        _check(self.lib.ptx_moments_read_samples(self.h, _ptr(out)), "ptx_moments_read_samples")
+        return out
+
     def summary(self, **params):
         """ptx_moments_summarize as a dict; params: floor, threshold"""
         p, out = default_moments_params(**params), MomentsSummary()
         _check(self.lib.ptx_moments_summarize(self.h, C.byref(p), C.byref(out)), "ptx_moments_summarize")
         return {k: getattr(out, k) for k, _ in MomentsSummary._fields_ if k != "reserved"}
+
+
+class AdaptiveParams(C.Structure):
+    """ptx_adaptive_params: when a tile stops (include/mi355x_pathtracer.h; defaults from ptx_default_adaptive_params)."""
+    _fields_ = [("target", C.c_float), ("floor", C.c_float), ("min_batches", C.c_int32), ("max_samples", C.c_int32)]
+
+
+class AdaptiveStatus(C.Structure):
+    """ptx_adaptive_status (include/mi355x_pathtracer.h)."""
+    _fields_ = [("samples_total", C.c_int64), ("pixels_active", C.c_int64), ("tiles", C.c_int32), ("tiles_active", C.c_int32),
+                ("samples_min", C.c_int32), ("samples_max", C.c_int32), ("worst_error", C.c_float), ("rounds", C.c_int32)]
+
+
+def default_adaptive_params(**kw):
+    """ptx_default_adaptive_params with keyword overrides (target, floor, min_batches, max_samples)."""
+    return _default_params(AdaptiveParams, "ptx_default_adaptive_params", ("min_batches", "max_samples"), **kw)
+
+
+def tile_pixels():
+    """ptx_tile_pixels: the pixels of one tile of the active-tile mask, tile = (y * W + x) // tile_pixels()"""
+    return int(load_library().ptx_tile_pixels())
+
+
+class Adaptive:
+    """Adaptive sampling by tiles on one device (opaque ptx_adaptive): render(tracer, moments) traces until every tile's measured error
+    is at its target, or step by step add(moments, tracer, k) after every k iterations, select(moments, tracer) for the next mask,
+    resolve(tracer) and read() for the frame.  Reset it together with the Moments it is used with."""
+
+    def __init__(self, device, width, height):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_adaptive_create(int(device), int(width), int(height), C.byref(h)), "ptx_adaptive_create")
+        self.h = h
+        self.device, self.width, self.height = int(device), int(width), int(height)
+        self.num_tiles = int(self.lib.ptx_adaptive_num_tiles(h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ptx_adaptive_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """every tile active with 0 samples, as after create"""
+        _check(self.lib.ptx_adaptive_reset(self.h), "ptx_adaptive_reset")
+
+    def add(self, moments, tracer, k):
+        """the tracer's last k iterations were rendered under the current mask: counts them and folds them into `moments` tile by tile"""
+        _check(self.lib.ptx_adaptive_add(self.h, moments.h, tracer.h, int(k)), "ptx_adaptive_add")
+
+    def select(self, moments, tracer, params=None, **kw):
+        """decides which tiles go on and makes that the tracer's mask; returns the status as a dict.  params: an AdaptiveParams, or its
+        fields as keywords (target, floor, min_batches, max_samples)"""
+        p = params if params is not None else default_adaptive_params(**kw)
+        out = AdaptiveStatus()
+        _check(self.lib.ptx_adaptive_select(self.h, moments.h, tracer.h, C.byref(p), C.byref(out)), "ptx_adaptive_select")
+        return {k: getattr(out, k) for k, _ in AdaptiveStatus._fields_}
+
+    def resolve(self, tracer):
+        """the tracer's accumulation buffer over each tile's own sample count, into the handle's frame (enqueued)"""
+        _check(self.lib.ptx_adaptive_resolve(self.h, tracer.h), "ptx_adaptive_resolve")
+
+    def read(self):
+        """dict of mean (H, W, 3) float32 = the last resolve's frame, samples (H, W) int32, tile_error (tiles) float32, tile_active
+        (tiles) bool"""
+        hh, ww = self.height, self.width
+        mean, spp = np.zeros((hh, ww, 3), np.float32), np.zeros((hh, ww), np.int32)
+        err, act = np.zeros(self.num_tiles, np.float32), np.zeros(self.num_tiles, np.uint8)
+        _check(self.lib.ptx_adaptive_read(self.h, _ptr(mean), _ptr(spp), _ptr(err), _ptr(act)), "ptx_adaptive_read")
+        return dict(mean=mean, samples=spp, tile_error=err, tile_active=act != 0)
+
+    def device_frame_ptr(self):
+        return self.lib.ptx_adaptive_device_frame(self.h)
+
+    def render(self, tracer, moments, batch=16, max_iterations=1 << 20, params=None, first_iteration=1, **kw):
+        """render `batch` iterations -> add -> select, until no tile is active or max_iterations have been rendered; resolves at the end.
+        Returns the list of the rounds' statuses; the last one's tiles_active is 0 unless the cap ended the run.  The handle, `moments`
+        and the tracer's image are taken as they are: start from reset ones for a new frame."""
+        p = params if params is not None else default_adaptive_params(**kw)
+        rounds, done = [], 0
+        while done < max_iterations:
+            k = min(int(batch), max_iterations - done)
+            tracer.render(first_iteration + done, k)
+            done += k
+            self.add(moments, tracer, k)
+            rounds.append(self.select(moments, tracer, params=p))
+            if rounds[-1]["tiles_active"] == 0:
+                break
+        self.resolve(tracer)
+        return rounds
 
 
 def _frame_arrays(fn, rgb, albedo, normal, position, hit):
@@ -534,6 +650,27 @@ def load_library():
     L.ptx_denoise_measured.argtypes = [vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), i, i]
     L.ptx_denoise_temporal_measured.restype = i
     L.ptx_denoise_temporal_measured.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(VarianceParams), i, i]
+    L.ptx_moments_add_host_tiled.restype, L.ptx_moments_add_host_tiled.argtypes = i, [vp, vp, vp, i]
+    L.ptx_moments_read_samples.restype, L.ptx_moments_read_samples.argtypes = i, [vp, vp]
+    L.ptx_tile_pixels.restype, L.ptx_tile_pixels.argtypes = i, []
+    L.ptx_num_tiles.restype, L.ptx_num_tiles.argtypes = i, [vp]
+    L.ptx_set_active_tiles.restype, L.ptx_set_active_tiles.argtypes = i, [vp, vp, i]
+    L.ptx_clear_active_tiles.restype, L.ptx_clear_active_tiles.argtypes = i, [vp]
+    L.ptx_sizeof_adaptive_params.restype = L.ptx_sizeof_adaptive_status.restype = C.c_size_t
+    if L.ptx_sizeof_adaptive_params() != C.sizeof(AdaptiveParams) or L.ptx_sizeof_adaptive_status() != C.sizeof(AdaptiveStatus):
+        raise PathTracerError("%s has adaptive structs of %d and %d B, this module expects %d and %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_adaptive_params(), L.ptx_sizeof_adaptive_status(), C.sizeof(AdaptiveParams), C.sizeof(AdaptiveStatus)))
+    L.ptx_default_adaptive_params.argtypes = [C.POINTER(AdaptiveParams)]
+    L.ptx_adaptive_create.restype, L.ptx_adaptive_create.argtypes = i, [i, i, i, C.POINTER(vp)]
+    L.ptx_adaptive_destroy.restype, L.ptx_adaptive_destroy.argtypes = None, [vp]
+    L.ptx_adaptive_reset.restype, L.ptx_adaptive_reset.argtypes = i, [vp]
+    L.ptx_adaptive_num_tiles.restype, L.ptx_adaptive_num_tiles.argtypes = i, [vp]
+    L.ptx_adaptive_add.restype, L.ptx_adaptive_add.argtypes = i, [vp, vp, vp, i]
+    L.ptx_adaptive_select.restype = i
+    L.ptx_adaptive_select.argtypes = [vp, vp, vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStatus)]
+    L.ptx_adaptive_resolve.restype, L.ptx_adaptive_resolve.argtypes = i, [vp, vp]
+    L.ptx_adaptive_read.restype, L.ptx_adaptive_read.argtypes = i, [vp, vp, vp, vp, vp]
+    L.ptx_adaptive_device_frame.restype, L.ptx_adaptive_device_frame.argtypes = vp, [vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -959,6 +1096,20 @@ class Tracer:
 
     def reset_image(self):
         _check(self.lib.ptx_reset_image(self.h), "ptx_reset_image")
+
+    # --- active tiles (include/mi355x_pathtracer.h: ptx_set_active_tiles) ----------------------------------
+    @property
+    def num_tiles(self):
+        """tiles of tile_pixels() owned pixels, tile = (y * W + x) // tile_pixels()"""
+        return int(self.lib.ptx_num_tiles(self.h))
+
+    def set_active_tiles(self, mask):
+        """num_tiles flags, nonzero = active: the camera bounce of the other tiles traces nothing, their pixels keep their sums"""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, np.uint8)
+        _check(self.lib.ptx_set_active_tiles(self.h, _ptr(m), len(m)), "ptx_set_active_tiles")
+
+    def clear_active_tiles(self):
+        _check(self.lib.ptx_clear_active_tiles(self.h), "ptx_clear_active_tiles")
 
     def read_image(self):
         out = np.zeros((self.width * self.height, 3), np.float32)

@@ -20,6 +20,13 @@
 //                                  [--until-error E [--error-floor F]]   (render in batches of 16 iterations, one ptx_moments_add after
 //                                                                      each; stop at the first check with mean_rel_se <= E, or at
 //                                                                      --iterations; F = ptx_moments_params.floor; not with --frames)
+//                                  [--adaptive E [--measure-every K] [--error-floor F]]   (adaptive sampling by tiles, ptx_adaptive_*: render
+//                                                                      in batches of K iterations (16), after each stop tracing the tiles of
+//                                                                      256 pixels whose error is at E; ends when no tile is left, or at
+//                                                                      --iterations.  One line per round, a closing line against the uniform
+//                                                                      render that gives every tile the worst tile's count; the frame saved is
+//                                                                      the one normalised tile by tile.  Not with --frames, --per-call,
+//                                                                      --checkpoint, --until-error or --denoise.)
 //                                  [--measured [--measure-every K]]   (with --denoise: the variance-guided filter on the variance the
 //                                                                      run measured, ptx_denoise_measured: a batch every K iterations,
 //                                                                      16 unless given.  Implies --variance.  With --frames the moments
@@ -99,13 +106,13 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
-    if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]]\n", argv[0]);
-        return 1;
+    if (argc < 2 || !strcmp(argv[1], "--help")) {
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F]]\n", argv[0]);
+        return argc < 2;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
     bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false, measured = false;
-    double until_error = -1.0;
+    double until_error = -1.0, adaptive = -1.0;
     ptx_moments_params mparams;
     ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
@@ -142,6 +149,7 @@ int main(int argc, char **argv) {
         else if (a == "--phi-luminance") { need(1); varianceParams().phi_luminance = (float)atof(argv[++i]); }
         else if (a == "--until-error") { need(1); until_error = atof(argv[++i]); }
         else if (a == "--error-floor") { need(1); mparams.floor = (float)atof(argv[++i]); }
+        else if (a == "--adaptive") { need(1); adaptive = atof(argv[++i]); }
         else if (a == "--measured") measured = true;
         else if (a == "--measure-every") { need(1); measure_every = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
@@ -153,6 +161,15 @@ int main(int argc, char **argv) {
     if (batches && (per_call || !ckpt_path.empty())) {
         fprintf(stderr, "--until-error and --measured do not combine with --per-call or --checkpoint\n");
         return 1;
+    }
+    if (adaptive >= 0.0) {
+        if (!(adaptive > 0.0)) { fprintf(stderr, "--adaptive needs E > 0\n"); return 1; }
+        if (frames > 0 || per_call || !ckpt_path.empty() || until_error >= 0.0 || denoise) {
+            fprintf(stderr, "--adaptive does not combine with --frames, --per-call, --checkpoint, --until-error or --denoise\n");
+            return 1;
+        }
+        adaptiveTarget() = (float)adaptive;
+        adaptiveParams().floor = mparams.floor;
     }
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
     if (variance && !denoise) { fprintf(stderr, "--variance needs --denoise\n"); return 1; }
@@ -190,7 +207,7 @@ int main(int argc, char **argv) {
         printf("Resumed %s at %d of %d samples.\n", resume_path.c_str(), done, n);
     }
     const int rendered = std::max(n - done, 0);
-    const int chunk = batches ? measure_every : (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
+    const int chunk = (batches || adaptive > 0.0) ? measure_every : (!ckpt_path.empty() && ckpt_every > 0) ? ckpt_every : n;
     double per_call_ms = 0.0;
     if (per_call) {
         // the reference's own loop (runCuda, src/main.cpp:128-148): one pathtrace(pbo, frame, iteration) per frame, the fp32 frame
@@ -212,6 +229,19 @@ int main(int argc, char **argv) {
             if (!ptimg::write_checkpoint(ckpt_path, width, height, done, &scene->state.image[0].x)) { fprintf(stderr, "cannot write %s\n", ckpt_path.c_str()); return 1; }
         }
         if (batches) pathtraceMomentsAdd(done);
+        if (adaptive > 0.0) {
+            pathtraceAdaptiveStep(count);
+            const ptx_adaptive_status &as = adaptiveStatus();
+            printf("round %d: %d iterations, %d of %d tiles active, %lld pixel-samples so far, worst tile error %.6g\n", (int)as.rounds, done,
+                   (int)as.tiles_active, (int)as.tiles, (long long)as.samples_total, (double)as.worst_error);
+            if (as.tiles_active == 0 || done >= n) {
+                const long long uniform = (long long)as.samples_max * width * height;
+                printf("adaptive: %s after %d iterations: %lld pixel-samples, %.1f %% of the %lld of a uniform render at the worst tile's %d\n",
+                       as.tiles_active == 0 ? "every tile at its target" : "stopped by --iterations", done, (long long)as.samples_total,
+                       100.0 * (double)as.samples_total / (double)uniform, uniform, (int)as.samples_max);
+                n = done;
+            }
+        }
         if (until_error >= 0.0) {
             ptx_moments_summary sum;
             if (ptx_moments_summarize(pathtraceMoments(), &mparams, &sum) != PTX_OK) { fprintf(stderr, "summary failed: %s\n", ptx_last_error()); return 1; }
@@ -234,10 +264,17 @@ int main(int argc, char **argv) {
     std::ostringstream ss;                                                              // saveImage, main.cpp:94-97
     ss << (out_prefix.empty() ? scene->state.imageName : out_prefix) << "." << startTimeString << "." << n << "samp";
     std::vector<uint8_t> rgb8;
-    ptimg::to_rgb8_mirrored(width, height, &scene->state.image[0].x, (float)n, rgb8);
+    float divisor = (float)n;
+    if (adaptive > 0.0) {                       // the frame normalised tile by tile: mean radiance already, so divided by 1
+        const float *frame = adaptiveFrame();
+        if (!frame) { fprintf(stderr, "--adaptive: no round was rendered\n"); return 1; }
+        memcpy(&scene->state.image[0].x, frame, sizeof(float) * 3 * (size_t)width * height);
+        divisor = 1.0f;
+    }
+    ptimg::to_rgb8_mirrored(width, height, &scene->state.image[0].x, divisor, rgb8);
     if (!ptimg::write_png_rgb8(ss.str() + ".png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.png\n", ss.str().c_str()); return 1; }
     printf("Saved %s.png.\n", ss.str().c_str());
-    if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", ss.str().c_str()); }
+    if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, divisor); printf("Saved %s.pfm.\n", ss.str().c_str()); }
     if (denoise && n > 0) {                     // the denoised frame next to it: mean radiance already, so divided by 1
         std::vector<float> den((size_t)width * height * 3);
         const int rc = measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
@@ -250,7 +287,7 @@ int main(int argc, char **argv) {
     }
     if (hdr) {                                                                          // img.saveHDR, main.cpp:101
         std::vector<float> mean;
-        ptimg::to_mean_mirrored(width, height, &scene->state.image[0].x, (float)n, mean);
+        ptimg::to_mean_mirrored(width, height, &scene->state.image[0].x, divisor, mean);
         if (!ptimg::write_hdr(ss.str() + ".hdr", width, height, mean.data())) { fprintf(stderr, "cannot write %s.hdr\n", ss.str().c_str()); return 1; }
         printf("Saved %s.hdr.\n", ss.str().c_str());
     }

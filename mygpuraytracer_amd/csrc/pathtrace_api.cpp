@@ -32,6 +32,9 @@ int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
 int g_device = 0;                    // the device of g_tracer
 ptx_moments *g_moments = nullptr;    // pathtrace()'s batch means with momentsBatch() > 0: created on first use
 int g_moments_key[3] = {0, 0, 0};    // its device, width, height
+ptx_adaptive *g_adaptive = nullptr;  // pathtrace()'s adaptive sampling with adaptiveTarget() > 0: created on first use, with g_moments' key
+ptx_adaptive_status g_adaptive_status = {};
+std::vector<float> g_adaptive_frame; // adaptiveFrame()'s host copy
 int g_calls = 0;                     // pathtrace() calls since pathtraceInit
 
 void check(int rc, const char *what) {
@@ -214,23 +217,68 @@ bool &denoiseMeasured() {
     return on;
 }
 
+float &adaptiveTarget() {
+    static float e = 0.f;
+    return e;
+}
+
+ptx_adaptive_params &adaptiveParams() {
+    static ptx_adaptive_params p;
+    static bool init = false;
+    if (!init) { ptx_default_adaptive_params(&p); init = true; }
+    return p;
+}
+
+ptx_adaptive *pathtraceAdaptive() { return g_adaptive; }
+const ptx_adaptive_status &adaptiveStatus() { return g_adaptive_status; }
+
 void GPUdenoiseRelease() {
     ptx_temporal_destroy(g_temporal);
     g_temporal = nullptr;
     ptx_moments_destroy(g_moments);
     g_moments = nullptr;
+    ptx_adaptive_destroy(g_adaptive);
+    g_adaptive = nullptr;
+}
+
+// the module-level moments handle for the current device and resolution, fresh when it had to be made
+static void moments_handle() {
+    const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+    const int key[3] = {g_device, w, h};
+    if (g_moments && memcmp(key, g_moments_key, sizeof key) != 0) {
+        ptx_moments_destroy(g_moments); g_moments = nullptr;
+        ptx_adaptive_destroy(g_adaptive); g_adaptive = nullptr;      // (the two are used together: one key)
+    }
+    if (!g_moments) {
+        check(ptx_moments_create(g_device, w, h, &g_moments), "pathtrace moments");
+        memcpy(g_moments_key, key, sizeof key);
+    }
+}
+
+// one round: the last k iterations into both handles, then the next mask
+void pathtraceAdaptiveStep(int k) {
+    if (!g_tracer || !hst_scene) { fprintf(stderr, "pathtraceAdaptiveStep called before pathtraceInit\n"); exit(EXIT_FAILURE); }
+    if (g_multi) { fprintf(stderr, "adaptive sampling does not run on several devices\n"); exit(EXIT_FAILURE); }
+    moments_handle();
+    if (!g_adaptive) check(ptx_adaptive_create(g_device, g_moments_key[1], g_moments_key[2], &g_adaptive), "pathtrace adaptive");
+    ptx_adaptive_params p = adaptiveParams();
+    p.target = adaptiveTarget();
+    check(ptx_adaptive_add(g_adaptive, g_moments, g_tracer, k), "pathtrace adaptive");
+    check(ptx_adaptive_select(g_adaptive, g_moments, g_tracer, &p, &g_adaptive_status), "pathtrace adaptive");
+}
+
+const float *adaptiveFrame() {
+    if (!g_tracer || !g_adaptive) return nullptr;
+    check(ptx_adaptive_resolve(g_adaptive, g_tracer), "adaptiveFrame");
+    g_adaptive_frame.resize((size_t)g_moments_key[1] * g_moments_key[2] * 3);
+    check(ptx_adaptive_read(g_adaptive, g_adaptive_frame.data(), nullptr, nullptr, nullptr), "adaptiveFrame");
+    return g_adaptive_frame.data();
 }
 
 // one batch: everything the frame gained since the last one
 void pathtraceMomentsAdd(int iter) {
     if (!g_tracer || !hst_scene) { fprintf(stderr, "pathtraceMomentsAdd called before pathtraceInit\n"); exit(EXIT_FAILURE); }
-    const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
-    const int key[3] = {g_device, w, h};
-    if (g_moments && memcmp(key, g_moments_key, sizeof key) != 0) { ptx_moments_destroy(g_moments); g_moments = nullptr; }
-    if (!g_moments) {
-        check(ptx_moments_create(g_device, w, h, &g_moments), "pathtrace moments");
-        memcpy(g_moments_key, key, sizeof key);
-    }
+    moments_handle();
     if (g_multi) check(ptx_moments_add_host(g_moments, &hst_scene->state.image[0].x, iter), "pathtrace moments");   // the assembled frame
     else check(ptx_moments_add(g_moments, g_tracer, iter), "pathtrace moments");
 }
@@ -239,7 +287,10 @@ void pathtraceMomentsAdd(int iter) {
 static void moments_step(int iter) {
     const int k = momentsBatch();
     g_calls++;
-    if (k > 0 && g_calls % k == 0) pathtraceMomentsAdd(iter);
+    if (k > 0 && g_calls % k == 0) {
+        if (adaptiveTarget() > 0.f) pathtraceAdaptiveStep(k);       // (the tiled add in place of the plain one, then the next mask)
+        else pathtraceMomentsAdd(iter);
+    }
 }
 
 void pathtraceInit(Scene *scene) {
@@ -249,6 +300,8 @@ void pathtraceInit(Scene *scene) {
     g_output_on_device = false;
     g_calls = 0;
     if (g_moments) ptx_moments_reset(g_moments);
+    if (g_adaptive) ptx_adaptive_reset(g_adaptive);      // (the tracer made below has no mask)
+    g_adaptive_status = ptx_adaptive_status();
     const std::vector<int> &devs = pathtraceDevices();
     if (devs.size() > 1) {
         // the C ABI's multi-device layer takes the loaded scene: hand it the caller's camera and depth first

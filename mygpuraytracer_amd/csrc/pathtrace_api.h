@@ -284,6 +284,19 @@ void pathtraceMomentsAdd(int iteration);
 // ptx_denoise_temporal_measured: the history's variance pooled with the measured one of the current view (pathtraceInit resets the
 // moments handle at every camera change, so its batches are that view's; fewer than 4 of them and the call is ptx_denoise_variance).
 bool &denoiseMeasured();
+// Adaptive sampling by tiles (ptx_adaptive_*): adaptiveTarget() = E > 0 together with momentsBatch() = k makes pathtrace(), after every
+// k-th call, count those k iterations tile by tile (ptx_adaptive_add, in place of the plain moments add) and switch off the tiles whose
+// error is at E (ptx_adaptive_select): later calls trace the others only.  adaptiveStatus() is the last round's; adaptiveFrame() resolves
+// and returns the frame, W*H*3 floats of mean radiance (state.image holds raw sums of unequal counts), NULL before the first round.
+// pathtraceInit resets the handle; its tracer starts without a mask.  Off (0) by default: the calls made are then exactly those above.
+// One device only; not with denoiseMeasured().  adaptiveParams(): floor, min_batches, max_samples (its target is adaptiveTarget()).
+float &adaptiveTarget();
+ptx_adaptive_params &adaptiveParams();
+ptx_adaptive *pathtraceAdaptive();
+const ptx_adaptive_status &adaptiveStatus();
+const float *adaptiveFrame();
+// The same round by hand, for a caller that renders through pathtraceHandle(): the last k iterations were rendered under the current mask.
+void pathtraceAdaptiveStep(int k);
 void GPUdenoiseRelease();
 
 namespace mi355x {

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/mi355x_pathtracer.h"
 
@@ -86,7 +87,14 @@ struct ptx_moments {
     bool used = false;                    // ev was recorded
     long long samples = 0;                // W: samples_total of the last add; 0 = fresh (the buffers are read as zeros)
     int batches = 0;                      // B
+    // adds in which the tiles of ptx_tile_pixels() pixels advance by different amounts (k_moments_add_tiled).  `tiled` from the first of
+    // them until ptx_moments_reset: samples and batches are then the maxima over the tiles, whose own are kept here
+    bool tiled = false;
+    std::vector<long long> tile_samples;
+    std::vector<int> tile_batches;
+    float2 *d_tile_kt = nullptr;          // ptx_moments_add_host_tiled's table (first use): (k, W') per tile
 };
+inline int pt_moments_tiles(int w, int h) { return (int)(((long long)w * h + ptx_tile_pixels() - 1) / ptx_tile_pixels()); }
 
 // Rec. 709 luminance, the one every variance of the denoiser is a variance of
 __host__ __device__ inline float pt_luminance(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
@@ -134,6 +142,11 @@ const char *pt_moments_params_problem(const ptx_moments_params &p);
 // One add on `st`: rgb = the accumulation buffer (W*H*3) holding `total` samples, k = total - the last add's; fresh: the state reads
 // as zeros (first add after create / reset).
 hipError_t pt_moments_add_enqueue(hipStream_t st, int w, int h, const float *rgb, float k, float total, int fresh, const PtMomentsState &s);
+// The add in which every tile advances by its own amount, on `st`: d_kt[tile] = (k, W') on the device, host_k[tile] = the same k for
+// the handle's own counts (0: the tile is idle and its pixels keep their state bit for bit; on a fresh handle they are written as
+// zeros).  tile = (y * W + x) / ptx_tile_pixels().  Waits for nothing and records nothing: the caller orders it, as with
+// pt_moments_add_enqueue.  An add in which no tile advances enqueues nothing.
+int pt_moments_add_tiled(ptx_moments *m, hipStream_t st, const float *rgb, const float2 *d_kt, const int32_t *host_k);
 // pt_atrous_prep_enqueue with the measured variance: c = float4(rgb / spp (demodulated on hit pixels), v), v = max(g^T C g, 0) / W on
 // hit pixels with B >= min_batches (>= 2), -1 on the other hit pixels (pt_variance_spatial_enqueue fills those in), 0 on miss pixels.
 hipError_t pt_moments_prep_enqueue(hipStream_t st, int w, int h, const float *rgb, float spp, const float4 *nh, const float4 *alb, int demod,

@@ -22,6 +22,7 @@
 #include "pt_scene.h"
 #include "pt_plan.h"
 #include "pt_denoise.h"
+#include "pt_adaptive.h"
 
 namespace {
 
@@ -309,6 +310,9 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     std::vector<float> h_aabb;                           // host copy of the world boxes (update_tile_geoms)
     std::vector<int32_t> h_geom_type, h_roots, h_depths, h_wroots, h_wneeds;      // host copies of the per-geom tree tables (ptx_debug_mesh_plan)
     DevBuf<uint32_t> d_tile_geoms; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
+    // the active-tile mask (ptx_set_active_tiles), both allocated when the first mask is set: the flags, one byte per tile, and the table
+    // the camera bounce reads instead of d_tile_geoms while mask_set (written by k_tile_mask alone)
+    DevBuf<uint8_t> d_tile_active; DevBuf<uint32_t> d_tile_eff; bool mask_set = false;
     DevBuf<BvhQuad> d_bvh_nodes; DevBuf<float> d_bvh_tris; DevBuf<int32_t> d_bvh_root, d_bvh_depth;                          // pt_bvh.h (NULL: no mesh has one)
     DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
     DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
@@ -410,6 +414,15 @@ void fastdiv_magic(uint32_t d, uint32_t &mul, uint32_t &sh) {
     mul = (uint32_t)(((1ull << (31 + l)) / d) + 1);
 }
 
+void ahead_discard(ptx_tracer *t);
+
+// enqueues k_tile_mask (pt_adaptive.hip: this unit holds the tracer's own kernels only) on the tracer's stream: the base table and the
+// flags into the effective table, and the flags into the tracer's copy
+int apply_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
+    HIPCHECK(pt_tile_mask_enqueue(t->stream, t->maxTiles, d_flags, t->d_tile_active.p, t->d_tile_geoms.p, t->d_tile_eff.p));
+    return PTX_OK;
+}
+
 int update_tile_geoms(ptx_tracer *t) {
     t->tile_geoms_valid = false;
     if (!t->cull || t->ngeoms > 32 || t->ngeoms < 1 || t->dbg.no_tile_geoms) return PTX_OK;
@@ -420,6 +433,36 @@ int update_tile_geoms(ptx_tracer *t) {
     HIPCHECK(hipMemcpyAsync(t->d_tile_geoms, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));      // (masks is a local)
     t->tile_geoms_valid = true;
+    if (t->mask_set) return apply_tile_mask(t, t->d_tile_active);      // the mask outlives a camera change
+    return PTX_OK;
+}
+
+// why this tracer cannot take a mask of `ntiles` flags (the code through `code`), or NULL
+const char *active_tiles_problem(const ptx_tracer *t, int ntiles, int &code) {
+    code = PTX_ERR_INVALID;
+    if (t->tm.tile_world > 1) return "this tracer renders a row tile (tile_world > 1)";
+    if (ntiles != t->maxTiles) return "ntiles differs from ptx_num_tiles";
+    code = PTX_ERR_UNSUPPORTED;
+    if (!t->tile_geoms_valid) return "this tracer has no per-tile geom table (no_cull, more than 32 geoms, or switched off for debugging)";
+    if (t->cache_active()) return "the first-bounce cache replays a camera bounce of the whole frame";
+    return nullptr;
+}
+
+// the order of a camera change (ptx_set_camera): what is on the tracer's stream ends, what was traced ahead is dropped, then the table
+// is written by a launch of its own; d_flags: one byte per tile on the device
+int mask_buffers(ptx_tracer *t) {                       // (on the first mask)
+    if (t->d_tile_eff) return PTX_OK;
+    HIPCHECK(t->d_tile_active.alloc((size_t)t->maxTiles));
+    HIPCHECK(t->d_tile_eff.alloc((size_t)t->maxTiles));
+    return PTX_OK;
+}
+
+int set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
+    if (const int rc = mask_buffers(t)) return rc;
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    ahead_discard(t);
+    if (const int rc = apply_tile_mask(t, d_flags ? d_flags : t->d_tile_active.p)) return rc;
+    t->mask_set = true;
     return PTX_OK;
 }
 
@@ -627,7 +670,7 @@ BounceParams fill_bounce_params(const ptx_tracer *t, const BatchSet &s, const Ba
     bp.fenced = reinterpret_cast<unsigned long long *>(t->d_stats + 65); bp.fence_slots_cap = (uint32_t)t->cap;
     bp.fence_slots = t->dbg.fence_slots > 0 ? (uint32_t)std::min<long long>(t->cap, t->dbg.fence_slots) : (uint32_t)t->cap;
     bp.last_inplace = t->dbg.last_inplace ? 1 : 0;
-    bp.tile_geoms = (first && t->tile_geoms_valid) ? t->d_tile_geoms : nullptr;
+    bp.tile_geoms = (first && t->tile_geoms_valid) ? (t->mask_set ? t->d_tile_eff : t->d_tile_geoms) : nullptr;
     if (t->split_mesh) {
         bp.keys = t->d_keys + seg0 * (size_t)t->cap; bp.seg_keys = (size_t)t->cap;
         bp.items = t->d_items + seg0 * t->seg_items; bp.seg_items = t->seg_items;
@@ -1041,6 +1084,31 @@ int ptx_set_camera(ptx_tracer *t, const ptx_camera *camera, int trace_depth) {
     return update_tile_geoms(t);
 }
 
+// ---- the active-tile mask (definition in include/mi355x_pathtracer.h) -------------------------------------------------------------
+int ptx_tile_pixels(void) { return TILE; }
+int ptx_num_tiles(const ptx_tracer *t) { return t ? t->maxTiles : 0; }
+
+int ptx_set_active_tiles(ptx_tracer *t, const uint8_t *host_active, int ntiles) {
+    if (!t || !host_active) return set_error(PTX_ERR_INVALID, "ptx_set_active_tiles: null tracer or mask");
+    int code = 0;
+    if (const char *why = active_tiles_problem(t, ntiles, code)) return set_error(code, std::string("ptx_set_active_tiles: ") + why);
+    HIPCHECK(hipSetDevice(t->device));
+    if (const int rc = mask_buffers(t)) return rc;
+    HIPCHECK(hipStreamSynchronize(t->stream));           // (no launch reads the flags now: only k_tile_mask does, on this stream)
+    HIPCHECK(hipMemcpy(t->d_tile_active, host_active, (size_t)ntiles, hipMemcpyHostToDevice));
+    return set_tile_mask(t, nullptr);
+}
+
+int ptx_clear_active_tiles(ptx_tracer *t) {
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_clear_active_tiles: null tracer");
+    if (!t->mask_set) return PTX_OK;
+    HIPCHECK(hipSetDevice(t->device));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    ahead_discard(t);
+    t->mask_set = false;
+    return PTX_OK;
+}
+
 int ptx_reset_image(ptx_tracer *t) {
     if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
     HIPCHECK(hipSetDevice(t->device));
@@ -1417,6 +1485,7 @@ int ptx_read_variance(ptx_tracer *t, float *input_var1, float *output_var1) {
 // ---- sample moments by batch means (pt_moments.hip; definition in include/mi355x_pathtracer.h) ---------------------------------------
 // The checks of denoise_begin on a moments handle.  The accumulation buffer is read on the tracer's stream, where every gather runs,
 // those of iterations traced ahead included (ahead_finish_segment): the order ptx_denoise's read of it has.
+static const char *const TILED_HANDLE = "this moments handle has had a tiled add: its tiles hold different sample counts until ptx_moments_reset";
 static int moments_begin(const std::string &fn, ptx_tracer *t, const ptx_moments *m) {
     if (t->tm.tile_world > 1)
         return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
@@ -1435,6 +1504,7 @@ int ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total) {
     if (samples_total <= m->samples)
         return set_error(PTX_ERR_INVALID, "ptx_moments_add: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
                                               std::to_string(m->samples));
+    if (m->tiled) return set_error(PTX_ERR_INVALID, "ptx_moments_add: " + std::string(TILED_HANDLE));
     if (const int rc = moments_begin("ptx_moments_add", t, m)) return rc;
     HIPCHECK(hipSetDevice(t->device));
     if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));     // the handle's last work, maybe on another tracer's stream
@@ -1457,6 +1527,7 @@ int ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params
     if (min_batches == 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: min_batches must be >= 2 (<= 0: the default, 4)");
     if (!t || !m) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: null tracer or moments handle");
     if (m->samples == 0) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: no add on this moments handle yet");
+    if (m->tiled) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: " + std::string(TILED_HANDLE));      // (one spp, one B per frame)
     if (const int rc = moments_begin("ptx_denoise_measured", t, m)) return rc;
     if (const int rc = denoise_begin("ptx_denoise_measured", t, nullptr, true)) return rc;
     const int W = t->cam.resx, H = t->cam.resy;
@@ -1489,6 +1560,7 @@ int ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m
         return set_error(PTX_ERR_INVALID, fn + ": ptx_denoise_params.demodulate must be != 0 (the state's moments are in demodulated space)");
     if (!t || !h || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, temporal handle or moments handle");
     if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on this moments handle yet");
+    if (m->tiled) return set_error(PTX_ERR_INVALID, fn + ": " + TILED_HANDLE);      // (one spp, one B per frame)
     if (const int rc = moments_begin(fn, t, m)) return rc;
     // too few batches for the measured variance: ptx_denoise_variance itself, so the same bits (the moments state is not read)
     if (m->batches < (min_batches <= 0 ? 4 : min_batches)) return ptx_denoise_variance(t, h, &dp, &tp, &vp, spp);
@@ -1507,6 +1579,85 @@ int ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m
     HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
     if (const int rc = temporal_done(t, h)) return rc;
     t->dn_done = t->var_done = true;
+    return PTX_OK;
+}
+
+// ---- adaptive sampling by tiles (pt_adaptive.hip; definition in include/mi355x_pathtracer.h) ------------------------------------------
+static int adaptive_begin(const std::string &fn, ptx_tracer *t, const ptx_adaptive *a) {
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (a->device != t->device)
+        return set_error(PTX_ERR_INVALID, fn + ": the adaptive handle was created on device " + std::to_string(a->device) +
+                                              ", the tracer runs on device " + std::to_string(t->device));
+    if (a->w != t->cam.resx || a->h != t->cam.resy || a->ntiles != t->maxTiles)
+        return set_error(PTX_ERR_INVALID, fn + ": the adaptive handle's size " + std::to_string(a->w) + " x " + std::to_string(a->h) +
+                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
+    return PTX_OK;
+}
+
+int ptx_adaptive_add(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, int k) {
+    if (k < 1 || k > (1 << 24)) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: k must be in 1 .. 2^24");
+    if (!a || !m || !t) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: null adaptive handle, moments handle or tracer");
+    if (const int rc = moments_begin("ptx_adaptive_add", t, m)) return rc;
+    if (const int rc = adaptive_begin("ptx_adaptive_add", t, a)) return rc;
+    // the two handles count the same samples tile by tile, or the (k, W') table would not describe the moments' state
+    for (int i = 0; i < a->ntiles; i++) {
+        const long long have = m->tile_samples.empty() ? m->samples : m->tile_samples[(size_t)i];
+        if (have != a->h_samples[(size_t)i])
+            return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: tile " + std::to_string(i) + " holds " + std::to_string(a->h_samples[(size_t)i]) +
+                                                  " samples, the moments handle has " + std::to_string(have) + " of it: reset both together");
+        if ((long long)a->h_samples[(size_t)i] + k > (1 << 24)) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: more than 2^24 samples in a tile");
+    }
+    HIPCHECK(hipSetDevice(t->device));
+    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
+    HIPCHECK(pt_adaptive_advance_enqueue(t->stream, *a, k));
+    for (int i = 0; i < a->ntiles; i++) {
+        a->h_k[(size_t)i] = a->h_active[(size_t)i] ? k : 0;
+        a->h_samples[(size_t)i] += a->h_k[(size_t)i];
+    }
+    const int rc = pt_moments_add_tiled(m, t->stream, t->d_image, a->d_kt, a->h_k.data());
+    HIPCHECK(hipEventRecord(a->ev, t->stream));
+    HIPCHECK(hipEventRecord(m->ev, t->stream));
+    a->used = m->used = true;
+    return rc;
+}
+
+int ptx_adaptive_select(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, const ptx_adaptive_params *params, ptx_adaptive_status *status) {
+    const ptx_adaptive_params p = params_or_default(params, ptx_default_adaptive_params);
+    if (const char *why = pt_adaptive_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
+    if (!a || !m || !t || !status) return set_error(PTX_ERR_INVALID, "ptx_adaptive_select: null adaptive handle, moments handle, tracer or status");
+    if (m->samples == 0) return set_error(PTX_ERR_INVALID, "ptx_adaptive_select: no add on this moments handle yet");
+    if (const int rc = moments_begin("ptx_adaptive_select", t, m)) return rc;
+    if (const int rc = adaptive_begin("ptx_adaptive_select", t, a)) return rc;
+    int code = 0;
+    if (const char *why = active_tiles_problem(t, a->ntiles, code)) return set_error(code, std::string("ptx_adaptive_select: ") + why);
+    HIPCHECK(hipSetDevice(t->device));
+    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
+    HIPCHECK(pt_adaptive_select_enqueue(t->stream, *a, m->st, p, a->rounds + 1));
+    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
+    m->used = true;
+    const size_t bytes = sizeof(ptx_adaptive_status) + (size_t)a->ntiles;
+    HIPCHECK(hipMemcpyAsync(a->h_out, a->d_out, bytes, hipMemcpyDeviceToHost, t->stream));      // the one small read: status and flags
+    const int rc = set_tile_mask(t, a->d_active());      // (waits for the stream: h_out is there)
+    HIPCHECK(hipEventRecord(a->ev, t->stream));          // behind k_tile_mask, which reads the flags
+    a->used = true;
+    if (rc != PTX_OK) return rc;
+    a->rounds++;
+    memcpy(status, a->h_out, sizeof *status);
+    memcpy(a->h_active.data(), a->h_out + sizeof(ptx_adaptive_status), (size_t)a->ntiles);
+    return PTX_OK;
+}
+
+int ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t) {
+    if (!a || !t) return set_error(PTX_ERR_INVALID, "ptx_adaptive_resolve: null adaptive handle or tracer");
+    if (const int rc = adaptive_begin("ptx_adaptive_resolve", t, a)) return rc;
+    HIPCHECK(hipSetDevice(t->device));
+    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
+    HIPCHECK(pt_adaptive_resolve_enqueue(t->stream, *a, t->d_image));
+    HIPCHECK(hipEventRecord(a->ev, t->stream));
+    a->used = true;
     return PTX_OK;
 }
 

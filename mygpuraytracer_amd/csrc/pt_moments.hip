@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include <math.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -77,6 +78,61 @@ __global__ __launch_bounds__(NT) void k_moments_add(int w, int h, int pairs, flo
     mean[p] = mu;
     ma[p] = A;
     if (even) mb[pb] = make_float4(rb, gb, nrb, ngb);
+}
+
+// k_moments_add with k and W' of the pixel's tile (kt[(y w + x) / tile_px]): the same arithmetic on the pixels of a tile that advances.
+// A tile with k == 0 is idle: its pixels are not stored (fresh: stored as zeros), and their half of a shared (rb, gb) record goes back
+// with the bits it came with -- a record whose two pixels are both idle is not stored at all.
+__global__ __launch_bounds__(NT) void k_moments_add_tiled(int w, int h, int pairs, int tile_px, const float2 *__restrict__ kt, int fresh,
+                                                          const float *__restrict__ rgb, float4 *__restrict__ snap, float4 *__restrict__ mean,
+                                                          float4 *__restrict__ ma, float4 *__restrict__ mb) {
+    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    const bool inside = x < w && y < h;                  // (no early return: the lanes outside still serve pair_swap)
+    const bool even = (threadIdx.x & 1) == 0;
+    const size_t p = (size_t)y * w + x, pb = (size_t)y * pairs + (x >> 1);
+    float k = 0.f, total = 0.f;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), mu = s, A = s, Bq = s;
+    if (inside) {
+        const float2 t = kt[p / (size_t)tile_px];
+        k = t.x; total = t.y;
+        if (k > 0.f) { a0 = rgb[3 * p]; a1 = rgb[3 * p + 1]; a2 = rgb[3 * p + 2]; }
+        if (!fresh) {
+            if (k > 0.f) { s = snap[p]; mu = mean[p]; A = ma[p]; }
+            if (even) Bq = mb[pb];
+        }
+    }
+    const bool live = k > 0.f;
+    const float orb = pair_swap(Bq.z), ogb = pair_swap(Bq.w);     // the odd lane's (rb, gb), held by its even neighbour
+    float rb = even ? Bq.x : orb, gb = even ? Bq.y : ogb;
+    if (live) {
+        const float wo = total - k;
+        if (wo > 0.f) {                                  // (k_moments_add's update, operation for operation)
+            const float kw = k * wo, den = kw * total, r = k / total;
+            float D[3];
+            const float acc[3] = {a0, a1, a2}, old[3] = {s.x, s.y, s.z};
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float p1 = acc[c] * wo, p2 = old[c] * total;
+                D[c] = (p1 - p2) + (__fmaf_rn(acc[c], wo, -p1) - __fmaf_rn(old[c], total, -p2));
+            }
+            mu.x = mu.x + r * (D[0] / kw); mu.y = mu.y + r * (D[1] / kw); mu.z = mu.z + r * (D[2] / kw);
+            A.x = A.x + (D[0] * D[0]) / den; A.y = A.y + (D[1] * D[1]) / den; A.z = A.z + (D[2] * D[2]) / den; A.w = A.w + (D[0] * D[1]) / den;
+            rb = rb + (D[0] * D[2]) / den; gb = gb + (D[1] * D[2]) / den;
+        } else {                                         // the tile's first add: one batch, no scatter yet
+            mu.x = a0 / k; mu.y = a1 / k; mu.z = a2 / k;
+        }
+        mu.w = mu.w + 1.f;
+    }
+    const float nrb = pair_swap(rb), ngb = pair_swap(gb);         // the neighbour's (zeros from a lane outside the frame)
+    const bool nlive = pair_swap(live ? 1.f : 0.f) != 0.f;
+    if (!inside) return;
+    if (live || fresh) {
+        snap[p] = live ? make_float4(a0, a1, a2, total) : s;      // (an idle pixel of a fresh handle: s, mu, A are zeros)
+        mean[p] = mu;
+        ma[p] = A;
+    }
+    if (even && (live || nlive || fresh)) mb[pb] = make_float4(rb, gb, nrb, ngb);
 }
 
 __device__ __forceinline__ void partial_add(PtMomentsPartial &a, const PtMomentsPartial &b) {
@@ -162,7 +218,7 @@ int no_device(const char *what) {
 
 void free_moments(ptx_moments *m) {
     (void)hipFree(m->st.snap); (void)hipFree(m->st.mean); (void)hipFree(m->st.ma); (void)hipFree(m->st.mb);
-    (void)hipFree(m->d_stage); (void)hipFree(m->d_part);
+    (void)hipFree(m->d_stage); (void)hipFree(m->d_part); (void)hipFree(m->d_tile_kt);
     if (m->ev) (void)hipEventDestroy(m->ev);
     delete m;
 }
@@ -199,6 +255,29 @@ hipError_t pt_moments_prep_enqueue(hipStream_t st, int w, int h, const float *rg
                        (const float4 *)s.snap, (const float4 *)s.mean, (const float4 *)s.ma, reinterpret_cast<const float2 *>(s.mb),
                        (float)min_batches, c);
     return hipGetLastError();
+}
+
+int pt_moments_add_tiled(ptx_moments *m, hipStream_t st, const float *rgb, const float2 *d_kt, const int32_t *host_k) {
+    const int ntiles = pt_moments_tiles(m->w, m->h);
+    bool any = false;
+    for (int i = 0; i < ntiles && !any; i++) any = host_k[i] > 0;
+    if (!any) return PTX_OK;
+    hipLaunchKernelGGL(k_moments_add_tiled, pt_pixel_grid(m->w, m->h), dim3(BX, BY), 0, st, m->w, m->h, pt_moments_pairs(m->w), ptx_tile_pixels(),
+                       d_kt, m->samples == 0 ? 1 : 0, rgb, m->st.snap, m->st.mean, m->st.ma, m->st.mb);
+    PT_HC(hipGetLastError());
+    if (m->tile_samples.empty()) {                       // the first tiled add: every tile stands where the handle stands
+        m->tile_samples.assign((size_t)ntiles, m->samples);
+        m->tile_batches.assign((size_t)ntiles, m->batches);
+    }
+    m->tiled = true;
+    for (int i = 0; i < ntiles; i++) {
+        if (host_k[i] <= 0) continue;
+        m->tile_samples[(size_t)i] += host_k[i];
+        m->tile_batches[(size_t)i]++;
+        m->samples = std::max(m->samples, m->tile_samples[(size_t)i]);
+        m->batches = std::max(m->batches, m->tile_batches[(size_t)i]);
+    }
+    return PTX_OK;
 }
 
 extern "C" {
@@ -239,6 +318,8 @@ int ptx_moments_reset(ptx_moments *m) {
     if (!m) return pt_fail(PTX_ERR_INVALID, "ptx_moments_reset: null moments handle");
     m->samples = 0;            // (the buffers are only read behind this: the next add takes them as zeros, and waits for the last)
     m->batches = 0;
+    m->tiled = false;
+    m->tile_samples.clear(); m->tile_batches.clear();
     return PTX_OK;
 }
 
@@ -248,6 +329,7 @@ int ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samp
     if (samples_total <= m->samples)
         return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
                                             std::to_string(m->samples));
+    if (m->tiled) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: this handle has had a tiled add; its tiles hold different sample counts until ptx_moments_reset");
     const size_t n = (size_t)m->w * m->h;
     PT_HC(hipSetDevice(m->device));
     if (m->used) PT_HC(hipEventSynchronize(m->ev));
@@ -258,6 +340,35 @@ int ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samp
     m->used = true;
     m->samples = samples_total;
     m->batches++;
+    PT_HC(hipEventSynchronize(m->ev));
+    return PTX_OK;
+}
+
+int ptx_moments_add_host_tiled(ptx_moments *m, const float *host_rgb_sum, const int64_t *tile_samples_total, int ntiles) {
+    if (!m || !host_rgb_sum || !tile_samples_total) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host_tiled: null moments handle, frame or table");
+    if (ntiles != pt_moments_tiles(m->w, m->h))
+        return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host_tiled: ntiles " + std::to_string(ntiles) + " is not the frame's " +
+                                            std::to_string(pt_moments_tiles(m->w, m->h)));
+    std::vector<float2> kt((size_t)ntiles);
+    std::vector<int32_t> hk((size_t)ntiles);
+    for (int i = 0; i < ntiles; i++) {
+        const long long last = m->tile_samples.empty() ? m->samples : m->tile_samples[(size_t)i], now = tile_samples_total[i];
+        if (now < last || now - last > (1 << 24) || now > (1 << 24))      // (W and k are held as floats: exact to 2^24)
+            return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host_tiled: tile " + std::to_string(i) + "'s total " + std::to_string(now) +
+                                                (now < last ? " is below its last add's " + std::to_string(last) : std::string(" is above 2^24")));
+        hk[(size_t)i] = (int32_t)(now - last);
+        kt[(size_t)i] = make_float2((float)(now - last), (float)now);
+    }
+    const size_t n = (size_t)m->w * m->h;
+    PT_HC(hipSetDevice(m->device));
+    if (m->used) PT_HC(hipEventSynchronize(m->ev));
+    if (!m->d_stage) PT_HC(hipMalloc(&m->d_stage, sizeof(float) * 3 * n));
+    if (!m->d_tile_kt) PT_HC(hipMalloc(&m->d_tile_kt, sizeof(float2) * (size_t)ntiles));
+    PT_HC(hipMemcpy(m->d_stage, host_rgb_sum, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+    PT_HC(hipMemcpy(m->d_tile_kt, kt.data(), sizeof(float2) * (size_t)ntiles, hipMemcpyHostToDevice));
+    if (const int rc = pt_moments_add_tiled(m, nullptr, m->d_stage, m->d_tile_kt, hk.data())) return rc;
+    PT_HC(hipEventRecord(m->ev, nullptr));
+    m->used = true;
     PT_HC(hipEventSynchronize(m->ev));
     return PTX_OK;
 }
@@ -295,6 +406,21 @@ int ptx_moments_read(ptx_moments *m, float *mean3, float *cov6, int32_t *batches
                 for (int j = 0; j < 6; j++) cov6[6 * i + j] = B >= 2.f ? v[j] / (B - 1.f) : 0.f;
             }
         }
+    return PTX_OK;
+}
+
+int ptx_moments_read_samples(ptx_moments *m, int32_t *samples1) {
+    if (!m || !samples1) return pt_fail(PTX_ERR_INVALID, "ptx_moments_read_samples: null moments handle or array");
+    const size_t n = (size_t)m->w * m->h;
+    if (m->samples == 0) {                               // fresh: everything reads as zero
+        for (size_t i = 0; i < n; i++) samples1[i] = 0;
+        return PTX_OK;
+    }
+    PT_HC(hipSetDevice(m->device));
+    PT_HC(hipEventSynchronize(m->ev));
+    std::vector<float4> s(n);
+    PT_HC(hipMemcpy(s.data(), m->st.snap, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) samples1[i] = (int32_t)s[i].w;
     return PTX_OK;
 }
 
