@@ -67,6 +67,54 @@ def test_random_stage_inputs(ref_lib, oracle_lib):
     assert beq(ref_lib.shade(9, 1, idx, ri, p), oracle_lib.shade(9, 1, idx, oi, p))
 
 
+def test_maps_of_different_non_square_sizes(ref_lib, oracle_lib, tmp_path):
+    """The stand-in ship with four generated maps of different, non-square sizes (kd 64x33, ks 5x9, ke 31x17, bump 12x40; P6 and PNG
+    mixed, 3 and 4 channels), loaded by the reference's own loader from files: a width used for a height, or one map's size used for
+    another's, changes the texel read.  The oracle equals the reference on computeIntersections (meshIntersectionTest's bump lookup among
+    it) for rays aimed at the mesh, on shadeFakeMaterial, and on 3 iterations of a 96x54 frame.  The reference's index is undefined
+    outside the map, so before it sees a coordinate the rule (tests/texel_ref.py) must say that no lookup is clamped."""
+    import texel_ref as TR
+    import texelcases as TC
+    from cpulibs import PATH_DTYPE
+    text = scene_text_with(open(os.path.join(REFERENCE_ROOT, "scenes", "cornellSpaceship.txt")).read(), (96, 54), 8)
+    path, written = TC.write_ship_scene(tmp_path, text)
+    ref_lib.load(path, cwd=str(tmp_path / "scenes"))
+    rd = ref_lib.dump()
+    gi = TC.mesh_index(rd)
+    assert {k: v.shape for k, v in rd["textures"].items()} == {(gi, w): img.shape for w, img in written.items()}
+    sizes = [(img.shape[1], img.shape[0]) for img in written.values()]
+    assert len(set(sizes)) == 4 and all(w != h for w, h in sizes)
+    # every texcoord a hit can have lies between the face corners' (barycentric weights in [0, 1], a rounding error beyond at most)
+    f = rd["faces"][gi]
+    u, v = f[:, [3, 8, 13]], f[:, [4, 9, 14]]
+    for w, h in sizes:
+        ends = TR.classes(np.float32([u.min() - 1e-3, u.max() + 1e-3]), np.float32([v.min() - 1e-3, v.max() + 1e-3]), w, h)
+        assert set(ends.tolist()) <= {TR.INTERIOR, TR.LAST_ROW, TR.LAST_TEXEL}
+    oracle_lib.set_libm(0)
+    oracle_lib.create(rd)
+    ref_lib.apply_runcuda_camera(); oracle_lib.apply_runcuda_camera()
+    ref_lib.pt_init(); oracle_lib.pt_init()
+    p = TC.mesh_rays(rd, gi, 6000, 77)
+    oi = oracle_lib.compute_intersections(p)
+    mesh = (oi["t"] > 0) & (oi["geomId"] == gi)
+    assert mesh.sum() >= 500
+    for w, h in sizes:
+        cls = TR.classes(oi["texcoord"][mesh, 0], oi["texcoord"][mesh, 1], w, h)
+        assert not TR.clamped(cls).any() and not (cls == TR.WRAP_ROW).any() and not (cls == TR.WRAP_OTHER).any()
+    ri = ref_lib.compute_intersections(p)
+    assert beq(ri, oi)
+    idx = np.random.default_rng(78).integers(0, 3_000_000, len(p)).astype(np.int32)
+    shaded = oracle_lib.shade(9, 1, idx, oi, p)
+    assert beq(ref_lib.shade(9, 1, idx, ri, p), shaded)
+    ended = mesh & (shaded["remainingBounces"] == 0) & (p["remainingBounces"] > 1)
+    assert ended.sum() >= 50 and (mesh & (shaded["remainingBounces"] > 0)).sum() >= 50        # both sides of the emissive test
+    for it in (1, 2, 3):
+        ref_lib.iterate(it); oracle_lib.iterate(it)
+        assert beq(ref_lib.live_counts(), oracle_lib.live_counts())
+    assert beq(ref_lib.image(), oracle_lib.image())
+    assert beq(ref_lib.paths(), oracle_lib.paths())
+
+
 def _cottage_scene_text(res=(96, 54), depth=6):
     """the reference's cornellObj.txt with its cube swapped for models/cottage_obj.obj (5 objects, 3 materials, 32
     triangles + 227 quads = 486 triangles), scaled into the box.  Read where it lies under /root/reference."""
