@@ -473,7 +473,7 @@ int  ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t sam
  * new.  Refused (PTX_ERR_INVALID): a total below the tile's last one, a wrong ntiles.  From its first tiled add until ptx_moments_reset
  * the handle's `samples` and `batches` are the maxima over the tiles, ptx_moments_add and ptx_moments_add_host are refused, and so are
  * ptx_denoise_measured and ptx_denoise_temporal_measured, which assume one spp and one B for the frame: the filter on an adaptive
- * frame is not done.  Synchronous. */
+ * frame is ptx_denoise_adaptive below, which takes both per tile.  Synchronous. */
 int  ptx_moments_add_host_tiled(ptx_moments *m, const float *host_rgb_sum, const int64_t *tile_samples_total, int ntiles);
 /* samples1: W*H int32 of the per-pixel W (one number per frame until a tiled add); waits for the handle's last work. */
 int  ptx_moments_read_samples(ptx_moments *m, int32_t *samples1);
@@ -530,7 +530,7 @@ int  ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *
  * The handle and the moments handle count the same samples: reset both together (and ptx_clear_active_tiles the tracer) whenever the
  * accumulation restarts; an add that finds them out of step is refused.  Refused like ptx_moments_add: a handle of another device or
  * size, tile_world > 1.  Each enqueueing call makes t's stream wait for both handles' previous work and records after its own.
- * Not done: reactivating a stopped tile on purpose, masks finer than a tile, multi-device tracers, the denoiser on such a frame. */
+ * Not done: reactivating a stopped tile on purpose, masks finer than a tile, multi-device tracers. */
 typedef struct ptx_adaptive ptx_adaptive;          /* opaque */
 typedef struct ptx_adaptive_params {
     float   target;            /* > 0: a tile stops when its error <= target; default 0.02 (stated, not tuned) */
@@ -560,6 +560,23 @@ int  ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t);
  * tile.  NULLs allowed; waits for the handle's last work. */
 int  ptx_adaptive_read(ptx_adaptive *a, float *mean_rgb, int32_t *samples_per_pixel, float *tile_error, uint8_t *tile_active);
 float *ptx_adaptive_device_frame(ptx_adaptive *a); /* the resolved frame on the device, W*H*3 floats */
+/* The variance-guided filter on an adaptive frame (k_adaptive_prep of csrc/pt_adaptive.hip): ptx_denoise_measured with the divisor, W
+ * and B of every pixel's own tile in place of one spp and one B for the frame.  Definition (tests/adaptive_denoise_ref.py
+ * restates it), with s = the samples of the pixel's tile:
+ *   input c = acc / s (divided by max(albedo, 1e-3) on hit pixels when demodulating), in fp32 and in ptx_denoise_measured's order;
+ *   v0 on a hit pixel with B >= min_batches: max(g^T C g, 0) / s, g_k = l_k (/ max(albedo_k, 1e-3)); on the other hit pixels the
+ *   spatial estimate of ptx_denoise_variance (n = 1); on miss pixels 0.  min_batches <= 0 means 4, 1 is refused.
+ *   Then the filter of ptx_denoise_variance.  A frame whose tiles all hold one count gives ptx_denoise_measured's bits.
+ * The un-demodulated acc / s goes into the handle's frame as well: the call includes ptx_adaptive_resolve, and ptx_adaptive_read's
+ * mean_rgb is current after it.  The result comes back through ptx_read_denoised and ptx_read_variance.  Nothing else moves: not the
+ * accumulation buffer, the moments state, the counts, the flags or the tracer's mask.
+ * Refused (PTX_ERR_INVALID, nothing enqueued): NULL handles, bad parameters, a handle of another device or size, tile_world > 1, no
+ * add yet, a tile without a sample, and handles that do not count the same samples tile by tile (ptx_adaptive_add's comparison:
+ * reset both together).  As for ptx_adaptive_resolve, the accumulation buffer must hold exactly what the last ptx_adaptive_add counted;
+ * that is the caller's to keep and cannot be detected.  t's stream waits for both handles' previous work, and both record after the
+ * prep.  Not done: combining with the temporal history (ptx_denoise_temporal_measured keeps refusing a tiled moments handle). */
+int  ptx_denoise_adaptive(ptx_tracer *t, ptx_adaptive *a, ptx_moments *m, const ptx_denoise_params *dp, const ptx_variance_params *vp,
+                          int min_batches);
 
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */

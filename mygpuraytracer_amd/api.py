@@ -299,7 +299,8 @@ def tile_pixels():
 class Adaptive:
     """Adaptive sampling by tiles on one device (opaque ptx_adaptive): render(tracer, moments) traces until every tile's measured error
     is at its target, or step by step add(moments, tracer, k) after every k iterations, select(moments, tracer) for the next mask,
-    resolve(tracer) and read() for the frame.  Reset it together with the Moments it is used with."""
+    resolve(tracer) and read() for the frame; Tracer.denoise_adaptive(adaptive, moments) filters it.  Reset it together with the Moments
+    it is used with."""
 
     def __init__(self, device, width, height):
         self.lib = load_library()
@@ -671,6 +672,8 @@ def load_library():
     L.ptx_adaptive_resolve.restype, L.ptx_adaptive_resolve.argtypes = i, [vp, vp]
     L.ptx_adaptive_read.restype, L.ptx_adaptive_read.argtypes = i, [vp, vp, vp, vp, vp]
     L.ptx_adaptive_device_frame.restype, L.ptx_adaptive_device_frame.argtypes = vp, [vp]
+    L.ptx_denoise_adaptive.restype = i
+    L.ptx_denoise_adaptive.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), i]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -1177,6 +1180,19 @@ class Tracer:
                 raise TypeError("denoise_measured: unknown parameter %r" % k)
         dp, _, vpar = _split_variance_params("denoise_measured", params)
         _check(self.lib.ptx_denoise_measured(self.h, moments.h, C.byref(dp), C.byref(vpar), mb, int(spp)), "ptx_denoise_measured")
+        return self.read_denoised() if read else None
+
+    def denoise_adaptive(self, adaptive, moments, min_batches=None, read=True, **params):
+        """denoise_measured() on an adaptively sampled frame (ptx_denoise_adaptive): the accumulation buffer over every tile's own count
+        from `adaptive` (an Adaptive), and the variance `moments` measured with every pixel's own W and B; hit pixels with fewer than
+        min_batches batches (None: 4) take the spatial estimate.  params: any field of ptx_denoise_params and ptx_variance_params.
+        Includes adaptive.resolve(tracer): adaptive.read()["mean"] is current after it.  variance() gives the v0 it used."""
+        for k in params:
+            if k not in _DENOISE_KEYS + _VARIANCE_KEYS:
+                raise TypeError("denoise_adaptive: unknown parameter %r" % k)
+        dp, _, vpar = _split_variance_params("denoise_adaptive", params)
+        _check(self.lib.ptx_denoise_adaptive(self.h, adaptive.h, moments.h, C.byref(dp), C.byref(vpar),
+                                             0 if min_batches is None else int(min_batches)), "ptx_denoise_adaptive")
         return self.read_denoised() if read else None
 
     def variance(self):

@@ -27,6 +27,10 @@
 //                                                                      render that gives every tile the worst tile's count; the frame saved is
 //                                                                      the one normalised tile by tile.  Not with --frames, --per-call,
 //                                                                      --checkpoint, --until-error or --denoise.)
+//                                  [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]   (with --adaptive E: also
+//                                                                      <out>.denoised.png / .pfm, the variance-guided filter on that frame
+//                                                                      with the variance the rounds measured, every tile with its own count:
+//                                                                      ptx_denoise_adaptive)
 //                                  [--measured [--measure-every K]]   (with --denoise: the variance-guided filter on the variance the
 //                                                                      run measured, ptx_denoise_measured: a batch every K iterations,
 //                                                                      16 unless given.  Implies --variance.  With --frames the moments
@@ -107,11 +111,11 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2 || !strcmp(argv[1], "--help")) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]]\n", argv[0]);
         return argc < 2;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
-    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false, measured = false;
+    bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false, measured = false, adaptive_denoise = false;
     double until_error = -1.0, adaptive = -1.0;
     ptx_moments_params mparams;
     ptx_default_moments_params(&mparams);
@@ -150,6 +154,7 @@ int main(int argc, char **argv) {
         else if (a == "--until-error") { need(1); until_error = atof(argv[++i]); }
         else if (a == "--error-floor") { need(1); mparams.floor = (float)atof(argv[++i]); }
         else if (a == "--adaptive") { need(1); adaptive = atof(argv[++i]); }
+        else if (a == "--adaptive-denoise") adaptive_denoise = true;
         else if (a == "--measured") measured = true;
         else if (a == "--measure-every") { need(1); measure_every = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
@@ -162,6 +167,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--until-error and --measured do not combine with --per-call or --checkpoint\n");
         return 1;
     }
+    if (adaptive_denoise && adaptive < 0.0) { fprintf(stderr, "--adaptive-denoise needs --adaptive E\n"); return 1; }
     if (adaptive >= 0.0) {
         if (!(adaptive > 0.0)) { fprintf(stderr, "--adaptive needs E > 0\n"); return 1; }
         if (frames > 0 || per_call || !ckpt_path.empty() || until_error >= 0.0 || denoise) {
@@ -170,6 +176,7 @@ int main(int argc, char **argv) {
         }
         adaptiveTarget() = (float)adaptive;
         adaptiveParams().floor = mparams.floor;
+        adaptiveDenoise() = adaptive_denoise;
     }
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
     if (variance && !denoise) { fprintf(stderr, "--variance needs --denoise\n"); return 1; }
@@ -284,6 +291,14 @@ int main(int argc, char **argv) {
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());
         if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den.data(), 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
+    }
+    if (adaptive_denoise) {                     // ptx_denoise_adaptive on the frame just saved: mean radiance, so divided by 1
+        const float *den = adaptiveDenoisedFrame();
+        if (!den) { fprintf(stderr, "--adaptive-denoise: no round was rendered\n"); return 1; }
+        ptimg::to_rgb8_mirrored(width, height, den, 1.0f, rgb8);
+        if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
+        printf("Saved %s.denoised.png.\n", ss.str().c_str());
+        if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den, 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
     }
     if (hdr) {                                                                          // img.saveHDR, main.cpp:101
         std::vector<float> mean;

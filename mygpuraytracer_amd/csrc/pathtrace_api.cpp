@@ -35,6 +35,7 @@ int g_moments_key[3] = {0, 0, 0};    // its device, width, height
 ptx_adaptive *g_adaptive = nullptr;  // pathtrace()'s adaptive sampling with adaptiveTarget() > 0: created on first use, with g_moments' key
 ptx_adaptive_status g_adaptive_status = {};
 std::vector<float> g_adaptive_frame; // adaptiveFrame()'s host copy
+std::vector<float> g_adaptive_denoised;      // adaptiveDenoisedFrame()'s
 int g_calls = 0;                     // pathtrace() calls since pathtraceInit
 
 void check(int rc, const char *what) {
@@ -273,6 +274,19 @@ const float *adaptiveFrame() {
     g_adaptive_frame.resize((size_t)g_moments_key[1] * g_moments_key[2] * 3);
     check(ptx_adaptive_read(g_adaptive, g_adaptive_frame.data(), nullptr, nullptr, nullptr), "adaptiveFrame");
     return g_adaptive_frame.data();
+}
+
+bool &adaptiveDenoise() {
+    static bool on = false;
+    return on;
+}
+
+const float *adaptiveDenoisedFrame() {
+    if (!adaptiveDenoise() || !g_tracer || !g_adaptive || !g_moments || g_adaptive_status.rounds < 1) return nullptr;
+    check(ptx_denoise_adaptive(g_tracer, g_adaptive, g_moments, &denoiseParams(), &varianceParams(), 0), "adaptiveDenoisedFrame");
+    g_adaptive_denoised.resize((size_t)g_moments_key[1] * g_moments_key[2] * 3);
+    check(ptx_read_denoised(g_tracer, g_adaptive_denoised.data()), "adaptiveDenoisedFrame");
+    return g_adaptive_denoised.data();
 }
 
 // one batch: everything the frame gained since the last one

@@ -295,6 +295,12 @@ ptx_adaptive_params &adaptiveParams();
 ptx_adaptive *pathtraceAdaptive();
 const ptx_adaptive_status &adaptiveStatus();
 const float *adaptiveFrame();
+// The variance-guided filter on that frame (ptx_denoise_adaptive, with denoiseParams() and varianceParams()): with adaptiveDenoise() on,
+// adaptiveDenoisedFrame() filters the frame as the rounds so far left it, with the variance they measured tile by tile, and returns
+// W*H*3 floats of mean radiance; it resolves as well, so adaptiveFrame() needs no call before it.  NULL before the first round, and
+// while the switch is off (the default): no call is then made that was not made without it.  Not combined with denoiseTemporal().
+bool &adaptiveDenoise();
+const float *adaptiveDenoisedFrame();
 // The same round by hand, for a caller that renders through pathtraceHandle(): the last k iterations were rendered under the current mask.
 void pathtraceAdaptiveStep(int k);
 void GPUdenoiseRelease();

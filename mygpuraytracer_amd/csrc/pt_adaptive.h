@@ -38,3 +38,9 @@ hipError_t pt_adaptive_advance_enqueue(hipStream_t st, const ptx_adaptive &a, in
 hipError_t pt_adaptive_select_enqueue(hipStream_t st, const ptx_adaptive &a, const PtMomentsState &s, const ptx_adaptive_params &p, int rounds);
 // frame[p] = acc[p] / samples[tile(p)], 0 where the tile has no sample
 hipError_t pt_adaptive_resolve_enqueue(hipStream_t st, const ptx_adaptive &a, const float *acc);
+// pt_moments_prep_enqueue on a frame of unequal counts: c = float4(acc / s (demodulated on hit pixels), v) with s = samples[tile(p)] > 0
+// on every tile, v = max(g^T C g, 0) / s on hit pixels with B >= min_batches (>= 2), -1 on the other hit pixels
+// (pt_variance_spatial_enqueue fills those in), 0 on miss pixels; and frame[p] = acc[p] / s, the resolve.  Every tile with the same
+// count: pt_moments_prep_enqueue's bits.
+hipError_t pt_adaptive_prep_enqueue(hipStream_t st, const ptx_adaptive &a, const float *acc, const float4 *nh, const float4 *alb, int demod,
+                                    const PtMomentsState &s, int min_batches, float4 *c);

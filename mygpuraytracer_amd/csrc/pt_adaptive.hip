@@ -1,7 +1,7 @@
 // pt_adaptive.hip -- adaptive sampling by tiles (ptx_adaptive_* of include/mi355x_pathtracer.h): per-tile sample counts, the tile error
 // from the batch-means moments (pt_moments.hip), the decision which tiles go on, and the frame normalised by per-tile counts.  The
-// tracer is not touched here: ptx_adaptive_add / _select / _resolve are pt_engine.hip's (they need its accumulation buffer, its stream
-// and its tile mask) and enqueue the kernels below.  State layout in pt_adaptive.h.
+// tracer is not touched here: ptx_adaptive_add / _select / _resolve and ptx_denoise_adaptive are pt_engine.hip's (they need its
+// accumulation buffer, its stream, its tile mask and its G-buffer) and enqueue the kernels below.  State layout in pt_adaptive.h.
 //
 // Kernels:
 //   k_tile_mask        : one thread per tile, the tracer's table of visible geoms ANDed with the flags (pt_engine.hip enqueues it: that
@@ -12,6 +12,8 @@
 //   k_adaptive_status  : one workgroup; thread t takes a contiguous run of tiles in index order, then the same tree.  Integers only but
 //       for the largest e_T, a maximum.
 //   k_adaptive_resolve : one thread per pixel, acc / samples of its tile.
+//   k_adaptive_prep    : the variance-guided filter's prep on a frame of unequal counts (ptx_denoise_adaptive): k_moments_prep with the
+//       divisor and W of the pixel's tile, and the resolve's store.  One thread per pixel on the filter's grid of 64 x 4 pixels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -138,6 +140,41 @@ __global__ __launch_bounds__(NT) void k_adaptive_resolve(int npix, int tile_px, 
     frame[i] = s > 0 ? acc[i] / n : 0.f; frame[i + 1] = s > 0 ? acc[i + 1] / n : 0.f; frame[i + 2] = s > 0 ? acc[i + 2] / n : 0.f;
 }
 
+// k_moments_prep (pt_moments.hip) with the divisor of the pixel's tile, operation for operation: c = float4(acc / s (demodulated on hit
+// pixels), v), v = max(g^T C g, 0) / W on hit pixels with B >= min_batches, -1 on the other hit pixels, 0 on miss pixels; and the
+// un-demodulated acc / s into frame (k_adaptive_resolve's store).  s = samples[tile] > 0 for every tile (ptx_denoise_adaptive checks
+// the host's mirror), and W = float(s): the state's snap.w holds the same number, which is therefore not read.  One thread per pixel
+// of the 64 x 4 grid, so a wave is one row segment and samples[] changes at most once inside it.  No LDS, no atomics.
+__global__ __launch_bounds__(PT_BX * PT_BY) void k_adaptive_prep(int w, int h, int pairs, int tile_px, const float *__restrict__ rgb,
+                                                                 const int32_t *__restrict__ samples, const float4 *__restrict__ nh,
+                                                                 const float4 *__restrict__ alb, int demod, const float4 *__restrict__ mean,
+                                                                 const float4 *__restrict__ ma, const float2 *__restrict__ mb2,
+                                                                 float min_batches, float4 *__restrict__ c, float *__restrict__ frame) {
+    const int x = blockIdx.x * PT_BX + threadIdx.x, y = blockIdx.y * PT_BY + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
+    const float spp = (float)samples[p / (size_t)tile_px];
+    float r = rgb[3 * p] / spp, g = rgb[3 * p + 1] / spp, b = rgb[3 * p + 2] / spp;
+    frame[3 * p] = r; frame[3 * p + 1] = g; frame[3 * p + 2] = b;
+    float v = 0.f;
+    if (nh[p].w != 0.f) {
+        float g0 = LR, g1 = LG, g2 = LB;
+        if (demod) {
+            const float4 a = alb[p];
+            const float f0 = fmaxf(a.x, 1e-3f), f1 = fmaxf(a.y, 1e-3f), f2 = fmaxf(a.z, 1e-3f);
+            r = r / f0; g = g / f1; b = b / f2;
+            g0 = g0 / f0; g1 = g1 / f1; g2 = g2 / f2;
+        }
+        const float B = mean[p].w;
+        v = -1.f;
+        if (B >= min_batches) {
+            const float2 m2 = mb2[(size_t)y * pairs * 2 + x];
+            v = fmaxf(quad_form(g0, g1, g2, ma[p], m2.x, m2.y, B), 0.f) / spp;
+        }
+    }
+    c[p] = make_float4(r, g, b, v);
+}
+
 void free_adaptive(ptx_adaptive *a) {
     (void)hipFree(a->d_samples); (void)hipFree(a->d_batches); (void)hipFree(a->d_nest); (void)hipFree(a->d_err); (void)hipFree(a->d_kt);
     (void)hipFree(a->d_out); (void)hipFree(a->d_frame);
@@ -213,6 +250,14 @@ hipError_t pt_adaptive_resolve_enqueue(hipStream_t st, const ptx_adaptive &a, co
     const int npix = a.w * a.h;
     hipLaunchKernelGGL(k_adaptive_resolve, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, st, npix, ptx_tile_pixels(), acc,
                        (const int32_t *)a.d_samples, a.d_frame);
+    return hipGetLastError();
+}
+
+hipError_t pt_adaptive_prep_enqueue(hipStream_t st, const ptx_adaptive &a, const float *acc, const float4 *nh, const float4 *alb, int demod,
+                                    const PtMomentsState &s, int min_batches, float4 *c) {
+    hipLaunchKernelGGL(k_adaptive_prep, pt_pixel_grid(a.w, a.h), dim3(PT_BX, PT_BY), 0, st, a.w, a.h, pt_moments_pairs(a.w), ptx_tile_pixels(), acc,
+                       (const int32_t *)a.d_samples, nh, alb, demod, (const float4 *)s.mean, (const float4 *)s.ma,
+                       reinterpret_cast<const float2 *>(s.mb), (float)min_batches, c, a.d_frame);
     return hipGetLastError();
 }
 

@@ -1661,6 +1661,45 @@ int ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t) {
     return PTX_OK;
 }
 
+// ptx_denoise_measured on a frame of unequal counts: k_adaptive_prep in place of k_moments_prep, the rest as there
+int ptx_denoise_adaptive(ptx_tracer *t, ptx_adaptive *a, ptx_moments *m, const ptx_denoise_params *dparams, const ptx_variance_params *vparams,
+                         int min_batches) {
+    const std::string fn = "ptx_denoise_adaptive";
+    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
+    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
+    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
+    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
+    if (min_batches == 1) return set_error(PTX_ERR_INVALID, fn + ": min_batches must be >= 2 (<= 0: the default, 4)");
+    if (!t || !a || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, adaptive handle or moments handle");
+    if (const int rc = moments_begin(fn, t, m)) return rc;
+    if (const int rc = adaptive_begin(fn, t, a)) return rc;
+    // the two handles count the same samples tile by tile (ptx_adaptive_add's comparison), and every tile holds some
+    for (int i = 0; i < a->ntiles; i++) {
+        const long long have = m->tile_samples.empty() ? m->samples : m->tile_samples[(size_t)i];
+        if (have != a->h_samples[(size_t)i])
+            return set_error(PTX_ERR_INVALID, fn + ": tile " + std::to_string(i) + " holds " + std::to_string(a->h_samples[(size_t)i]) +
+                                                  " samples, the moments handle has " + std::to_string(have) + " of it: reset both together");
+    }
+    if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on these handles yet");
+    for (int i = 0; i < a->ntiles; i++)
+        if (a->h_samples[(size_t)i] < 1) return set_error(PTX_ERR_INVALID, fn + ": tile " + std::to_string(i) + " holds no sample");
+    if (const int rc = denoise_begin(fn, t, nullptr, true)) return rc;
+    const int W = t->cam.resx, H = t->cam.resy;
+    const size_t n = (size_t)W * H;
+    const float4 *g = t->d_gbuf;
+    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
+    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
+    HIPCHECK(pt_adaptive_prep_enqueue(t->stream, *a, t->d_image, g, g + 2 * n, dp.demodulate ? 1 : 0, m->st, min_batches <= 0 ? 4 : min_batches,
+                                      t->d_dn_tmp));
+    HIPCHECK(hipEventRecord(a->ev, t->stream));          // (the handle's frame was written: ptx_adaptive_read waits for it)
+    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
+    a->used = m->used = true;
+    HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
+    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
+    t->dn_done = t->var_done = true;
+    return PTX_OK;
+}
+
 int ptx_read_denoised(ptx_tracer *t, float *host_rgb) {
     if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
     if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_read_denoised: no ptx_denoise on this tracer yet");
