@@ -284,10 +284,20 @@ int ptx_get_kernel_times(ptx_tracer *t, double ms_by_kind[4], int64_t launches_b
 
 /* ---- denoiser: edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on the device, csrc/pt_denoise.hip -------------
  * The GPU counterpart of the OIDN step of apps/src/main.cpp:167-219 (colour + albedo in, state.output out).  Guide images come from a
- * G-buffer pass: per pixel the pixel-centre pinhole ray (no antialiasing jitter, no depth of field -- with DoF on, the guides are the
- * sharp pinhole view) through the same intersection as the path, giving hit flag, world position o + t*d, shading normal (bump-mapped
- * where the path's is), albedo (the apps-variant AOV's rule) and material / geom ids.  It is computed on the tracer's stream on the
- * first ptx_denoise after ptx_create or a ptx_set_camera that changed the camera, into buffers allocated on that first use.
+ * G-buffer pass through the same intersection as the path, giving per pixel hit flag, world position o + t*d, shading normal
+ * (bump-mapped where the path's is), albedo (the apps-variant AOV's rule) and material / geom ids.  Two modes (ptx_set_guide_samples):
+ *   pixel-centre guides (the default): one pixel-centre pinhole ray per pixel, no antialiasing jitter, no depth of field -- with DoF
+ *   on, the guides are the sharp pinhole view while the colour is not;
+ *   sampled guides (count = K >= 1): the average over the camera rays of iterations iter_first .. iter_first + K - 1 exactly as the
+ *   path kernels generate them, jitter and lens included (a camera ray is a pure function of iteration, pixel and trace depth), so
+ *   the guides are as soft as the colour they guide.  Of the H samples that hit: normal = sum n / H (NOT renormalised: a crease or a
+ *   blurred silhouette gives a shorter normal), position = sum (o + t*d) / H, t = sum t / H, ids = the first hit sample's, hit = 1;
+ *   albedo = sum albedo / K and coverage = H / K (coverage-weighted as the colour is: a miss deposits nothing).  H = 0: a miss, all
+ *   zeros.  The sums begin with the first hit sample and add in iteration order, fp32, no contraction, IEEE division: with
+ *   antialiasing = depth_of_field = 0 and K = 1 this is the pixel-centre record bit for bit.
+ * Either is computed on the tracer's stream on the first ptx_denoise* / ptx_read_gbuffer after ptx_create, after a ptx_set_camera that
+ * changed the camera or the trace depth (the rays' seed depends on it), or after a ptx_set_guide_samples that changed the mode, into
+ * buffers allocated on that first use.
  *
  * The filter, exactly (tests/atrous_ref.py restates it):
  *   c = rgb / spp per channel (mean radiance); demodulate: c / max(albedo, 1e-3) per channel on hit pixels.
@@ -316,6 +326,18 @@ int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4);   /*
 /* The G-buffer as the last ptx_denoise used it (computed now if stale): W*H*3 floats each of position, normal, albedo, W*H*2 int32
  * (material id, geom id), W*H floats of t and W*H bytes of hit flag; any pointer may be NULL.  Misses read as zeros. */
 int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1);
+/* count = 0 (the default): pixel-centre guides, today's behaviour exactly.  count >= 1: sampled guides over
+ * iterations iter_first .. iter_first+count-1.  Marks the G-buffer stale; the next denoise / read recomputes it.
+ * PTX_ERR_INVALID: iter_first < 1, count < 0, count > 4096 (the cap: the pass costs about count pixel-centre passes), a row-tile tracer
+ * (tile_world > 1).  count may exceed the spp of the denoise call: the guides are an independent estimate of the same expectation.
+ * While count > 0, ptx_denoise_temporal and ptx_denoise_variance / ptx_denoise_temporal_measured with a history handle return
+ * PTX_ERR_UNSUPPORTED: reprojection and history matching need one surface per pixel.  ptx_denoise, ptx_denoise_variance without a
+ * handle, ptx_denoise_measured and ptx_denoise_adaptive take the sampled guides as they take the others.  On an adaptive frame, whose
+ * tiles hold different sample counts, the albedo's coverage equals the colour's only in expectation (on a uniform frame with
+ * iter_first = 1 and count = spp they are the same rays). */
+int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count);
+int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count);
+int ptx_read_guide_coverage(ptx_tracer *t, float *coverage1);   /* W*H floats, H/K (pixel-centre guides: the hit flag); computed now if stale */
 /* The filter alone over caller-owned host buffers (W*H*3 floats; hit W*H bytes, != 0 = hit): rgb is mean radiance (spp = 1), out_rgb
  * receives the result.  alb3 may be NULL when p->demodulate is 0.  Runs on `device`, synchronously; PTX_ERR_NODEVICE without one. */
 int ptx_denoise_buffers(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, const float *pos3,

@@ -621,6 +621,10 @@ def load_library():
     L.ptx_device_denoised.restype, L.ptx_device_denoised.argtypes = vp, [vp]
     L.ptx_write_denoised_pbo_from_device.restype, L.ptx_write_denoised_pbo_from_device.argtypes = i, [vp, vp]
     L.ptx_read_gbuffer.restype, L.ptx_read_gbuffer.argtypes = i, [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ptx_set_guide_samples"):     # (absent from the older builds the A/B scripts load through PTX_AB_LIBRARY)
+        L.ptx_set_guide_samples.restype, L.ptx_set_guide_samples.argtypes = i, [vp, i, i]
+        L.ptx_get_guide_samples.restype, L.ptx_get_guide_samples.argtypes = i, [vp, C.POINTER(i), C.POINTER(i)]
+        L.ptx_read_guide_coverage.restype, L.ptx_read_guide_coverage.argtypes = i, [vp, vp]
     L.ptx_denoise_buffers.restype = i
     L.ptx_denoise_buffers.argtypes = [i, i, i, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
     L.ptx_default_temporal_params.argtypes = [C.POINTER(TemporalParams)]
@@ -1221,6 +1225,23 @@ class Tracer:
         ids, t, hit = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.float32), np.zeros((h, w), np.uint8)
         _check(self.lib.ptx_read_gbuffer(self.h, _ptr(pos), _ptr(nrm), _ptr(alb), _ptr(ids), _ptr(t), _ptr(hit)), "ptx_read_gbuffer")
         return dict(position=pos, normal=nrm, albedo=alb, material=ids[..., 0].copy(), geom=ids[..., 1].copy(), t=t, hit=hit != 0)
+
+    def set_guide_samples(self, count, iter_first=1):
+        """count >= 1: the denoiser's guides averaged over the camera rays of iterations iter_first .. iter_first + count - 1, with the
+        tracer's own antialiasing jitter and lens (ptx_set_guide_samples); 0: the pixel-centre guides, the default"""
+        _check(self.lib.ptx_set_guide_samples(self.h, int(iter_first), int(count)), "ptx_set_guide_samples")
+
+    def guide_samples(self):
+        """(count, iter_first) as set_guide_samples left them"""
+        first, count = C.c_int(0), C.c_int(0)
+        _check(self.lib.ptx_get_guide_samples(self.h, C.byref(first), C.byref(count)), "ptx_get_guide_samples")
+        return count.value, first.value
+
+    def guide_coverage(self):
+        """(H, W) float32: the share of the guide samples that hit a surface (pixel-centre guides: the hit flag)"""
+        out = np.zeros((self.height, self.width), np.float32)
+        _check(self.lib.ptx_read_guide_coverage(self.h, _ptr(out)), "ptx_read_guide_coverage")
+        return out
 
     def pbo(self, iteration):
         out = np.zeros((self.width * self.height, 4), np.uint8)

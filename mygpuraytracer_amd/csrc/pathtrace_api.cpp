@@ -201,6 +201,20 @@ bool &denoiseVariance() {
     return on;
 }
 
+int &guideSamples() {
+    static int k = 0;
+    return k;
+}
+
+// guideSamples() onto the tracer before a filter call: the camera rays of iterations 1 .. min(K, the iterations rendered)
+static void apply_guide_samples(const char *what, int rendered) {
+    static bool applied = false;      // (while the switch has never been on, the tracer's own setting is left alone)
+    const int k = guideSamples() > 0 ? std::min(guideSamples(), std::max(rendered, 1)) : 0;
+    if (k == 0 && !applied) return;
+    check(ptx_set_guide_samples(g_tracer, 1, k), what);
+    applied = k > 0;
+}
+
 ptx_variance_params &varianceParams() {
     if (!g_variance_params_init) { ptx_default_variance_params(&g_variance_params); g_variance_params_init = true; }
     return g_variance_params;
@@ -283,6 +297,7 @@ bool &adaptiveDenoise() {
 
 const float *adaptiveDenoisedFrame() {
     if (!adaptiveDenoise() || !g_tracer || !g_adaptive || !g_moments || g_adaptive_status.rounds < 1) return nullptr;
+    apply_guide_samples("adaptiveDenoisedFrame", (int)g_adaptive_status.samples_max);      // (the worst tile's count: the iterations rendered)
     check(ptx_denoise_adaptive(g_tracer, g_adaptive, g_moments, &denoiseParams(), &varianceParams(), 0), "adaptiveDenoisedFrame");
     g_adaptive_denoised.resize((size_t)g_moments_key[1] * g_moments_key[2] * 3);
     check(ptx_read_denoised(g_tracer, g_adaptive_denoised.data()), "adaptiveDenoisedFrame");
@@ -404,6 +419,7 @@ void GPUdenoise(bool keep_on_device) {
         fprintf(stderr, "GPUdenoise: denoiseMeasured() needs momentsBatch() > 0 and at least one batch\n");
         exit(EXIT_FAILURE);
     }
+    apply_guide_samples("GPUdenoise", g_last_iter);
     if (denoiseMeasured() && !denoiseTemporal()) {
         check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");
     } else if (denoiseTemporal()) {

@@ -270,6 +270,11 @@ ptx_temporal_params &temporalParams();                  // what it reprojects wi
 // the spatial estimate alone.
 bool &denoiseVariance();
 ptx_variance_params &varianceParams();                  // what it filters with (ptx_default_variance_params until changed)
+// Sampled guides (ptx_set_guide_samples): guideSamples() = K > 0 makes GPUdenoise -- plain, denoiseVariance() and denoiseMeasured() -- and
+// adaptiveDenoisedFrame() take their guides from the camera rays of iterations 1 .. min(K, iterations rendered), antialiasing jitter
+// and lens included, instead of the pixel-centre pinhole ray; 0, the default, is off.  Not with denoiseTemporal(): the call fails as
+// the C ABI's does (PTX_ERR_UNSUPPORTED).
+int &guideSamples();
 // Sample moments by batch means (ptx_moments_*): momentsBatch() = k > 0 makes pathtrace() add one batch to a module-level handle after
 // every k-th call since pathtraceInit (which resets it: a new tracer starts a new accumulation); 0, the default, is off.  The handle is
 // created on first use, recreated when the device or the resolution changes, and freed by GPUdenoiseRelease(); pathtraceMoments() hands

@@ -6,7 +6,8 @@
 // Device layout of the guide images, one record per pixel, pixelIndex = x + y*W (the frame's own order):
 //   nh[i]  = float4(shading normal xyz, hit ? 1 : 0)
 //   xt[i]  = float4(world position xyz, t)              (t is not read by the filter; ptx_read_gbuffer hands it out)
-//   alb[i] = float4(albedo rgb, 0)
+//   alb[i] = float4(albedo rgb, 0)                       (sampled guides: the fourth float is the coverage H / K; nothing reads it but
+//                                                         ptx_read_guide_coverage)
 // Misses are all zeros.  The filter's colour ping-pong buffers are float4(rgb, v) per pixel: v is 0 in the plain filter and the variance
 // of the pixel's luminance (v0 = V / n going in) in the variance-guided one.  Before that one runs, -1 in that float (a hit pixel's)
 // means "no estimate yet": pt_variance_spatial_enqueue replaces it.
@@ -137,6 +138,13 @@ hipError_t pt_variance_spatial_enqueue(hipStream_t st, int w, int h, const ptx_d
 hipError_t pt_atrous_enqueue(hipStream_t st, int w, int h, const float4 *nh, const float4 *xt, const float4 *alb, float4 *tmp0,
                              float4 *tmp1, float *out_rgb, const ptx_denoise_params &dp, const ptx_variance_params *vp = nullptr,
                              float *var_in = nullptr, float *var_out = nullptr);
+
+// The sampled guides (pt_guides.hip; ptx_set_guide_samples): the guide images above averaged over the camera rays of iterations
+// iter_first .. iter_first + count - 1 (count >= 1) with the tracer's antialiasing / depth-of-field options and trace depth, into the
+// same four arrays; alb[i].w receives the coverage H / count.  sc / cam: the tracer's scene and camera (pt_device.h).
+namespace ptd { struct DScene; struct DCamera; }
+hipError_t pt_guides_enqueue(hipStream_t st, const ptd::DScene &sc, const ptd::DCamera &cam, int traceDepth, int aa, int dof, int iter_first,
+                             int count, float4 *nh, float4 *xt, float4 *alb, int2 *ids);
 
 const char *pt_moments_params_problem(const ptx_moments_params &p);
 // One add on `st`: rgb = the accumulation buffer (W*H*3) holding `total` samples, k = total - the last add's; fresh: the state reads

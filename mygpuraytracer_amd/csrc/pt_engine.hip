@@ -354,6 +354,7 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     DevBuf<float4> d_gbuf, d_dn_tmp;
     DevBuf<float> d_dn_out;
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
+    int guide_first = 1, guide_count = 0;                // ptx_set_guide_samples: count 0 = k_gbuffer's pixel-centre guides, else k_guides over these iterations
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
     DevBuf<uint8_t> d_spec;                              // its device copy, on the first ptx_denoise_temporal
     DevBuf<float> d_var;                                 // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
@@ -1325,6 +1326,12 @@ static int ensure_gbuffer(ptx_tracer *t) {
     if (!t->d_gbuf) HIPCHECK(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
     const DScene sc = t->scene();
+    if (t->guide_count > 0) {                            // sampled guides (pt_guides.hip): the same arrays, the coverage in alb.w
+        HIPCHECK(pt_guides_enqueue(t->stream, sc, t->cam, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, t->guide_first, t->guide_count,
+                                   t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n)));
+        t->gbuf_valid = true;
+        return PTX_OK;
+    }
     hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, sc, t->cam, t->traceDepth,
                        t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n));
     HIPCHECK(hipGetLastError());
@@ -1333,6 +1340,38 @@ static int ensure_gbuffer(ptx_tracer *t) {
 }
 
 static_assert(sizeof(DCamera) == sizeof(ptx_camera), "camera layout");
+
+// ---- sampled guides (pt_guides.hip; definition in include/mi355x_pathtracer.h) ------------------------------------------------------
+static const int GUIDE_SAMPLES_MAX = 4096;
+int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count) {
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: null tracer");
+    if (iter_first < 1) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first must be >= 1 (iterations count from 1)");
+    if (count < 0) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: count must be >= 0 (0: the pixel-centre guides)");
+    if (count > GUIDE_SAMPLES_MAX)
+        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: count " + std::to_string(count) + " exceeds the cap of " +
+                                              std::to_string(GUIDE_SAMPLES_MAX) + " samples per pixel");
+    if (iter_first > INT32_MAX - GUIDE_SAMPLES_MAX)
+        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first + count would pass the largest iteration number");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (count == t->guide_count && (count == 0 || iter_first == t->guide_first)) return PTX_OK;      // (the same guides: nothing is stale)
+    t->guide_first = iter_first; t->guide_count = count;
+    t->gbuf_valid = false;
+    return PTX_OK;
+}
+
+int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count) {
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_get_guide_samples: null tracer");
+    if (iter_first) *iter_first = t->guide_first;
+    if (count) *count = t->guide_count;
+    return PTX_OK;
+}
+
+// What the entry points that carry a history say while sampled guides are on
+static int guides_refuse_history(const std::string &fn) {
+    return set_error(PTX_ERR_UNSUPPORTED, fn + ": sampled guides are on (ptx_set_guide_samples, count > 0); reprojection and history "
+                                               "matching need one surface per pixel -- set count 0 for the temporal path");
+}
 
 // What the three ptx_denoise* entry points share; `fn` is the entry point's name, for its messages.
 extern "C++" template <class P> static P params_or_default(const P *given, void (*defaults)(P *)) {
@@ -1424,6 +1463,7 @@ int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_param
     if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
     if (spp < 1) return bad_spp("ptx_denoise_temporal");
     if (!t || !h) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: null tracer or temporal handle");
+    if (t->guide_count > 0) return guides_refuse_history("ptx_denoise_temporal");
     if (const int rc = denoise_begin("ptx_denoise_temporal", t, h, false)) return rc;
     if (const int rc = temporal_step(t, h, tp, spp, false)) return rc;
     const int W = t->cam.resx, H = t->cam.resy;
@@ -1451,6 +1491,7 @@ int ptx_denoise_variance(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_param
         return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: with a temporal handle ptx_denoise_params.demodulate must be != 0 "
                                           "(the state's moments are in demodulated space)");
     if (!t) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: null tracer");
+    if (h && t->guide_count > 0) return guides_refuse_history("ptx_denoise_variance");
     if (const int rc = denoise_begin("ptx_denoise_variance", t, h, true)) return rc;
     const int W = t->cam.resx, H = t->cam.resy;
     const size_t n = (size_t)W * H;
@@ -1559,6 +1600,7 @@ int ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m
     if (!dp.demodulate)
         return set_error(PTX_ERR_INVALID, fn + ": ptx_denoise_params.demodulate must be != 0 (the state's moments are in demodulated space)");
     if (!t || !h || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, temporal handle or moments handle");
+    if (t->guide_count > 0) return guides_refuse_history(fn);
     if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on this moments handle yet");
     if (m->tiled) return set_error(PTX_ERR_INVALID, fn + ": " + TILED_HANDLE);      // (one spp, one B per frame)
     if (const int rc = moments_begin(fn, t, m)) return rc;
@@ -1744,6 +1786,21 @@ int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32
         if (t1) t1[i] = xt.w;
         if (hit1) hit1[i] = nh.w != 0.f ? 1 : 0;
     }
+    return PTX_OK;
+}
+
+int ptx_read_guide_coverage(ptx_tracer *t, float *coverage1) {
+    if (!t || !coverage1) return set_error(PTX_ERR_INVALID, "ptx_read_guide_coverage: null tracer or buffer");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_read_guide_coverage: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    HIPCHECK(hipSetDevice(t->device));
+    if (const int rc = ensure_gbuffer(t)) return rc;
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    // the fourth float of the albedo records; the pixel-centre guides write 0 there, their coverage is the hit flag: nh's fourth float
+    std::vector<float4> a(n);
+    HIPCHECK(hipMemcpyAsync(a.data(), t->d_gbuf + (t->guide_count > 0 ? 2 * n : 0), sizeof(float4) * n, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    for (size_t i = 0; i < n; i++) coverage1[i] = a[i].w;
     return PTX_OK;
 }
 
