@@ -600,6 +600,90 @@ float *ptx_adaptive_device_frame(ptx_adaptive *a); /* the resolved frame on the 
 int  ptx_denoise_adaptive(ptx_tracer *t, ptx_adaptive *a, ptx_moments *m, const ptx_denoise_params *dp, const ptx_variance_params *vp,
                           int min_batches);
 
+/* ---- display transform: automatic exposure, tone curve, sRGB transfer, 8-bit codes, csrc/pt_display.hip ------------------------------
+ * The accumulation buffer is scene-referred HDR; ptx_write_pbo (the reference's sendImageToPBO) shows it as clamp(int(mean * 255)),
+ * linear, exposure 1.  This stage is the same last step with an exposure, a tone curve and a transfer function, on the device, as one
+ * more opaque handle.  Nothing of ptx_write_pbo* changes.  Definition (tests/display_ref.py restates it in float64).
+ * Input: a W*H*3 fp32 frame rgb and a divisor `samples`.
+ *   1 Sanitise: c = rgb / samples (an IEEE fp32 division, as ptx_write_pbo does it); NaN -> 0; c clamped to [0, 65504] per channel
+ *     (OIDN's HDR_Y_MAX, the largest half float -- not its pos_max -- so that a block's sum cannot overflow).
+ *   2 Meter (meter == PTX_METER_BLOCKS; after OIDN's getAutoexposure, core/color.cpp:33-84, core/color.ispc:180-197): HK = (H + 8) / 16,
+ *     WK = (W + 8) / 16; block (i, j) covers rows i*H/HK .. (i+1)*H/HK and columns j*W/WK .. (j+1)*W/WK (integer arithmetic; at most
+ *     23 x 23 pixels); L_ij = the block's mean of l(c), l = 0.2126 r + 0.7152 g + 0.0722 b (this library's one luminance, not OIDN's
+ *     weights).  Over the blocks with L_ij > 1e-8: m = the mean of log2 L_ij, metered = key / 2^m.  No such block (a black frame,
+ *     W < 8 or H < 8: HK * WK = 0): metered = 1.  Block sums are fp32 in a fixed order, the sum over blocks is in double; no float
+ *     atomics: the same bits on every run.  A per-pixel histogram is deliberately not the meter: most pixels of a path-traced frame
+ *     at low sample counts are exactly zero, and its percentiles move by 10x between 1 and 16 spp where the block rule moves by 6 %.
+ *   3 Adaptation: the first metered frame after create / reset: applied = metered.  Later frames:
+ *     log2 applied += adapt * (log2 metered - log2 applied), in double, on the device; adapt in (0, 1], 1 = no inertia.
+ *   4 Exposure: E = applied * exposure (PTX_METER_BLOCKS) or E = exposure (PTX_METER_MANUAL: nothing is metered, the state is not
+ *     touched).  x = c * E in fp32.  The map reads `applied` from device memory: the host never waits for an exposure.
+ *   5 Tone: PTX_TONE_CLAMP y = x; PTX_TONE_REINHARD y = x (1 + L / white^2) / (1 + L), L = l(x); PTX_TONE_ACES per channel
+ *     y = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14) (Narkowicz's fit).  Then y is clamped to [0, 1].
+ *   6 Transfer: PTX_TRANSFER_LINEAR z = y; PTX_TRANSFER_SRGB z = 12.92 y for y <= 0.0031308, else 1.055 y^(1/2.4) - 0.055.
+ *   7 Quantise, alpha 0 as ptx_write_pbo: quantize == 0: (int)((double)z * 255.0), the reference's truncation; quantize == 1:
+ *     (int)(z * 255.f + 0.5f); with dither == 1 (read only when quantize == 1): (int)(z * 255.f + t[y & 7][x & 7]),
+ *     t = (2 B + 1) / 128 from the 8 x 8 Bayer matrix B (exact in fp32).  The code is the quantisation of exactly the fp32 z that
+ *     keep_float stores.
+ * meter MANUAL, exposure 1, tone CLAMP, transfer LINEAR, quantize 0 is by construction ptx_write_pbo, byte for byte.
+ * A handle serves one W x H on one device, across tracers and streams, like ptx_moments: each enqueueing call makes its stream wait
+ * for the handle's previous work and records an event after its own. */
+#define PTX_METER_MANUAL 0
+#define PTX_METER_BLOCKS 1
+#define PTX_TONE_CLAMP 0
+#define PTX_TONE_REINHARD 1
+#define PTX_TONE_ACES 2
+#define PTX_TRANSFER_LINEAR 0
+#define PTX_TRANSFER_SRGB 1
+#define PTX_DISPLAY_IMAGE 0        /* ptx_display_tracer: the accumulation buffer, divided by spp */
+#define PTX_DISPLAY_DENOISED 1     /* the last ptx_denoise* result, divisor 1 */
+typedef struct ptx_display ptx_display;            /* opaque: block luminances, exposure state, last result; one W x H on one device */
+typedef struct ptx_display_params {
+    int   meter;               /* PTX_METER_*; default PTX_METER_BLOCKS */
+    float exposure;            /* > 0: the whole exposure (MANUAL) or a factor on the metered one (BLOCKS); default 1 */
+    float key;                 /* > 0: the luminance the geometric mean is mapped to; default 0.18 */
+    float adapt;               /* in (0, 1]: the share of the way to the metered exposure taken per frame; default 1 */
+    int   tone;                /* PTX_TONE_*; default PTX_TONE_ACES */
+    float white;               /* > 0: Reinhard's white point; default 4 */
+    int   transfer;            /* PTX_TRANSFER_*; default PTX_TRANSFER_SRGB */
+    int   quantize;            /* 0 truncate (the reference's), 1 round; default 1 */
+    int   dither;              /* 0 / 1: ordered dither of the rounding quantiser; default 0 */
+    int   keep_float;          /* 0 / 1: keep z (W*H*3 floats) for ptx_display_read; default 0 */
+} ptx_display_params;
+typedef struct ptx_display_status {
+    float   metered, applied;  /* the last metered frame's exposure and the adapted one the map multiplied by (1, 1 before any) */
+    float   log2_mean;         /* m */
+    int     blocks_used, blocks_total;     /* blocks with L > 1e-8, HK * WK */
+    int64_t frames;            /* metered frames since create / reset */
+} ptx_display_status;
+void   ptx_default_display_params(ptx_display_params *p);
+size_t ptx_sizeof_display_params(void);
+size_t ptx_sizeof_display_status(void);
+int  ptx_display_create(int device, int width, int height, ptx_display **out);   /* PTX_ERR_NODEVICE without a device */
+void ptx_display_destroy(ptx_display *d);          /* NULL is a no-op; waits for its last use */
+int  ptx_display_reset(ptx_display *d);            /* forget the adapted exposure: the next metered frame jumps */
+/* Enqueues meter + map on t's stream, ordered after every iteration rendered so far and after the last ptx_denoise*, as
+ * ptx_write_pbo_device is.  source = PTX_DISPLAY_IMAGE: the accumulation buffer over spp (>= 1); PTX_DISPLAY_DENOISED: the denoised
+ * frame, divisor 1 (spp is not read), PTX_ERR_INVALID before the first denoise.  p NULL = defaults.  device_uchar4: W*H uchar4 on the
+ * tracer's device; NULL leaves the codes in the handle's own buffer for ptx_display_read.  The accumulation buffer, statistics and
+ * what later iterations compute are untouched.  Refused (PTX_ERR_INVALID, nothing enqueued): bad parameters, a handle of another
+ * device or size, tile_world > 1. */
+int  ptx_display_tracer(ptx_display *d, ptx_tracer *t, int source, int spp, const ptx_display_params *p, void *device_uchar4);
+/* The same for any W*H*3 float frame on the handle's device (ptx_adaptive_device_frame; ptx_multi_device_image after
+ * ptx_multi_assemble), on `stream` (a hipStream_t; NULL = the default stream): the caller orders the frame's producer before it on
+ * that stream.  Pointers that are not 16-byte aligned take a per-pixel form of the map; same results. */
+int  ptx_display_device(ptx_display *d, const float *device_rgb, float samples, const ptx_display_params *p, void *device_uchar4, void *stream);
+/* The same from a host frame through a staging buffer the handle owns; host_rgba (W*H*4 bytes) may be NULL; waits */
+int  ptx_display_host(ptx_display *d, const float *host_rgb, float samples, const ptx_display_params *p, uint8_t *host_rgba);
+/* last result; either may be NULL; rgb3 (W*H*3 floats of z) needs keep_float in the last call, rgba4 (W*H*4 bytes) that the last call
+ * left its codes in the handle's buffer (device_uchar4 NULL); waits */
+int  ptx_display_read(ptx_display *d, float *rgb3, uint8_t *rgba4);
+int  ptx_display_read_blocks(ptx_display *d, float *block_lum);                  /* HK*WK floats of the last metered frame; waits */
+int  ptx_display_get_status(ptx_display *d, ptx_display_status *out);            /* waits */
+/* Host only: the block grid of a w x h frame.  *hk, *wk = HK, WK (0, 0 when either is 0: no block); row_begin (HK + 1 entries) and
+ * col_begin (WK + 1 entries), NULLs allowed, receive where each block starts, the last entry being h / w. */
+int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin, int32_t *col_begin);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);

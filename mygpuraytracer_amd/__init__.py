@@ -20,6 +20,10 @@ from .api import (  # noqa: F401
     AdaptiveParams,
     AdaptiveStatus,
     Adaptive,
+    DisplayParams,
+    DisplayStatus,
+    Display,
+    default_display_params,
     Scene,
     Tracer,
     Temporal,
@@ -38,6 +42,6 @@ from .api import (  # noqa: F401
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
            "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "default_adaptive_params", "tile_pixels", "denoise_buffers",
            "denoise_buffers_variance", "load_library"]

@@ -377,6 +377,134 @@ class Adaptive:
         return rounds
 
 
+class DisplayParams(C.Structure):
+    """ptx_display_params: meter, exposure, tone curve, transfer and quantiser of the display transform (include/mi355x_pathtracer.h;
+    defaults from ptx_default_display_params)."""
+    _fields_ = [("meter", C.c_int), ("exposure", C.c_float), ("key", C.c_float), ("adapt", C.c_float), ("tone", C.c_int),
+                ("white", C.c_float), ("transfer", C.c_int), ("quantize", C.c_int), ("dither", C.c_int), ("keep_float", C.c_int)]
+
+
+class DisplayStatus(C.Structure):
+    """ptx_display_status (include/mi355x_pathtracer.h)."""
+    _fields_ = [("metered", C.c_float), ("applied", C.c_float), ("log2_mean", C.c_float), ("blocks_used", C.c_int),
+                ("blocks_total", C.c_int), ("frames", C.c_int64)]
+
+
+METER_MANUAL, METER_BLOCKS = 0, 1
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
+DISPLAY_IMAGE, DISPLAY_DENOISED = 0, 1
+_DISPLAY_NAMES = dict(meter=dict(manual=METER_MANUAL, blocks=METER_BLOCKS), tone=dict(clamp=TONE_CLAMP, reinhard=TONE_REINHARD, aces=TONE_ACES),
+                      transfer=dict(linear=TRANSFER_LINEAR, srgb=TRANSFER_SRGB))
+_DISPLAY_SOURCES = dict(image=DISPLAY_IMAGE, denoised=DISPLAY_DENOISED)
+
+
+def default_display_params(**kw):
+    """ptx_default_display_params with keyword overrides (meter, exposure, key, adapt, tone, white, transfer, quantize, dither,
+    keep_float); meter, tone and transfer take the PTX_* numbers or their names ("manual" / "blocks", "clamp" / "reinhard" / "aces",
+    "linear" / "srgb")."""
+    kw = {k: _DISPLAY_NAMES[k][v] if k in _DISPLAY_NAMES and isinstance(v, str) else v for k, v in kw.items()}
+    return _default_params(DisplayParams, "ptx_default_display_params", ("meter", "tone", "transfer", "quantize", "dither", "keep_float"), **kw)
+
+
+def debug_display_blocks(width, height):
+    """ptx_debug_display_blocks: (row_begin, col_begin) of the meter's block grid, HK + 1 and WK + 1 int32 (empty when there is no block)"""
+    hk, wk = C.c_int(), C.c_int()
+    rows, cols = np.zeros((int(height) + 8) // 16 + 1, np.int32), np.zeros((int(width) + 8) // 16 + 1, np.int32)
+    _check(load_library().ptx_debug_display_blocks(int(width), int(height), C.byref(hk), C.byref(wk), _ptr(rows), _ptr(cols)),
+           "ptx_debug_display_blocks")
+    if hk.value == 0:
+        return rows[:0], cols[:0]
+    return rows[:hk.value + 1], cols[:wk.value + 1]
+
+
+class Display:
+    """The display transform on one device (opaque ptx_display): automatic exposure from block luminances, tone curve, sRGB transfer,
+    8-bit codes.  tracer(T, spp) maps a tracer's frame, device(ptr, samples) any W*H*3 float frame on the device, host(rgb) a numpy
+    frame; params are ptx_display_params' fields as keywords.  The adapted exposure lives in the handle: reset() forgets it."""
+
+    def __init__(self, width, height, device=0):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_display_create(int(device), int(width), int(height), C.byref(h)), "ptx_display_create")
+        self.h = h
+        self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ptx_display_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """forget the adapted exposure: the next metered frame's applied exposure is its metered one"""
+        _check(self.lib.ptx_display_reset(self.h), "ptx_display_reset")
+
+    def tracer(self, tracer, spp, source="image", pbo=None, **params):
+        """the tracer's accumulation buffer over spp (source "image") or its last denoised frame (source "denoised"), enqueued on the
+        tracer's stream; pbo: a device pointer to W*H uchar4, None = the handle's own buffer (read())"""
+        p = default_display_params(**params)
+        src = _DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        _check(self.lib.ptx_display_tracer(self.h, tracer.h, src, int(spp), C.byref(p), vp(pbo) if pbo else None), "ptx_display_tracer")
+
+    def device(self, ptr, samples, stream=0, pbo=None, **params):
+        """a W*H*3 float frame at device pointer `ptr`, divided by `samples`, enqueued on `stream` (a hipStream_t as an integer)"""
+        p = default_display_params(**params)
+        _check(self.lib.ptx_display_device(self.h, vp(ptr), float(samples), C.byref(p), vp(pbo) if pbo else None, vp(stream) if stream else None),
+               "ptx_display_device")
+
+    def host(self, rgb, samples=1, **params):
+        """a host frame (H, W, 3) or (W*H, 3); returns the codes (H, W, 4) uint8"""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.size != self.width * self.height * 3:
+            raise ValueError("Display.host: the frame has %d floats, the handle's size needs %d" % (rgb.size, self.width * self.height * 3))
+        p = default_display_params(**params)
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        _check(self.lib.ptx_display_host(self.h, _ptr(rgb), float(samples), C.byref(p), _ptr(out)), "ptx_display_host")
+        return out
+
+    def read(self, float_frame=False):
+        """the last result's codes (H, W, 4) uint8; with float_frame=True (the last call had keep_float=1) a pair (z (H, W, 3) float32, codes)"""
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        if not float_frame:
+            _check(self.lib.ptx_display_read(self.h, None, _ptr(out)), "ptx_display_read")
+            return out
+        z = np.zeros((self.height, self.width, 3), np.float32)
+        _check(self.lib.ptx_display_read(self.h, _ptr(z), _ptr(out)), "ptx_display_read")
+        return z, out
+
+    def read_float(self):
+        """z (H, W, 3) float32 of the last call (it had keep_float=1), wherever that call left its codes"""
+        z = np.zeros((self.height, self.width, 3), np.float32)
+        _check(self.lib.ptx_display_read(self.h, _ptr(z), None), "ptx_display_read")
+        return z
+
+    def blocks(self):
+        """(HK, WK) float32: the block luminances of the last metered frame"""
+        hk, wk = (self.height + 8) // 16, (self.width + 8) // 16
+        out = np.zeros((hk, wk) if hk and wk else (0, 0), np.float32)
+        scratch = out if out.size else np.zeros(1, np.float32)
+        _check(self.lib.ptx_display_read_blocks(self.h, _ptr(scratch)), "ptx_display_read_blocks")
+        return out
+
+    def status(self):
+        """ptx_display_get_status as a dict"""
+        out = DisplayStatus()
+        _check(self.lib.ptx_display_get_status(self.h, C.byref(out)), "ptx_display_get_status")
+        return {k: getattr(out, k) for k, _ in DisplayStatus._fields_}
+
+
 def _frame_arrays(fn, rgb, albedo, normal, position, hit):
     """one (H, W) frame as the ptx_denoise_buffers* entry points take it: h, w, rgb (H, W, 3) float32, albedo (or None) / normal /
     position (H*W, 3) float32, hit (H*W) uint8"""
@@ -678,6 +806,21 @@ def load_library():
     L.ptx_adaptive_device_frame.restype, L.ptx_adaptive_device_frame.argtypes = vp, [vp]
     L.ptx_denoise_adaptive.restype = i
     L.ptx_denoise_adaptive.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), C.POINTER(VarianceParams), i]
+    L.ptx_sizeof_display_params.restype = L.ptx_sizeof_display_status.restype = C.c_size_t
+    if L.ptx_sizeof_display_params() != C.sizeof(DisplayParams) or L.ptx_sizeof_display_status() != C.sizeof(DisplayStatus):
+        raise PathTracerError("%s has display structs of %d and %d B, this module expects %d and %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_display_params(), L.ptx_sizeof_display_status(), C.sizeof(DisplayParams), C.sizeof(DisplayStatus)))
+    L.ptx_default_display_params.argtypes = [C.POINTER(DisplayParams)]
+    L.ptx_display_create.restype, L.ptx_display_create.argtypes = i, [i, i, i, C.POINTER(vp)]
+    L.ptx_display_destroy.restype, L.ptx_display_destroy.argtypes = None, [vp]
+    L.ptx_display_reset.restype, L.ptx_display_reset.argtypes = i, [vp]
+    L.ptx_display_tracer.restype, L.ptx_display_tracer.argtypes = i, [vp, vp, i, i, C.POINTER(DisplayParams), vp]
+    L.ptx_display_device.restype, L.ptx_display_device.argtypes = i, [vp, vp, f, C.POINTER(DisplayParams), vp, vp]
+    L.ptx_display_host.restype, L.ptx_display_host.argtypes = i, [vp, vp, f, C.POINTER(DisplayParams), vp]
+    L.ptx_display_read.restype, L.ptx_display_read.argtypes = i, [vp, vp, vp]
+    L.ptx_display_read_blocks.restype, L.ptx_display_read_blocks.argtypes = i, [vp, vp]
+    L.ptx_display_get_status.restype, L.ptx_display_get_status.argtypes = i, [vp, C.POINTER(DisplayStatus)]
+    L.ptx_debug_display_blocks.restype, L.ptx_debug_display_blocks.argtypes = i, [i, i, C.POINTER(i), C.POINTER(i), vp, vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -944,6 +1087,10 @@ class MultiTracer:
 
     def assemble(self):
         _check(self.lib.ptx_multi_assemble(self.h), "ptx_multi_assemble")
+
+    def device_image_ptr(self):
+        """ptx_multi_device_image: the assembled frame on the first device, W*H*3 floats (current after assemble())"""
+        return self.lib.ptx_multi_device_image(self.h)
 
     def read_image(self):
         out = np.zeros((self.width * self.height, 3), np.float32)

@@ -42,6 +42,15 @@
 //                                                                      the filter's guides averaged over the camera rays of iterations
 //                                                                      1 .. min(K, iterations), jitter and lens included, instead of the
 //                                                                      pixel-centre pinhole ray: ptx_set_guide_samples.  Not with --temporal.)
+//                                  [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]   (the display
+//                                                                      transform, ptx_display_*: when any is given, every .png and
+//                                                                      .denoised.png takes its bytes from it -- automatic exposure from block
+//                                                                      luminances (auto, the default once a flag is given) or a fixed scale, a
+//                                                                      tone curve (aces unless named), the sRGB transfer with --srgb, rounding
+//                                                                      to the nearest code, with an ordered dither with --dither; A in (0, 1] is the share of the way
+//                                                                      to the metered exposure taken per frame with --frames.  One line per file
+//                                                                      with the metered and applied exposure.  .pfm, .hdr and checkpoints are
+//                                                                      untouched; without these flags every file is what it was.)
 //
 // RES / DEPTH / ITERATIONS overrides and the four switches are what the reference can only change by editing the
 // scene file or the #defines of src/pathtrace.cu:36-40.
@@ -63,6 +72,45 @@ static std::string currentTimeString() {          // src/preview.cpp:13-19
     char buf[sizeof "0000-00-00_00-00-00z"];
     strftime(buf, sizeof buf, "%Y-%m-%d_%H-%M-%Sz", gmtime(&now));
     return std::string(buf);
+}
+
+// The display transform of the --tonemap / --exposure / --srgb / --dither / --adapt flags: a handle for the frames and one for the
+// denoised frames (each adapts to its own sequence), created on first use.
+struct DisplayOut {
+    bool on = false;
+    int device = 0;
+    ptx_display_params params;
+    ptx_display *handle[2] = {nullptr, nullptr};
+    std::vector<uint8_t> rgba;
+    // rgb8 as to_rgb8_mirrored lays it out, from the display stage's codes for sum_rgb / samples; false (message printed) on failure
+    bool rgb8_mirrored(int which, int w, int h, const float *sum_rgb, float samples, const std::string &file, std::vector<uint8_t> &out) {
+        if (!handle[which] && ptx_display_create(device, w, h, &handle[which]) != PTX_OK) { fprintf(stderr, "display failed: %s\n", ptx_last_error()); return false; }
+        rgba.resize((size_t)w * h * 4);
+        ptx_display_status st;
+        if (ptx_display_host(handle[which], sum_rgb, samples, &params, rgba.data()) != PTX_OK || ptx_display_get_status(handle[which], &st) != PTX_OK) {
+            fprintf(stderr, "display failed: %s\n", ptx_last_error());
+            return false;
+        }
+        out.resize((size_t)w * h * 3);
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++)
+                for (int k = 0; k < 3; k++) out[((size_t)(w - 1 - x) + (size_t)y * w) * 3 + k] = rgba[((size_t)x + (size_t)y * w) * 4 + k];
+        if (params.meter == PTX_METER_BLOCKS)
+            printf("display %s: metered exposure %.6g, applied %.6g (x %g), %d of %d blocks\n", file.c_str(), (double)st.metered, (double)st.applied,
+                   (double)params.exposure, (int)st.blocks_used, (int)st.blocks_total);
+        else
+            printf("display %s: manual exposure %.6g (nothing metered)\n", file.c_str(), (double)params.exposure);
+        return true;
+    }
+    void release() { ptx_display_destroy(handle[0]); ptx_display_destroy(handle[1]); handle[0] = handle[1] = nullptr; }
+};
+static DisplayOut g_display;
+
+// a frame's 8-bit pixels as the file takes them: the reference's preview rule, or the display stage when its flags are given
+static bool frame_rgb8(int which, int w, int h, const float *sum_rgb, float samples, const std::string &file, std::vector<uint8_t> &out) {
+    if (g_display.on) return g_display.rgb8_mirrored(which, w, h, sum_rgb, samples, file, out);
+    ptimg::to_rgb8_mirrored(w, h, sum_rgb, samples, out);
+    return true;
 }
 
 // --frames: the camera-change loop of apps/src/main.cpp:221-271 over an orbit, one tracer per frame, the denoiser's history (with
@@ -89,7 +137,7 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
         char tag[16];
         snprintf(tag, sizeof tag, ".f%03d", f);
         const std::string name = prefix + tag;
-        ptimg::to_rgb8_mirrored(width, height, &scene->state.image[0].x, (float)n, rgb8);
+        if (!frame_rgb8(0, width, height, &scene->state.image[0].x, (float)n, name + ".png", rgb8)) return 1;
         if (!ptimg::write_png_rgb8(name + ".png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.png\n", name.c_str()); return 1; }
         printf("Saved %s.png.\n", name.c_str());
         if (pfm) { ptimg::write_pfm(name + ".pfm", width, height, &scene->state.image[0].x, (float)n); printf("Saved %s.pfm.\n", name.c_str()); }
@@ -100,12 +148,13 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
                        measure_every);
             denoiseMeasured() = nbatches > 0;    // (no batch at all: there is no moments handle to hand over)
             GPUdenoise();                        // state.output = the denoised mean radiance
-            ptimg::to_rgb8_mirrored(width, height, &scene->state.output[0].x, 1.0f, rgb8);
+            if (!frame_rgb8(1, width, height, &scene->state.output[0].x, 1.0f, name + ".denoised.png", rgb8)) return 1;
             if (!ptimg::write_png_rgb8(name + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", name.c_str()); return 1; }
             printf("Saved %s.denoised.png.\n", name.c_str());
             if (pfm) { ptimg::write_pfm(name + ".denoised.pfm", width, height, &scene->state.output[0].x, 1.0f); printf("Saved %s.denoised.pfm.\n", name.c_str()); }
         }
     }
+    g_display.release();
     GPUdenoiseRelease();
     pathtraceFree();
     delete scene;
@@ -115,7 +164,7 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2 || !strcmp(argv[1], "--help")) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K] [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]\n", argv[0]);
         return argc < 2;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
@@ -127,6 +176,9 @@ int main(int argc, char **argv) {
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
     int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0;
     ptx_options &opt = pathtraceOptions();
+    ptx_display_params &disp = g_display.params;
+    ptx_default_display_params(&disp);
+    disp.transfer = PTX_TRANSFER_LINEAR;         // the library's defaults (metered exposure, ACES, rounding) but for the transfer: --srgb names it
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "%s needs %d value(s)\n", a.c_str(), n); exit(1); } };
@@ -161,9 +213,38 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-denoise") adaptive_denoise = true;
         else if (a == "--measured") measured = true;
         else if (a == "--guide-samples") { need(1); guide_samples = atoi(argv[++i]); if (guide_samples < 1) { fprintf(stderr, "--guide-samples needs K >= 1\n"); return 1; } }
+        else if (a == "--tonemap") {
+            need(1);
+            const std::string v = argv[++i];
+            if (v == "clamp") disp.tone = PTX_TONE_CLAMP;
+            else if (v == "reinhard") disp.tone = PTX_TONE_REINHARD;
+            else if (v == "aces") disp.tone = PTX_TONE_ACES;
+            else { fprintf(stderr, "--tonemap needs clamp, reinhard or aces\n"); return 1; }
+            g_display.on = true;
+        }
+        else if (a == "--exposure") {
+            need(1);
+            const std::string v = argv[++i];
+            if (v == "auto") disp.meter = PTX_METER_BLOCKS;
+            else {
+                disp.meter = PTX_METER_MANUAL;
+                disp.exposure = (float)atof(v.c_str());
+                if (!(disp.exposure > 0.f)) { fprintf(stderr, "--exposure needs auto or a scale > 0\n"); return 1; }
+            }
+            g_display.on = true;
+        }
+        else if (a == "--srgb") { disp.transfer = PTX_TRANSFER_SRGB; g_display.on = true; }
+        else if (a == "--dither") { disp.dither = 1; g_display.on = true; }
+        else if (a == "--adapt") {
+            need(1);
+            disp.adapt = (float)atof(argv[++i]);
+            if (!(disp.adapt > 0.f) || disp.adapt > 1.f) { fprintf(stderr, "--adapt needs A in (0, 1]\n"); return 1; }
+            g_display.on = true;
+        }
         else if (a == "--measure-every") { need(1); measure_every = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
     }
+    g_display.device = opt.device < 0 ? 0 : opt.device;
     const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of measure_every iterations, a ptx_moments_add after each
     if (measured && !denoise) { fprintf(stderr, "--measured needs --denoise\n"); return 1; }
     if (measure_every < 1) { fprintf(stderr, "--measure-every needs K >= 1\n"); return 1; }
@@ -289,7 +370,7 @@ int main(int argc, char **argv) {
         memcpy(&scene->state.image[0].x, frame, sizeof(float) * 3 * (size_t)width * height);
         divisor = 1.0f;
     }
-    ptimg::to_rgb8_mirrored(width, height, &scene->state.image[0].x, divisor, rgb8);
+    if (!frame_rgb8(0, width, height, &scene->state.image[0].x, divisor, ss.str() + ".png", rgb8)) return 1;
     if (!ptimg::write_png_rgb8(ss.str() + ".png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.png\n", ss.str().c_str()); return 1; }
     printf("Saved %s.png.\n", ss.str().c_str());
     if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, divisor); printf("Saved %s.pfm.\n", ss.str().c_str()); }
@@ -299,7 +380,7 @@ int main(int argc, char **argv) {
         const int rc = measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
                      : variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);
         if (rc != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
-        ptimg::to_rgb8_mirrored(width, height, den.data(), 1.0f, rgb8);
+        if (!frame_rgb8(1, width, height, den.data(), 1.0f, ss.str() + ".denoised.png", rgb8)) return 1;
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());
         if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den.data(), 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
@@ -307,7 +388,7 @@ int main(int argc, char **argv) {
     if (adaptive_denoise) {                     // ptx_denoise_adaptive on the frame just saved: mean radiance, so divided by 1
         const float *den = adaptiveDenoisedFrame();
         if (!den) { fprintf(stderr, "--adaptive-denoise: no round was rendered\n"); return 1; }
-        ptimg::to_rgb8_mirrored(width, height, den, 1.0f, rgb8);
+        if (!frame_rgb8(1, width, height, den, 1.0f, ss.str() + ".denoised.png", rgb8)) return 1;
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());
         if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den, 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
@@ -318,6 +399,7 @@ int main(int argc, char **argv) {
         if (!ptimg::write_hdr(ss.str() + ".hdr", width, height, mean.data())) { fprintf(stderr, "cannot write %s.hdr\n", ss.str().c_str()); return 1; }
         printf("Saved %s.hdr.\n", ss.str().c_str());
     }
+    g_display.release();
     GPUdenoiseRelease();
     pathtraceFree();
     delete scene;

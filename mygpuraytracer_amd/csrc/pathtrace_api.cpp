@@ -36,6 +36,10 @@ ptx_adaptive *g_adaptive = nullptr;  // pathtrace()'s adaptive sampling with ada
 ptx_adaptive_status g_adaptive_status = {};
 std::vector<float> g_adaptive_frame; // adaptiveFrame()'s host copy
 std::vector<float> g_adaptive_denoised;      // adaptiveDenoisedFrame()'s
+ptx_display *g_display = nullptr;    // the preview's display transform with displayTransform() on: created on first use
+int g_display_key[3] = {0, 0, 0};    // its device, width, height
+ptx_display_status g_display_status = {};
+std::vector<uint8_t> g_display_codes;        // sendToGPU's codes of a host frame on their way to the pbo
 int g_calls = 0;                     // pathtrace() calls since pathtraceInit
 
 void check(int rc, const char *what) {
@@ -247,7 +251,47 @@ ptx_adaptive_params &adaptiveParams() {
 ptx_adaptive *pathtraceAdaptive() { return g_adaptive; }
 const ptx_adaptive_status &adaptiveStatus() { return g_adaptive_status; }
 
+bool &displayTransform() {
+    static bool on = false;
+    return on;
+}
+
+ptx_display_params &displayParams() {
+    static ptx_display_params p;
+    static bool init = false;
+    if (!init) { ptx_default_display_params(&p); init = true; }
+    return p;
+}
+
+const ptx_display_status &displayStatus() {
+    g_display_status = ptx_display_status();
+    g_display_status.metered = g_display_status.applied = 1.f;
+    if (g_display) check(ptx_display_get_status(g_display, &g_display_status), "displayStatus");
+    return g_display_status;
+}
+
+// the module-level display handle for the current device and resolution
+static void display_handle(const char *what) {
+    if (g_multi) { fprintf(stderr, "%s: the display transform runs on one device; pathtraceDevices() names several\n", what); exit(EXIT_FAILURE); }
+    const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+    const int key[3] = {g_device, w, h};
+    if (g_display && memcmp(key, g_display_key, sizeof key) != 0) { ptx_display_destroy(g_display); g_display = nullptr; }
+    if (!g_display) {
+        check(ptx_display_create(g_device, w, h, &g_display), what);
+        memcpy(g_display_key, key, sizeof key);
+    }
+}
+
+// pathtrace()'s preview: the reference's rule, or the display stage on the same buffer
+static void write_preview(int iter, void *pbo) {
+    if (!displayTransform() || !pbo) { check(ptx_write_pbo_device(g_tracer, iter, pbo), "sendImageToPBO"); return; }
+    display_handle("pathtrace");
+    check(ptx_display_tracer(g_display, g_tracer, PTX_DISPLAY_IMAGE, iter, &displayParams(), pbo), "pathtrace display");
+}
+
 void GPUdenoiseRelease() {
+    ptx_display_destroy(g_display);
+    g_display = nullptr;
     ptx_temporal_destroy(g_temporal);
     g_temporal = nullptr;
     ptx_moments_destroy(g_moments);
@@ -378,7 +422,7 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
         check(ptx_multi_set_camera(g_multi, hst_scene->state.camera.c_abi(), hst_scene->state.traceDepth), "pathtrace camera");
         check(ptx_multi_iterate(g_multi, iter), "pathtrace");
         check(ptx_multi_read_image(g_multi, &hst_scene->state.image[0].x), "image readback");      // assemble + :555-556
-        if (!apps) check(ptx_write_pbo_device(g_tracer, iter, pbo), "sendImageToPBO");             // from the assembled frame
+        if (!apps) write_preview(iter, pbo);                                                       // from the assembled frame
         // the AOV is written by iteration 1 alone (apps/src/pathtrace.cu:412-462): merged from the devices once, when it is new,
         // not n full-frame reads and a host merge per call
         if (apps && (iter == 1 || !g_albedo_read)) {
@@ -393,7 +437,7 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
     check(ptx_iterate(g_tracer, iter), "pathtrace");
     // apps/src builds with AI_DENOISE: no preview from here (sendToGPU shows the denoised frame), the albedo AOV comes back
     // with the image (apps/src/pathtrace.cu:658-669)
-    if (!apps) check(ptx_write_pbo_device(g_tracer, iter, pbo), "sendImageToPBO");
+    if (!apps) write_preview(iter, pbo);
     check(ptx_read_image(g_tracer, &hst_scene->state.image[0].x), "image readback");     // :555-556
     if (apps) check(ptx_read_albedo(g_tracer, &hst_scene->state.albedo[0].x), "albedo readback");
     moments_step(iter);
@@ -403,6 +447,22 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
 void mi355x::sendToGPU_raw(void *pbo, int iter) {
     (void)iter;                  // passed to the kernel but unused there as well (apps/src/pathtrace.cu:96-116)
     if (!g_tracer || !hst_scene) { fprintf(stderr, "sendToGPU called before pathtraceInit\n"); exit(EXIT_FAILURE); }
+    if (displayTransform() && pbo) {
+        display_handle("sendToGPU");
+        if (g_output_on_device) {
+            check(ptx_display_tracer(g_display, g_tracer, PTX_DISPLAY_DENOISED, 1, &displayParams(), pbo), "sendToGPU display");
+            check(ptx_synchronize(g_tracer), "sendToGPU");
+            return;
+        }
+        // a host frame: through the handle's staging buffer, then the codes into the pbo
+        g_display_codes.resize(hst_scene->state.output.size() * 4);
+        check(ptx_display_host(g_display, &hst_scene->state.output[0].x, 1.f, &displayParams(), g_display_codes.data()), "sendToGPU display");
+        if (hipMemcpy(pbo, g_display_codes.data(), g_display_codes.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            fprintf(stderr, "mi355x pathtracer error (sendToGPU display): the codes could not be copied into the pbo\n");
+            exit(EXIT_FAILURE);
+        }
+        return;
+    }
     if (g_output_on_device) {
         check(ptx_write_denoised_pbo_from_device(g_tracer, pbo), "sendToGPU");
         check(ptx_synchronize(g_tracer), "sendToGPU");

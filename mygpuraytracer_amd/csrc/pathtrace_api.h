@@ -308,6 +308,16 @@ bool &adaptiveDenoise();
 const float *adaptiveDenoisedFrame();
 // The same round by hand, for a caller that renders through pathtraceHandle(): the last k iterations were rendered under the current mask.
 void pathtraceAdaptiveStep(int k);
+// Display transform (ptx_display_*): displayTransform() on sends the preview pathtrace(pbo, ...) writes and the frame sendToGPU writes
+// through the display stage -- automatic exposure from block luminances, tone curve, sRGB transfer, rounding -- with displayParams()
+// (ptx_default_display_params until changed) in place of the reference's clamp(int(mean * 255)).  The module-level handle is created
+// on first use, recreated when the device or the resolution changes and freed by GPUdenoiseRelease(); pathtraceInit does NOT reset it:
+// with displayParams().adapt < 1 a camera change adapts, it does not jump.  displayStatus() is the last metered frame's (it waits).
+// A NULL pbo writes nothing and meters nothing, as before.  Off by default: the calls made are then exactly those above.  One device
+// only: with several pathtraceDevices() it prints an error and exits.
+bool &displayTransform();
+ptx_display_params &displayParams();
+const ptx_display_status &displayStatus();
 void GPUdenoiseRelease();
 
 namespace mi355x {

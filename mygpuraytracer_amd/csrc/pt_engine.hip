@@ -23,6 +23,7 @@
 #include "pt_plan.h"
 #include "pt_denoise.h"
 #include "pt_adaptive.h"
+#include "pt_display.h"
 
 namespace {
 
@@ -1762,6 +1763,30 @@ int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4) {
     hipLaunchKernelGGL(k_pbo, dim3((n + 255) / 256), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, n, 1, t->d_dn_out);   // iter = 1: no /iter
     HIPCHECK(hipGetLastError());
     return PTX_OK;
+}
+
+// ---- display transform (pt_display.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------
+// The checks of moments_begin on a display handle, then meter + map on the tracer's stream, where every gather and the denoiser run.
+int ptx_display_tracer(ptx_display *d, ptx_tracer *t, int source, int spp, const ptx_display_params *params, void *device_uchar4) {
+    ptx_display_params p = params_or_default(params, ptx_default_display_params);
+    if (source != PTX_DISPLAY_IMAGE && source != PTX_DISPLAY_DENOISED)
+        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: source must be PTX_DISPLAY_IMAGE or PTX_DISPLAY_DENOISED");
+    const float samples = source == PTX_DISPLAY_IMAGE ? (float)spp : 1.f;
+    if (source == PTX_DISPLAY_IMAGE && spp < 1) return bad_spp("ptx_display_tracer");
+    if (const char *why = pt_display_params_problem(p, samples)) return set_error(PTX_ERR_INVALID, why);
+    if (!d || !t) return set_error(PTX_ERR_INVALID, "ptx_display_tracer: null display handle or tracer");
+    if (t->tm.tile_world > 1)
+        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (d->device != t->device)
+        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: the display handle was created on device " + std::to_string(d->device) +
+                                              ", the tracer runs on device " + std::to_string(t->device));
+    if (d->w != t->cam.resx || d->h != t->cam.resy)
+        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: the display handle's size " + std::to_string(d->w) + " x " + std::to_string(d->h) +
+                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
+    if (source == PTX_DISPLAY_DENOISED && !t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_display_tracer: no ptx_denoise on this tracer yet");
+    HIPCHECK(hipSetDevice(t->device));
+    return pt_display_enqueue(d, t->stream, source == PTX_DISPLAY_IMAGE ? (const float *)t->d_image : (const float *)t->d_dn_out, samples, p,
+                              device_uchar4);
 }
 
 int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1) {
