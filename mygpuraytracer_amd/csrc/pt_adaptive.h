@@ -1,6 +1,6 @@
 // pt_adaptive.h -- internal interface between the adaptive-sampling handle (pt_adaptive.hip: its state, its kernels, create / reset /
-// read) and the tracer (pt_engine.hip: ptx_adaptive_add / _select / _resolve, which need the tracer's accumulation buffer, stream and
-// tile mask).  Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
+// read) and the tracer (pt_post.hip: ptx_adaptive_add / _select / _resolve and ptx_denoise_adaptive, which need the tracer's
+// accumulation buffer, stream and tile mask; the mask itself is set by pt_engine.hip).  Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
 //
 // State per tile of ptx_tile_pixels() pixels, tile = (y * W + x) / ptx_tile_pixels():
 //   samples[tile] int32  iterations its pixels hold        batches[tile] int32  adds it took part in

@@ -1,6 +1,6 @@
-// pt_denoise.h -- internal interface between the tracer (pt_engine.hip: G-buffer pass, ptx_denoise / ptx_denoise_temporal /
-// ptx_denoise_variance / ptx_denoise_measured / ptx_denoise_temporal_measured, ptx_moments_add), the a-trous filter with its variance
-// guidance (pt_denoise.hip), the temporal reprojection (pt_temporal.hip) and the batch-means moments (pt_moments.hip).
+// pt_denoise.h -- internal interface between the tracer (pt_engine.hip: the G-buffer pass; pt_post.hip: the six ptx_denoise* entry
+// points and ptx_moments_add), the a-trous filter with its variance guidance (pt_denoise.hip), the temporal reprojection
+// (pt_temporal.hip) and the batch-means moments (pt_moments.hip).
 // Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definitions.
 //
 // Device layout of the guide images, one record per pixel, pixelIndex = x + y*W (the frame's own order):
@@ -109,7 +109,7 @@ __device__ __forceinline__ float quad_form(float g0, float g1, float g2, const f
 }
 
 // What pt_denoise.hip and pt_temporal.hip share: the pixel kernels' workgroup of 64 x 4 pixels (a wave is one 64-pixel row segment)
-// and its grid, the ptx_last_error of a failed call, and the checked HIP call of their entry points.
+// and its grid; and, with every unit but pt_engine.hip, the ptx_last_error of a failed call and the checked HIP call of their entry points.
 constexpr int PT_BX = 64, PT_BY = 4;
 inline dim3 pt_pixel_grid(int w, int h) { return dim3((unsigned)((w + PT_BX - 1) / PT_BX), (unsigned)((h + PT_BY - 1) / PT_BY)); }
 extern "C" void ptx_internal_set_error(const char *msg);

@@ -1,5 +1,5 @@
 // pt_display.h -- internal interface of the display transform (pt_display.hip: ptx_display_* of include/mi355x_pathtracer.h) towards
-// the tracer (pt_engine.hip: ptx_display_tracer, which needs the tracer's accumulation buffer, denoised frame and stream).
+// the tracer (pt_post.hip: ptx_display_tracer, which needs the tracer's accumulation buffer, denoised frame and stream).
 // Not part of the C ABI; include/mi355x_pathtracer.h has the public side and the definition of the rule.
 //
 // Device state of a handle:

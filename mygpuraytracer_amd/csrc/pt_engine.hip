@@ -1,7 +1,9 @@
-// pt_engine.hip -- the host unit of the MI355X (gfx950) path-tracing engine behind include/mi355x_pathtracer.h: the ptx_tracer struct, scene
-// upload, buffers, every ptx_* entry point that needs a device, and the kernels that are the same at every arithmetic
-// level (debug capture, cache replay, gather, statistics, preview, G-buffer, k_kat_fast_exact, k_hold).  Scene preparation: pt_scene.hip.
+// pt_engine.hip -- the host unit of the MI355X (gfx950) path-tracing engine behind include/mi355x_pathtracer.h: scene upload, the
+// tracer's buffers (the ptx_tracer struct itself: pt_tracer.h), the ptx_* entry points that create, render, read and examine a tracer,
+// and the kernels that are the same at every arithmetic level (debug capture, cache replay, gather, statistics, preview, G-buffer,
+// k_kat_fast_exact, k_hold) with the entry points that launch them.  Scene preparation: pt_scene.hip.
 // The debug switches and the launch plans (iterations per set, grids, LDS bytes, the cut of a short run): pt_plan.hip.
+// What is done with a traced frame -- the ptx_denoise* entry points, moments, adaptive sampling, the display transform: pt_post.hip.
 //
 // What belongs here: everything that is level 0 by nature.  This file is compiled ONCE, at the exact level; the kernels whose results
 // depend on the arithmetic level (k_bounce, k_mesh, k_finish, the per-stage test kernels) are pt_kernels.hip's, one code object per
@@ -18,12 +20,9 @@
 #include <cmath>
 
 #include "../../include/mi355x_pathtracer.h"
-#include "pt_kernels.h"
-#include "pt_scene.h"
-#include "pt_plan.h"
+#include "pt_tracer.h"
 #include "pt_denoise.h"
 #include "pt_adaptive.h"
-#include "pt_display.h"
 
 namespace {
 
@@ -249,151 +248,9 @@ __global__ __launch_bounds__(256) void k_gbuffer(const DScene sc, const DCamera 
 }
 }  // namespace
 
-// The kernel unit's tables, one per arithmetic level (pt_kernels.hip).  Levels 1 and 2 are weak: a library linked without their
-// objects still loads, and refuses arith != 0.
-extern "C" const void *ptx_arith_kernels_0(void);
-extern "C" const void *ptx_arith_kernels_1(void) __attribute__((weak));
-extern "C" const void *ptx_arith_kernels_2(void) __attribute__((weak));
-extern "C" const void *ptx_arith_last_0(void);      // (pt_kernels_last.hip: the light-only last bounce of each level)
-extern "C" const void *ptx_arith_last_1(void) __attribute__((weak));
-extern "C" const void *ptx_arith_last_2(void) __attribute__((weak));
-// the exact and the contracted level once more, compiled with -DPT_UNIT_RSQRT=0 -DPT_SHARED_RCP=0 (pt_device.h): the plain second normalize
-// and six divisions per cube pair, for PTX_DEBUG_NO_UNIT_RSQRT -- a switch inside the kernels would cost them a scalar register
-extern "C" const void *ptx_arith_kernels_0p(void) __attribute__((weak));
-extern "C" const void *ptx_arith_kernels_1p(void) __attribute__((weak));
-extern "C" const void *ptx_arith_last_0p(void) __attribute__((weak));
-extern "C" const void *ptx_arith_last_1p(void) __attribute__((weak));
 // pt_kat_unit.hip: the known-answer kernels of pt_rsqrt_unit and pt_div_pairs3 (ptx_kat_unit_rsqrt)
 namespace ptd { void launch_kat_unit_rsqrt(int cus, hipStream_t stream, unsigned long long *out, int exponent_reps, unsigned long long random_sets); }
 
-// An owned device array -- every device buffer of the tracer, the scratch of the per-stage entry points -- freed when its owner goes, on
-// every way out (a HIPCHECK that fails returns from the middle).  Each step hands back the hipError_t: ptx_create looks for out-of-memory.
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;                              // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    operator T *() const { return p; }
-    hipError_t alloc(size_t count) { n = count; return hipMalloc(&p, sizeof(T) * count); }      // (once per buffer; contents undefined)
-    hipError_t zero() { return hipMemset(p, 0, sizeof(T) * n); }
-    hipError_t upload(const void *src, size_t count) { const hipError_t e = alloc(count); return e != hipSuccess ? e : hipMemcpy(p, src, sizeof(T) * count, hipMemcpyHostToDevice); }
-    hipError_t upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
-    hipError_t download(void *dst) const { return hipMemcpy(dst, p, sizeof(T) * n, hipMemcpyDeviceToHost); }
-};
-
-// ---------------------------------------------------------------------------------------------------------------
-struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on and the debug switches `dbg`, pt_plan.h; what the scene decides, pt_scene.h)
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool timing_valid = false;
-    ptx_options opt{};
-    DCamera cam{};
-    int traceDepth = 0;
-    TileMap tm{};
-    int cap = 0;                               // slots of one segment: maxTiles x TILE
-    // device memory
-    DevBuf<DGeom> d_geoms; DevBuf<DMaterial> d_mats; DevBuf<float> d_faces; DevBuf<uint8_t> d_texels;
-    float *d_image = nullptr; DevBuf<float> d_image_own; // d_image: the caller's buffer, or d_image_own
-    DevBuf<float> d_fbuf[3];                             // stream, stage, cache
-    DevBuf<int32_t> d_ibuf[3];
-    PathSoA soa[3];                                      // 0, 1 = the two stages (bounce b writes soa[1 - (b & 1)], b + 1 reads it), 2 = first-bounce cache
-    DevBuf<int32_t> d_counts;                            // per segment: [2][nbins][maxTiles] prefix tables + [maxTiles] stored paths per tile
-    DevBuf<int32_t> d_chunk;                             // [segments][2 (bounce parity)][3][nbins x grid_seg]: the run tables (BounceParams::chunk)
-    DevBuf<int32_t> d_cache_chunk;                       // [3][nbins x grid_seg]: the cached bounce 0's
-    DevBuf<int32_t> d_cache_super;                       // [2][nbins][nsuper]: the cached bounce 0's
-    int cache_gx = 0;                                    // workgroups per segment of the launch that filled the cache (its run tables' width)
-    DevBuf<int32_t> d_totals;                            // [maxBounces][2][nbins] then [maxBounces][2][nbins][nsuper]
-    int32_t *d_super = nullptr;                          // (points into d_totals' allocation)
-    DevBuf<float> d_tri9, d_gtab, d_aabb, d_objcull;
-    std::vector<float> h_aabb;                           // host copy of the world boxes (update_tile_geoms)
-    std::vector<int32_t> h_geom_type, h_roots, h_depths, h_wroots, h_wneeds;      // host copies of the per-geom tree tables (ptx_debug_mesh_plan)
-    DevBuf<uint32_t> d_tile_geoms; bool tile_geoms_valid = false;      // BounceParams::tile_geoms of the current camera
-    // the active-tile mask (ptx_set_active_tiles), both allocated when the first mask is set: the flags, one byte per tile, and the table
-    // the camera bounce reads instead of d_tile_geoms while mask_set (written by k_tile_mask alone)
-    DevBuf<uint8_t> d_tile_active; DevBuf<uint32_t> d_tile_eff; bool mask_set = false;
-    DevBuf<BvhQuad> d_bvh_nodes; DevBuf<float> d_bvh_tris; DevBuf<int32_t> d_bvh_root, d_bvh_depth;                          // pt_bvh.h (NULL: no mesh has one)
-    DevBuf<BvhWide4> d_bvh_wide; DevBuf<int32_t> d_bvh_wroot, d_bvh_wneed;                                                   // four-wide nodes of the same trees (k_mesh)
-    DevBuf<float> d_fnorm, d_cnorm;                      // precomputed normals (DScene::fnorm / cnorm)
-    DevBuf<float> d_ctan;                                // tangent frames of the cubes' tabulated normals (DScene::ctan)
-    DevBuf<float> d_ldsblob;                             // DScene::ldsblob for the ntri_lds k_bounce is launched with
-    DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_items; DevBuf<int32_t> d_item_count;
-    DevBuf<int32_t> d_tile_done;                         // split first bounce: [segments][maxTiles], see BounceParams::tile_done
-    size_t seg_items = 0;
-    int nsuper = 1;
-    size_t totals_bytes = 0, seg_totals = 0, field_stride = 0, seg_part = 0;
-    int kmax = 1;                                        // iterations per launch set (segments)
-    // (lanes, pt_plan.h: each launch set in flight runs on a stream of its own with its own kmax segments of every per-iteration buffer)
-    hipStream_t lane_stream[MAX_LANES] = {};      // [0] = `stream`, the others are the tracer's own
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {}, ev_chain[MAX_LANES] = {};
-    // Render-ahead for the one-iteration-per-call shape (ptx_iterate = the reference's pathtrace(iter)): lanes 1 and 2 take
-    // turns tracing the NEXT kmax iterations into their per-iteration radiance buffers while the caller works the current
-    // batch off, one k_gather (+ k_stats) per call on the main stream.  What a call returns is unchanged: the image holds
-    // exactly the iterations asked for so far, summed in the same order.
-    struct Ahead { int first = 0, count = 0, next = 0, unfolded = 0; bool use_cache = false, valid = false, timed = false;
-                   unsigned long long dir_bins = ~0ull, ntab_bins = 0ull; };      // (the record masks the batch was written with: k_stats)
-    Ahead ahead[MAX_LANES];
-    int ahead_cur = -1, ahead_nxt = -1;                  // lane whose batch is being consumed / lane holding the batch after it
-    bool render_ahead = false;
-    int last_ahead_lane = -1;                            // != -1: the previous operation was a call served from that lane's batch
-    hipEvent_t ev_ahead0[MAX_LANES] = {}, ev_ahead1[MAX_LANES] = {};
-    // The lit planes and totals of a lane's segments are zero between its launch sets: the set's k_gather and k_stats clear what they
-    // read.  Where that may not hold -- nothing has run yet, a traced-ahead batch was dropped unfinished, a set ended early on an error,
-    // the image was reset -- the lane's next set starts with a full clear of both (enqueue_batch).
-    bool aux_dirty[MAX_LANES] = {};
-    unsigned long long cache_dir_bins = ~0ull, cache_ntab_bins = 0ull;      // ... as the cached camera bounce was written
-    int cache_idx16 = 0;                                                    // ... and its local index (BounceParams::idx16)
-    bool cache_loop = false;                                                // ... and that index's layout (bit 0 of BounceParams::loop_idx)
-    IndexPlan ix;                                                           // the local index's layout, for every launch of this tracer
-    DevBuf<uchar4> d_pbo;                                // ptx_write_pbo's device staging (allocated on first use)
-    DevBuf<float> d_denoised;                            // ptx_write_denoised_pbo_device's copy of the host frame (first use)
-    DevBuf<float> d_albedo;                              // apps variant only: W*H*3
-    // denoiser (ptx_denoise), all allocated on its first call: G-buffer [nh | xt | alb] x W*H float4 then W*H int2 ids (pt_denoise.h),
-    // the filter's two float4 colour buffers, its W*H*3 result
-    DevBuf<float4> d_gbuf, d_dn_tmp;
-    DevBuf<float> d_dn_out;
-    bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
-    int guide_first = 1, guide_count = 0;                // ptx_set_guide_samples: count 0 = k_gbuffer's pixel-centre guides, else k_guides over these iterations
-    std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
-    DevBuf<uint8_t> d_spec;                              // its device copy, on the first ptx_denoise_temporal
-    DevBuf<float> d_var;                                 // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
-    bool var_done = false;
-    DevBuf<unsigned long long> d_stamps;                 // diagnostic build only
-    DevBuf<float> d_part;                                // [kmax][W*H*3] per-iteration radiance (batched mode)
-    DevBuf<int32_t> d_cache_totals;                      // [2][nbins] of bounce 0 (cache)
-    DevBuf<int32_t> d_emit_count, d_emit_pix; DevBuf<float> d_emit_rgb;
-    DevBuf<int64_t> d_stats;                             // [64] last iteration, [64] = running total, [65] = fenced indices (BounceParams::fenced), [66..68] = stored paths: all, with direction, with normal code
-    int maxBounces = 0;
-    bool cache_valid = false;
-    int64_t iterations = 0;
-    double loop_ms_total = 0.0;
-    // optional per-kernel timing (bench.py's roofline leg): events around every launch of an iteration
-    bool ktiming = false;
-    std::vector<hipEvent_t> kev;                         // pairs (start, stop)
-    std::vector<int> kev_kind;                           // per pair: 0 k_bounce<first>, 1 k_bounce, 2 k_mesh + k_finish, 3 pass 2 of the split bounce (the ranking pass)
-    size_t kev_used = 0;
-    // debug capture
-    int capture_bounce = -1;
-    DevBuf<int32_t> d_cap;                               // pix, idx, mg [cap each] + totals
-    DevBuf<float> d_cap_f;                               // the 15 float fields [cap each]
-    bool cap_filled = false;
-    DScene scene() const {
-        DScene s; s.geoms = d_geoms; s.mats = d_mats; s.faces = d_faces; s.tri9 = d_tri9; s.texels = d_texels; s.ngeoms = ngeoms; s.nmats = nmats;
-        s.gtab = d_gtab; s.aabb = d_aabb; s.cull = 0; s.cube_bits = cube_bits; s.sphere_bits = sphere_bits; s.mesh_bits = mesh_bits; s.light_bits = light_bits;
-        s.objcull = d_objcull; s.objcull_bits = objcull_bits;
-        s.bvh_nodes = d_bvh_nodes; s.bvh_tris = d_bvh_tris; s.bvh_root = d_bvh_root; s.bvh_depth = d_bvh_depth; s.bvh_wide = d_bvh_wide; s.bvh_wroot = d_bvh_wroot; s.bvh_wneed = d_bvh_wneed; s.bvh_stack = 0; s.ntri_lds = 0; s.mesh_chunks = mesh_chunks;
-        s.fnorm = d_fnorm; s.cnorm = d_cnorm; s.bump_bits = bump_bits;
-        s.ctan = dbg.no_tangents ? nullptr : d_ctan.p;
-        s.tri_lds = 0; s.ntri = ntri;      // tri_lds is switched on only by launches that stage the table (k_bounce)
-        s.ldsblob = nullptr;               // (set by enqueue_batch together with tri_lds / ntri_lds: the blob is laid out for those)
-        return s;
-    }
-    bool cache_active() const { return opt.cache_first_bounce && !opt.antialiasing && !opt.depth_of_field; }
-    const KernelSet *ks = static_cast<const KernelSet *>(ptx_arith_kernels_0());      // the code object the arithmetic-bearing kernels are launched from (ptx_options.arith)
-    const LastKernelSet *ksl = static_cast<const LastKernelSet *>(ptx_arith_last_0());    // ... and the same level's light-only last bounce
-};
 
 namespace {
 
@@ -439,8 +296,18 @@ int update_tile_geoms(ptx_tracer *t) {
     return PTX_OK;
 }
 
+int mask_buffers(ptx_tracer *t) {                       // (on the first mask)
+    if (t->d_tile_eff) return PTX_OK;
+    HIPCHECK(t->d_tile_active.alloc((size_t)t->maxTiles));
+    HIPCHECK(t->d_tile_eff.alloc((size_t)t->maxTiles));
+    return PTX_OK;
+}
+
+}  // namespace
+
+// (pt_tracer.h: pt_post.hip's ptx_adaptive_select calls these two)
 // why this tracer cannot take a mask of `ntiles` flags (the code through `code`), or NULL
-const char *active_tiles_problem(const ptx_tracer *t, int ntiles, int &code) {
+const char *pt_active_tiles_problem(const ptx_tracer *t, int ntiles, int &code) {
     code = PTX_ERR_INVALID;
     if (t->tm.tile_world > 1) return "this tracer renders a row tile (tile_world > 1)";
     if (ntiles != t->maxTiles) return "ntiles differs from ptx_num_tiles";
@@ -452,14 +319,7 @@ const char *active_tiles_problem(const ptx_tracer *t, int ntiles, int &code) {
 
 // the order of a camera change (ptx_set_camera): what is on the tracer's stream ends, what was traced ahead is dropped, then the table
 // is written by a launch of its own; d_flags: one byte per tile on the device
-int mask_buffers(ptx_tracer *t) {                       // (on the first mask)
-    if (t->d_tile_eff) return PTX_OK;
-    HIPCHECK(t->d_tile_active.alloc((size_t)t->maxTiles));
-    HIPCHECK(t->d_tile_eff.alloc((size_t)t->maxTiles));
-    return PTX_OK;
-}
-
-int set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
+int pt_set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
     if (const int rc = mask_buffers(t)) return rc;
     HIPCHECK(hipStreamSynchronize(t->stream));
     ahead_discard(t);
@@ -467,6 +327,8 @@ int set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
     t->mask_set = true;
     return PTX_OK;
 }
+
+namespace {
 
 int free_tracer(ptx_tracer *t) {
     if (!t) return PTX_OK;
@@ -1093,12 +955,12 @@ int ptx_num_tiles(const ptx_tracer *t) { return t ? t->maxTiles : 0; }
 int ptx_set_active_tiles(ptx_tracer *t, const uint8_t *host_active, int ntiles) {
     if (!t || !host_active) return set_error(PTX_ERR_INVALID, "ptx_set_active_tiles: null tracer or mask");
     int code = 0;
-    if (const char *why = active_tiles_problem(t, ntiles, code)) return set_error(code, std::string("ptx_set_active_tiles: ") + why);
+    if (const char *why = pt_active_tiles_problem(t, ntiles, code)) return set_error(code, std::string("ptx_set_active_tiles: ") + why);
     HIPCHECK(hipSetDevice(t->device));
     if (const int rc = mask_buffers(t)) return rc;
     HIPCHECK(hipStreamSynchronize(t->stream));           // (no launch reads the flags now: only k_tile_mask does, on this stream)
     HIPCHECK(hipMemcpy(t->d_tile_active, host_active, (size_t)ntiles, hipMemcpyHostToDevice));
-    return set_tile_mask(t, nullptr);
+    return pt_set_tile_mask(t, nullptr);
 }
 
 int ptx_clear_active_tiles(ptx_tracer *t) {
@@ -1322,7 +1184,7 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
 
 // ---- denoiser (pt_denoise.hip, pt_temporal.hip; definition in include/mi355x_pathtracer.h) --------------------------------------
 // The G-buffer of the current camera on the tracer's stream, buffers allocated on first use
-static int ensure_gbuffer(ptx_tracer *t) {
+extern "C++" int pt_ensure_gbuffer(ptx_tracer *t) {
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     if (!t->d_gbuf) HIPCHECK(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
@@ -1353,8 +1215,7 @@ int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count) {
                                               std::to_string(GUIDE_SAMPLES_MAX) + " samples per pixel");
     if (iter_first > INT32_MAX - GUIDE_SAMPLES_MAX)
         return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first + count would pass the largest iteration number");
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (const int rc = pt_whole_frame_problem("ptx_set_guide_samples", t)) return rc;
     if (count == t->guide_count && (count == 0 || iter_first == t->guide_first)) return PTX_OK;      // (the same guides: nothing is stale)
     t->guide_first = iter_first; t->guide_count = count;
     t->gbuf_valid = false;
@@ -1368,392 +1229,6 @@ int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count) {
     return PTX_OK;
 }
 
-// What the entry points that carry a history say while sampled guides are on
-static int guides_refuse_history(const std::string &fn) {
-    return set_error(PTX_ERR_UNSUPPORTED, fn + ": sampled guides are on (ptx_set_guide_samples, count > 0); reprojection and history "
-                                               "matching need one surface per pixel -- set count 0 for the temporal path");
-}
-
-// What the three ptx_denoise* entry points share; `fn` is the entry point's name, for its messages.
-extern "C++" template <class P> static P params_or_default(const P *given, void (*defaults)(P *)) {
-    P p;
-    if (given) p = *given;
-    else defaults(&p);
-    return p;
-}
-
-static int bad_spp(const std::string &fn) {
-    return set_error(PTX_ERR_INVALID, fn + ": spp must be >= 1 (the iterations summed in the accumulation buffer)");
-}
-
-// The checks on the tracer (not NULL) and on the handle (may be NULL), then the buffers the filter needs, allocated on first use, and
-// the G-buffer of the current camera.  variance: ptx_denoise_variance's d_var too.
-static int denoise_begin(const std::string &fn, ptx_tracer *t, const ptx_temporal *h, bool variance) {
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (h && h->device != t->device)
-        return set_error(PTX_ERR_INVALID, fn + ": the temporal handle was created on device " + std::to_string(h->device) +
-                                              ", the tracer runs on device " + std::to_string(t->device));
-    if (h && (h->w != t->cam.resx || h->h != t->cam.resy))
-        return set_error(PTX_ERR_INVALID, fn + ": the temporal handle's size " + std::to_string(h->w) + " x " + std::to_string(h->h) +
-                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
-    HIPCHECK(hipSetDevice(t->device));
-    const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_dn_tmp) HIPCHECK(t->d_dn_tmp.alloc(2 * n));
-    if (!t->d_dn_out) HIPCHECK(t->d_dn_out.alloc(3 * n));
-    if (variance && !t->d_var) HIPCHECK(t->d_var.alloc(2 * n));
-    if (h && !t->d_spec) {
-        HIPCHECK(t->d_spec.alloc(t->h_spec.size()));
-        HIPCHECK(hipMemcpyAsync(t->d_spec, t->h_spec.data(), t->h_spec.size(), hipMemcpyHostToDevice, t->stream));
-    }
-    return ensure_gbuffer(t);
-}
-
-// The handle's step on the tracer's stream: wait for the handle's last work, start a new segment when the camera changed (cur becomes
-// hist), then reproject hist into the current view and mix (with V when variance; moments: ptx_denoise_temporal_measured's V, from that
-// state with its `batches`).
-static int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_params &tp, int spp, bool variance,
-                         const PtMomentsState *moments = nullptr, int batches = 0) {
-    if (h->used) HIPCHECK(hipStreamWaitEvent(t->stream, h->ev, 0));     // the handle's last work, maybe on another tracer's stream
-    ptx_camera cam;
-    memcpy(&cam, &t->cam, sizeof cam);
-    if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {
-        if (h->cur_valid) { h->cur ^= 1; h->hist_valid = true; }
-        h->cam[h->cur] = cam;
-        h->cur_valid = true;
-    }
-    const int hi = h->cur ^ 1;
-    const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    const float4 *g = t->d_gbuf;
-    PtTemporalCamD camd;
-    const PtTemporalCam hcam = pt_temporal_camera(h->cam[hi], h->hist_valid, &camd);
-    HIPCHECK(pt_temporal_enqueue(t->stream, t->cam.resx, t->cam.resy, hcam, tp, t->d_image,
-                                 (float)spp, g, g + n, g + 2 * n, reinterpret_cast<const int2 *>(g + 3 * n), t->d_spec,
-                                 (int)t->h_spec.size(), h->st[h->cur], h->st[hi], h->d_mix, h->d_hn, variance ? 1 : 0,
-                                 variance && h->hist_valid && h->has_v[hi] ? 1 : 0, moments, batches, &camd));
-    return PTX_OK;
-}
-
-// The handle's end of a call: its event after the call's work
-static int temporal_done(ptx_tracer *t, ptx_temporal *h) {
-    HIPCHECK(hipEventRecord(h->ev, t->stream));
-    h->used = h->done = true;
-    return PTX_OK;
-}
-
-int ptx_denoise(ptx_tracer *t, const ptx_denoise_params *params, int spp) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    const ptx_denoise_params p = params_or_default(params, ptx_default_denoise_params);
-    if (spp < 1) return bad_spp("ptx_denoise");
-    if (const char *why = pt_denoise_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
-    if (const int rc = denoise_begin("ptx_denoise", t, nullptr, false)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, p.demodulate ? 1 : 0, 0, nullptr, t->d_dn_tmp));
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, p));
-    t->dn_done = true;
-    return PTX_OK;
-}
-
-// ---- temporal reuse (pt_temporal.hip; definition in include/mi355x_pathtracer.h) ----------------------------------------------------
-int ptx_denoise_temporal(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams, int spp) {
-    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
-    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return bad_spp("ptx_denoise_temporal");
-    if (!t || !h) return set_error(PTX_ERR_INVALID, "ptx_denoise_temporal: null tracer or temporal handle");
-    if (t->guide_count > 0) return guides_refuse_history("ptx_denoise_temporal");
-    if (const int rc = denoise_begin("ptx_denoise_temporal", t, h, false)) return rc;
-    if (const int rc = temporal_step(t, h, tp, spp, false)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, h->d_mix, 1.0f, g, g + 2 * n, dp.demodulate ? 1 : 0, 0, nullptr, t->d_dn_tmp));
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp));
-    if (const int rc = temporal_done(t, h)) return rc;
-    h->has_v[h->cur] = false;                            // dd.w = 0: a later ptx_denoise_variance takes its spatial estimate
-    t->dn_done = true;
-    return PTX_OK;
-}
-
-// ---- variance guidance (pt_denoise.hip; definition in include/mi355x_pathtracer.h) --------------------------------------------------
-int ptx_denoise_variance(ptx_tracer *t, ptx_temporal *h, const ptx_denoise_params *dparams, const ptx_temporal_params *tparams,
-                         const ptx_variance_params *vparams, int spp) {
-    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
-    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
-    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return bad_spp("ptx_denoise_variance");
-    if (h && !dp.demodulate)
-        return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: with a temporal handle ptx_denoise_params.demodulate must be != 0 "
-                                          "(the state's moments are in demodulated space)");
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_denoise_variance: null tracer");
-    if (h && t->guide_count > 0) return guides_refuse_history("ptx_denoise_variance");
-    if (const int rc = denoise_begin("ptx_denoise_variance", t, h, true)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    if (h) {
-        if (const int rc = temporal_step(t, h, tp, spp, true)) return rc;
-        const PtTemporalState &cur = h->st[h->cur];
-        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, cur.nh, cur.xn, cur.ids, 1, cur.dd));
-        HIPCHECK(pt_variance_prep_state_enqueue(t->stream, (int)n, cur, t->d_dn_tmp));
-        h->has_v[h->cur] = true;
-    } else {
-        HIPCHECK(pt_atrous_prep_enqueue(t->stream, (int)n, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, 1, nullptr, t->d_dn_tmp));
-        HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
-    }
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
-    if (const int rc = h ? temporal_done(t, h) : PTX_OK) return rc;
-    t->dn_done = t->var_done = true;
-    return PTX_OK;
-}
-
-int ptx_read_variance(ptx_tracer *t, float *input_var1, float *output_var1) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    if (!t->var_done) return set_error(PTX_ERR_INVALID, "ptx_read_variance: no ptx_denoise_variance on this tracer yet");
-    HIPCHECK(hipSetDevice(t->device));
-    const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (input_var1) HIPCHECK(hipMemcpyAsync(input_var1, t->d_var, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
-    if (output_var1) HIPCHECK(hipMemcpyAsync(output_var1, t->d_var + n, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return PTX_OK;
-}
-
-// ---- sample moments by batch means (pt_moments.hip; definition in include/mi355x_pathtracer.h) ---------------------------------------
-// The checks of denoise_begin on a moments handle.  The accumulation buffer is read on the tracer's stream, where every gather runs,
-// those of iterations traced ahead included (ahead_finish_segment): the order ptx_denoise's read of it has.
-static const char *const TILED_HANDLE = "this moments handle has had a tiled add: its tiles hold different sample counts until ptx_moments_reset";
-static int moments_begin(const std::string &fn, ptx_tracer *t, const ptx_moments *m) {
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (m->device != t->device)
-        return set_error(PTX_ERR_INVALID, fn + ": the moments handle was created on device " + std::to_string(m->device) +
-                                              ", the tracer runs on device " + std::to_string(t->device));
-    if (m->w != t->cam.resx || m->h != t->cam.resy)
-        return set_error(PTX_ERR_INVALID, fn + ": the moments handle's size " + std::to_string(m->w) + " x " + std::to_string(m->h) +
-                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
-    return PTX_OK;
-}
-
-int ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total) {
-    if (samples_total < 1) return set_error(PTX_ERR_INVALID, "ptx_moments_add: samples_total must be >= 1");
-    if (!m || !t) return set_error(PTX_ERR_INVALID, "ptx_moments_add: null moments handle or tracer");
-    if (samples_total <= m->samples)
-        return set_error(PTX_ERR_INVALID, "ptx_moments_add: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
-                                              std::to_string(m->samples));
-    if (m->tiled) return set_error(PTX_ERR_INVALID, "ptx_moments_add: " + std::string(TILED_HANDLE));
-    if (const int rc = moments_begin("ptx_moments_add", t, m)) return rc;
-    HIPCHECK(hipSetDevice(t->device));
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));     // the handle's last work, maybe on another tracer's stream
-    HIPCHECK(pt_moments_add_enqueue(t->stream, m->w, m->h, t->d_image, (float)(samples_total - m->samples), (float)samples_total,
-                                    m->samples == 0, m->st));
-    HIPCHECK(hipEventRecord(m->ev, t->stream));
-    m->used = true;
-    m->samples = samples_total;
-    m->batches++;
-    return PTX_OK;
-}
-
-int ptx_denoise_measured(ptx_tracer *t, ptx_moments *m, const ptx_denoise_params *dparams, const ptx_variance_params *vparams, int min_batches,
-                         int spp) {
-    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
-    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return bad_spp("ptx_denoise_measured");
-    if (min_batches == 1) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: min_batches must be >= 2 (<= 0: the default, 4)");
-    if (!t || !m) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: null tracer or moments handle");
-    if (m->samples == 0) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: no add on this moments handle yet");
-    if (m->tiled) return set_error(PTX_ERR_INVALID, "ptx_denoise_measured: " + std::string(TILED_HANDLE));      // (one spp, one B per frame)
-    if (const int rc = moments_begin("ptx_denoise_measured", t, m)) return rc;
-    if (const int rc = denoise_begin("ptx_denoise_measured", t, nullptr, true)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
-    HIPCHECK(pt_moments_prep_enqueue(t->stream, W, H, t->d_image, (float)spp, g, g + 2 * n, dp.demodulate ? 1 : 0, m->st,
-                                     min_batches <= 0 ? 4 : min_batches, t->d_dn_tmp));
-    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
-    m->used = true;
-    HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
-    t->dn_done = t->var_done = true;
-    return PTX_OK;
-}
-
-// ---- the two together: the temporal history's V pooled with the measured variance (definition in include/mi355x_pathtracer.h) --------
-int ptx_denoise_temporal_measured(ptx_tracer *t, ptx_temporal *h, ptx_moments *m, const ptx_denoise_params *dparams,
-                                  const ptx_temporal_params *tparams, const ptx_variance_params *vparams, int min_batches, int spp) {
-    const std::string fn = "ptx_denoise_temporal_measured";
-    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
-    const ptx_temporal_params tp = params_or_default(tparams, ptx_default_temporal_params);
-    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_temporal_params_problem(tp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
-    if (spp < 1) return bad_spp(fn);
-    if (min_batches == 1) return set_error(PTX_ERR_INVALID, fn + ": min_batches must be >= 2 (<= 0: the default, 4)");
-    if (!dp.demodulate)
-        return set_error(PTX_ERR_INVALID, fn + ": ptx_denoise_params.demodulate must be != 0 (the state's moments are in demodulated space)");
-    if (!t || !h || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, temporal handle or moments handle");
-    if (t->guide_count > 0) return guides_refuse_history(fn);
-    if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on this moments handle yet");
-    if (m->tiled) return set_error(PTX_ERR_INVALID, fn + ": " + TILED_HANDLE);      // (one spp, one B per frame)
-    if (const int rc = moments_begin(fn, t, m)) return rc;
-    // too few batches for the measured variance: ptx_denoise_variance itself, so the same bits (the moments state is not read)
-    if (m->batches < (min_batches <= 0 ? 4 : min_batches)) return ptx_denoise_variance(t, h, &dp, &tp, &vp, spp);
-    if (const int rc = denoise_begin(fn, t, h, true)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
-    if (const int rc = temporal_step(t, h, tp, spp, true, &m->st, m->batches)) return rc;
-    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
-    m->used = true;
-    const PtTemporalState &cur = h->st[h->cur];
-    // (no spatial pass: every hit pixel's dd.w is a V already, nothing is marked -1)
-    HIPCHECK(pt_variance_prep_state_enqueue(t->stream, (int)n, cur, t->d_dn_tmp));
-    h->has_v[h->cur] = true;
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
-    if (const int rc = temporal_done(t, h)) return rc;
-    t->dn_done = t->var_done = true;
-    return PTX_OK;
-}
-
-// ---- adaptive sampling by tiles (pt_adaptive.hip; definition in include/mi355x_pathtracer.h) ------------------------------------------
-static int adaptive_begin(const std::string &fn, ptx_tracer *t, const ptx_adaptive *a) {
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, fn + ": this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (a->device != t->device)
-        return set_error(PTX_ERR_INVALID, fn + ": the adaptive handle was created on device " + std::to_string(a->device) +
-                                              ", the tracer runs on device " + std::to_string(t->device));
-    if (a->w != t->cam.resx || a->h != t->cam.resy || a->ntiles != t->maxTiles)
-        return set_error(PTX_ERR_INVALID, fn + ": the adaptive handle's size " + std::to_string(a->w) + " x " + std::to_string(a->h) +
-                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
-    return PTX_OK;
-}
-
-int ptx_adaptive_add(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, int k) {
-    if (k < 1 || k > (1 << 24)) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: k must be in 1 .. 2^24");
-    if (!a || !m || !t) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: null adaptive handle, moments handle or tracer");
-    if (const int rc = moments_begin("ptx_adaptive_add", t, m)) return rc;
-    if (const int rc = adaptive_begin("ptx_adaptive_add", t, a)) return rc;
-    // the two handles count the same samples tile by tile, or the (k, W') table would not describe the moments' state
-    for (int i = 0; i < a->ntiles; i++) {
-        const long long have = m->tile_samples.empty() ? m->samples : m->tile_samples[(size_t)i];
-        if (have != a->h_samples[(size_t)i])
-            return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: tile " + std::to_string(i) + " holds " + std::to_string(a->h_samples[(size_t)i]) +
-                                                  " samples, the moments handle has " + std::to_string(have) + " of it: reset both together");
-        if ((long long)a->h_samples[(size_t)i] + k > (1 << 24)) return set_error(PTX_ERR_INVALID, "ptx_adaptive_add: more than 2^24 samples in a tile");
-    }
-    HIPCHECK(hipSetDevice(t->device));
-    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
-    HIPCHECK(pt_adaptive_advance_enqueue(t->stream, *a, k));
-    for (int i = 0; i < a->ntiles; i++) {
-        a->h_k[(size_t)i] = a->h_active[(size_t)i] ? k : 0;
-        a->h_samples[(size_t)i] += a->h_k[(size_t)i];
-    }
-    const int rc = pt_moments_add_tiled(m, t->stream, t->d_image, a->d_kt, a->h_k.data());
-    HIPCHECK(hipEventRecord(a->ev, t->stream));
-    HIPCHECK(hipEventRecord(m->ev, t->stream));
-    a->used = m->used = true;
-    return rc;
-}
-
-int ptx_adaptive_select(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, const ptx_adaptive_params *params, ptx_adaptive_status *status) {
-    const ptx_adaptive_params p = params_or_default(params, ptx_default_adaptive_params);
-    if (const char *why = pt_adaptive_params_problem(p)) return set_error(PTX_ERR_INVALID, why);
-    if (!a || !m || !t || !status) return set_error(PTX_ERR_INVALID, "ptx_adaptive_select: null adaptive handle, moments handle, tracer or status");
-    if (m->samples == 0) return set_error(PTX_ERR_INVALID, "ptx_adaptive_select: no add on this moments handle yet");
-    if (const int rc = moments_begin("ptx_adaptive_select", t, m)) return rc;
-    if (const int rc = adaptive_begin("ptx_adaptive_select", t, a)) return rc;
-    int code = 0;
-    if (const char *why = active_tiles_problem(t, a->ntiles, code)) return set_error(code, std::string("ptx_adaptive_select: ") + why);
-    HIPCHECK(hipSetDevice(t->device));
-    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
-    HIPCHECK(pt_adaptive_select_enqueue(t->stream, *a, m->st, p, a->rounds + 1));
-    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
-    m->used = true;
-    const size_t bytes = sizeof(ptx_adaptive_status) + (size_t)a->ntiles;
-    HIPCHECK(hipMemcpyAsync(a->h_out, a->d_out, bytes, hipMemcpyDeviceToHost, t->stream));      // the one small read: status and flags
-    const int rc = set_tile_mask(t, a->d_active());      // (waits for the stream: h_out is there)
-    HIPCHECK(hipEventRecord(a->ev, t->stream));          // behind k_tile_mask, which reads the flags
-    a->used = true;
-    if (rc != PTX_OK) return rc;
-    a->rounds++;
-    memcpy(status, a->h_out, sizeof *status);
-    memcpy(a->h_active.data(), a->h_out + sizeof(ptx_adaptive_status), (size_t)a->ntiles);
-    return PTX_OK;
-}
-
-int ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t) {
-    if (!a || !t) return set_error(PTX_ERR_INVALID, "ptx_adaptive_resolve: null adaptive handle or tracer");
-    if (const int rc = adaptive_begin("ptx_adaptive_resolve", t, a)) return rc;
-    HIPCHECK(hipSetDevice(t->device));
-    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
-    HIPCHECK(pt_adaptive_resolve_enqueue(t->stream, *a, t->d_image));
-    HIPCHECK(hipEventRecord(a->ev, t->stream));
-    a->used = true;
-    return PTX_OK;
-}
-
-// ptx_denoise_measured on a frame of unequal counts: k_adaptive_prep in place of k_moments_prep, the rest as there
-int ptx_denoise_adaptive(ptx_tracer *t, ptx_adaptive *a, ptx_moments *m, const ptx_denoise_params *dparams, const ptx_variance_params *vparams,
-                         int min_batches) {
-    const std::string fn = "ptx_denoise_adaptive";
-    const ptx_denoise_params dp = params_or_default(dparams, ptx_default_denoise_params);
-    const ptx_variance_params vp = params_or_default(vparams, ptx_default_variance_params);
-    if (const char *why = pt_denoise_params_problem(dp)) return set_error(PTX_ERR_INVALID, why);
-    if (const char *why = pt_variance_params_problem(vp)) return set_error(PTX_ERR_INVALID, why);
-    if (min_batches == 1) return set_error(PTX_ERR_INVALID, fn + ": min_batches must be >= 2 (<= 0: the default, 4)");
-    if (!t || !a || !m) return set_error(PTX_ERR_INVALID, fn + ": null tracer, adaptive handle or moments handle");
-    if (const int rc = moments_begin(fn, t, m)) return rc;
-    if (const int rc = adaptive_begin(fn, t, a)) return rc;
-    // the two handles count the same samples tile by tile (ptx_adaptive_add's comparison), and every tile holds some
-    for (int i = 0; i < a->ntiles; i++) {
-        const long long have = m->tile_samples.empty() ? m->samples : m->tile_samples[(size_t)i];
-        if (have != a->h_samples[(size_t)i])
-            return set_error(PTX_ERR_INVALID, fn + ": tile " + std::to_string(i) + " holds " + std::to_string(a->h_samples[(size_t)i]) +
-                                                  " samples, the moments handle has " + std::to_string(have) + " of it: reset both together");
-    }
-    if (m->samples == 0) return set_error(PTX_ERR_INVALID, fn + ": no add on these handles yet");
-    for (int i = 0; i < a->ntiles; i++)
-        if (a->h_samples[(size_t)i] < 1) return set_error(PTX_ERR_INVALID, fn + ": tile " + std::to_string(i) + " holds no sample");
-    if (const int rc = denoise_begin(fn, t, nullptr, true)) return rc;
-    const int W = t->cam.resx, H = t->cam.resy;
-    const size_t n = (size_t)W * H;
-    const float4 *g = t->d_gbuf;
-    if (a->used) HIPCHECK(hipStreamWaitEvent(t->stream, a->ev, 0));
-    if (m->used) HIPCHECK(hipStreamWaitEvent(t->stream, m->ev, 0));
-    HIPCHECK(pt_adaptive_prep_enqueue(t->stream, *a, t->d_image, g, g + 2 * n, dp.demodulate ? 1 : 0, m->st, min_batches <= 0 ? 4 : min_batches,
-                                      t->d_dn_tmp));
-    HIPCHECK(hipEventRecord(a->ev, t->stream));          // (the handle's frame was written: ptx_adaptive_read waits for it)
-    HIPCHECK(hipEventRecord(m->ev, t->stream));          // (the handle's next add, maybe on another stream, waits for this read)
-    a->used = m->used = true;
-    HIPCHECK(pt_variance_spatial_enqueue(t->stream, W, H, dp, vp, g, g + n, reinterpret_cast<const int2 *>(g + 3 * n), 0, t->d_dn_tmp));
-    HIPCHECK(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, dp, &vp, t->d_var, t->d_var + n));
-    t->dn_done = t->var_done = true;
-    return PTX_OK;
-}
-
-int ptx_read_denoised(ptx_tracer *t, float *host_rgb) {
-    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
-    if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_read_denoised: no ptx_denoise on this tracer yet");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipMemcpyAsync(host_rgb, t->d_dn_out, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return PTX_OK;
-}
-
-float *ptx_device_denoised(ptx_tracer *t) { return t && t->dn_done ? t->d_dn_out : nullptr; }
-
 int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4) {
     if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
     if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_write_denoised_pbo_from_device: no ptx_denoise on this tracer yet");
@@ -1765,36 +1240,12 @@ int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4) {
     return PTX_OK;
 }
 
-// ---- display transform (pt_display.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------
-// The checks of moments_begin on a display handle, then meter + map on the tracer's stream, where every gather and the denoiser run.
-int ptx_display_tracer(ptx_display *d, ptx_tracer *t, int source, int spp, const ptx_display_params *params, void *device_uchar4) {
-    ptx_display_params p = params_or_default(params, ptx_default_display_params);
-    if (source != PTX_DISPLAY_IMAGE && source != PTX_DISPLAY_DENOISED)
-        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: source must be PTX_DISPLAY_IMAGE or PTX_DISPLAY_DENOISED");
-    const float samples = source == PTX_DISPLAY_IMAGE ? (float)spp : 1.f;
-    if (source == PTX_DISPLAY_IMAGE && spp < 1) return bad_spp("ptx_display_tracer");
-    if (const char *why = pt_display_params_problem(p, samples)) return set_error(PTX_ERR_INVALID, why);
-    if (!d || !t) return set_error(PTX_ERR_INVALID, "ptx_display_tracer: null display handle or tracer");
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
-    if (d->device != t->device)
-        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: the display handle was created on device " + std::to_string(d->device) +
-                                              ", the tracer runs on device " + std::to_string(t->device));
-    if (d->w != t->cam.resx || d->h != t->cam.resy)
-        return set_error(PTX_ERR_INVALID, "ptx_display_tracer: the display handle's size " + std::to_string(d->w) + " x " + std::to_string(d->h) +
-                                              " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
-    if (source == PTX_DISPLAY_DENOISED && !t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_display_tracer: no ptx_denoise on this tracer yet");
-    HIPCHECK(hipSetDevice(t->device));
-    return pt_display_enqueue(d, t->stream, source == PTX_DISPLAY_IMAGE ? (const float *)t->d_image : (const float *)t->d_dn_out, samples, p,
-                              device_uchar4);
-}
-
 int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1) {
     if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
     if (t->tm.tile_world > 1)
         return set_error(PTX_ERR_INVALID, "ptx_read_gbuffer: this tracer renders a row tile (tile_world > 1); the denoiser needs the whole frame");
     HIPCHECK(hipSetDevice(t->device));
-    const int rc = ensure_gbuffer(t);
+    const int rc = pt_ensure_gbuffer(t);
     if (rc != PTX_OK) return rc;
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     std::vector<float4> g(3 * n);
@@ -1816,10 +1267,9 @@ int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32
 
 int ptx_read_guide_coverage(ptx_tracer *t, float *coverage1) {
     if (!t || !coverage1) return set_error(PTX_ERR_INVALID, "ptx_read_guide_coverage: null tracer or buffer");
-    if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_read_guide_coverage: this tracer renders a row tile (tile_world > 1); its frame holds only its own rows");
+    if (const int rc = pt_whole_frame_problem("ptx_read_guide_coverage", t)) return rc;
     HIPCHECK(hipSetDevice(t->device));
-    if (const int rc = ensure_gbuffer(t)) return rc;
+    if (const int rc = pt_ensure_gbuffer(t)) return rc;
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     // the fourth float of the albedo records; the pixel-centre guides write 0 there, their coverage is the hit flag: nh's fourth float
     std::vector<float4> a(n);
