@@ -21,7 +21,8 @@ PROVENANCE -- how much of the reference each fixture really pins (see PROVENANCE
              "unpinned by the reference" in the task's sense, pinned only against this restatement.
 Neither kind reproduces the reference's real CUDA build bit for bit (FMA contraction, CUDA libm): the tolerance against
 such an arithmetic is stated and tested in tests/test_fp_tolerance.py.  Consumers: tests/test_oracle_golden.py (CPU, pins the plain-C oracle),
-tests/test_loader.py (CPU, pins the product's scene loader), tests/test_gpu_parity.py (GPU).
+tests/test_loader.py (CPU, pins the product's scene loader), tests/test_gpu_parity.py (GPU); the material zoo's two files (`materials`):
+tests/test_materials_cpu.py and tests/test_gpu_materials.py.
 """
 import os
 import sys
@@ -48,6 +49,8 @@ PROVENANCE = {
     "shade_kat_": "direct+restated",     # scatterRay itself, inside the restated body of shadeFakeMaterial; inputs captured mid-render
     "render_": "restated",               # whole frames, per-bounce counts, sorted streams, 8-bit previews
     "render_apps_": "restated",          # the same with the apps/src deltas (x PI gather, albedo AOV)
+    "shade_kat_zoo": "direct+restated",  # the material zoo of tests/materialcases.py: scatterRay itself on every branch its fields select
+    "render_zoo": "restated",            # ... and its whole frames, streams and counts, the apps variant's image and albedo among them
     "fullres_counts": "restated",        # per-bounce live counts at BASELINE's sizes
     "png_textures": "direct", "jpeg_textures": "direct", "loader_ngons": "direct",     # vendored stb_image / tinyobj through the loader
     "png_files": "direct", "hdr_files": "direct",                                       # vendored stb_image_write through src/image.cpp's calls
@@ -359,10 +362,78 @@ def cottage(R):
           "counts", out["counts_it1"].tolist())
 
 
+def materials(R):
+    """The material zoo of tests/materialcases.py (exponents 0.5 to 200, fractional and negative REFL, indices of refraction <= 1,
+    emitting mirror, negative emittance) through the reference's functions: shade_kat_zoo.npz as the other shade_kat_* files are made
+    (48x36, iteration 1, bounces 0-3, scene text inside) and render_zoo.npz (96x72: images after 1, 2 and 4 iterations, counts, the
+    sorted streams of iteration 1; the apps variant's image after 3 iterations and its albedo)."""
+    import materialcases
+    rng = np.random.default_rng(20261020)
+    text = materialcases.zoo_text((48, 36), 8)
+    R.load_text(text, cwd=REPO_SCENES)
+    R.apply_runcuda_camera()
+    R.pt_init()
+    out, total = {}, 0
+    R.pt_generate(1)
+    for b in range(4):
+        n = R.num_paths()
+        R.pt_bounce(1, 3)
+        paths, isects = R.paths()[:n], R.isects()[:n]
+        R.pt_bounce(1, 12)
+        idx = rng.integers(0, 2_000_000, n).astype(np.int32)
+        key = "it1_b%d" % b
+        out[key + "_paths"], out[key + "_isects"], out[key + "_idx"], out[key + "_shaded"] = paths, isects, idx, R.shade(1, b + 1, idx, isects, paths)
+        total += n
+    out["scene_text"] = np.frombuffer(text.encode(), np.uint8)
+    np.savez_compressed(os.path.join(HERE, "shade_kat_zoo.npz"), **out)
+
+    text = materialcases.zoo_text((96, 72), 8)
+    opt = dict(aa=1, dof=0, sort=1, cache=1)
+    R.load_text(text, cwd=REPO_SCENES)
+    R.apply_runcuda_camera()
+    R.set_options(**opt)
+    R.pt_init()
+    out = dict(options=np.array([opt["aa"], opt["dof"], opt["sort"], opt["cache"]], np.int32), scene_text=np.frombuffer(text.encode(), np.uint8))
+    for it in (1, 2, 3, 4):
+        if it == 1:
+            R.pt_generate(1)
+            b = 0
+            while True:
+                n = R.num_paths()
+                R.pt_bounce(1, 3)
+                out["stream_pix_b%d" % b] = R.paths()["pixelIndex"][:n].copy()
+                out["stream_mat_b%d" % b] = R.isects()["materialId"][:n].copy()
+                out["stream_t_b%d" % b] = R.isects()["t"][:n].copy()
+                if R.pt_bounce(1, 12) == 0:
+                    break
+                b += 1
+            R.pt_final_gather()
+        else:
+            R.iterate(it)
+        if it in (1, 2, 4):
+            out["image_spp%d" % it] = R.image()
+            out["counts_it%d" % it] = R.live_counts()
+    R.load_text(text, cwd=REPO_SCENES)
+    R.apply_runcuda_camera()
+    R.set_apps_variant(1)
+    R.pt_init()
+    for it in (1, 2, 3):
+        R.iterate(it)
+    out["apps_image_spp3"], out["apps_albedo"], out["apps_counts_it3"] = R.image(), R.albedo(), R.live_counts()
+    np.savez_compressed(os.path.join(HERE, "render_zoo.npz"), **out)
+    for name in ("shade_kat_zoo.npz", "render_zoo.npz"):
+        assert os.path.getsize(os.path.join(HERE, name)) < 614000, name
+    print("zoo:", total, "shade records,", os.path.getsize(os.path.join(HERE, "shade_kat_zoo.npz")), "+",
+          os.path.getsize(os.path.join(HERE, "render_zoo.npz")), "bytes, counts", out["counts_it1"].tolist())
+
+
 def main():
     so = build_ref()
     if not so:
         sys.exit("oracle/_ref/libptref.so cannot be built here (no /root/reference)")
+    if sys.argv[1:] == ["materials"]:
+        materials(RefLib(so))
+        return
     if sys.argv[1:] in (["hdr"], ["png"]):           # only this fixture (the others are unchanged by it)
         (hdr_files if sys.argv[1] == "hdr" else png_files)(so)
         return
@@ -526,6 +597,7 @@ def main():
     jpeg_textures(R)
     ngon_faces(R)
     cottage(R)
+    materials(R)
     hdr_files(so)
     png_files(so)
     print("golden fixtures written to", HERE)
