@@ -141,20 +141,14 @@ def _split_variance_params(fn, params):
             default_variance_params(**pick(_VARIANCE_KEYS)))
 
 
-class Temporal:
-    """The history of one W x H view sequence on one device (opaque ptx_temporal), for Tracer.denoise_temporal.  It outlives any
-    tracer: hand the same handle to a new Tracer after a camera change and the previous view's samples are reused."""
-
-    def __init__(self, device, width, height):
-        self.lib = load_library()
-        h = vp()
-        _check(self.lib.ptx_temporal_create(int(device), int(width), int(height), C.byref(h)), "ptx_temporal_create")
-        self.h = h
-        self.device, self.width, self.height = int(device), int(width), int(height)
+class _Owned:
+    """An object that owns one native handle: `lib`, the loaded library, and `h`, the handle (None once closed, absent while the create
+    call has not succeeded).  _destroy names the library function that frees it."""
+    _destroy = None
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.ptx_temporal_destroy(self.h)
+            getattr(self.lib, self._destroy)(self.h)
             self.h = None
 
     def __del__(self):
@@ -168,6 +162,19 @@ class Temporal:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Temporal(_Owned):
+    """The history of one W x H view sequence on one device (opaque ptx_temporal), for Tracer.denoise_temporal.  It outlives any
+    tracer: hand the same handle to a new Tracer after a camera change and the previous view's samples are reused."""
+    _destroy = "ptx_temporal_destroy"
+
+    def __init__(self, device, width, height):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_temporal_create(int(device), int(width), int(height), C.byref(h)), "ptx_temporal_create")
+        self.h = h
+        self.device, self.width, self.height = int(device), int(width), int(height)
 
     def reset(self):
         """forget all history: the next denoise_temporal is Tracer.denoise bit for bit"""
@@ -199,10 +206,11 @@ def default_moments_params(**kw):
     return _default_params(MomentsParams, "ptx_default_moments_params", (), **kw)
 
 
-class Moments:
+class Moments(_Owned):
     """Per-pixel sample moments by batch means on one device (opaque ptx_moments): add(tracer, samples) whenever `samples` iterations
     are in the tracer's accumulation buffer, then summary() for the frame's error estimate, read() for the per-pixel mean and
     covariance, or Tracer.denoise_measured(moments, spp).  After Tracer.reset_image call reset()."""
+    _destroy = "ptx_moments_destroy"
 
     def __init__(self, device, width, height):
         self.lib = load_library()
@@ -210,23 +218,6 @@ class Moments:
         _check(self.lib.ptx_moments_create(int(device), int(width), int(height), C.byref(h)), "ptx_moments_create")
         self.h = h
         self.device, self.width, self.height = int(device), int(width), int(height)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ptx_moments_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         """forget everything: the next add takes the whole buffer as one batch"""
@@ -296,11 +287,12 @@ def tile_pixels():
     return int(load_library().ptx_tile_pixels())
 
 
-class Adaptive:
+class Adaptive(_Owned):
     """Adaptive sampling by tiles on one device (opaque ptx_adaptive): render(tracer, moments) traces until every tile's measured error
     is at its target, or step by step add(moments, tracer, k) after every k iterations, select(moments, tracer) for the next mask,
     resolve(tracer) and read() for the frame; Tracer.denoise_adaptive(adaptive, moments) filters it.  Reset it together with the Moments
     it is used with."""
+    _destroy = "ptx_adaptive_destroy"
 
     def __init__(self, device, width, height):
         self.lib = load_library()
@@ -309,23 +301,6 @@ class Adaptive:
         self.h = h
         self.device, self.width, self.height = int(device), int(width), int(height)
         self.num_tiles = int(self.lib.ptx_adaptive_num_tiles(h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ptx_adaptive_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         """every tile active with 0 samples, as after create"""
@@ -418,10 +393,12 @@ def debug_display_blocks(width, height):
     return rows[:hk.value + 1], cols[:wk.value + 1]
 
 
-class Display:
+class Display(_Owned):
     """The display transform on one device (opaque ptx_display): automatic exposure from block luminances, tone curve, sRGB transfer,
     8-bit codes.  tracer(T, spp) maps a tracer's frame, device(ptr, samples) any W*H*3 float frame on the device, host(rgb) a numpy
     frame; params are ptx_display_params' fields as keywords.  The adapted exposure lives in the handle: reset() forgets it."""
+
+    _destroy = "ptx_display_destroy"
 
     def __init__(self, width, height, device=0):
         self.lib = load_library()
@@ -429,23 +406,6 @@ class Display:
         _check(self.lib.ptx_display_create(int(device), int(width), int(height), C.byref(h)), "ptx_display_create")
         self.h = h
         self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ptx_display_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         """forget the adapted exposure: the next metered frame's applied exposure is its metered one"""
@@ -921,8 +881,9 @@ def default_options(**kw):
     return o
 
 
-class Scene:
+class Scene(_Owned):
     """A loaded scenes/*.txt (class Scene, src/scene.h)."""
+    _destroy = "ptx_scene_free"
 
     def __init__(self, path, base_dir=None, res=None, depth=None):
         self.lib = load_library()
@@ -934,17 +895,6 @@ class Scene:
             self.set_resolution(*res)
         if depth is not None:
             self.set_trace_depth(depth)
-
-    def close(self):
-        if self.h:
-            self.lib.ptx_scene_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def num_geoms(self):
@@ -1045,9 +995,10 @@ class Scene:
                     textures=textures)
 
 
-class MultiTracer:
+class MultiTracer(_Owned):
     """The frame split into interleaved row blocks over several devices of one node, one process (opaque ptx_multi; the C/C++
     side of the tile split -- include/mi355x_pathtracer.h "N GPUs of one node").  `devices` may repeat an ordinal."""
+    _destroy = "ptx_multi_destroy"
 
     def __init__(self, scene, devices, tile_rows=8, options=None, **opt_kw):
         self.lib = load_library()
@@ -1059,19 +1010,6 @@ class MultiTracer:
         _check(self.lib.ptx_multi_create(scene.h, C.byref(self.options), devs, len(devices), tile_rows, C.byref(h)), "ptx_multi_create")
         self.h, self.n = h, len(devices)
         self.width, self.height = scene.resolution
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ptx_multi_destroy(self.h)
-            self.h = None
-
-    __del__ = lambda self: self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def render(self, iter_first, count):
         _check(self.lib.ptx_multi_render(self.h, iter_first, count), "ptx_multi_render")
@@ -1110,8 +1048,9 @@ class MultiTracer:
                     stored_with_direction=int(s.stored_with_direction), stored_with_normal_code=int(s.stored_with_normal_code))
 
 
-class Tracer:
+class Tracer(_Owned):
     """pathtraceInit / pathtrace / pathtraceFree on one device (opaque ptx_tracer)."""
+    _destroy = "ptx_destroy"
 
     def __init__(self, scene, options=None, external_image_ptr=None, stream_ptr=None, **opt_kw):
         self.lib = load_library()
@@ -1175,23 +1114,6 @@ class Tracer:
         self.trace_depth = int(ci[3])
         self.iteration = 0
         return self
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ptx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     # --- the reference's per-frame call -----------------------------------------------------------------
     def pathtrace(self, iteration, read_image=False):

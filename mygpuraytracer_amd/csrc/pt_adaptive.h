@@ -12,19 +12,18 @@
 #pragma once
 #include "pt_denoise.h"
 
-struct ptx_adaptive {
-    int device = 0, w = 0, h = 0, ntiles = 0;
-    int32_t *d_samples = nullptr, *d_batches = nullptr, *d_nest = nullptr;
-    float *d_err = nullptr;
-    float2 *d_kt = nullptr;
-    uint8_t *d_out = nullptr;             // [sizeof(ptx_adaptive_status) | active: ntiles bytes], contiguous for the one read
+struct ptx_adaptive : PtHandle {
+    int ntiles = 0;
+    DevBuf<int32_t> d_samples, d_batches, d_nest;
+    DevBuf<float> d_err;
+    DevBuf<float2> d_kt;
+    DevBuf<uint8_t> d_out;                // [sizeof(ptx_adaptive_status) | active: ntiles bytes], contiguous for the one read
     uint8_t *h_out = nullptr;             // its pinned host copy
-    float *d_frame = nullptr;             // W*H*3
-    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
-    bool used = false;
+    DevBuf<float> d_frame;                // W*H*3
     std::vector<uint8_t> h_active;        // the flags as the last select left them (all 1 after create / reset)
     std::vector<int32_t> h_samples, h_k;  // the host's mirror of samples, and the last add's k per tile
     int rounds = 0;
+    ~ptx_adaptive() { if (h_out) (void)hipHostFree(h_out); }
     uint8_t *d_active() const { return d_out + sizeof(ptx_adaptive_status); }
 };
 

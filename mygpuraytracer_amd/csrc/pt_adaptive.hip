@@ -175,23 +175,15 @@ __global__ __launch_bounds__(PT_BX * PT_BY) void k_adaptive_prep(int w, int h, i
     c[p] = make_float4(r, g, b, v);
 }
 
-void free_adaptive(ptx_adaptive *a) {
-    (void)hipFree(a->d_samples); (void)hipFree(a->d_batches); (void)hipFree(a->d_nest); (void)hipFree(a->d_err); (void)hipFree(a->d_kt);
-    (void)hipFree(a->d_out); (void)hipFree(a->d_frame);
-    if (a->h_out) (void)hipHostFree(a->h_out);
-    if (a->ev) (void)hipEventDestroy(a->ev);
-    delete a;
-}
-
 // everything as after create, on the null stream, synchronously
 int clear_adaptive(ptx_adaptive *a) {
     const size_t nt = (size_t)a->ntiles;
-    PT_HC(hipMemset(a->d_samples, 0, sizeof(int32_t) * nt)); PT_HC(hipMemset(a->d_batches, 0, sizeof(int32_t) * nt));
-    PT_HC(hipMemset(a->d_nest, 0, sizeof(int32_t) * nt)); PT_HC(hipMemset(a->d_err, 0, sizeof(float) * nt));
-    PT_HC(hipMemset(a->d_kt, 0, sizeof(float2) * nt));
+    PT_HC(a->d_samples.zero()); PT_HC(a->d_batches.zero());
+    PT_HC(a->d_nest.zero()); PT_HC(a->d_err.zero());
+    PT_HC(a->d_kt.zero());
     PT_HC(hipMemset(a->d_out, 0, sizeof(ptx_adaptive_status)));
     PT_HC(hipMemset(a->d_active(), 1, nt));
-    PT_HC(hipMemset(a->d_frame, 0, sizeof(float) * 3 * (size_t)a->w * a->h));
+    PT_HC(a->d_frame.zero());
     PT_HC(hipDeviceSynchronize());
     a->h_active.assign(nt, 1); a->h_samples.assign(nt, 0); a->h_k.assign(nt, 0);
     a->rounds = 0;
@@ -199,14 +191,15 @@ int clear_adaptive(ptx_adaptive *a) {
 }
 
 int alloc_adaptive(ptx_adaptive *a) {
+    a->ntiles = pt_moments_tiles(a->w, a->h);
     const size_t nt = (size_t)a->ntiles, bytes = sizeof(ptx_adaptive_status) + nt;
     PT_HC(hipSetDevice(a->device));
-    PT_HC(hipMalloc(&a->d_samples, sizeof(int32_t) * nt)); PT_HC(hipMalloc(&a->d_batches, sizeof(int32_t) * nt));
-    PT_HC(hipMalloc(&a->d_nest, sizeof(int32_t) * nt)); PT_HC(hipMalloc(&a->d_err, sizeof(float) * nt));
-    PT_HC(hipMalloc(&a->d_kt, sizeof(float2) * nt));
-    PT_HC(hipMalloc(&a->d_out, bytes));
+    PT_HC(a->d_samples.alloc(nt)); PT_HC(a->d_batches.alloc(nt));
+    PT_HC(a->d_nest.alloc(nt)); PT_HC(a->d_err.alloc(nt));
+    PT_HC(a->d_kt.alloc(nt));
+    PT_HC(a->d_out.alloc(bytes));
     PT_HC(hipHostMalloc(&a->h_out, bytes, hipHostMallocDefault));
-    PT_HC(hipMalloc(&a->d_frame, sizeof(float) * 3 * (size_t)a->w * a->h));
+    PT_HC(a->d_frame.alloc(3 * (size_t)a->w * a->h));
     PT_HC(hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
     return clear_adaptive(a);
 }
@@ -242,7 +235,7 @@ hipError_t pt_adaptive_select_enqueue(hipStream_t st, const ptx_adaptive &a, con
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_adaptive_status, dim3(1), dim3(NT), 0, st, a.ntiles, npix, ptx_tile_pixels(), rounds, (const int32_t *)a.d_samples,
                        (const float *)a.d_err, (const int32_t *)a.d_nest, (const uint8_t *)a.d_active(),
-                       reinterpret_cast<ptx_adaptive_status *>(a.d_out));
+                       reinterpret_cast<ptx_adaptive_status *>(a.d_out.p));
     return hipGetLastError();
 }
 
@@ -275,35 +268,15 @@ size_t ptx_sizeof_adaptive_params(void) { return sizeof(ptx_adaptive_params); }
 size_t ptx_sizeof_adaptive_status(void) { return sizeof(ptx_adaptive_status); }
 
 int ptx_adaptive_create(int device, int width, int height, ptx_adaptive **out) {
-    if (!out) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_create: out is NULL");
-    *out = nullptr;
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 4) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_create: bad frame size");
-    if (device < 0) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_create: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return pt_fail(PTX_ERR_NODEVICE, "no HIP device available; the adaptive handle has no CPU path");
-    }
-    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_create: device ordinal out of range");
-    ptx_adaptive *a = new ptx_adaptive();
-    a->device = device; a->w = width; a->h = height; a->ntiles = pt_moments_tiles(width, height);
-    const int rc = alloc_adaptive(a);
-    if (rc != PTX_OK) { free_adaptive(a); return rc; }
-    *out = a;
-    return PTX_OK;
+    return pt_handle_create("ptx_adaptive_create", "the adaptive handle", device, width, height, INT_MAX / 4, out, alloc_adaptive);
 }
 
-void ptx_adaptive_destroy(ptx_adaptive *a) {
-    if (!a) return;
-    (void)hipSetDevice(a->device);
-    if (a->used) (void)hipEventSynchronize(a->ev);
-    free_adaptive(a);
-}
+void ptx_adaptive_destroy(ptx_adaptive *a) { pt_handle_destroy(a); }
 
 int ptx_adaptive_reset(ptx_adaptive *a) {
     if (!a) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_reset: null adaptive handle");
     PT_HC(hipSetDevice(a->device));
-    if (a->used) PT_HC(hipEventSynchronize(a->ev));
+    PT_HC(a->wait_host());
     return clear_adaptive(a);
 }
 
@@ -311,7 +284,7 @@ int ptx_adaptive_read(ptx_adaptive *a, float *mean_rgb, int32_t *samples_per_pix
     if (!a) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_read: null adaptive handle");
     const size_t n = (size_t)a->w * a->h, nt = (size_t)a->ntiles;
     PT_HC(hipSetDevice(a->device));
-    if (a->used) PT_HC(hipEventSynchronize(a->ev));
+    PT_HC(a->wait_host());
     if (mean_rgb) PT_HC(hipMemcpy(mean_rgb, a->d_frame, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
     if (tile_error) PT_HC(hipMemcpy(tile_error, a->d_err, sizeof(float) * nt, hipMemcpyDeviceToHost));
     if (tile_active) PT_HC(hipMemcpy(tile_active, a->d_active(), nt, hipMemcpyDeviceToHost));

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/mi355x_pathtracer.h"
+#include "pt_handle.h"
 
 struct PtTemporalState {
     float4 *nh = nullptr, *xn = nullptr, *dd = nullptr;
@@ -55,17 +56,17 @@ struct PtTemporalCamD {
     double minv[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
-struct ptx_temporal {
-    int device = 0, w = 0, h = 0;
-    PtTemporalState st[2];
+struct ptx_temporal : PtHandle {
+    DevBuf<float4> d_nh[2], d_xn[2], d_dd[2];
+    DevBuf<int2> d_ids[2];
+    PtTemporalState st[2];                // views of the four above, filled once, at create: what the kernels take
     int cur = 0;                          // st[cur] is cur, st[cur ^ 1] is hist
     ptx_camera cam[2];                    // the camera of each state
     bool cur_valid = false, hist_valid = false;
     bool has_v[2] = {false, false};       // st[i].dd.w holds a V (not after ptx_denoise_temporal, which writes 0 there)
-    float *d_mix = nullptr;               // W*H*3: the last call's mix (the filter's input)
-    float4 *d_hn = nullptr;               // W*H: the last call's (h rgb, n_h)
-    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
-    bool used = false, done = false;      // ev was recorded / d_mix, d_hn hold a result
+    DevBuf<float> d_mix;                  // W*H*3: the last call's mix (the filter's input)
+    DevBuf<float4> d_hn;                  // W*H: the last call's (h rgb, n_h)
+    bool done = false;                    // d_mix, d_hn hold a result
 };
 
 struct PtMomentsState {
@@ -79,13 +80,11 @@ struct PtMomentsPartial {
     unsigned long long n, over;
 };
 
-struct ptx_moments {
-    int device = 0, w = 0, h = 0;
-    PtMomentsState st;
-    float *d_stage = nullptr;             // W*H*3: ptx_moments_add_host's upload (first use)
-    PtMomentsPartial *d_part = nullptr;   // one per workgroup of the pixel grid, then the total
-    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
-    bool used = false;                    // ev was recorded
+struct ptx_moments : PtHandle {
+    DevBuf<float4> d_snap, d_mean, d_ma, d_mb;
+    PtMomentsState st;                    // a view of the four above, filled once, at create: what the kernels take
+    DevBuf<float> d_stage;                // W*H*3: ptx_moments_add_host's upload (first use)
+    DevBuf<PtMomentsPartial> d_part;      // one per workgroup of the pixel grid, then the total
     long long samples = 0;                // W: samples_total of the last add; 0 = fresh (the buffers are read as zeros)
     int batches = 0;                      // B
     // adds in which the tiles of ptx_tile_pixels() pixels advance by different amounts (k_moments_add_tiled).  `tiled` from the first of
@@ -93,7 +92,7 @@ struct ptx_moments {
     bool tiled = false;
     std::vector<long long> tile_samples;
     std::vector<int> tile_batches;
-    float2 *d_tile_kt = nullptr;          // ptx_moments_add_host_tiled's table (first use): (k, W') per tile
+    DevBuf<float2> d_tile_kt;             // ptx_moments_add_host_tiled's table (first use): (k, W') per tile
 };
 inline int pt_moments_tiles(int w, int h) { return (int)(((long long)w * h + ptx_tile_pixels() - 1) / ptx_tile_pixels()); }
 
@@ -109,12 +108,9 @@ __device__ __forceinline__ float quad_form(float g0, float g1, float g2, const f
 }
 
 // What pt_denoise.hip and pt_temporal.hip share: the pixel kernels' workgroup of 64 x 4 pixels (a wave is one 64-pixel row segment)
-// and its grid; and, with every unit but pt_engine.hip, the ptx_last_error of a failed call and the checked HIP call of their entry points.
+// and its grid (pt_fail and PT_HC, which every unit but pt_engine.hip reports through, are pt_handle.h's).
 constexpr int PT_BX = 64, PT_BY = 4;
 inline dim3 pt_pixel_grid(int w, int h) { return dim3((unsigned)((w + PT_BX - 1) / PT_BX), (unsigned)((h + PT_BY - 1) / PT_BY)); }
-extern "C" void ptx_internal_set_error(const char *msg);
-inline int pt_fail(int code, const std::string &msg) { ptx_internal_set_error(msg.c_str()); return code; }
-#define PT_HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return pt_fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 // NULL when the parameters are usable, else what is wrong with them (the ptx_last_error message)
 const char *pt_denoise_params_problem(const ptx_denoise_params &p);

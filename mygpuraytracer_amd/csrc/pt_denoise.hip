@@ -195,19 +195,6 @@ __global__ __launch_bounds__(BX * BY) void k_atrous_pass(int w, int h, int step,
     }
 }
 
-template <class T> struct DevMem {
-    T *p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem &) = delete;
-    DevMem &operator=(const DevMem &) = delete;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, sizeof(T) * (n ? n : 1)); }
-    hipError_t upload(const void *src, size_t n) {
-        const hipError_t e = alloc(n);
-        return e != hipSuccess ? e : hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice);
-    }
-};
-
 // The two ptx_denoise_buffers* entry points: arguments checked under the caller's name `fn`, float3 -> float4 staging, upload, the
 // filter on the null stream, download.  variance == false: the plain filter (ids2, var1, vparams and out_var1 are not looked at).
 int denoise_buffers(const char *fn, bool variance, int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3,
@@ -240,9 +227,9 @@ int denoise_buffers(const char *fn, bool variance, int device, int w, int h, con
         hal[i] = alb3 ? make_float4(alb3[3 * i], alb3[3 * i + 1], alb3[3 * i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     PT_HC(hipSetDevice(device));
-    DevMem<float> d_rgb, d_out, d_var, d_vout;
-    DevMem<float4> d_nh, d_xt, d_al, d_t0, d_t1;
-    DevMem<int2> d_ids;
+    DevBuf<float> d_rgb, d_out, d_var, d_vout;           // (n >= 1: no array of no elements)
+    DevBuf<float4> d_nh, d_xt, d_al, d_t0, d_t1;
+    DevBuf<int2> d_ids;
     PT_HC(d_out.alloc(3 * n)); PT_HC(d_t0.alloc(n)); PT_HC(d_t1.alloc(n));
     PT_HC(d_rgb.upload(rgb, 3 * n));
     PT_HC(d_nh.upload(hnh.data(), n)); PT_HC(d_xt.upload(hxt.data(), n)); PT_HC(d_al.upload(hal.data(), n));

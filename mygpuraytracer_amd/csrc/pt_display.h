@@ -24,17 +24,14 @@ struct PtDisplayState {
     long long frames;                     // metered frames since create / reset
 };
 
-struct ptx_display {
-    int device = 0, w = 0, h = 0;
+struct ptx_display : PtHandle {
     int hk = 0, wk = 0;                   // the block grid: (h + 8) / 16 x (w + 8) / 16
-    float *d_blocks = nullptr;
-    int32_t *d_begin = nullptr;           // hk + 1 row boundaries, then wk + 1 column boundaries
-    PtDisplayState *d_state = nullptr;
-    uchar4 *d_codes = nullptr;
-    float *d_float = nullptr;             // first keep_float call
-    float *d_stage = nullptr;             // W*H*3: ptx_display_host's upload (first use)
-    hipEvent_t ev = nullptr;              // recorded after each call's work (on that call's stream)
-    bool used = false;                    // ev was recorded
+    DevBuf<float> d_blocks;
+    DevBuf<int32_t> d_begin;              // hk + 1 row boundaries, then wk + 1 column boundaries
+    DevBuf<PtDisplayState> d_state;
+    DevBuf<uchar4> d_codes;
+    DevBuf<float> d_float;                // first keep_float call
+    DevBuf<float> d_stage;                // W*H*3: ptx_display_host's upload (first use)
     bool fresh = true;                    // the next metered frame is the first after create / reset: applied = metered
     bool metered = false;                 // d_blocks and d_state hold a frame's (since create / reset)
     bool codes_own = false;               // the last call's codes are in d_codes (else in the caller's buffer, or there was no call)

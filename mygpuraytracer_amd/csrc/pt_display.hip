@@ -186,28 +186,18 @@ __global__ __launch_bounds__(NT) void k_display_map(int n, MapArgs a, const PtDi
     if (KEEP) { zout[3 * (size_t)p] = zr; zout[3 * (size_t)p + 1] = zg; zout[3 * (size_t)p + 2] = zb; }
 }
 
-int no_device(const char *what) {
-    (void)hipGetLastError();
-    return pt_fail(PTX_ERR_NODEVICE, std::string("no HIP device available; ") + what + " has no CPU path");
-}
-
-void free_display(ptx_display *d) {
-    (void)hipFree(d->d_blocks); (void)hipFree(d->d_begin); (void)hipFree(d->d_state); (void)hipFree(d->d_codes); (void)hipFree(d->d_float); (void)hipFree(d->d_stage);
-    if (d->ev) (void)hipEventDestroy(d->ev);
-    delete d;
-}
-
 int alloc_display(ptx_display *d) {
     const size_t n = (size_t)d->w * d->h;
+    pt_display_grid(d->w, d->h, &d->hk, &d->wk);
+    if (d->hk == 0 || d->wk == 0) d->hk = d->wk = 0;
     PT_HC(hipSetDevice(d->device));
-    PT_HC(hipMalloc(&d->d_blocks, sizeof(float) * std::max<size_t>((size_t)d->hk * d->wk, 1)));
+    PT_HC(d->d_blocks.alloc(std::max<size_t>((size_t)d->hk * d->wk, 1)));
     std::vector<int32_t> begin((size_t)d->hk + d->wk + 2, 0);
     pt_display_begins(d->w, d->h, d->hk, d->wk, begin.data(), begin.data() + d->hk + 1);
-    PT_HC(hipMalloc(&d->d_begin, sizeof(int32_t) * begin.size()));
-    PT_HC(hipMemcpy(d->d_begin, begin.data(), sizeof(int32_t) * begin.size(), hipMemcpyHostToDevice));
-    PT_HC(hipMalloc(&d->d_state, sizeof(PtDisplayState)));
-    PT_HC(hipMemset(d->d_state, 0, sizeof(PtDisplayState)));
-    PT_HC(hipMalloc(&d->d_codes, sizeof(uchar4) * n));
+    PT_HC(d->d_begin.upload(begin));
+    PT_HC(d->d_state.alloc(1));
+    PT_HC(d->d_state.zero());
+    PT_HC(d->d_codes.alloc(n));
     PT_HC(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
     return PTX_OK;
 }
@@ -249,8 +239,8 @@ const char *pt_display_params_problem(const ptx_display_params &p, float samples
 
 int pt_display_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float samples, const ptx_display_params &p, void *device_uchar4) {
     const int n = d->w * d->h, nblocks = d->hk * d->wk;
-    if (p.keep_float && !d->d_float) PT_HC(hipMalloc(&d->d_float, sizeof(float) * 3 * (size_t)n));      // 12 B per pixel, only for who asks
-    if (d->used) PT_HC(hipStreamWaitEvent(st, d->ev, 0));            // the handle's last work, maybe on another stream
+    if (p.keep_float && !d->d_float) PT_HC(d->d_float.alloc(3 * (size_t)n));      // 12 B per pixel, only for who asks
+    PT_HC(d->wait_stream(st));                                       // the handle's last work, maybe on another stream
     const bool blocks = p.meter == PTX_METER_BLOCKS;
     if (blocks) {
         if (nblocks > 0) {
@@ -269,13 +259,12 @@ int pt_display_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float s
     a.tone = p.tone; a.transfer = p.transfer; a.quantize = p.quantize; a.dither = p.quantize && p.dither ? 1 : 0;
     a.w = d->w;
     unsigned *out = reinterpret_cast<unsigned *>(device_uchar4 ? device_uchar4 : (void *)d->d_codes);
-    float *zout = p.keep_float ? d->d_float : nullptr;
-    const PtDisplayState *state = blocks ? d->d_state : nullptr;
+    float *zout = p.keep_float ? d->d_float.p : nullptr;
+    const PtDisplayState *state = blocks ? d->d_state.p : nullptr;
     if (aligned16(rgb) && aligned16(out)) launch_map<true>(st, n, a, state, rgb, out, zout);
     else launch_map<false>(st, n, a, state, rgb, out, zout);         // a caller's pointer off the 16-byte grid: the per-pixel form
     PT_HC(hipGetLastError());
-    PT_HC(hipEventRecord(d->ev, st));
-    d->used = true;
+    PT_HC(d->record(st));
     d->codes_own = device_uchar4 == nullptr;
     d->float_valid = p.keep_float != 0;
     return PTX_OK;
@@ -309,29 +298,10 @@ int ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin,
 }
 
 int ptx_display_create(int device, int width, int height, ptx_display **out) {
-    if (!out) return pt_fail(PTX_ERR_INVALID, "ptx_display_create: out is NULL");
-    *out = nullptr;
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 4) return pt_fail(PTX_ERR_INVALID, "ptx_display_create: bad frame size");
-    if (device < 0) return pt_fail(PTX_ERR_INVALID, "ptx_display_create: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device("the display handle");
-    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, "ptx_display_create: device ordinal out of range");
-    ptx_display *d = new ptx_display();
-    d->device = device; d->w = width; d->h = height;
-    pt_display_grid(width, height, &d->hk, &d->wk);
-    if (d->hk == 0 || d->wk == 0) d->hk = d->wk = 0;
-    const int rc = alloc_display(d);
-    if (rc != PTX_OK) { free_display(d); return rc; }
-    *out = d;
-    return PTX_OK;
+    return pt_handle_create("ptx_display_create", "the display handle", device, width, height, INT_MAX / 4, out, alloc_display);
 }
 
-void ptx_display_destroy(ptx_display *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    if (d->used) (void)hipEventSynchronize(d->ev);
-    free_display(d);
-}
+void ptx_display_destroy(ptx_display *d) { pt_handle_destroy(d); }
 
 int ptx_display_reset(ptx_display *d) {
     if (!d) return pt_fail(PTX_ERR_INVALID, "ptx_display_reset: null display handle");
@@ -358,8 +328,8 @@ int ptx_display_host(ptx_display *d, const float *host_rgb, float samples, const
     if (!d || !host_rgb) return pt_fail(PTX_ERR_INVALID, "ptx_display_host: null display handle or frame");
     const size_t n = (size_t)d->w * d->h;
     PT_HC(hipSetDevice(d->device));
-    if (d->used) PT_HC(hipEventSynchronize(d->ev));
-    if (!d->d_stage) PT_HC(hipMalloc(&d->d_stage, sizeof(float) * 3 * n));
+    PT_HC(d->wait_host());
+    if (!d->d_stage) PT_HC(d->d_stage.alloc(3 * n));
     PT_HC(hipMemcpy(d->d_stage, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
     if (const int rc = pt_display_enqueue(d, nullptr, d->d_stage, samples, p, nullptr)) return rc;
     PT_HC(hipEventSynchronize(d->ev));

@@ -211,26 +211,15 @@ __global__ __launch_bounds__(NT) void k_moments_prep(int w, int h, int pairs, co
     c[p] = make_float4(r, g, b, v);
 }
 
-int no_device(const char *what) {
-    (void)hipGetLastError();
-    return pt_fail(PTX_ERR_NODEVICE, std::string("no HIP device available; ") + what + " has no CPU path");
-}
-
-void free_moments(ptx_moments *m) {
-    (void)hipFree(m->st.snap); (void)hipFree(m->st.mean); (void)hipFree(m->st.ma); (void)hipFree(m->st.mb);
-    (void)hipFree(m->d_stage); (void)hipFree(m->d_part); (void)hipFree(m->d_tile_kt);
-    if (m->ev) (void)hipEventDestroy(m->ev);
-    delete m;
-}
-
 int alloc_moments(ptx_moments *m) {
     const size_t n = (size_t)m->w * m->h;
     const dim3 grid = pt_pixel_grid(m->w, m->h);
     PT_HC(hipSetDevice(m->device));
-    PT_HC(hipMalloc(&m->st.snap, sizeof(float4) * n)); PT_HC(hipMalloc(&m->st.mean, sizeof(float4) * n));
-    PT_HC(hipMalloc(&m->st.ma, sizeof(float4) * n));
-    PT_HC(hipMalloc(&m->st.mb, sizeof(float4) * (size_t)pt_moments_pairs(m->w) * m->h));
-    PT_HC(hipMalloc(&m->d_part, sizeof(PtMomentsPartial) * ((size_t)grid.x * grid.y + 1)));
+    PT_HC(m->d_snap.alloc(n)); PT_HC(m->d_mean.alloc(n));
+    PT_HC(m->d_ma.alloc(n));
+    PT_HC(m->d_mb.alloc((size_t)pt_moments_pairs(m->w) * m->h));
+    m->st.snap = m->d_snap; m->st.mean = m->d_mean; m->st.ma = m->d_ma; m->st.mb = m->d_mb;
+    PT_HC(m->d_part.alloc((size_t)grid.x * grid.y + 1));
     PT_HC(hipEventCreateWithFlags(&m->ev, hipEventDisableTiming));
     return PTX_OK;
 }
@@ -292,27 +281,10 @@ size_t ptx_sizeof_moments_params(void) { return sizeof(ptx_moments_params); }
 size_t ptx_sizeof_moments_summary(void) { return sizeof(ptx_moments_summary); }
 
 int ptx_moments_create(int device, int width, int height, ptx_moments **out) {
-    if (!out) return pt_fail(PTX_ERR_INVALID, "ptx_moments_create: out is NULL");
-    *out = nullptr;
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 4) return pt_fail(PTX_ERR_INVALID, "ptx_moments_create: bad frame size");
-    if (device < 0) return pt_fail(PTX_ERR_INVALID, "ptx_moments_create: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device("the moments handle");
-    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, "ptx_moments_create: device ordinal out of range");
-    ptx_moments *m = new ptx_moments();
-    m->device = device; m->w = width; m->h = height;
-    const int rc = alloc_moments(m);
-    if (rc != PTX_OK) { free_moments(m); return rc; }
-    *out = m;
-    return PTX_OK;
+    return pt_handle_create("ptx_moments_create", "the moments handle", device, width, height, INT_MAX / 4, out, alloc_moments);
 }
 
-void ptx_moments_destroy(ptx_moments *m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->used) (void)hipEventSynchronize(m->ev);
-    free_moments(m);
-}
+void ptx_moments_destroy(ptx_moments *m) { pt_handle_destroy(m); }
 
 int ptx_moments_reset(ptx_moments *m) {
     if (!m) return pt_fail(PTX_ERR_INVALID, "ptx_moments_reset: null moments handle");
@@ -332,12 +304,11 @@ int ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samp
     if (m->tiled) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: this handle has had a tiled add; its tiles hold different sample counts until ptx_moments_reset");
     const size_t n = (size_t)m->w * m->h;
     PT_HC(hipSetDevice(m->device));
-    if (m->used) PT_HC(hipEventSynchronize(m->ev));
-    if (!m->d_stage) PT_HC(hipMalloc(&m->d_stage, sizeof(float) * 3 * n));
+    PT_HC(m->wait_host());
+    if (!m->d_stage) PT_HC(m->d_stage.alloc(3 * n));
     PT_HC(hipMemcpy(m->d_stage, host_rgb_sum, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
     PT_HC(pt_moments_add_enqueue(nullptr, m->w, m->h, m->d_stage, (float)(samples_total - m->samples), (float)samples_total, m->samples == 0, m->st));
-    PT_HC(hipEventRecord(m->ev, nullptr));
-    m->used = true;
+    PT_HC(m->record(nullptr));
     m->samples = samples_total;
     m->batches++;
     PT_HC(hipEventSynchronize(m->ev));
@@ -361,14 +332,13 @@ int ptx_moments_add_host_tiled(ptx_moments *m, const float *host_rgb_sum, const 
     }
     const size_t n = (size_t)m->w * m->h;
     PT_HC(hipSetDevice(m->device));
-    if (m->used) PT_HC(hipEventSynchronize(m->ev));
-    if (!m->d_stage) PT_HC(hipMalloc(&m->d_stage, sizeof(float) * 3 * n));
-    if (!m->d_tile_kt) PT_HC(hipMalloc(&m->d_tile_kt, sizeof(float2) * (size_t)ntiles));
+    PT_HC(m->wait_host());
+    if (!m->d_stage) PT_HC(m->d_stage.alloc(3 * n));
+    if (!m->d_tile_kt) PT_HC(m->d_tile_kt.alloc((size_t)ntiles));
     PT_HC(hipMemcpy(m->d_stage, host_rgb_sum, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
     PT_HC(hipMemcpy(m->d_tile_kt, kt.data(), sizeof(float2) * (size_t)ntiles, hipMemcpyHostToDevice));
     if (const int rc = pt_moments_add_tiled(m, nullptr, m->d_stage, m->d_tile_kt, hk.data())) return rc;
-    PT_HC(hipEventRecord(m->ev, nullptr));
-    m->used = true;
+    PT_HC(m->record(nullptr));
     PT_HC(hipEventSynchronize(m->ev));
     return PTX_OK;
 }

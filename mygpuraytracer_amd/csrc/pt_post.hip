@@ -2,7 +2,7 @@
 // (pt_tracer.h) to the post-processing units -- the a-trous filter and its variance guidance (pt_denoise.hip), the temporal reprojection
 // (pt_temporal.hip), the batch-means moments (pt_moments.hip), adaptive sampling (pt_adaptive.hip) and the display transform
 // (pt_display.hip).  No __global__ function, no launch and no environment read: the kernels are those units', the G-buffer pass and the
-// tile mask are pt_engine.hip's (pt_ensure_gbuffer, pt_set_tile_mask).  Errors go through pt_fail / PT_HC (pt_denoise.h), which set the
+// tile mask are pt_engine.hip's (pt_ensure_gbuffer, pt_set_tile_mask).  Errors go through pt_fail / PT_HC (pt_handle.h), which set the
 // thread's ptx_last_error as pt_engine.hip's own do.
 //
 // The six ptx_denoise* entry points are one pipeline, denoise_run: each of them defaults its parameters, says in a DenoiseCall what it
@@ -39,21 +39,21 @@ int guides_refuse_history(const char *fn) {
 
 // A handle against the tracer it is used with: the tracer holds the whole frame, and the handle (`kind`: "temporal", "moments",
 // "adaptive", "display") was made on its device and for its size.  same_tiles: the adaptive handle's tile count, part of its size.
-int frame_handle_problem(const char *fn, const ptx_tracer *t, const char *kind, int device, int w, int h, bool same_tiles = true) {
+int frame_handle_problem(const char *fn, const ptx_tracer *t, const char *kind, const PtHandle &x, bool same_tiles = true) {
     if (const int rc = pt_whole_frame_problem(fn, t)) return rc;
-    if (device != t->device)
-        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the " + kind + " handle was created on device " + std::to_string(device) +
+    if (x.device != t->device)
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the " + kind + " handle was created on device " + std::to_string(x.device) +
                                             ", the tracer runs on device " + std::to_string(t->device));
-    if (w != t->cam.resx || h != t->cam.resy || !same_tiles)
-        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the " + kind + " handle's size " + std::to_string(w) + " x " + std::to_string(h) +
+    if (x.w != t->cam.resx || x.h != t->cam.resy || !same_tiles)
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the " + kind + " handle's size " + std::to_string(x.w) + " x " + std::to_string(x.h) +
                                             " differs from the tracer's " + std::to_string(t->cam.resx) + " x " + std::to_string(t->cam.resy));
     return PTX_OK;
 }
 int moments_problem(const char *fn, const ptx_tracer *t, const ptx_moments *m) {
-    return frame_handle_problem(fn, t, "moments", m->device, m->w, m->h);
+    return frame_handle_problem(fn, t, "moments", *m);
 }
 int adaptive_problem(const char *fn, const ptx_tracer *t, const ptx_adaptive *a) {
-    return frame_handle_problem(fn, t, "adaptive", a->device, a->w, a->h, a->ntiles == t->maxTiles);
+    return frame_handle_problem(fn, t, "adaptive", *a, a->ntiles == t->maxTiles);
 }
 
 const char *const TILED_HANDLE = "this moments handle has had a tiled add: its tiles hold different sample counts until ptx_moments_reset";
@@ -71,22 +71,12 @@ int tile_samples_problem(const char *fn, const ptx_adaptive *a, const ptx_moment
     return PTX_OK;
 }
 
-// A handle's order with the tracer's stream (ptx_temporal, ptx_moments, ptx_adaptive: `ev`, `used`).  wait_for: what the call enqueues
-// next runs after the handle's last work, maybe on another tracer's stream.  mark: the handle's event behind what the call has enqueued
-// so far, for the next call on the handle to wait for.
-template <class Hd> hipError_t wait_for(ptx_tracer *t, const Hd *x) { return x->used ? hipStreamWaitEvent(t->stream, x->ev, 0) : hipSuccess; }
-template <class Hd> hipError_t mark(ptx_tracer *t, Hd *x) {
-    const hipError_t e = hipEventRecord(x->ev, t->stream);
-    if (e == hipSuccess) x->used = true;
-    return e;
-}
-
 // The handle's step on the tracer's stream: wait for the handle's last work, start a new segment when the camera changed (cur becomes
 // hist), then reproject hist into the current view and mix (with V when variance; moments: ptx_denoise_temporal_measured's V, from that
 // state with its `batches`).
 int temporal_step(ptx_tracer *t, ptx_temporal *h, const ptx_temporal_params &tp, int spp, bool variance, const PtMomentsState *moments,
                   int batches) {
-    PT_HC(wait_for(t, h));
+    PT_HC(h->wait_stream(t->stream));
     ptx_camera cam;
     memcpy(&cam, &t->cam, sizeof cam);
     if (!h->cur_valid || memcmp(&cam, &h->cam[h->cur], sizeof cam) != 0) {
@@ -160,7 +150,7 @@ int denoise_run(const DenoiseCall &c) {
         // messages (the moments state is not read: the handle is neither waited for nor marked)
         if (h && m->batches < min_batches) return ptx_denoise_variance(t, h, &c.dp, &c.tp, &c.vp, c.spp);
     }
-    if (const int rc = h ? frame_handle_problem(fn, t, "temporal", h->device, h->w, h->h) : pt_whole_frame_problem(fn, t)) return rc;
+    if (const int rc = h ? frame_handle_problem(fn, t, "temporal", *h) : pt_whole_frame_problem(fn, t)) return rc;
 
     // the buffers the filter needs, allocated on first use (d_var: by the variance-guided calls; the specular flags: by the first call
     // with a temporal handle), and the G-buffer of the current camera
@@ -181,8 +171,8 @@ int denoise_run(const DenoiseCall &c) {
 
     // the filter's input into d_dn_tmp.  The accumulation buffer is read on the tracer's stream, where every gather runs, those of
     // iterations traced ahead included.
-    if (a) PT_HC(wait_for(t, a));
-    if (m) PT_HC(wait_for(t, m));
+    if (a) PT_HC(a->wait_stream(t->stream));
+    if (m) PT_HC(m->wait_stream(t->stream));
     const enum { ACCUMULATED, HISTORY, MOMENTS, TILES } input = h ? HISTORY : c.kind == MEASURED ? MOMENTS : c.kind == ADAPTIVE ? TILES : ACCUMULATED;
     switch (input) {
     case ACCUMULATED:                                    // PLAIN, VARIANCE without a handle
@@ -190,7 +180,7 @@ int denoise_run(const DenoiseCall &c) {
         break;
     case HISTORY: {                                      // TEMPORAL: the mix; VARIANCE with a handle, TEMPORAL_MEASURED: the state, with its V
         if (const int rc = temporal_step(t, h, c.tp, c.spp, variance, m ? &m->st : nullptr, m ? m->batches : 0)) return rc;
-        if (m) PT_HC(mark(t, m));                        // (the handle's next add, maybe on another stream, waits for this read)
+        if (m) PT_HC(m->record(t->stream));              // (the handle's next add, maybe on another stream, waits for this read)
         const PtTemporalState &cur = h->st[h->cur];
         if (!variance) PT_HC(pt_atrous_prep_enqueue(t->stream, (int)n, h->d_mix, 1.0f, g, g + 2 * n, demod, 0, nullptr, t->d_dn_tmp));
         // the spatial estimate where hist supplied no V (with the moments none: every hit pixel's dd.w is a V already, nothing is -1)
@@ -201,12 +191,12 @@ int denoise_run(const DenoiseCall &c) {
     }
     case MOMENTS:
         PT_HC(pt_moments_prep_enqueue(t->stream, W, H, t->d_image, (float)c.spp, g, g + 2 * n, demod, m->st, min_batches, t->d_dn_tmp));
-        PT_HC(mark(t, m));                               // (the handle's next add, maybe on another stream, waits for this read)
+        PT_HC(m->record(t->stream));                     // (the handle's next add, maybe on another stream, waits for this read)
         break;
     case TILES:                                          // k_adaptive_prep in place of k_moments_prep, the rest as there
         PT_HC(pt_adaptive_prep_enqueue(t->stream, *a, t->d_image, g, g + 2 * n, demod, m->st, min_batches, t->d_dn_tmp));
-        PT_HC(mark(t, a));                               // (the handle's frame was written: ptx_adaptive_read waits for it)
-        PT_HC(mark(t, m));                               // (the handle's next add, maybe on another stream, waits for this read)
+        PT_HC(a->record(t->stream));                     // (the handle's frame was written: ptx_adaptive_read waits for it)
+        PT_HC(m->record(t->stream));                     // (the handle's next add, maybe on another stream, waits for this read)
         break;
     }
     // the spatial estimate for the hit pixels the input left at -1
@@ -215,7 +205,7 @@ int denoise_run(const DenoiseCall &c) {
     if (variance) PT_HC(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, c.dp, &c.vp, t->d_var, t->d_var + n));
     else PT_HC(pt_atrous_enqueue(t->stream, W, H, g, g + n, g + 2 * n, t->d_dn_tmp, t->d_dn_tmp + n, t->d_dn_out, c.dp));
     if (h) {                                             // the handle's end of a call: its event after the call's work
-        PT_HC(mark(t, h));
+        PT_HC(h->record(t->stream));
         h->done = true;
     }
     t->dn_done = true;
@@ -303,10 +293,10 @@ int ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total) {
     if (m->tiled) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add: " + std::string(TILED_HANDLE));
     if (const int rc = moments_problem("ptx_moments_add", t, m)) return rc;
     PT_HC(hipSetDevice(t->device));
-    PT_HC(wait_for(t, m));
+    PT_HC(m->wait_stream(t->stream));
     PT_HC(pt_moments_add_enqueue(t->stream, m->w, m->h, t->d_image, (float)(samples_total - m->samples), (float)samples_total,
                                  m->samples == 0, m->st));
-    PT_HC(mark(t, m));
+    PT_HC(m->record(t->stream));
     m->samples = samples_total;
     m->batches++;
     return PTX_OK;
@@ -320,16 +310,16 @@ int ptx_adaptive_add(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, int k) {
     if (const int rc = adaptive_problem("ptx_adaptive_add", t, a)) return rc;
     if (const int rc = tile_samples_problem("ptx_adaptive_add", a, m, k)) return rc;
     PT_HC(hipSetDevice(t->device));
-    PT_HC(wait_for(t, a));
-    PT_HC(wait_for(t, m));
+    PT_HC(a->wait_stream(t->stream));
+    PT_HC(m->wait_stream(t->stream));
     PT_HC(pt_adaptive_advance_enqueue(t->stream, *a, k));
     for (int i = 0; i < a->ntiles; i++) {
         a->h_k[(size_t)i] = a->h_active[(size_t)i] ? k : 0;
         a->h_samples[(size_t)i] += a->h_k[(size_t)i];
     }
     const int rc = pt_moments_add_tiled(m, t->stream, t->d_image, a->d_kt, a->h_k.data());
-    PT_HC(mark(t, a));
-    PT_HC(mark(t, m));
+    PT_HC(a->record(t->stream));
+    PT_HC(m->record(t->stream));
     return rc;
 }
 
@@ -343,14 +333,14 @@ int ptx_adaptive_select(ptx_adaptive *a, ptx_moments *m, ptx_tracer *t, const pt
     int code = 0;
     if (const char *why = pt_active_tiles_problem(t, a->ntiles, code)) return pt_fail(code, std::string("ptx_adaptive_select: ") + why);
     PT_HC(hipSetDevice(t->device));
-    PT_HC(wait_for(t, a));
-    PT_HC(wait_for(t, m));
+    PT_HC(a->wait_stream(t->stream));
+    PT_HC(m->wait_stream(t->stream));
     PT_HC(pt_adaptive_select_enqueue(t->stream, *a, m->st, p, a->rounds + 1));
-    PT_HC(mark(t, m));                                   // (the handle's next add, maybe on another stream, waits for this read)
+    PT_HC(m->record(t->stream));                         // (the handle's next add, maybe on another stream, waits for this read)
     const size_t bytes = sizeof(ptx_adaptive_status) + (size_t)a->ntiles;
     PT_HC(hipMemcpyAsync(a->h_out, a->d_out, bytes, hipMemcpyDeviceToHost, t->stream));      // the one small read: status and flags
     const int rc = pt_set_tile_mask(t, a->d_active());   // (waits for the stream: h_out is there)
-    PT_HC(mark(t, a));                                   // behind k_tile_mask, which reads the flags
+    PT_HC(a->record(t->stream));                         // behind k_tile_mask, which reads the flags
     if (rc != PTX_OK) return rc;
     a->rounds++;
     memcpy(status, a->h_out, sizeof *status);
@@ -362,9 +352,9 @@ int ptx_adaptive_resolve(ptx_adaptive *a, ptx_tracer *t) {
     if (!a || !t) return pt_fail(PTX_ERR_INVALID, "ptx_adaptive_resolve: null adaptive handle or tracer");
     if (const int rc = adaptive_problem("ptx_adaptive_resolve", t, a)) return rc;
     PT_HC(hipSetDevice(t->device));
-    PT_HC(wait_for(t, a));
+    PT_HC(a->wait_stream(t->stream));
     PT_HC(pt_adaptive_resolve_enqueue(t->stream, *a, t->d_image));
-    PT_HC(mark(t, a));
+    PT_HC(a->record(t->stream));
     return PTX_OK;
 }
 
@@ -378,7 +368,7 @@ int ptx_display_tracer(ptx_display *d, ptx_tracer *t, int source, int spp, const
     if (source == PTX_DISPLAY_IMAGE && spp < 1) return bad_spp("ptx_display_tracer");
     if (const char *why = pt_display_params_problem(p, samples)) return pt_fail(PTX_ERR_INVALID, why);
     if (!d || !t) return pt_fail(PTX_ERR_INVALID, "ptx_display_tracer: null display handle or tracer");
-    if (const int rc = frame_handle_problem("ptx_display_tracer", t, "display", d->device, d->w, d->h)) return rc;
+    if (const int rc = frame_handle_problem("ptx_display_tracer", t, "display", *d)) return rc;
     if (source == PTX_DISPLAY_DENOISED && !t->dn_done) return pt_fail(PTX_ERR_INVALID, "ptx_display_tracer: no ptx_denoise on this tracer yet");
     PT_HC(hipSetDevice(t->device));
     return pt_display_enqueue(d, t->stream, source == PTX_DISPLAY_IMAGE ? (const float *)t->d_image : (const float *)t->d_dn_out, samples, p,

@@ -237,52 +237,25 @@ void ptx_default_temporal_params(ptx_temporal_params *p) {
 
 size_t ptx_sizeof_temporal_params(void) { return sizeof(ptx_temporal_params); }
 
-static void free_temporal(ptx_temporal *t) {
-    for (PtTemporalState &s : t->st) { (void)hipFree(s.nh); (void)hipFree(s.xn); (void)hipFree(s.dd); (void)hipFree(s.ids); }
-    (void)hipFree(t->d_mix);
-    (void)hipFree(t->d_hn);
-    if (t->ev) (void)hipEventDestroy(t->ev);
-    delete t;
-}
-
 static int alloc_temporal(ptx_temporal *t) {
     const size_t n = (size_t)t->w * t->h;
     PT_HC(hipSetDevice(t->device));
-    for (PtTemporalState &s : t->st) {
-        PT_HC(hipMalloc(&s.nh, sizeof(float4) * n)); PT_HC(hipMalloc(&s.xn, sizeof(float4) * n));
-        PT_HC(hipMalloc(&s.dd, sizeof(float4) * n)); PT_HC(hipMalloc(&s.ids, sizeof(int2) * n));
+    for (int i = 0; i < 2; i++) {
+        PT_HC(t->d_nh[i].alloc(n)); PT_HC(t->d_xn[i].alloc(n));
+        PT_HC(t->d_dd[i].alloc(n)); PT_HC(t->d_ids[i].alloc(n));
+        t->st[i].nh = t->d_nh[i]; t->st[i].xn = t->d_xn[i]; t->st[i].dd = t->d_dd[i]; t->st[i].ids = t->d_ids[i];
     }
-    PT_HC(hipMalloc(&t->d_mix, sizeof(float) * 3 * n));
-    PT_HC(hipMalloc(&t->d_hn, sizeof(float4) * n));
+    PT_HC(t->d_mix.alloc(3 * n));
+    PT_HC(t->d_hn.alloc(n));
     PT_HC(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
     return PTX_OK;
 }
 
 int ptx_temporal_create(int device, int width, int height, ptx_temporal **out) {
-    if (!out) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: out is NULL");
-    *out = nullptr;
-    if (width < 1 || height < 1 || (long long)width * height > INT_MAX / 3) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: bad frame size");
-    if (device < 0) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return pt_fail(PTX_ERR_NODEVICE, "no HIP device available; the temporal denoiser has no CPU path");
-    }
-    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, "ptx_temporal_create: device ordinal out of range");
-    ptx_temporal *t = new ptx_temporal();
-    t->device = device; t->w = width; t->h = height;
-    const int rc = alloc_temporal(t);
-    if (rc != PTX_OK) { free_temporal(t); return rc; }
-    *out = t;
-    return PTX_OK;
+    return pt_handle_create("ptx_temporal_create", "the temporal denoiser", device, width, height, INT_MAX / 3, out, alloc_temporal);
 }
 
-void ptx_temporal_destroy(ptx_temporal *t) {
-    if (!t) return;
-    (void)hipSetDevice(t->device);
-    if (t->used) (void)hipEventSynchronize(t->ev);
-    free_temporal(t);
-}
+void ptx_temporal_destroy(ptx_temporal *t) { pt_handle_destroy(t); }
 
 int ptx_temporal_reset(ptx_temporal *t) {
     if (!t) return pt_fail(PTX_ERR_INVALID, "null temporal handle");
@@ -298,15 +271,12 @@ int ptx_temporal_read(ptx_temporal *t, float *hist_rgb3, float *hist_count1, flo
     PT_HC(hipEventSynchronize(t->ev));
     if (mix_rgb3) PT_HC(hipMemcpy(mix_rgb3, t->d_mix, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
     if (hist_rgb3 || hist_count1) {
-        float4 *hn = new float4[n];
-        const hipError_t e = hipMemcpy(hn, t->d_hn, sizeof(float4) * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess)
-            for (size_t i = 0; i < n; i++) {
-                if (hist_rgb3) { hist_rgb3[3 * i] = hn[i].x; hist_rgb3[3 * i + 1] = hn[i].y; hist_rgb3[3 * i + 2] = hn[i].z; }
-                if (hist_count1) hist_count1[i] = hn[i].w;
-            }
-        delete[] hn;
-        PT_HC(e);
+        std::vector<float4> hn(n);
+        PT_HC(hipMemcpy(hn.data(), t->d_hn, sizeof(float4) * n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) {
+            if (hist_rgb3) { hist_rgb3[3 * i] = hn[i].x; hist_rgb3[3 * i + 1] = hn[i].y; hist_rgb3[3 * i + 2] = hn[i].z; }
+            if (hist_count1) hist_count1[i] = hn[i].w;
+        }
     }
     return PTX_OK;
 }

@@ -1,5 +1,5 @@
 // pt_tracer.h -- the tracer itself, for the host units that work on one: struct ptx_tracer with the owned device array its buffers
-// are (DevBuf), and the few functions of pt_engine.hip that pt_post.hip calls.  pt_engine.hip creates, renders and frees a tracer;
+// are (DevBuf, pt_handle.h), and the few functions of pt_engine.hip that pt_post.hip calls.  pt_engine.hip creates, renders and frees a tracer;
 // pt_post.hip hands its buffers to the post-processing units (pt_denoise.hip, pt_temporal.hip, pt_moments.hip, pt_adaptive.hip,
 // pt_display.hip).  Not part of the C ABI.
 #pragma once
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mi355x_pathtracer.h"
+#include "pt_handle.h"
 #include "pt_kernels.h"
 #include "pt_scene.h"
 #include "pt_plan.h"
@@ -28,22 +29,6 @@ extern "C" const void *ptx_arith_kernels_0p(void) __attribute__((weak));
 extern "C" const void *ptx_arith_kernels_1p(void) __attribute__((weak));
 extern "C" const void *ptx_arith_last_0p(void) __attribute__((weak));
 extern "C" const void *ptx_arith_last_1p(void) __attribute__((weak));
-
-// An owned device array -- every device buffer of the tracer, the scratch of the per-stage entry points -- freed when its owner goes, on
-// every way out (a HIPCHECK that fails returns from the middle).  Each step hands back the hipError_t: ptx_create looks for out-of-memory.
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;                              // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    operator T *() const { return p; }
-    hipError_t alloc(size_t count) { n = count; return hipMalloc(&p, sizeof(T) * count); }      // (once per buffer; contents undefined)
-    hipError_t zero() { return hipMemset(p, 0, sizeof(T) * n); }
-    hipError_t upload(const void *src, size_t count) { const hipError_t e = alloc(count); return e != hipSuccess ? e : hipMemcpy(p, src, sizeof(T) * count, hipMemcpyHostToDevice); }
-    hipError_t upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
-    hipError_t download(void *dst) const { return hipMemcpy(dst, p, sizeof(T) * n, hipMemcpyDeviceToHost); }
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on and the debug switches `dbg`, pt_plan.h; what the scene decides, pt_scene.h)
