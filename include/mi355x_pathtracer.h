@@ -685,7 +685,8 @@ int  ptx_display_get_status(ptx_display *d, ptx_display_status *out);           
 int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin, int32_t *col_begin);
 
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
- *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device) --------------------------- */
+ *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
+ *      reprojection alone and needs no tracer ------------------------------------------------------------------- */
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10);
 /* objTriIntersectionTest / triangleIntersectionLocalTest, src/intersections.h:175-205, 284-315: dead code in the reference (its call is
  * commented out, src/pathtrace.cu:313) and on no path here; a known-answer entry point only.  out8 per ray: t (object space), world
@@ -716,6 +717,21 @@ int ptx_kat_fast_exact(ptx_tracer *t, int64_t mismatches[3]);
  * the guard's bounds) and random_sets random sets from the slab test's range; counts[3]: sets that took the shared reciprocal.  Two NaNs
  * count as equal.  counts[0] == counts[2] == 0 is the only acceptable answer. */
 int ptx_kat_unit_rsqrt(ptx_tracer *t, int exponent_reps, int64_t random_sets, int64_t counts[4]);
+/* The reprojection and mix of ptx_denoise_temporal (variant 0), ptx_denoise_variance (1) and ptx_denoise_temporal_measured (2) alone,
+ * over caller-owned host arrays of one W x H frame (as ptx_denoise_buffers; tests/test_gpu_temporal_grid.py): staged into the device
+ * layouts and run through the same camera set-up and launch as those entry points, synchronously on `device`.
+ *   hist_cam: the committed history's camera, resolution W x H; NULL = no history (the hist_* arrays are then not read).
+ *   tp NULL = defaults; spp >= 1; rgb = the accumulation (W*H*3), nrm3 / pos3 / alb3 (W*H*3), ids2 (W*H*2: material, geom) and hit
+ *   (W*H bytes) = the current guides; spec = nmats bytes (!= 0: reflective or refractive), may be NULL when nmats == 0.
+ *   hist_*: the hist state: hit bytes, normal, position, sample count n, D, V (NULL = the state carries none) and ids.
+ *   variant 2: scatter6 = W*H*6 floats (rr, gg, bb, rg, rb, gb) of a moments state's M and batches = its B >= 2.
+ * Outputs (NULLs allowed), the records the kernel writes: the new state's nh4 (normal, hit), xn4 (position, n), dd4 (D, V) and ids2,
+ * mix3 and hn4 (h, n_h).  Bad arguments: PTX_ERR_INVALID before the device is looked for; PTX_ERR_NODEVICE without one. */
+int ptx_kat_reproject(int device, int w, int h, int variant, const ptx_camera *hist_cam, const ptx_temporal_params *tp, int spp,
+                      const float *rgb, const float *nrm3, const float *pos3, const float *alb3, const int32_t *ids2, const uint8_t *hit,
+                      const uint8_t *spec, int nmats, const uint8_t *hist_hit, const float *hist_nrm3, const float *hist_pos3,
+                      const float *hist_n1, const float *hist_D3, const float *hist_V1, const int32_t *hist_ids2, const float *scatter6,
+                      int batches, float *out_nh4, float *out_xn4, float *out_dd4, int32_t *out_ids2, float *out_mix3, float *out_hn4);
 /* CPU-only (no device, no tracer): the per-tile geom masks the camera-ray bounce uses (bit g of masks_out[tile] clear = no camera ray of
  * that tile of 256 owned pixels can reach box g; boxes6 = lo xyz, hi xyz per geom, <= 32 geoms), for a camera, depth of field on / off and a
  * row-tile split.  Returns the number of tiles, -1 on a bad argument.  The CPU tests check the superset property ray by ray. */

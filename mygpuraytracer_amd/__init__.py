@@ -39,9 +39,10 @@ from .api import (  # noqa: F401
     tile_pixels,
     denoise_buffers,
     denoise_buffers_variance,
+    reproject_buffers,
     load_library,
 )
 
 __all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
            "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "default_adaptive_params", "tile_pixels", "denoise_buffers",
-           "denoise_buffers_variance", "load_library"]
+           "denoise_buffers_variance", "reproject_buffers", "load_library"]

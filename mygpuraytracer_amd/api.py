@@ -508,6 +508,56 @@ def denoise_buffers_variance(rgb, albedo, normal, position, hit, ids=None, varia
     return out, vout
 
 
+def _camera_struct(cam, w, h):
+    """a Camera, or a mapping with position / view / right / up (3 each) and pl or pixelLength (2), as a Camera of resolution w x h"""
+    if isinstance(cam, Camera):
+        return cam
+    c = Camera()
+    c.resolution[0], c.resolution[1] = int(cam.get("W", w)), int(cam.get("H", h))
+    for k in ("position", "view", "right", "up"):
+        for j in range(3):
+            getattr(c, k)[j] = float(cam[k][j])
+    pl = cam["pl"] if "pl" in cam else cam["pixelLength"]
+    c.pixelLength[0], c.pixelLength[1] = float(pl[0]), float(pl[1])
+    return c
+
+
+def reproject_buffers(rgb, albedo, normal, position, ids, hit, spec, hist=None, hist_camera=None, spp=1, variant=0, scatter=None,
+                      batches=0, device=0, **params):
+    """The temporal reprojection and mix alone (ptx_kat_reproject) on host arrays of one (H, W) frame, as denoise_buffers: rgb = the
+    accumulation of spp samples, albedo / normal / position (H, W, 3), ids (H, W, 2) int32 of (material, geom), hit (H, W), spec = one
+    flag per material.  hist_camera (a Camera, or a mapping with position, view, right, up, pl) and hist = dict(hit, normal, position, n,
+    D, ids and, when the state carries one, V) are the committed history; hist_camera None = none.  variant 0 / 1 / 2 = the kernel of
+    denoise_temporal / denoise_variance / denoise_temporal_measured; 2 takes scatter (H, W, 6) = (rr, gg, bb, rg, rb, gb) and batches.
+    params: the temporal parameters.  Returns a dict of float32 arrays nh (H, W, 4), xn (H, W, 4), dd (H, W, 4), mix (H, W, 3),
+    hn (H, W, 4) and ids (H, W, 2) int32: the new state's records, the mix and (h, n_h)."""
+    L = load_library()
+    h, w, rgb, alb, nrm, pos, hit = _frame_arrays("reproject_buffers", rgb, albedo, normal, position, hit)
+    f3 = lambda a: np.ascontiguousarray(a, np.float32).reshape(h * w, 3)
+    i2 = lambda a: np.ascontiguousarray(a, np.int32).reshape(h * w, 2)
+    ids = None if ids is None else i2(ids)
+    spec = np.ascontiguousarray(np.asarray(spec).reshape(-1) != 0, np.uint8)
+    cam, hh = None, [None] * 7
+    if hist_camera is not None:
+        cam = _camera_struct(hist_camera, w, h)
+        if hist is not None:
+            hh = [np.ascontiguousarray(np.asarray(hist["hit"]).reshape(h * w) != 0, np.uint8), f3(hist["normal"]), f3(hist["position"]),
+                  np.ascontiguousarray(hist["n"], np.float32).reshape(h * w), f3(hist["D"]),
+                  None if hist.get("V") is None else np.ascontiguousarray(hist["V"], np.float32).reshape(h * w), i2(hist["ids"])]
+    sc = None if scatter is None else np.ascontiguousarray(scatter, np.float32).reshape(h * w, 6)
+    for k in params:
+        if k not in _TEMPORAL_KEYS:
+            raise TypeError("reproject_buffers: unknown parameter %r" % (k,))
+    tp = default_temporal_params(**params)
+    out = dict(nh=np.zeros((h, w, 4), np.float32), xn=np.zeros((h, w, 4), np.float32), dd=np.zeros((h, w, 4), np.float32),
+               ids=np.zeros((h, w, 2), np.int32), mix=np.zeros((h, w, 3), np.float32), hn=np.zeros((h, w, 4), np.float32))
+    _check(L.ptx_kat_reproject(int(device), w, h, int(variant), None if cam is None else C.byref(cam), C.byref(tp), int(spp), _ptr(rgb),
+                               _opt_ptr(nrm), _opt_ptr(pos), _opt_ptr(alb), _opt_ptr(ids), _ptr(hit), _ptr(spec) if spec.size else None,
+                               int(spec.size), *[_opt_ptr(a) for a in hh], _opt_ptr(sc), int(batches), _ptr(out["nh"]), _ptr(out["xn"]),
+                               _ptr(out["dd"]), _ptr(out["ids"]), _ptr(out["mix"]), _ptr(out["hn"])), "ptx_kat_reproject")
+    return out
+
+
 def debug_tile_geoms(camera, boxes6, depth_of_field=False, tile=None):
     """CPU only: the per-tile geom masks of the camera-ray bounce (ptx_debug_tile_geoms) for a ctypes Camera, an (n, 6) array of world
     boxes (lo xyz, hi xyz) and an optional row-tile split (rows, rank, world).  Returns a uint32 array, one word per tile of 256 owned
@@ -795,6 +845,8 @@ def load_library():
     L.ptx_kat_shade.restype, L.ptx_kat_shade.argtypes = i, [vp, i, i, vp, vp, vp]
     L.ptx_kat_generate.restype, L.ptx_kat_generate.argtypes = i, [vp, i, vp]
     L.ptx_kat_libm.restype, L.ptx_kat_libm.argtypes = i, [vp, i, vp, vp, vp, vp, vp, vp, vp]
+    L.ptx_kat_reproject.restype = i
+    L.ptx_kat_reproject.argtypes = [i, i, i, i, C.POINTER(Camera), C.POINTER(TemporalParams), i] + [vp] * 7 + [i] + [vp] * 8 + [i] + [vp] * 6
     if hasattr(L, "ptx_debug_tile_geoms"):
         L.ptx_debug_tile_geoms.restype, L.ptx_debug_tile_geoms.argtypes = i, [vp, i, vp, i, i, i, i, vp, i]
     if hasattr(L, "ptx_debug_cull_boxes"):

@@ -281,4 +281,105 @@ int ptx_temporal_read(ptx_temporal *t, float *hist_rgb3, float *hist_count1, flo
     return PTX_OK;
 }
 
+// The reprojection alone over caller-owned host arrays (tests/test_gpu_temporal_grid.py): arguments checked, float3 -> float4 staging
+// into the layouts of pt_denoise.h, then pt_temporal_camera and pt_temporal_enqueue -- what temporal_step (pt_post.hip) calls -- on the
+// null stream, and the raw records back.  No kernel is launched here.
+int ptx_kat_reproject(int device, int w, int h, int variant, const ptx_camera *hist_cam, const ptx_temporal_params *params, int spp,
+                      const float *rgb, const float *nrm3, const float *pos3, const float *alb3, const int32_t *ids2, const uint8_t *hit,
+                      const uint8_t *spec, int nmats, const uint8_t *hist_hit, const float *hist_nrm3, const float *hist_pos3,
+                      const float *hist_n1, const float *hist_D3, const float *hist_V1, const int32_t *hist_ids2, const float *scatter6,
+                      int batches, float *out_nh4, float *out_xn4, float *out_dd4, int32_t *out_ids2, float *out_mix3, float *out_hn4) {
+    const std::string name = "ptx_kat_reproject";
+    ptx_temporal_params tp;
+    if (params) tp = *params;
+    else ptx_default_temporal_params(&tp);
+    if (w < 1 || h < 1 || (long long)w * h > INT_MAX / 4)
+        return pt_fail(PTX_ERR_INVALID, name + ": bad frame size " + std::to_string(w) + " x " + std::to_string(h));
+    if (variant < 0 || variant > 2) return pt_fail(PTX_ERR_INVALID, name + ": variant must be 0, 1 or 2, not " + std::to_string(variant));
+    if (spp < 1) return pt_fail(PTX_ERR_INVALID, name + ": spp must be >= 1, not " + std::to_string(spp));
+    if (nmats < 0) return pt_fail(PTX_ERR_INVALID, name + ": nmats must be >= 0, not " + std::to_string(nmats));
+    if (!rgb || !nrm3 || !pos3 || !alb3 || !ids2 || !hit) return pt_fail(PTX_ERR_INVALID, name + ": rgb, nrm3, pos3, alb3, ids2 and hit are required");
+    if (nmats > 0 && !spec) return pt_fail(PTX_ERR_INVALID, name + ": spec is required for nmats = " + std::to_string(nmats));
+    if (hist_cam && (!hist_hit || !hist_nrm3 || !hist_pos3 || !hist_n1 || !hist_D3 || !hist_ids2))
+        return pt_fail(PTX_ERR_INVALID, name + ": a hist camera needs hist_hit, hist_nrm3, hist_pos3, hist_n1, hist_D3 and hist_ids2");
+    if (hist_cam && (hist_cam->resolution[0] != w || hist_cam->resolution[1] != h))
+        return pt_fail(PTX_ERR_INVALID, name + ": the hist camera's resolution is " + std::to_string(hist_cam->resolution[0]) + " x " +
+                                            std::to_string(hist_cam->resolution[1]) + ", the frame " + std::to_string(w) + " x " + std::to_string(h));
+    if (variant == 2 && !scatter6) return pt_fail(PTX_ERR_INVALID, name + ": variant 2 needs scatter6");
+    if (variant == 2 && batches < 2) return pt_fail(PTX_ERR_INVALID, name + ": variant 2 needs batches >= 2, not " + std::to_string(batches));
+    if (const char *why = pt_temporal_params_problem(tp)) return pt_fail(PTX_ERR_INVALID, why);
+    if (device < 0) return pt_fail(PTX_ERR_INVALID, name + ": device ordinal out of range: " + std::to_string(device));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        return pt_fail(PTX_ERR_NODEVICE, "no HIP device available; the temporal denoiser has no CPU path");
+    }
+    if (device >= ndev) return pt_fail(PTX_ERR_INVALID, name + ": device ordinal out of range: " + std::to_string(device));
+
+    const size_t n = (size_t)w * h;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    std::vector<float4> gnh(n), gxt(n), gal(n), hnh(n, zero), hxn(n, zero), hdd(n, zero);
+    std::vector<int2> gid(n), hid(n, make_int2(0, 0));
+    for (size_t i = 0; i < n; i++) {
+        gnh[i] = make_float4(nrm3[3 * i], nrm3[3 * i + 1], nrm3[3 * i + 2], hit[i] ? 1.f : 0.f);
+        gxt[i] = make_float4(pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2], 0.f);
+        gal[i] = make_float4(alb3[3 * i], alb3[3 * i + 1], alb3[3 * i + 2], 0.f);
+        gid[i] = make_int2(ids2[2 * i], ids2[2 * i + 1]);
+        if (!hist_cam) continue;
+        hnh[i] = make_float4(hist_nrm3[3 * i], hist_nrm3[3 * i + 1], hist_nrm3[3 * i + 2], hist_hit[i] ? 1.f : 0.f);
+        hxn[i] = make_float4(hist_pos3[3 * i], hist_pos3[3 * i + 1], hist_pos3[3 * i + 2], hist_n1[i]);
+        hdd[i] = make_float4(hist_D3[3 * i], hist_D3[3 * i + 1], hist_D3[3 * i + 2], hist_V1 ? hist_V1[i] : 0.f);
+        hid[i] = make_int2(hist_ids2[2 * i], hist_ids2[2 * i + 1]);
+    }
+    const int pairs = pt_moments_pairs(w);
+    std::vector<float4> hma, hmb;
+    if (variant == 2) {                                  // pt_denoise.h: ma = (rr, gg, bb, rg), mb = (rb, gb) of a row's pixel pairs
+        hma.resize(n);
+        hmb.assign((size_t)h * pairs, zero);             // (the second half of an odd row's last record stays 0)
+        float2 *mb2 = reinterpret_cast<float2 *>(hmb.data());
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) {
+                const float *m = scatter6 + 6 * ((size_t)y * w + x);
+                hma[(size_t)y * w + x] = make_float4(m[0], m[1], m[2], m[3]);
+                mb2[(size_t)y * pairs * 2 + x] = make_float2(m[4], m[5]);
+            }
+    }
+    ptx_camera cam;
+    memset(&cam, 0, sizeof cam);
+    if (hist_cam) cam = *hist_cam;
+    PtTemporalCamD camd;
+    const PtTemporalCam hcam = pt_temporal_camera(cam, hist_cam != nullptr, &camd);
+
+    PT_HC(hipSetDevice(device));
+    DevBuf<float> d_rgb, d_mix;
+    DevBuf<float4> d_gnh, d_gxt, d_gal, d_hnh, d_hxn, d_hdd, d_cnh, d_cxn, d_cdd, d_hn, d_ma, d_mb;
+    DevBuf<int2> d_gid, d_hid, d_cid;
+    DevBuf<uint8_t> d_spec;
+    PT_HC(d_rgb.upload(rgb, 3 * n));
+    PT_HC(d_gnh.upload(gnh)); PT_HC(d_gxt.upload(gxt)); PT_HC(d_gal.upload(gal)); PT_HC(d_gid.upload(gid));
+    PT_HC(d_hnh.upload(hnh)); PT_HC(d_hxn.upload(hxn)); PT_HC(d_hdd.upload(hdd)); PT_HC(d_hid.upload(hid));
+    if (nmats > 0) PT_HC(d_spec.upload(spec, (size_t)nmats));
+    PT_HC(d_cnh.alloc(n)); PT_HC(d_cxn.alloc(n)); PT_HC(d_cdd.alloc(n)); PT_HC(d_cid.alloc(n));
+    PT_HC(d_mix.alloc(3 * n)); PT_HC(d_hn.alloc(n));
+    PtTemporalState cur, hist;
+    cur.nh = d_cnh; cur.xn = d_cxn; cur.dd = d_cdd; cur.ids = d_cid;
+    hist.nh = d_hnh; hist.xn = d_hxn; hist.dd = d_hdd; hist.ids = d_hid;
+    PtMomentsState ms;
+    if (variant == 2) {
+        PT_HC(d_ma.upload(hma)); PT_HC(d_mb.upload(hmb));
+        ms.ma = d_ma; ms.mb = d_mb;
+    }
+    PT_HC(pt_temporal_enqueue(nullptr, w, h, hcam, tp, d_rgb, (float)spp, d_gnh, d_gxt, d_gal, d_gid, d_spec, nmats, cur, hist, d_mix, d_hn,
+                              variant >= 1 ? 1 : 0, variant >= 1 && hist_cam && hist_V1 ? 1 : 0, variant == 2 ? &ms : nullptr,
+                              variant == 2 ? batches : 0, &camd));
+    PT_HC(hipStreamSynchronize(nullptr));
+    if (out_nh4) PT_HC(d_cnh.download(out_nh4));
+    if (out_xn4) PT_HC(d_cxn.download(out_xn4));
+    if (out_dd4) PT_HC(d_cdd.download(out_dd4));
+    if (out_ids2) PT_HC(d_cid.download(out_ids2));
+    if (out_mix3) PT_HC(d_mix.download(out_mix3));
+    if (out_hn4) PT_HC(d_hn.download(out_hn4));
+    return PTX_OK;
+}
+
 }  // extern "C"

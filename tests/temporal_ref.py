@@ -50,10 +50,13 @@ def state(gbuf, mix, n):
     return dict(gbuf=gbuf, D=np.where(hit[..., None], mix / a, mix), n=np.asarray(n, np.float64))
 
 
-def reproject(prev_cam, cur, prev, spec, max_history=16, specular_history=0, normal_cos=0.9, plane_tolerance=0.01):
+def reproject(prev_cam, cur, prev, spec, max_history=16, specular_history=0, normal_cos=0.9, plane_tolerance=0.01, reasons=None):
     """cur: the current G-buffer (Tracer.gbuffer()); prev: state() of the previous segment, prev_cam its camera_dict.
     Returns h (H, W, 3), n_h (H, W) and `near` (H, W): pixels where a decision of the definition is within EPS (relative) of its
-    threshold, or u or v within EPS pixels of an integer -- where fp32 and float64 may decide differently."""
+    threshold, or u or v within EPS pixels of an integer -- where fp32 and float64 may decide differently.
+    reasons: a dict that receives `near` by reason, "s", "grid" (u or v), "normal" and "plane" (H, W) each; their union is `near`.  It
+    also receives what tests/temporalcases.py asks of a case: "u", "v" (NaN where there is no projection), "capped" (sum w n / S above
+    max_history), and per test "normal_rejected", "normal_accepted", "plane_rejected", "plane_accepted": pixels with such a tap."""
     hit = np.asarray(cur["hit"]) != 0
     H, W = hit.shape
     xp = np.asarray(cur["position"], np.float64)
@@ -69,11 +72,13 @@ def reproject(prev_cam, cur, prev, spec, max_history=16, specular_history=0, nor
     s, u, v = project(prev_cam, xp)
     ok = considered & (s > 0) & np.isfinite(u) & np.isfinite(v)
     smax = np.abs(np.where(considered, s, 0.0)).max() if considered.any() else 1.0
-    near = considered & (np.abs(s) <= EPS * smax)
+    near_s = considered & (np.abs(s) <= EPS * smax)
     uu, vv = np.where(ok, u, -10.0), np.where(ok, v, -10.0)
     u0, v0 = np.floor(uu), np.floor(vv)
     fu, fv = uu - u0, vv - v0
-    near |= ok & ((fu <= EPS) | (fu >= 1 - EPS) | (fv <= EPS) | (fv >= 1 - EPS))
+    near_grid = ok & ((fu <= EPS) | (fu >= 1 - EPS) | (fv <= EPS) | (fv >= 1 - EPS))
+    near_normal, near_plane = np.zeros((H, W), bool), np.zeros((H, W), bool)
+    taps = {k: np.zeros((H, W), bool) for k in ("normal_rejected", "normal_accepted", "plane_rejected", "plane_accepted")}
     dist = np.linalg.norm(xp - prev_cam["position"], axis=-1)
     lim = plane_tolerance * dist
     sw, sn, sd = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W, 3))
@@ -86,9 +91,13 @@ def reproject(prev_cam, cur, prev, spec, max_history=16, specular_history=0, nor
             same = inside & phit[cy, cx] & (pmat[cy, cx] == mat) & (pgeom[cy, cx] == geom)
             dn = (npn * pnq[cy, cx]).sum(-1)
             pl = np.abs((npn * (pxq[cy, cx] - xp)).sum(-1))
-            near |= same & (np.abs(dn - normal_cos) <= EPS * max(abs(normal_cos), 1e-3))
-            near |= same & (dn >= normal_cos) & (np.abs(pl - lim) <= EPS * lim + 1e-9)
+            near_normal |= same & (np.abs(dn - normal_cos) <= EPS * max(abs(normal_cos), 1e-3))
+            near_plane |= same & (dn >= normal_cos) & (np.abs(pl - lim) <= EPS * lim + 1e-9)
             acc = same & (dn >= normal_cos) & (pl <= lim)
+            taps["normal_rejected"] |= same & ~(dn >= normal_cos)
+            taps["normal_accepted"] |= same & (dn >= normal_cos)
+            taps["plane_rejected"] |= same & (dn >= normal_cos) & ~(pl <= lim)
+            taps["plane_accepted"] |= acc
             w = np.where(acc, wt, 0.0)
             sw += w
             sn += w * prev["n"][cy, cx]
@@ -97,6 +106,10 @@ def reproject(prev_cam, cur, prev, spec, max_history=16, specular_history=0, nor
     nh = np.where(sw > 0, np.minimum(sn / safe, float(max_history)), 0.0)
     a = np.maximum(np.asarray(cur["albedo"], np.float64), 1e-3)
     h = np.where((nh > 0)[..., None], sd / safe[..., None] * a, 0.0)
+    near = near_s | near_grid | near_normal | near_plane
+    if reasons is not None:
+        reasons.update(taps, s=near_s, grid=near_grid, normal=near_normal, plane=near_plane, u=np.where(ok, u, np.nan),
+                       v=np.where(ok, v, np.nan), capped=(sw > 0) & (sn / safe > float(max_history)))
     return h, nh, near
 
 

@@ -1,7 +1,8 @@
 """GPU: temporal reuse in front of the a-trous denoiser (include/mi355x_pathtracer.h: ptx_denoise_temporal ...).  Without history it is
 ptx_denoise bit for bit; the reprojection and mix against their float64 restatement (tests/temporal_ref.py); segments; the history
 outliving the tracer; no side effect on what the tracer renders; determinism; a quality floor against a 1024-spp ground truth; and the
-surfaces a user meets it through (Python, the C++ veneer, the headless driver, argument checks)."""
+surfaces a user meets it through (Python, the C++ veneer, the headless driver, argument checks).  The comparisons with the restatement
+here run at the default temporal parameters; tests/test_gpu_temporal_grid.py holds the kernels to it at every other value."""
 import ctypes
 import os
 import subprocess
