@@ -338,6 +338,23 @@ int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32
 int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count);
 int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count);
 int ptx_read_guide_coverage(ptx_tracer *t, float *coverage1);   /* W*H floats, H/K (pixel-centre guides: the hit flag); computed now if stale */
+/* Guides through mirrors and glass.  bounces = 0 (the default): the guides describe the first surface a guide ray hits, today's
+ * behaviour exactly.  bounces = B >= 1: every guide ray -- the pixel-centre ray, or each of the count rays of ptx_set_guide_samples --
+ * is followed through perfectly specular surfaces, at most min(B, trace depth - 1) times, and the surface seen at the end of the
+ * chain is recorded in place of the first hit (for a perfect mirror, what OIDN asks its callers for: albedo and normal of the first
+ * non-specular hit).  A hit is followed when its geom is not an OBJ mesh, its material has emittance <= 0 and hasReflective > 0 or
+ * else hasRefractive > 0; the ray is continued by the deterministic parts of the path's own scatterRay: the reflective branch whole,
+ * the refractive branch with its random draw taken as "not reflected" (refract, unless the branch's total-internal-reflection test
+ * reflects), fp32, no contraction.  The chain ends on a hit that is not followed, on the budget, or on a continued ray that misses;
+ * the recorded surface is the last one hit (after such a miss: the specular surface the ray left).  Per ray: normal and ids of the
+ * recorded surface, position = o + t*d of its own segment, t = the segments' t summed in order, albedo = T x albedo of the recorded
+ * hit, T = the product of the colour factors of the surfaces the ray was followed through (1 when none).  The samples are averaged
+ * as ptx_set_guide_samples states.  A pixel none of whose rays is followed gets the record of bounces = 0 bit for bit.
+ * Changing the value marks the G-buffer stale (setting the same value does not).  PTX_ERR_INVALID: bounces < 0, bounces > 64, a
+ * row-tile tracer.  While bounces > 0 the calls that take a temporal history return PTX_ERR_UNSUPPORTED, as with sampled guides:
+ * reprojection needs the first surface.  The reflected branch of glass is not followed. */
+int ptx_set_guide_bounces(ptx_tracer *t, int bounces);
+int ptx_get_guide_bounces(const ptx_tracer *t, int *bounces);
 /* The filter alone over caller-owned host buffers (W*H*3 floats; hit W*H bytes, != 0 = hit): rgb is mean radiance (spp = 1), out_rgb
  * receives the result.  alb3 may be NULL when p->demodulate is 0.  Runs on `device`, synchronously; PTX_ERR_NODEVICE without one. */
 int ptx_denoise_buffers(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, const float *pos3,

@@ -763,6 +763,9 @@ def load_library():
         L.ptx_set_guide_samples.restype, L.ptx_set_guide_samples.argtypes = i, [vp, i, i]
         L.ptx_get_guide_samples.restype, L.ptx_get_guide_samples.argtypes = i, [vp, C.POINTER(i), C.POINTER(i)]
         L.ptx_read_guide_coverage.restype, L.ptx_read_guide_coverage.argtypes = i, [vp, vp]
+    if hasattr(L, "ptx_set_guide_bounces"):
+        L.ptx_set_guide_bounces.restype, L.ptx_set_guide_bounces.argtypes = i, [vp, i]
+        L.ptx_get_guide_bounces.restype, L.ptx_get_guide_bounces.argtypes = i, [vp, C.POINTER(i)]
     L.ptx_denoise_buffers.restype = i
     L.ptx_denoise_buffers.argtypes = [i, i, i, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp]
     L.ptx_default_temporal_params.argtypes = [C.POINTER(TemporalParams)]
@@ -1357,6 +1360,17 @@ class Tracer(_Owned):
         first, count = C.c_int(0), C.c_int(0)
         _check(self.lib.ptx_get_guide_samples(self.h, C.byref(first), C.byref(count)), "ptx_get_guide_samples")
         return count.value, first.value
+
+    def set_guide_bounces(self, bounces):
+        """bounces >= 1: the denoiser's guide rays followed through mirrors and glass, at most min(bounces, trace depth - 1) times, to
+        the surface seen in them (ptx_set_guide_bounces); 0: the first surface, the default"""
+        _check(self.lib.ptx_set_guide_bounces(self.h, int(bounces)), "ptx_set_guide_bounces")
+
+    def guide_bounces(self):
+        """the value set_guide_bounces left"""
+        b = C.c_int()
+        _check(self.lib.ptx_get_guide_bounces(self.h, C.byref(b)), "ptx_get_guide_bounces")
+        return b.value
 
     def guide_coverage(self):
         """(H, W) float32: the share of the guide samples that hit a surface (pixel-centre guides: the hit flag)"""

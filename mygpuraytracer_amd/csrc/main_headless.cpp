@@ -42,6 +42,8 @@
 //                                                                      the filter's guides averaged over the camera rays of iterations
 //                                                                      1 .. min(K, iterations), jitter and lens included, instead of the
 //                                                                      pixel-centre pinhole ray: ptx_set_guide_samples.  Not with --temporal.)
+//                                  [--guide-bounces B]   (with the same: every guide ray followed through at most B mirrors / glass surfaces to the
+//                                                                      surface seen in them: ptx_set_guide_bounces.  Not with --temporal.)
 //                                  [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]   (the display
 //                                                                      transform, ptx_display_*: when any is given, every .png and
 //                                                                      .denoised.png takes its bytes from it -- automatic exposure from block
@@ -164,7 +166,7 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2 || !strcmp(argv[1], "--help")) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K] [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K] [--guide-bounces B] [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]\n", argv[0]);
         return argc < 2;
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
@@ -174,7 +176,7 @@ int main(int argc, char **argv) {
     ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step;
-    int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0;
+    int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0, guide_bounces = 0;
     ptx_options &opt = pathtraceOptions();
     ptx_display_params &disp = g_display.params;
     ptx_default_display_params(&disp);
@@ -212,6 +214,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive") { need(1); adaptive = atof(argv[++i]); }
         else if (a == "--adaptive-denoise") adaptive_denoise = true;
         else if (a == "--measured") measured = true;
+        else if (a == "--guide-bounces") { need(1); guide_bounces = atoi(argv[++i]); if (guide_bounces < 1 || guide_bounces > 64) { fprintf(stderr, "--guide-bounces needs 1 <= B <= 64\n"); return 1; } }
         else if (a == "--guide-samples") { need(1); guide_samples = atoi(argv[++i]); if (guide_samples < 1) { fprintf(stderr, "--guide-samples needs K >= 1\n"); return 1; } }
         else if (a == "--tonemap") {
             need(1);
@@ -269,6 +272,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--guide-samples does not combine with --temporal: reprojection and history matching need one surface per pixel\n");
         return 1;
     }
+    if (guide_bounces > 0 && !denoise && !adaptive_denoise) { fprintf(stderr, "--guide-bounces needs --denoise or --adaptive-denoise\n"); return 1; }
+    if (guide_bounces > 0 && temporal) {
+        fprintf(stderr, "--guide-bounces does not combine with --temporal: reprojection and history matching need the first surface\n");
+        return 1;
+    }
+    guideBounces() = guide_bounces;
     guideSamples() = guide_samples;              // (GPUdenoise with --frames, adaptiveDenoisedFrame; the single frame below sets it itself)
     if (temporal && !denoise) { fprintf(stderr, "--temporal needs --denoise\n"); return 1; }
     if (variance && !denoise) { fprintf(stderr, "--variance needs --denoise\n"); return 1; }
@@ -376,6 +385,7 @@ int main(int argc, char **argv) {
     if (pfm) { ptimg::write_pfm(ss.str() + ".pfm", width, height, &scene->state.image[0].x, divisor); printf("Saved %s.pfm.\n", ss.str().c_str()); }
     if (denoise && n > 0) {                     // the denoised frame next to it: mean radiance already, so divided by 1
         std::vector<float> den((size_t)width * height * 3);
+        if (guide_bounces > 0 && ptx_set_guide_bounces(t, guide_bounces) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         if (guide_samples > 0 && ptx_set_guide_samples(t, 1, std::min(guide_samples, n)) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         const int rc = measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
                      : variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);

@@ -219,6 +219,20 @@ static void apply_guide_samples(const char *what, int rendered) {
     applied = k > 0;
 }
 
+int &guideBounces() {
+    static int b = 0;
+    return b;
+}
+
+// guideBounces() onto the tracer before a filter call, next to guideSamples()
+static void apply_guide_bounces(const char *what) {
+    static bool applied = false;      // (while the switch has never been on, the tracer's own setting is left alone)
+    const int b = guideBounces();
+    if (b == 0 && !applied) return;
+    check(ptx_set_guide_bounces(g_tracer, b), what);
+    applied = b != 0;
+}
+
 ptx_variance_params &varianceParams() {
     if (!g_variance_params_init) { ptx_default_variance_params(&g_variance_params); g_variance_params_init = true; }
     return g_variance_params;
@@ -342,6 +356,7 @@ bool &adaptiveDenoise() {
 const float *adaptiveDenoisedFrame() {
     if (!adaptiveDenoise() || !g_tracer || !g_adaptive || !g_moments || g_adaptive_status.rounds < 1) return nullptr;
     apply_guide_samples("adaptiveDenoisedFrame", (int)g_adaptive_status.samples_max);      // (the worst tile's count: the iterations rendered)
+    apply_guide_bounces("adaptiveDenoisedFrame");
     check(ptx_denoise_adaptive(g_tracer, g_adaptive, g_moments, &denoiseParams(), &varianceParams(), 0), "adaptiveDenoisedFrame");
     g_adaptive_denoised.resize((size_t)g_moments_key[1] * g_moments_key[2] * 3);
     check(ptx_read_denoised(g_tracer, g_adaptive_denoised.data()), "adaptiveDenoisedFrame");
@@ -480,6 +495,7 @@ void GPUdenoise(bool keep_on_device) {
         exit(EXIT_FAILURE);
     }
     apply_guide_samples("GPUdenoise", g_last_iter);
+    apply_guide_bounces("GPUdenoise");
     if (denoiseMeasured() && !denoiseTemporal()) {
         check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");
     } else if (denoiseTemporal()) {

@@ -275,6 +275,10 @@ ptx_variance_params &varianceParams();                  // what it filters with 
 // and lens included, instead of the pixel-centre pinhole ray; 0, the default, is off.  Not with denoiseTemporal(): the call fails as
 // the C ABI's does (PTX_ERR_UNSUPPORTED).
 int &guideSamples();
+// Guides through mirrors and glass (ptx_set_guide_bounces): guideBounces() = B > 0 makes the same calls follow every guide ray through
+// at most B perfectly specular surfaces and guide by the surface seen in them; 0, the default, is off.  Applied where guideSamples()
+// is, and refused with denoiseTemporal() the same way (a B outside 0 .. 64 fails the call as the C ABI does).
+int &guideBounces();
 // Sample moments by batch means (ptx_moments_*): momentsBatch() = k > 0 makes pathtrace() add one batch to a module-level handle after
 // every k-th call since pathtraceInit (which resets it: a new tracer starts a new accumulation); 0, the default, is off.  The handle is
 // created on first use, recreated when the device or the resolution changes, and freed by GPUdenoiseRelease(); pathtraceMoments() hands

@@ -141,6 +141,11 @@ hipError_t pt_atrous_enqueue(hipStream_t st, int w, int h, const float4 *nh, con
 namespace ptd { struct DScene; struct DCamera; }
 hipError_t pt_guides_enqueue(hipStream_t st, const ptd::DScene &sc, const ptd::DCamera &cam, int traceDepth, int aa, int dof, int iter_first,
                              int count, float4 *nh, float4 *xt, float4 *alb, int2 *ids);
+// The same guides followed through mirrors and glass (pt_guides_follow.hip; ptx_set_guide_bounces): every one of the `count` rays is
+// continued through at most `bounces` perfectly specular hits and the last surface hit is recorded, its albedo times the chain's
+// throughput.  aa = dof = 0, count = 1: the pixel-centre ray.  bounces: already min(B, traceDepth - 1), >= 0.
+hipError_t pt_guides_follow_enqueue(hipStream_t st, const ptd::DScene &sc, const ptd::DCamera &cam, int traceDepth, int aa, int dof,
+                                    int iter_first, int count, int bounces, float4 *nh, float4 *xt, float4 *alb, int2 *ids);
 
 const char *pt_moments_params_problem(const ptx_moments_params &p);
 // One add on `st`: rgb = the accumulation buffer (W*H*3) holding `total` samples, k = total - the last add's; fresh: the state reads

@@ -1189,6 +1189,15 @@ extern "C++" int pt_ensure_gbuffer(ptx_tracer *t) {
     if (!t->d_gbuf) HIPCHECK(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
     const DScene sc = t->scene();
+    if (t->guide_bounces > 0) {                          // either mode followed through mirrors and glass (pt_guides_follow.hip): the same arrays
+        const bool sampled = t->guide_count > 0;         // (the pixel-centre mode: one ray, no jitter, no lens -- k_gbuffer's ray)
+        const int beff = std::max(std::min(t->guide_bounces, t->traceDepth - 1), 0);      // a path of depth d has at most d segments
+        HIPCHECK(pt_guides_follow_enqueue(t->stream, sc, t->cam, t->traceDepth, sampled ? t->opt.antialiasing : 0, sampled ? t->opt.depth_of_field : 0,
+                                          sampled ? t->guide_first : 1, sampled ? t->guide_count : 1, beff,
+                                          t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n)));
+        t->gbuf_valid = true;
+        return PTX_OK;
+    }
     if (t->guide_count > 0) {                            // sampled guides (pt_guides.hip): the same arrays, the coverage in alb.w
         HIPCHECK(pt_guides_enqueue(t->stream, sc, t->cam, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, t->guide_first, t->guide_count,
                                    t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n)));
@@ -1226,6 +1235,27 @@ int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count) {
     if (!t) return set_error(PTX_ERR_INVALID, "ptx_get_guide_samples: null tracer");
     if (iter_first) *iter_first = t->guide_first;
     if (count) *count = t->guide_count;
+    return PTX_OK;
+}
+
+// ---- guides through mirrors and glass (pt_guides_follow.hip; definition in include/mi355x_pathtracer.h) -------------------------------
+static const int GUIDE_BOUNCES_MAX = 64;
+int ptx_set_guide_bounces(ptx_tracer *t, int bounces) {
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: null tracer");
+    if (bounces < 0) return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces must be >= 0 (0: the first surface)");
+    if (bounces > GUIDE_BOUNCES_MAX)
+        return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces " + std::to_string(bounces) + " exceeds the cap of " +
+                                              std::to_string(GUIDE_BOUNCES_MAX) + " continuations per ray");
+    if (const int rc = pt_whole_frame_problem("ptx_set_guide_bounces", t)) return rc;
+    if (bounces == t->guide_bounces) return PTX_OK;      // (the same guides: nothing is stale)
+    t->guide_bounces = bounces;
+    t->gbuf_valid = false;
+    return PTX_OK;
+}
+
+int ptx_get_guide_bounces(const ptx_tracer *t, int *bounces) {
+    if (!t) return set_error(PTX_ERR_INVALID, "ptx_get_guide_bounces: null tracer");
+    if (bounces) *bounces = t->guide_bounces;
     return PTX_OK;
 }
 

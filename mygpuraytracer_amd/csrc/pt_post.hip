@@ -31,8 +31,11 @@ int bad_spp(const char *fn) {
     return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": spp must be >= 1 (the iterations summed in the accumulation buffer)");
 }
 
-// What the entry points that carry a history say while sampled guides are on
-int guides_refuse_history(const char *fn) {
+// What the entry points that carry a history say while sampled guides are on ...
+int guides_refuse_history(const char *fn, const ptx_tracer *t) {
+    if (t->guide_count == 0)                             // ... or while the guides are followed through mirrors and glass
+        return pt_fail(PTX_ERR_UNSUPPORTED, std::string(fn) + ": followed guides are on (ptx_set_guide_bounces, bounces > 0); reprojection and "
+                                                 "history matching need the first surface -- set bounces 0 for the temporal path");
     return pt_fail(PTX_ERR_UNSUPPORTED, std::string(fn) + ": sampled guides are on (ptx_set_guide_samples, count > 0); reprojection and history "
                                              "matching need one surface per pixel -- set count 0 for the temporal path");
 }
@@ -132,7 +135,7 @@ int denoise_run(const DenoiseCall &c) {
     ptx_temporal *h = c.h;
     ptx_moments *m = c.m;
     ptx_adaptive *a = c.a;
-    if (h && t->guide_count > 0) return guides_refuse_history(fn);
+    if (h && (t->guide_count > 0 || t->guide_bounces > 0)) return guides_refuse_history(fn, t);
     const int min_batches = c.min_batches <= 0 ? 4 : c.min_batches;
     if (a) {
         if (const int rc = moments_problem(fn, t, m)) return rc;

@@ -104,6 +104,7 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     DevBuf<float> d_dn_out;
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
     int guide_first = 1, guide_count = 0;                // ptx_set_guide_samples: count 0 = k_gbuffer's pixel-centre guides, else k_guides over these iterations
+    int guide_bounces = 0;                               // ptx_set_guide_bounces: > 0 = k_guides_follow in either mode, the guide rays continued through mirrors and glass
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
     DevBuf<uint8_t> d_spec;                              // its device copy, on the first ptx_denoise_temporal
     DevBuf<float> d_var;                                 // [2][W*H]: v0 and the last pass's v of the last ptx_denoise_variance (first use)
