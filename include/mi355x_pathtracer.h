@@ -701,6 +701,87 @@ int  ptx_display_get_status(ptx_display *d, ptx_display_status *out);           
  * col_begin (WK + 1 entries), NULLs allowed, receive where each block starts, the last entry being h / w. */
 int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin, int32_t *col_begin);
 
+/* ---- network denoiser: Open Image Denoise's RT filter (a U-Net) run from a caller's .tza weight file, csrc/pt_nn.hip ----------------
+ * The reference denoises with OIDN's `RT` filter (apps/src/main.cpp: colour + albedo, hdr off).  This is that filter's data-parallel
+ * part on the matrix cores, as one more opaque handle.  No trained weights ship: the caller brings an OIDN 1.4.x weight file, and
+ * nothing here claims image quality.  Every other entry point, default and struct is unchanged.  Definition (DESIGN.md 10;
+ * tests/unet_ref.py restates it):
+ *   Blob: TZA format version 2 (magic 0x41D7; a uint64 table offset; per tensor a name, ndims, dims, a layout x / oihw, a type f / h,
+ *     a uint64 data offset), read with every access checked (csrc/pt_tza.h).  A refused blob is PTX_ERR_INVALID and ptx_last_error
+ *     names the tensor.
+ *   Graph: enc_conv0, enc_conv1, pool, enc_conv2, pool, enc_conv3, pool, enc_conv4, pool, enc_conv5a, enc_conv5b, then for l = 4 .. 1
+ *     {upsample (nearest, 2x), concat with the skip, dec_conv<l>a, dec_conv<l>b}, then dec_conv0.  Skips: pool3, pool2, pool1, the
+ *     network's input; the upsampled tensor comes first in the channel order.  All convolutions are 3 x 3 with zero padding and a ReLU,
+ *     except dec_conv0, which has none.  Channel counts are the blob's: enc_conv0 takes 3, 6 or 9, dec_conv0 gives 3, none above 256.
+ *   Frame: W x H zero-padded on the right and bottom to multiples of 16, the image at the top left; one tile is the whole frame, at
+ *     most 7680 x 4320.
+ *   Arithmetic: activations are fp16 (round to nearest even), channels-last, each tensor's channel count zero-padded to a multiple of
+ *     16 (the two sources of a concat separately).  Weights are rounded to fp16 once, at create; biases stay fp32.  A convolution's
+ *     output = the fp32 sum, in any order, of the exact fp16 x fp16 products, plus the bias; ReLU; one rounding to fp16.  dec_conv0's
+ *     three channels stay fp32.  Pool, upsample and concat are exact.  No atomics: the same bits on every run.
+ *   Input: colour c = rgb / samples (IEEE fp32 division) * scale; NaN -> 0; clamp to [0, 1] (hdr == 0) or [0, FLT_MAX]; then the
+ *     forward transfer: hdr: PU(c) / PU(65504), PU(y) = 1412.83765 y (y <= 1.57945760e-6), 1.64593172 y^0.431384981 - 2.94139609e-3
+ *     (y <= 3.22087631e-2), else 0.192653254 ln(y + 6.26026094e-3) + 0.998620152; hdr == 0 and srgb == 0: the sRGB curve of the display
+ *     transform's step 6 (with powf); srgb != 0: c.  Albedo: NaN -> 0, clamp to [0, 1].  Normal: NaN -> 0, clamp to [-1, 1], * 0.5 + 0.5.
+ *   Output: NaN -> 0, clamp to [0, FLT_MAX]; the inverse transfer; min(., 1) when hdr == 0; times 1 / scale (0 when scale is 0).
+ *   scale: input_scale when it is not NaN; else, with hdr, the display transform's block meter at key 0.18 on rgb / samples (steps 1
+ *     and 2 above, its kernels; the value stays on the device, and the meter's sanitising rule holds where it differs from OIDN's);
+ *     else 1.
+ * A handle serves one W x H on one device with one blob, across tracers and streams, with ptx_display's event ordering. */
+#define PTX_NN_LAYERS 16
+#define PTX_NN_MAX_WIDTH 7680
+#define PTX_NN_MAX_HEIGHT 4320
+typedef struct ptx_nn ptx_nn;                      /* opaque: packed weights, scratch, the meter; one W x H on one device */
+typedef struct ptx_nn_params {
+    int   hdr;                 /* 0 / 1: the PU transfer and an unbounded colour; default 0 */
+    int   srgb;                /* 0 / 1: the colour is sRGB-encoded already (read only when hdr == 0); default 0 */
+    float input_scale;         /* NaN: automatic (hdr: the block meter; else 1); default NaN */
+} ptx_nn_params;
+typedef struct ptx_nn_info {
+    int      width, height, padded_width, padded_height;
+    int      input_channels;                       /* 3 colour, 6 + albedo, 9 + normal */
+    int      layers;                               /* PTX_NN_LAYERS */
+    int      cin[PTX_NN_LAYERS], cout[PTX_NN_LAYERS];      /* the blob's counts, in the graph's order */
+    char     name[PTX_NN_LAYERS][16];
+    uint64_t scratch_bytes;                        /* the activations' device memory, planned at create */
+    uint64_t macs;                                 /* multiply-adds of one run: the sum over layers of 9 Cin Cout padded pixels at its level */
+} ptx_nn_info;
+void   ptx_default_nn_params(ptx_nn_params *p);
+size_t ptx_sizeof_nn_params(void);
+size_t ptx_sizeof_nn_info(void);
+int  ptx_nn_create(int device, int width, int height, const void *tza, size_t bytes, ptx_nn **out);
+int  ptx_nn_create_from_file(int device, int width, int height, const char *path, ptx_nn **out);
+void ptx_nn_destroy(ptx_nn *n);                    /* NULL is a no-op; waits for its last use */
+int  ptx_nn_get_info(ptx_nn *n, ptx_nn_info *out);
+/* One denoise of a W*H*3 float frame on the handle's device, on `stream` (NULL = the default stream): rgb / samples in, out_rgb out.
+ * alb3 / nrm3 (W*H*3 floats each) are required exactly when the blob takes 6 / 9 inputs and refused otherwise.  p NULL = defaults. */
+int  ptx_nn_denoise_device(ptx_nn *n, const float *device_rgb, float samples, const float *device_alb3, const float *device_nrm3,
+                           const ptx_nn_params *p, float *device_out_rgb, void *stream);
+/* the same from host frames through staging buffers the handle owns; waits */
+int  ptx_nn_denoise_host(ptx_nn *n, const float *rgb, float samples, const float *alb3, const float *nrm3, const ptx_nn_params *p, float *out_rgb);
+int  ptx_nn_read_scale(ptx_nn *n, float *scale);   /* the scale the last denoise's input kernel used; waits */
+/* The tracer's accumulation buffer over spp, with albedo and normals from its G-buffer in the guide mode that is set, through the
+ * network into the tracer's denoised frame: ptx_read_denoised, ptx_device_denoised, ptx_write_denoised_pbo_from_device and
+ * ptx_display_tracer(.. PTX_DISPLAY_DENOISED ..) then work as after ptx_denoise.  Enqueued on the tracer's stream; the accumulation
+ * buffer, statistics and later iterations are untouched.  Refused like ptx_denoise: tile_world > 1, a handle of another size or device. */
+int  ptx_denoise_nn(ptx_tracer *t, ptx_nn *n, const ptx_nn_params *p, int spp);
+/* Known-answer entry points over host arrays; they run the production kernels.
+ * One convolution: output w x h (before the pool).  src0: fp16 bits, [h][w][cin0], or [h/2][w/2][cin0] when upsample; src1 (cin1 > 0):
+ * [h][w][cin1], the second source of a concat.  weights: fp32 [cout][cin0 + cin1][3][3], rounded to fp16 here; bias fp32 [cout].
+ * out_half: fp16 bits [h][w][cout], or [h/2][w/2][cout] when pool (2 x 2 max).  out_f32 (optional, cout <= 4, no pool): [h][w][4]. */
+int  ptx_kat_nn_conv(int device, int w, int h, int cin0, const uint16_t *src0, int upsample, int cin1, const uint16_t *src1, int cout,
+                     const float *weights, const float *bias, int relu, int pool, uint16_t *out_half, float *out_f32);
+/* The transfer functions alone on a w x h frame.  inverse == 0: the input kernel; out9 = w*h*9 floats, per pixel the colour, albedo
+ * and normal as the network would get them, before the rounding to fp16 (alb3 / nrm3 NULL: zeros).  inverse != 0: rgb is the
+ * network's output; the output kernel; out9 = w*h*3 floats.  scale as ptx_nn_params.input_scale, NaN excluded. */
+int  ptx_kat_nn_transfer(int device, int w, int h, const float *rgb, const float *alb3, const float *nrm3, int hdr, int srgb, float scale,
+                         int inverse, float *out9);
+/* Host only: the blob's table as text, one line per tensor: name, ndims, the dims, layout, type, data offset, separated by blanks.
+ * *needed = the text's length with its final 0; the text is written when cap >= *needed. */
+int  ptx_debug_tza_list(const void *tza, size_t bytes, char *out, size_t cap, size_t *needed);
+/* Host only: the plan of the blob (the refusals of ptx_nn_create that need no device); out may be NULL */
+int  ptx_debug_nn_plan(const void *tza, size_t bytes, ptx_nn_info *out);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
  *      reprojection alone and needs no tracer ------------------------------------------------------------------- */

@@ -24,6 +24,15 @@ from .api import (  # noqa: F401
     DisplayStatus,
     Display,
     default_display_params,
+    NNParams,
+    NNInfo,
+    NN,
+    default_nn_params,
+    nn_denoise_buffers,
+    debug_tza_list,
+    debug_nn_plan,
+    kat_nn_conv,
+    kat_nn_transfer,
     Scene,
     Tracer,
     Temporal,
@@ -43,6 +52,6 @@ from .api import (  # noqa: F401
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
+__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "NNParams", "NNInfo", "NN", "default_nn_params", "nn_denoise_buffers", "debug_tza_list", "debug_nn_plan", "kat_nn_conv", "kat_nn_transfer", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
            "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "default_adaptive_params", "tile_pixels", "denoise_buffers",
            "denoise_buffers_variance", "reproject_buffers", "load_library"]

@@ -465,6 +465,158 @@ class Display(_Owned):
         return {k: getattr(out, k) for k, _ in DisplayStatus._fields_}
 
 
+NN_LAYERS = 16
+
+
+class NNParams(C.Structure):
+    """ptx_nn_params: the network denoiser's transfer mode and input scale (include/mi355x_pathtracer.h; defaults from
+    ptx_default_nn_params: hdr 0, srgb 0, input_scale NaN = automatic)."""
+    _fields_ = [("hdr", C.c_int), ("srgb", C.c_int), ("input_scale", C.c_float)]
+
+
+class NNInfo(C.Structure):
+    """ptx_nn_info (include/mi355x_pathtracer.h)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("padded_width", C.c_int), ("padded_height", C.c_int), ("input_channels", C.c_int),
+                ("layers", C.c_int), ("cin", C.c_int * NN_LAYERS), ("cout", C.c_int * NN_LAYERS), ("name", (C.c_char * 16) * NN_LAYERS),
+                ("scratch_bytes", C.c_uint64), ("macs", C.c_uint64)]
+
+
+def default_nn_params(**kw):
+    """ptx_default_nn_params with keyword overrides (hdr, srgb, input_scale)."""
+    return _default_params(NNParams, "ptx_default_nn_params", ("hdr", "srgb"), **kw)
+
+
+def _nn_info_dict(info):
+    layers = [(info.name[k].value.decode(), info.cin[k], info.cout[k]) for k in range(info.layers)]
+    return dict(width=info.width, height=info.height, padded_width=info.padded_width, padded_height=info.padded_height,
+                input_channels=info.input_channels, layers=layers, scratch_bytes=info.scratch_bytes, macs=info.macs)
+
+
+def _blob_buffer(tza):
+    blob = bytes(tza)
+    return blob, C.cast(C.c_char_p(blob), vp)
+
+
+def debug_tza_list(tza):
+    """ptx_debug_tza_list: the table of a TZA weight blob (bytes) as a list of (name, dims, layout, type, offset); no device needed.
+    A blob the reader refuses raises PathTracerError."""
+    L = load_library()
+    blob, ptr = _blob_buffer(tza)
+    need = C.c_size_t(0)
+    _check(L.ptx_debug_tza_list(ptr, len(blob), None, 0, C.byref(need)), "ptx_debug_tza_list")
+    buf = C.create_string_buffer(need.value)
+    _check(L.ptx_debug_tza_list(ptr, len(blob), buf, need.value, C.byref(need)), "ptx_debug_tza_list")
+    out = []
+    for line in buf.value.decode().splitlines():
+        f = line.split(" ")
+        nd = int(f[1])
+        out.append((f[0], tuple(int(v) for v in f[2:2 + nd]), f[2 + nd], f[3 + nd], int(f[4 + nd])))
+    return out
+
+
+def debug_nn_plan(tza):
+    """ptx_debug_nn_plan: the network plan of a TZA weight blob (input channels, per-layer channel table) as a dict; no device needed.
+    A blob that is no such network raises PathTracerError naming the tensor."""
+    blob, ptr = _blob_buffer(tza)
+    info = NNInfo()
+    _check(load_library().ptx_debug_nn_plan(ptr, len(blob), C.byref(info)), "ptx_debug_nn_plan")
+    return _nn_info_dict(info)
+
+
+class NN(_Owned):
+    """The network denoiser on one device (opaque ptx_nn): Open Image Denoise's RT filter run from the caller's TZA weights (`tza`:
+    bytes, or a path) for one W x H.  host(rgb, albedo, normal) denoises a numpy frame, device(...) a frame on the device,
+    Tracer.denoise_nn(nn, spp) a tracer's; params are ptx_nn_params' fields as keywords."""
+
+    _destroy = "ptx_nn_destroy"
+
+    def __init__(self, width, height, tza, device=0):
+        self.lib = load_library()
+        h = vp()
+        if isinstance(tza, (str, os.PathLike)):
+            _check(self.lib.ptx_nn_create_from_file(int(device), int(width), int(height), os.fsencode(tza), C.byref(h)), "ptx_nn_create_from_file")
+        else:
+            blob, ptr = _blob_buffer(tza)
+            _check(self.lib.ptx_nn_create(int(device), int(width), int(height), ptr, len(blob), C.byref(h)), "ptx_nn_create")
+        self.h = h
+        self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
+
+    def info(self):
+        """ptx_nn_get_info as a dict: sizes, input_channels, layers = [(name, cin, cout)], scratch_bytes, macs"""
+        info = NNInfo()
+        _check(self.lib.ptx_nn_get_info(self.h, C.byref(info)), "ptx_nn_get_info")
+        return _nn_info_dict(info)
+
+    def device(self, rgb_ptr, out_ptr, samples=1, albedo_ptr=None, normal_ptr=None, stream=0, **params):
+        """W*H*3 float frames at device pointers, enqueued on `stream` (a hipStream_t as an integer)"""
+        p = default_nn_params(**params)
+        opt = lambda a: vp(a) if a else None
+        _check(self.lib.ptx_nn_denoise_device(self.h, vp(rgb_ptr), float(samples), opt(albedo_ptr), opt(normal_ptr), C.byref(p), vp(out_ptr),
+                                              opt(stream)), "ptx_nn_denoise_device")
+
+    def host(self, rgb, albedo=None, normal=None, samples=1, **params):
+        """host frames (H, W, 3); returns the denoised (H, W, 3) float32"""
+        n = self.width * self.height * 3
+        frames = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (rgb, albedo, normal)]
+        for a in frames:
+            if a is not None and a.size != n:
+                raise ValueError("NN.host: a frame has %d floats, the handle's size needs %d" % (a.size, n))
+        p = default_nn_params(**params)
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        _check(self.lib.ptx_nn_denoise_host(self.h, _ptr(frames[0]), float(samples), _opt_ptr(frames[1]), _opt_ptr(frames[2]), C.byref(p), _ptr(out)),
+               "ptx_nn_denoise_host")
+        return out
+
+    def scale(self):
+        """the scale the last denoise's input kernel used (the metered exposure in hdr mode with an automatic scale)"""
+        s = C.c_float()
+        _check(self.lib.ptx_nn_read_scale(self.h, C.byref(s)), "ptx_nn_read_scale")
+        return np.float32(s.value)
+
+
+def nn_denoise_buffers(tza, rgb, albedo=None, normal=None, samples=1, device=0, **params):
+    """The network denoiser alone on host arrays of one (H, W, 3) frame: a handle for the frame's size from `tza` (bytes or a path), one
+    NN.host call.  Returns the denoised (H, W, 3) float32.  Needs a HIP device: there is no CPU path."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise PathTracerError("nn_denoise_buffers: rgb must be (H, W, 3)")
+    with NN(rgb.shape[1], rgb.shape[0], tza, device=device) as nn:
+        return nn.host(rgb, albedo, normal, samples=samples, **params)
+
+
+def kat_nn_conv(src0, weights, bias, src1=None, upsample=False, relu=True, pool=False, f32=False, device=0):
+    """ptx_kat_nn_conv: one convolution layer by the production kernel.  src0 (h0, w0, cin0) float16, (h0, w0) = the output's (h, w) or
+    half of it when upsample; src1 (h, w, cin1) float16 or None; weights (cout, cin0 + cin1, 3, 3) float32; bias (cout) float32.
+    Returns float16 (h, w, cout), (h / 2, w / 2, cout) when pool, or float32 (h, w, 4) when f32."""
+    src0 = np.ascontiguousarray(src0, np.float16)
+    h, w = (2 * src0.shape[0], 2 * src0.shape[1]) if upsample else src0.shape[:2]
+    src1 = None if src1 is None else np.ascontiguousarray(src1, np.float16)
+    weights, bias = np.ascontiguousarray(weights, np.float32), np.ascontiguousarray(bias, np.float32)
+    cout = weights.shape[0]
+    cin1 = 0 if src1 is None else src1.shape[2]
+    if weights.shape != (cout, src0.shape[2] + cin1, 3, 3) or bias.shape != (cout,) or (src1 is not None and src1.shape[:2] != (h, w)):
+        raise ValueError("kat_nn_conv: shapes do not fit")
+    out16 = np.zeros((h // 2, w // 2, cout) if pool else (h, w, cout), np.float16)
+    out32 = np.zeros((h, w, 4), np.float32) if f32 else None
+    _check(load_library().ptx_kat_nn_conv(int(device), w, h, src0.shape[2], _ptr(src0), int(bool(upsample)), cin1, _opt_ptr(src1), cout,
+                                          _ptr(weights), _ptr(bias), int(bool(relu)), int(bool(pool)), None if f32 else _ptr(out16),
+                                          _opt_ptr(out32)), "ptx_kat_nn_conv")
+    return out32 if f32 else out16
+
+
+def kat_nn_transfer(rgb, albedo=None, normal=None, hdr=0, srgb=0, scale=1.0, inverse=False, device=0):
+    """ptx_kat_nn_transfer on (H, W, 3) float32 frames: forward = the input kernel's nine fp32 values per pixel before the rounding to
+    fp16, (H, W, 9); inverse = the output kernel on a network output, (H, W, 3)."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    as3 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(h, w, 3)
+    alb, nrm = as3(albedo), as3(normal)
+    out = np.zeros((h, w, 3 if inverse else 9), np.float32)
+    _check(load_library().ptx_kat_nn_transfer(int(device), w, h, _ptr(rgb), _opt_ptr(alb), _opt_ptr(nrm), int(hdr), int(srgb), float(scale),
+                                              int(bool(inverse)), _ptr(out)), "ptx_kat_nn_transfer")
+    return out
+
+
 def _frame_arrays(fn, rgb, albedo, normal, position, hit):
     """one (H, W) frame as the ptx_denoise_buffers* entry points take it: h, w, rgb (H, W, 3) float32, albedo (or None) / normal /
     position (H*W, 3) float32, hit (H*W) uint8"""
@@ -834,6 +986,24 @@ def load_library():
     L.ptx_display_read_blocks.restype, L.ptx_display_read_blocks.argtypes = i, [vp, vp]
     L.ptx_display_get_status.restype, L.ptx_display_get_status.argtypes = i, [vp, C.POINTER(DisplayStatus)]
     L.ptx_debug_display_blocks.restype, L.ptx_debug_display_blocks.argtypes = i, [i, i, C.POINTER(i), C.POINTER(i), vp, vp]
+    # network denoiser
+    L.ptx_sizeof_nn_params.restype = L.ptx_sizeof_nn_info.restype = C.c_size_t
+    if L.ptx_sizeof_nn_params() != C.sizeof(NNParams) or L.ptx_sizeof_nn_info() != C.sizeof(NNInfo):
+        raise PathTracerError("%s has network denoiser structs of %d and %d B, this module expects %d and %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_nn_params(), L.ptx_sizeof_nn_info(), C.sizeof(NNParams), C.sizeof(NNInfo)))
+    L.ptx_default_nn_params.argtypes = [C.POINTER(NNParams)]
+    L.ptx_nn_create.restype, L.ptx_nn_create.argtypes = i, [i, i, i, vp, C.c_size_t, C.POINTER(vp)]
+    L.ptx_nn_create_from_file.restype, L.ptx_nn_create_from_file.argtypes = i, [i, i, i, C.c_char_p, C.POINTER(vp)]
+    L.ptx_nn_destroy.restype, L.ptx_nn_destroy.argtypes = None, [vp]
+    L.ptx_nn_get_info.restype, L.ptx_nn_get_info.argtypes = i, [vp, C.POINTER(NNInfo)]
+    L.ptx_nn_denoise_device.restype, L.ptx_nn_denoise_device.argtypes = i, [vp, vp, f, vp, vp, C.POINTER(NNParams), vp, vp]
+    L.ptx_nn_denoise_host.restype, L.ptx_nn_denoise_host.argtypes = i, [vp, vp, f, vp, vp, C.POINTER(NNParams), vp]
+    L.ptx_nn_read_scale.restype, L.ptx_nn_read_scale.argtypes = i, [vp, C.POINTER(f)]
+    L.ptx_denoise_nn.restype, L.ptx_denoise_nn.argtypes = i, [vp, vp, C.POINTER(NNParams), i]
+    L.ptx_kat_nn_conv.restype, L.ptx_kat_nn_conv.argtypes = i, [i, i, i, i, vp, i, i, vp, i, vp, vp, i, i, vp, vp]
+    L.ptx_kat_nn_transfer.restype, L.ptx_kat_nn_transfer.argtypes = i, [i, i, i, vp, vp, vp, i, i, f, i, vp]
+    L.ptx_debug_tza_list.restype, L.ptx_debug_tza_list.argtypes = i, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ptx_debug_nn_plan.restype, L.ptx_debug_nn_plan.argtypes = i, [vp, C.c_size_t, C.POINTER(NNInfo)]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -1321,6 +1491,14 @@ class Tracer(_Owned):
         dp, _, vpar = _split_variance_params("denoise_adaptive", params)
         _check(self.lib.ptx_denoise_adaptive(self.h, adaptive.h, moments.h, C.byref(dp), C.byref(vpar),
                                              0 if min_batches is None else int(min_batches)), "ptx_denoise_adaptive")
+        return self.read_denoised() if read else None
+
+    def denoise_nn(self, nn, spp, read=True, **params):
+        """The network denoiser (ptx_denoise_nn) on the accumulation buffer / spp with albedo and normals from the G-buffer in the guide
+        mode that is set, `nn` an NN of this tracer's size and device; params: ptx_nn_params' fields (hdr, srgb, input_scale).  Returns the
+        (H, W, 3) float32 frame (read=False: only enqueues it); the result is the tracer's denoised frame, as after denoise()."""
+        p = default_nn_params(**params)
+        _check(self.lib.ptx_denoise_nn(self.h, nn.h, C.byref(p), int(spp)), "ptx_denoise_nn")
         return self.read_denoised() if read else None
 
     def variance(self):

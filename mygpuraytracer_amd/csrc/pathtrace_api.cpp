@@ -29,6 +29,9 @@ ptx_variance_params g_variance_params;
 bool g_variance_params_init = false;
 ptx_temporal *g_temporal = nullptr;  // GPUdenoise's history with denoiseTemporal() on: kept across pathtraceFree / pathtraceInit
 int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
+ptx_nn *g_nn = nullptr;              // GPUdenoise's network with nnWeights() set: kept like g_temporal
+int g_nn_key[3] = {0, 0, 0};         // its device, width, height
+std::string g_nn_path;               // ... and the weight file it was made from
 int g_device = 0;                    // the device of g_tracer
 ptx_moments *g_moments = nullptr;    // pathtrace()'s batch means with momentsBatch() > 0: created on first use
 int g_moments_key[3] = {0, 0, 0};    // its device, width, height
@@ -250,6 +253,18 @@ bool &denoiseMeasured() {
     return on;
 }
 
+std::string &nnWeights() {
+    static std::string path;
+    return path;
+}
+
+ptx_nn_params &nnParams() {
+    static ptx_nn_params p;
+    static bool init = false;
+    if (!init) { ptx_default_nn_params(&p); init = true; }
+    return p;
+}
+
 float &adaptiveTarget() {
     static float e = 0.f;
     return e;
@@ -308,6 +323,8 @@ void GPUdenoiseRelease() {
     g_display = nullptr;
     ptx_temporal_destroy(g_temporal);
     g_temporal = nullptr;
+    ptx_nn_destroy(g_nn);
+    g_nn = nullptr;
     ptx_moments_destroy(g_moments);
     g_moments = nullptr;
     ptx_adaptive_destroy(g_adaptive);
@@ -496,7 +513,24 @@ void GPUdenoise(bool keep_on_device) {
     }
     apply_guide_samples("GPUdenoise", g_last_iter);
     apply_guide_bounces("GPUdenoise");
-    if (denoiseMeasured() && !denoiseTemporal()) {
+    if (!nnWeights().empty()) {
+        if (denoiseTemporal() || denoiseVariance() || denoiseMeasured()) {
+            fprintf(stderr, "GPUdenoise: nnWeights() does not combine with denoiseTemporal(), denoiseVariance() or denoiseMeasured()\n");
+            exit(EXIT_FAILURE);
+        }
+        const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+        const int key[3] = {g_device, w, h};
+        if (g_nn && (memcmp(key, g_nn_key, sizeof key) != 0 || g_nn_path != nnWeights())) {
+            ptx_nn_destroy(g_nn);
+            g_nn = nullptr;
+        }
+        if (!g_nn) {
+            check(ptx_nn_create_from_file(g_device, w, h, nnWeights().c_str(), &g_nn), "GPUdenoise");
+            memcpy(g_nn_key, key, sizeof key);
+            g_nn_path = nnWeights();
+        }
+        check(ptx_denoise_nn(g_tracer, g_nn, &nnParams(), g_last_iter), "GPUdenoise");
+    } else if (denoiseMeasured() && !denoiseTemporal()) {
         check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");
     } else if (denoiseTemporal()) {
         const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];

@@ -293,6 +293,13 @@ void pathtraceMomentsAdd(int iteration);
 // ptx_denoise_temporal_measured: the history's variance pooled with the measured one of the current view (pathtraceInit resets the
 // moments handle at every camera change, so its batches are that view's; fewer than 4 of them and the call is ptx_denoise_variance).
 bool &denoiseMeasured();
+// The network denoiser (ptx_denoise_nn): nnWeights() = "file.tza" makes GPUdenoise run Open Image Denoise's RT filter from that OIDN
+// 1.4.x weight file, with nnParams() (hdr, srgb, input_scale), in place of the a-trous filter; albedo and normals come from the G-buffer
+// in the guide mode that is set.  The handle is created on first use, recreated when the file, the device or the resolution changes,
+// and freed by GPUdenoiseRelease().  Empty (the default): the calls made are exactly those above.  Not combined with denoiseTemporal(),
+// denoiseVariance() or denoiseMeasured().
+std::string &nnWeights();
+ptx_nn_params &nnParams();
 // Adaptive sampling by tiles (ptx_adaptive_*): adaptiveTarget() = E > 0 together with momentsBatch() = k makes pathtrace(), after every
 // k-th call, count those k iterations tile by tile (ptx_adaptive_add, in place of the plain moments add) and switch off the tiles whose
 // error is at E (ptx_adaptive_select): later calls trace the others only.  adaptiveStatus() is the last round's; adaptiveFrame() resolves

@@ -50,3 +50,7 @@ const char *pt_display_params_problem(const ptx_display_params &p, float samples
 // work, enqueues the meter (p.meter == PTX_METER_BLOCKS) and the map, records the handle's event.  Codes go to device_uchar4, or to
 // the handle's own buffer when that is NULL.  The caller has checked p (pt_display_params_problem) and set the device.
 int pt_display_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float samples, const ptx_display_params &p, void *device_uchar4);
+
+// The block meter alone on `st` (k_display_blocks, k_display_meter at adapt 1): d_state's `metered` is then this frame's.  For a handle
+// that its caller owns and orders itself (pt_nn.hip's automatic scale): no wait, no event, none of the handle's flags.
+int pt_display_meter_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float samples, float key);

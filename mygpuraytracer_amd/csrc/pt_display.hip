@@ -270,6 +270,20 @@ int pt_display_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float s
     return PTX_OK;
 }
 
+// The meter alone, for the network denoiser's automatic scale (pt_nn.hip): steps 1 and 2 at `key`, adapt 1, so state->metered is the
+// frame's.  The handle is the caller's own and never shown: it orders it, and neither the event nor the flags of a display call move.
+int pt_display_meter_enqueue(ptx_display *d, hipStream_t st, const float *rgb, float samples, float key) {
+    const int nblocks = d->hk * d->wk;
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(k_display_blocks, dim3((unsigned)d->wk, (unsigned)d->hk), dim3(NT), 0, st, d->w, d->hk, samples,
+                           (const int *)d->d_begin, rgb, d->d_blocks);
+        PT_HC(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_display_meter, dim3(1), dim3(NTM), 0, st, nblocks, (const float *)d->d_blocks, key, 1.f, 1, d->d_state);
+    PT_HC(hipGetLastError());
+    return PTX_OK;
+}
+
 extern "C" {
 
 void ptx_default_display_params(ptx_display_params *p) {

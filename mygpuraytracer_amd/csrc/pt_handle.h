@@ -1,7 +1,7 @@
 // pt_handle.h -- what the host units build their state from: the ptx_last_error of a failed call and the checked HIP call (every unit
-// but pt_engine.hip), the owned device array (DevBuf: the tracer's buffers, pt_tracer.h, and the handles'), and the base of the four
+// but pt_engine.hip), the owned device array (DevBuf: the tracer's buffers, pt_tracer.h, and the handles'), and the base of the five
 // post-processing handles (PtHandle: ptx_temporal and ptx_moments, pt_denoise.h; ptx_adaptive, pt_adaptive.h; ptx_display,
-// pt_display.h) with their one create and destroy path.  Not part of the C ABI.
+// pt_display.h; ptx_nn, pt_nn.h) with their one create and destroy path.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>

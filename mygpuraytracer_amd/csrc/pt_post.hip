@@ -1,9 +1,9 @@
 // pt_post.hip -- what happens to a tracer's frame after tracing, as host code: the ptx_* entry points that hand the tracer's buffers
 // (pt_tracer.h) to the post-processing units -- the a-trous filter and its variance guidance (pt_denoise.hip), the temporal reprojection
-// (pt_temporal.hip), the batch-means moments (pt_moments.hip), adaptive sampling (pt_adaptive.hip) and the display transform
-// (pt_display.hip).  No __global__ function, no launch and no environment read: the kernels are those units', the G-buffer pass and the
-// tile mask are pt_engine.hip's (pt_ensure_gbuffer, pt_set_tile_mask).  Errors go through pt_fail / PT_HC (pt_handle.h), which set the
-// thread's ptx_last_error as pt_engine.hip's own do.
+// (pt_temporal.hip), the batch-means moments (pt_moments.hip), adaptive sampling (pt_adaptive.hip), the display transform
+// (pt_display.hip) and the network denoiser (pt_nn.hip).  No __global__ function, no launch and no environment read: the kernels are
+// those units', the G-buffer pass and the tile mask are pt_engine.hip's (pt_ensure_gbuffer, pt_set_tile_mask).  Errors go through
+// pt_fail / PT_HC (pt_handle.h), which set the thread's ptx_last_error as pt_engine.hip's own do.
 //
 // The six ptx_denoise* entry points are one pipeline, denoise_run: each of them defaults its parameters, says in a DenoiseCall what it
 // takes, and calls it.
@@ -17,6 +17,7 @@
 #include "pt_denoise.h"
 #include "pt_adaptive.h"
 #include "pt_display.h"
+#include "pt_nn.h"
 
 namespace {
 
@@ -283,6 +284,31 @@ int ptx_read_denoised(ptx_tracer *t, float *host_rgb) {
 }
 
 float *ptx_device_denoised(ptx_tracer *t) { return t && t->dn_done ? t->d_dn_out : nullptr; }
+
+// ---- network denoiser (pt_nn.hip; definition in include/mi355x_pathtracer.h) -----------------------------------------------------------
+// Colour = the accumulation buffer over spp; albedo and normals = the G-buffer's float4 records in the guide mode that is set.  On the
+// tracer's stream, the order ptx_denoise's read of the accumulation buffer has; the result is the tracer's denoised frame.
+int ptx_denoise_nn(ptx_tracer *t, ptx_nn *nn, const ptx_nn_params *params, int spp) {
+    const char *fn = "ptx_denoise_nn";
+    const ptx_nn_params p = params_or_default(params, ptx_default_nn_params);
+    if (spp < 1) return bad_spp(fn);
+    if (const char *why = pt_nn_params_problem(p, (float)spp)) return pt_fail(PTX_ERR_INVALID, why);
+    if (!t || !nn) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": null tracer or network handle");
+    if (const int rc = frame_handle_problem(fn, t, "network", *nn)) return rc;
+    PT_HC(hipSetDevice(t->device));
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (!t->d_dn_out) PT_HC(t->d_dn_out.alloc(3 * n));
+    const float *alb = nullptr, *nrm = nullptr;
+    if (nn->ic >= 6) {
+        if (const int rc = pt_ensure_gbuffer(t)) return rc;
+        const float4 *g = t->d_gbuf;
+        alb = reinterpret_cast<const float *>(g + 2 * n);
+        if (nn->ic >= 9) nrm = reinterpret_cast<const float *>(g);
+    }
+    if (const int rc = pt_nn_enqueue(nn, t->stream, t->d_image, (float)spp, alb, 4, nrm, 4, p, t->d_dn_out)) return rc;
+    t->dn_done = true;
+    return PTX_OK;
+}
 
 // ---- sample moments by batch means (pt_moments.hip; definition in include/mi355x_pathtracer.h) ---------------------------------------
 // The accumulation buffer is read on the tracer's stream, where every gather runs, those of iterations traced ahead included
