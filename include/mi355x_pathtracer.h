@@ -718,7 +718,9 @@ int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin
  *   Arithmetic: activations are fp16 (round to nearest even), channels-last, each tensor's channel count zero-padded to a multiple of
  *     16 (the two sources of a concat separately).  Weights are rounded to fp16 once, at create; biases stay fp32.  A convolution's
  *     output = the fp32 sum, in any order, of the exact fp16 x fp16 products, plus the bias; ReLU; one rounding to fp16.  dec_conv0's
- *     three channels stay fp32.  Pool, upsample and concat are exact.  No atomics: the same bits on every run.
+ *     three channels stay fp32.  Pool, upsample and concat are exact.  No atomics: the same bits on every run.  Subnormal fp16
+ *     operands and results are kept, in activations and weights alike (measured on gfx950: the matrix core multiplies them exactly
+ *     and the rounding of a sum below 2^-14 gives the subnormal); a sum of 65520 or more in magnitude rounds to +-inf.
  *   Input: colour c = rgb / samples (IEEE fp32 division) * scale; NaN -> 0; clamp to [0, 1] (hdr == 0) or [0, FLT_MAX]; then the
  *     forward transfer: hdr: PU(c) / PU(65504), PU(y) = 1412.83765 y (y <= 1.57945760e-6), 1.64593172 y^0.431384981 - 2.94139609e-3
  *     (y <= 3.22087631e-2), else 0.192653254 ln(y + 6.26026094e-3) + 0.998620152; hdr == 0 and srgb == 0: the sRGB curve of the display

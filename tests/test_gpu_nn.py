@@ -12,6 +12,7 @@ import pytest
 
 import unet_ref as U
 from conftest import ROOT, beq
+from nncases import exact_case as _exact_case, random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -23,52 +24,6 @@ PLAIN = sorted({(sum(cin) if isinstance(cin, tuple) else cin, cout) for ic in IC
 TWO = sorted({cin + (cout,) for ic in ICS for _, cin, cout in U.standard_channels(ic) if isinstance(cin, tuple)})
 # enc_conv1 .. 4, which write only their pooled output
 POOLED = [(U.EC1, U.EC1), (U.EC1, U.EC2), (U.EC2, U.EC3), (U.EC3, U.EC4)]
-
-
-def _int_conv(x, w):
-    """(H, W, Cout) int64: the 3 x 3 cross-correlation with zero padding of integer x (H, W, Cin) and w (Cout, Cin, 3, 3)"""
-    h, wd, _ = x.shape
-    xp = np.zeros((h + 2, wd + 2, x.shape[2]), w.dtype)
-    xp[1:-1, 1:-1] = x
-    out = np.zeros((h, wd, w.shape[0]), w.dtype)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[ky:ky + h, kx:kx + wd] @ w[:, :, ky, kx].T
-    return out
-
-
-def _up(x):
-    return x.repeat(2, axis=0).repeat(2, axis=1)
-
-
-def _pool(x):
-    h, w, c = x.shape
-    return x.reshape(h // 2, 2, w // 2, 2, c).max(axis=(1, 3))
-
-
-def _exact_case(pt, w, h, cin0, cin1, cout, pool, seed):
-    """inputs in {0, 1}, weights in {-1, 0, 1} / 16, biases multiples of 1 / 16: at most 9 * 160 terms, so every sum is an integer
-    multiple of 2^-4 below 128 = 2048 * 2^-4, exact in fp32 and in fp16; the device's bits are those of integer arithmetic"""
-    rng = np.random.default_rng(seed)
-    two = cin1 > 0
-    x0 = rng.integers(0, 2, ((h // 2, w // 2, cin0) if two else (h, w, cin0))).astype(np.int64)
-    x1 = rng.integers(0, 2, (h, w, cin1)).astype(np.int64) if two else None
-    wi = rng.integers(-1, 2, (cout, cin0 + cin1, 3, 3)).astype(np.int64)      # no symmetry among taps, channels or outputs
-    bi = rng.integers(-8, 9, cout).astype(np.int64)
-    x = np.concatenate([_up(x0), x1], axis=2) if two else x0
-    for relu in ((True, False) if not pool and not two else (True,)):
-        want = _int_conv(x, wi) + bi
-        if relu:
-            want = np.maximum(want, 0)
-        if pool:
-            want = _pool(want)
-        assert np.abs(want).max() < 2048
-        got = pt.kat_nn_conv(x0.astype(np.float16), wi.astype(np.float32) / 16, bi.astype(np.float32) / 16,
-                             src1=None if x1 is None else x1.astype(np.float16), upsample=two, relu=relu, pool=pool)
-        assert beq(got, (want / 16.0).astype(np.float16)), (w, h, cin0, cin1, cout, pool, relu, int((got != (want / 16.0).astype(np.float16)).sum()))
-        if cout <= 4 and not pool:
-            got32 = pt.kat_nn_conv(x0.astype(np.float16), wi.astype(np.float32) / 16, bi.astype(np.float32) / 16, relu=relu, f32=True)
-            assert beq(got32[..., :cout], (want / 16.0).astype(np.float32)), (w, h, cin0, cout)
 
 
 @pytest.mark.parametrize("cin,cout", PLAIN)
@@ -94,26 +49,7 @@ def test_one_layer_random_within_the_summation_bound(gpu_product, cin0, cin1, co
     """Inputs from {0} and [2^-10, 2) (no fp16 subnormals), He-scaled weights, both fp16 values.  s = the float64 result on them;
     E = 2 K 2^-24 (|b| + sum |w| |x|), K = 9 Cin: twice the standard summation bound, the matrix core's order and rounding being its own;
     every output is within E + 2^-11 (|relu(s)| + E) + 2^-25 of relu(s): the sum's error, then one rounding to fp16."""
-    pt = gpu_product
-    w, h = 38, 22
-    rng = np.random.default_rng(50000 + 300 * cin0 + 7 * cin1 + cout)
-    two = cin1 > 0
-    draw = lambda shape: np.where(rng.random(shape) < 0.2, 0.0, 2.0 ** rng.uniform(-10, 0.999, shape)).astype(np.float16)
-    x0 = draw((h // 2, w // 2, cin0) if two else (h, w, cin0))
-    x1 = draw((h, w, cin1)) if two else None
-    cin = cin0 + cin1
-    wt = (rng.standard_normal((cout, cin, 3, 3)) * np.sqrt(2.0 / (9 * cin))).astype(np.float16)
-    b = (rng.standard_normal(cout) * 0.1).astype(np.float32)
-    assert x0.max() < 2 and (x0[x0 > 0].min() >= 2.0 ** -10)
-    x = np.concatenate([_up(x0), x1], axis=2) if two else x0
-    s = _int_conv(x.astype(np.float64), wt.astype(np.float64)) + b.astype(np.float64)
-    mag = _int_conv(np.abs(x).astype(np.float64), np.abs(wt).astype(np.float64)) + np.abs(b).astype(np.float64)
-    E = 2 * 9 * cin * 2.0 ** -24 * mag
-    want = np.maximum(s, 0.0)
-    got = pt.kat_nn_conv(x0, wt.astype(np.float32), b, src1=x1, upsample=two).astype(np.float64)
-    excess = np.abs(got - want) - (E + 2.0 ** -11 * (want + E) + 2.0 ** -25)
-    print("cin %d+%d cout %d: max |gpu - relu(s)| %.3g, largest excess over the bound %.3g" % (cin0, cin1, cout, np.abs(got - want).max(), excess.max()))
-    assert (excess <= 0).all()
+    random_case(gpu_product, cin0, cin1, cout)
 
 
 def _sweep():

@@ -71,6 +71,27 @@ def test_the_restatements_reader_reads_its_writer_and_the_library_lists_it(produ
         assert plan["layers"] == [(n, sum(ci) if isinstance(ci, tuple) else ci, co) for n, ci, co in U.standard_channels(6)]
 
 
+@pytest.mark.parametrize("dtype,code", [(np.float32, "f"), (np.float16, "h")])
+@pytest.mark.parametrize("counts", [U.NARROW, U.WIDE], ids=["narrow", "wide"])
+@pytest.mark.parametrize("ic", [3, 6, 9])
+def test_the_plan_accepts_tables_off_the_standard_one(product, ic, counts, dtype, code):
+    """channel counts are the blob's: any in 1 .. 256 that follow the graph, in tensors of type f or h; the plan reports them"""
+    channels = U.table(ic, *counts)
+    blob = U.weights_blob(U.synthetic_weights(ic, 4, channels=channels, dtype=dtype))
+    listed = product.debug_tza_list(blob)
+    assert listed == U.table_of(blob) and len(listed) == 32 and {t[3] for t in listed} == {code}
+    assert [t[1] for t in listed[::2]] == [(co, sum(ci) if isinstance(ci, tuple) else ci, 3, 3) for _, ci, co in channels]
+    plan = product.debug_nn_plan(blob)
+    assert plan["input_channels"] == ic
+    assert plan["layers"] == [(n, sum(ci) if isinstance(ci, tuple) else ci, co) for n, ci, co in channels]
+    assert max(co for _, _, co in plan["layers"]) == max(counts)
+
+
+def test_table_restates_the_standard_channels():
+    for ic in (3, 6, 9):
+        assert U.table(ic, U.EC1, U.EC2, U.EC3, U.EC4, U.EC5, U.DC4, U.DC3, U.DC2, U.DC1A, U.DC1B) == U.standard_channels(ic)
+
+
 def _refused(product, weights, match):
     with pytest.raises(product.PathTracerError, match=match):
         product.debug_nn_plan(U.weights_blob(weights))

@@ -3,7 +3,7 @@ Nothing here reads the library or the reference tree:
   * a TZA writer and reader of their own (format version 2), on struct + numpy;
   * the U-Net on CPU torch tensors with the definition's fp16 rounding points, in float64 or float32;
   * the transfer functions and the input / output transforms in numpy float64 (constants rounded to float32 first, as the device has them);
-  * synthetic weights (He-normal, seeded) for the standard channel table."""
+  * synthetic weights (He-normal, seeded) for the standard channel table or any other that follows the graph (table())."""
 import struct
 
 import numpy as np
@@ -22,6 +22,24 @@ def standard_channels(ic):
             ("enc_conv5a", EC4, EC5), ("enc_conv5b", EC5, EC5), ("dec_conv4a", (EC5, EC3), DC4), ("dec_conv4b", DC4, DC4),
             ("dec_conv3a", (DC4, EC2), DC3), ("dec_conv3b", DC3, DC3), ("dec_conv2a", (DC3, EC1), DC2), ("dec_conv2b", DC2, DC2),
             ("dec_conv1a", (DC2, ic), DC1A), ("dec_conv1b", DC1A, DC1B), ("dec_conv0", DC1B, 3)]
+
+
+def table(ic, e1, e2, e3, e4, e5, d4, d3, d2, d1a, d1b):
+    """[(name, cin, cout)] of the same graph with channel counts of the caller's (each in 1 .. 256): what a blob may bring.
+    standard_channels(ic) == table(ic, 32, 48, 64, 80, 96, 112, 96, 64, 64, 32)"""
+    return [("enc_conv0", ic, e1), ("enc_conv1", e1, e1), ("enc_conv2", e1, e2), ("enc_conv3", e2, e3), ("enc_conv4", e3, e4),
+            ("enc_conv5a", e4, e5), ("enc_conv5b", e5, e5), ("dec_conv4a", (e5, e3), d4), ("dec_conv4b", d4, d4),
+            ("dec_conv3a", (d4, e2), d3), ("dec_conv3b", d3, d3), ("dec_conv2a", (d3, e1), d2), ("dec_conv2b", d2, d2),
+            ("dec_conv1a", (d2, ic), d1a), ("dec_conv1b", d1a, d1b), ("dec_conv0", d1b, 3)]
+
+
+# two tables off the standard one (tests/test_gpu_nn_channels.py, tests/test_nn_cpu.py).  NARROW: counts that are no multiple of 16, 8 or
+# 4, a layer below one block (8, 5), ragged two-source layers.  WIDE: Cout of 8 blocks in one group (128), above 128 (two groups: 144,
+# 256, 200, 136, and 129, whose tenth block is padding), Cin up to 256 + 144 over two sources.
+NARROW = (20, 40, 8, 17, 33, 50, 24, 12, 31, 5)
+WIDE = (48, 72, 128, 144, 256, 200, 136, 129, 16, 64)
+# the level (frame >> level) of each layer's output before its pool, in the graph's order: ptx_nn_info.macs sums 9 Cin Cout pixels over it
+LEVELS = (0, 0, 1, 2, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0, 0)
 
 
 # ---- TZA -----------------------------------------------------------------------------------------------------------------------------
@@ -175,7 +193,9 @@ def _torch():
 
 
 def _h(x, dtype):
-    """one rounding to fp16 (nearest even), carried on in dtype"""
+    """one rounding to fp16 (nearest even), carried on in dtype.  Subnormal fp16 values are kept, as results here and as operands of
+    the next convolution: that is the definition, and what the device does (measured on gfx950, tests/test_gpu_nn_channels.py), so
+    the restatement has no flush-to-zero switch.  65520 and above rounds to inf."""
     torch = _torch()
     return x.to(torch.float16).to(dtype)
 
