@@ -636,7 +636,9 @@ int  ptx_denoise_adaptive(ptx_tracer *t, ptx_adaptive *a, ptx_moments *m, const 
  *   4 Exposure: E = applied * exposure (PTX_METER_BLOCKS) or E = exposure (PTX_METER_MANUAL: nothing is metered, the state is not
  *     touched).  x = c * E in fp32.  The map reads `applied` from device memory: the host never waits for an exposure.
  *   5 Tone: PTX_TONE_CLAMP y = x; PTX_TONE_REINHARD y = x (1 + L / white^2) / (1 + L), L = l(x); PTX_TONE_ACES per channel
- *     y = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14) (Narkowicz's fit).  Then y is clamped to [0, 1].
+ *     y = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14) (Narkowicz's fit).  Then y is clamped to [0, 1].  The curves are those of
+ *     the real numbers for every x in [0, +inf], x = c E beyond fp32's range included: a channel they take to 1 or beyond reads
+ *     transfer(1), never 0, and under Reinhard the ratios between a pixel's channels and L are kept there.
  *   6 Transfer: PTX_TRANSFER_LINEAR z = y; PTX_TRANSFER_SRGB z = 12.92 y for y <= 0.0031308, else 1.055 y^(1/2.4) - 0.055.
  *   7 Quantise, alpha 0 as ptx_write_pbo: quantize == 0: (int)((double)z * 255.0), the reference's truncation; quantize == 1:
  *     (int)(z * 255.f + 0.5f); with dither == 1 (read only when quantize == 1): (int)(z * 255.f + t[y & 7][x & 7]),

@@ -124,6 +124,22 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 
 __device__ __forceinline__ float aces(float x) { return (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f); }
 
+// Beyond what fp32 holds.  x = c E reaches 65504 * FLT_MAX, and a curve written as the rule writes it then divides inf by inf: both
+// products of aces() overflow from x of about 1.2e19, Reinhard is inf * inf / inf at x = inf, and clamp01 takes the NaN to 0 -- a
+// saturated channel came out black.  The two curves are kept the real numbers' curves in different ways, because ACES is a function
+// of one channel and Reinhard of the ratios between three:
+//   ACES     : x is held to X_CAP = 2^60 inside the curve.  The clamped curve is exactly 1 from x = 7.25 on, the largest product at
+//       the cap is 2^121, and no bit below the cap changes.  A select, not fminf: a NaN (0 * inf when applied * exposure overflowed)
+//       stays one and clamps to 0 as before.
+//   Reinhard : no channel is capped -- that would change x / L.  From L = 2^60 on, 1 + L is L to 2^-60, so
+//       y = x / L + x / white^2, and both terms are formed from c, where E cancels or can be multiplied in last:
+//       c / l(c) + ((c / white) * E) / white.  Below that L, x and L are finite and the rule's own expression stands, but for
+//       1 + L / white^2 = inf (a white below about 1e-19 beside any light), where x * inf would be 1 even for a channel of 1e-40
+//       whose y = x / white^2 is below 1: there the same quotient is taken with the large factor last.
+// tests/test_display_grid_cpu.py restates all of it in numpy float32 on non-grey pixels.
+constexpr float X_CAP = 0x1p60f;
+constexpr float F_MAX = 3.402823466e38f;
+
 // (the power through the hardware's log2 / exp2, about an ulp each: y is a normal number in (0.003, 1] here, and the result is held to
 // 1e-4 of the float64 restatement, not to libm's last bit; powf is a long routine, three times per pixel)
 __device__ __forceinline__ float transfer_srgb(float y) {
@@ -137,14 +153,25 @@ __device__ __forceinline__ unsigned quantise(float z, const MapArgs &a, float th
 
 // steps 1, 4 - 7 on one pixel: z into zr, zg, zb, the uchar4 (alpha 0) as the return value's four bytes
 __device__ __forceinline__ unsigned map_pixel(float r, float g, float b, float E, const MapArgs &a, int pixel, float &zr, float &zg, float &zb) {
-    const float xr = sanitise(r, a.samples) * E, xg = sanitise(g, a.samples) * E, xb = sanitise(b, a.samples) * E;
+    const float cr = sanitise(r, a.samples), cg = sanitise(g, a.samples), cb = sanitise(b, a.samples);
+    const float xr = cr * E, xg = cg * E, xb = cb * E;
     float yr = xr, yg = xg, yb = xb;
     if (a.tone == PTX_TONE_REINHARD) {
         const float L = pt_luminance(xr, xg, xb);
-        const float num = 1.f + L / (a.white * a.white), den = 1.f + L;
-        yr = xr * num / den; yg = xg * num / den; yb = xb * num / den;
+        const float w2 = a.white * a.white;
+        const float num = 1.f + L / w2, den = 1.f + L;
+        if (!(L < X_CAP)) {
+            const float Lc = pt_luminance(cr, cg, cb);
+            yr = cr / Lc + cr / a.white * E / a.white; yg = cg / Lc + cg / a.white * E / a.white; yb = cb / Lc + cb / a.white * E / a.white;
+        } else if (num > F_MAX) {
+            // (x / (1 + L), left out, is below 2^-128 of what stays; white^2 = 0: x / 0 = inf and 0 / 0 = NaN clamp to 1 and 0, as they should)
+            const float s = L / den;
+            yr = xr / w2 * s; yg = xg / w2 * s; yb = xb / w2 * s;
+        } else {
+            yr = xr * num / den; yg = xg * num / den; yb = xb * num / den;
+        }
     } else if (a.tone == PTX_TONE_ACES) {
-        yr = aces(xr); yg = aces(xg); yb = aces(xb);
+        yr = aces(xr > X_CAP ? X_CAP : xr); yg = aces(xg > X_CAP ? X_CAP : xg); yb = aces(xb > X_CAP ? X_CAP : xb);
     }
     yr = clamp01(yr); yg = clamp01(yg); yb = clamp01(yb);
     if (a.transfer == PTX_TRANSFER_SRGB) { yr = transfer_srgb(yr); yg = transfer_srgb(yg); yb = transfer_srgb(yb); }
