@@ -470,7 +470,10 @@ int  ptx_denoise_buffers_variance(int device, int w, int h, const float *rgb, co
  * Precision: everything is fp32.  acc - snap is exact or correctly rounded, but acc itself carries ulp(acc) / 2 per gather, so a batch
  * mean carries about ulp(acc) / k = 2^-23 N / k of the pixel's mean in rounding noise, against a sampling noise of sigma / sqrt(k):
  * negligible (below 1 % of the batch's standard deviation for sigma >= the mean / 10) below about 10^5 samples per pixel with batches
- * of at least 8.  W and B are held as floats: exact to 2^24.
+ * of at least 8.  W, k and B are held as floats, exact to 2^24: an add whose samples_total exceeds 2^24 is refused on every path
+ * (above it W' rounds, and an error of 1 in W' shifts D = W acc - W' snap by acc, as much as D itself once sigma / mean nears
+ * sqrt(k / W)).  Up to there the state stays within (B + 8) 2^-23 sqrt(C_ii C_jj) per covariance entry and (B + 2) 2^-23 |mean| per
+ * channel of the float64 definition fed the same buffers, however small the noise (tests/test_gpu_moments_grid.py).
  * The handle never looks at what the buffer holds: after ptx_reset_image (or ptx_write_image, or a camera change that restarts the
  * accumulation) the caller MUST call ptx_moments_reset before the next add, or that add's batch is the difference of two unrelated
  * frames.  A handle serves one W x H on one device, across tracers and streams, like ptx_temporal: each enqueueing call makes the
@@ -499,11 +502,11 @@ void ptx_moments_destroy(ptx_moments *m);          /* NULL is a no-op; waits for
 int  ptx_moments_reset(ptx_moments *m);            /* forget everything: required after ptx_reset_image (see above) */
 /* Enqueues one add on t's stream, ordered after every iteration rendered so far (render-ahead included: an iteration is in the buffer
  * once its ptx_iterate / ptx_render returned, exactly what ptx_denoise reads).  The accumulation buffer, statistics and what later
- * iterations compute are untouched.  Refused (PTX_ERR_INVALID, nothing enqueued): samples_total <= the last add's, a handle of another
- * device or size, tile_world > 1. */
+ * iterations compute are untouched.  Refused (PTX_ERR_INVALID, nothing enqueued): samples_total <= the last add's, samples_total >
+ * 2^24 (before any device call; the message names the value), a handle of another device or size, tile_world > 1. */
 int  ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total);
 /* The same from a host frame (W*H*3 floats, a sum of samples_total samples, e.g. after ptx_multi_read_image), through a staging buffer
- * the handle owns; synchronous. */
+ * the handle owns; synchronous.  samples_total > 2^24 is refused in the same way. */
 int  ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samples_total);
 /* The add in which tiles advance by different amounts (adaptive sampling below; multi-device callers): tile_samples_total[tile] = the
  * samples tile's pixels hold now, tile = (y * W + x) / ptx_tile_pixels(), ntiles = ceil(W * H / ptx_tile_pixels()).  The same update

@@ -54,7 +54,9 @@ __global__ __launch_bounds__(NT) void k_moments_add(int w, int h, int pairs, flo
     // d = x - mean with mean = snap / W (the weighted mean of the batch means IS the buffer over its samples), so
     // d = D / (k W), D = W acc - W' snap, and the scatter term k d (x - mean')^T = D D^T / (k W W').  D is formed from the two buffers by
     // exact products (the fma returns a product's rounding error), so it is right to an ulp of ITSELF however close the batch mean is to
-    // the running one; through x = fl(acc - snap) / k and a stored mean it would carry an ulp of the colour.
+    // the running one; through x = fl(acc - snap) / k and a stored mean it would carry an ulp of the colour.  This needs the unit's
+    // -ffp-contract=off: p1 - p2 contracted into fma(acc, wo, -p2) is no longer the difference the two residuals complete.  Held to
+    // (B + 8) 2^-23 sqrt(C_ii C_jj) by tests/test_gpu_moments_grid.py down to a relative noise of 1e-6 and up to W' = 2^24.
     const float wo = total - k;
     if (wo > 0.f) {
         const float kw = k * wo, den = kw * total, r = k / total;
@@ -302,6 +304,8 @@ int ptx_moments_add_host(ptx_moments *m, const float *host_rgb_sum, int64_t samp
         return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
                                             std::to_string(m->samples));
     if (m->tiled) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: this handle has had a tiled add; its tiles hold different sample counts until ptx_moments_reset");
+    if (samples_total > (1 << 24))                       // (W and k are held as floats: exact to 2^24)
+        return pt_fail(PTX_ERR_INVALID, "ptx_moments_add_host: samples_total " + std::to_string(samples_total) + " is above 2^24");
     const size_t n = (size_t)m->w * m->h;
     PT_HC(hipSetDevice(m->device));
     PT_HC(m->wait_host());

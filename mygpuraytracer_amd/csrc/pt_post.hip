@@ -320,6 +320,8 @@ int ptx_moments_add(ptx_moments *m, ptx_tracer *t, int64_t samples_total) {
         return pt_fail(PTX_ERR_INVALID, "ptx_moments_add: samples_total " + std::to_string(samples_total) + " does not exceed the last add's " +
                                             std::to_string(m->samples));
     if (m->tiled) return pt_fail(PTX_ERR_INVALID, "ptx_moments_add: " + std::string(TILED_HANDLE));
+    if (samples_total > (1 << 24))                       // (W and k are held as floats: exact to 2^24)
+        return pt_fail(PTX_ERR_INVALID, "ptx_moments_add: samples_total " + std::to_string(samples_total) + " is above 2^24");
     if (const int rc = moments_problem("ptx_moments_add", t, m)) return rc;
     PT_HC(hipSetDevice(t->device));
     PT_HC(m->wait_stream(t->stream));
