@@ -3,7 +3,7 @@
 // print-and-exit error policy (checkCUDAError, src/pathtrace.cu:42-60); the C ABI underneath returns codes.
 #include "pathtrace_api.h"
 
-#include <hip/hip_runtime_api.h>
+#include "pt_handle.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -70,13 +70,13 @@ Scene::Scene(const std::string &filename, const std::string &base_dir) : impl_(n
 Scene::~Scene() { ptx_scene_free(impl_); }
 
 void Scene::applyRunCudaCamera() {
-    *ptx_scene_camera(impl_) = *state.camera.c_abi();
+    *ptx_scene_camera(impl_) = ptx_camera(state.camera);
     ptx_scene_apply_runcuda_camera(impl_);
     state.camera = *ptx_scene_camera(impl_);
 }
 
 bool Scene::runOrbitScript(const std::string &script) {
-    *ptx_scene_camera(impl_) = *state.camera.c_abi();
+    *ptx_scene_camera(impl_) = ptx_camera(state.camera);
     ptx_orbit o;
     ptx_orbit_init(impl_, &o);
     ptx_orbit_apply(impl_, &o);
@@ -122,8 +122,8 @@ bool &pathtraceRenderAhead() {
 }
 
 PerformanceTimer &timer() {
-    static PerformanceTimer t;
-    return t;
+    static PerformanceTimer *t = new PerformanceTimer;      // (never destroyed: no HIP call from a static destructor, after the runtime may have gone)
+    return *t;
 }
 
 std::vector<int> &pathtraceDevices() {
@@ -132,13 +132,11 @@ std::vector<int> &pathtraceDevices() {
 }
 
 // ---- PerformanceTimer, src/timer.h:17-100 ---------------------------------------------------------------------------------
-// (events are created on first use: the instance behind timer() is a function-local static that may be constructed before the
-// process has picked a device)
+// (the two events of a GPU interval live from startGpuTimer to endGpuTimer; pathtraceFree() releases what the module's timer still
+// holds, the destructor what any other does)
 PerformanceTimer::PerformanceTimer() {}
-PerformanceTimer::~PerformanceTimer() {
-    if (event_start) (void)hipEventDestroy((hipEvent_t)event_start);
-    if (event_end) (void)hipEventDestroy((hipEvent_t)event_end);
-}
+PerformanceTimer::~PerformanceTimer() { mi355x_timer_release(*this); }
+void mi355x_timer_release(PerformanceTimer &t) { delete t.gpu_region; t.gpu_region = nullptr; }
 
 void PerformanceTimer::startCpuTimer() {
     if (cpu_timer_started) throw std::runtime_error("CPU timer already started");
@@ -158,18 +156,24 @@ void PerformanceTimer::endCpuTimer() {
 // between start and end, as it does in the reference.
 static hipStream_t timer_stream() { return g_tracer ? (hipStream_t)ptx_stream(g_tracer) : (hipStream_t) nullptr; }
 
+// The events are made where they are recorded: with the tracer's device current, or on the current device while there is no tracer.
+// A create or record that fails leaves no region, and the interval at 0.
 void PerformanceTimer::startGpuTimer() {
     if (gpu_timer_started) throw std::runtime_error("GPU timer already started");
     gpu_timer_started = true;
-    if (!event_start) { hipEvent_t a = nullptr, b = nullptr; (void)hipEventCreate(&a); (void)hipEventCreate(&b); event_start = a; event_end = b; }
-    if (event_start) (void)hipEventRecord((hipEvent_t)event_start, timer_stream());
+    mi355x_timer_release(*this);
+    gpu_region = new TimedRegion;
+    if ((g_tracer && hipSetDevice(g_device) != hipSuccess) || gpu_region->begin(timer_stream()) != hipSuccess) {
+        (void)hipGetLastError();
+        mi355x_timer_release(*this);
+    }
 }
 
 void PerformanceTimer::endGpuTimer() {
-    if (event_end) { (void)hipEventRecord((hipEvent_t)event_end, timer_stream()); (void)hipEventSynchronize((hipEvent_t)event_end); }
-    if (!gpu_timer_started) throw std::runtime_error("GPU timer not started");
     float ms = 0.f;
-    if (event_start && event_end && hipEventElapsedTime(&ms, (hipEvent_t)event_start, (hipEvent_t)event_end) != hipSuccess) { ms = 0.f; (void)hipGetLastError(); }
+    if (gpu_region && gpu_region->end(&ms) != hipSuccess) { ms = 0.f; (void)hipGetLastError(); }
+    mi355x_timer_release(*this);
+    if (!gpu_timer_started) throw std::runtime_error("GPU timer not started");
     prev_elapsed_time_gpu_milliseconds = ms;
     gpu_timer_started = false;
     gpu_interval_is_callers = true;
@@ -410,7 +414,7 @@ void pathtraceInit(Scene *scene) {
     const std::vector<int> &devs = pathtraceDevices();
     if (devs.size() > 1) {
         // the C ABI's multi-device layer takes the loaded scene: hand it the caller's camera and depth first
-        *ptx_scene_camera(scene->handle()) = *scene->state.camera.c_abi();
+        *ptx_scene_camera(scene->handle()) = ptx_camera(scene->state.camera);
         ptx_scene_set_trace_depth(scene->handle(), scene->state.traceDepth);
         check(ptx_multi_create(scene->handle(), &pathtraceOptions(), devs.data(), (int)devs.size(), 0, &g_multi), "pathtraceInit");
         g_tracer = ptx_multi_tracer(g_multi, 0);
@@ -419,8 +423,9 @@ void pathtraceInit(Scene *scene) {
     } else {
         ptx_options o = pathtraceOptions();
         if (devs.size() == 1) o.device = devs[0];
+        const ptx_camera cam = scene->state.camera;
         check(ptx_create((int)scene->geoms.size(), scene->geoms.data(), (int)scene->materials.size(), scene->materials.data(),
-                         scene->state.camera.c_abi(), scene->state.traceDepth, &o, nullptr, nullptr, &g_tracer),
+                         &cam, scene->state.traceDepth, &o, nullptr, nullptr, &g_tracer),
               "pathtraceInit");
         check(ptx_set_render_ahead(g_tracer, pathtraceRenderAhead() ? 1 : 0), "pathtraceInit");
         g_device = o.device;
@@ -435,6 +440,7 @@ void pathtraceInit(Scene *scene) {
 }
 
 void pathtraceFree() {          // safe before init and idempotent, as main.cpp:129 relies on
+    mi355x_timer_release(timer());      // (an interval begun and not ended: its events go before the stream they were recorded on)
     for (void *&p : g_pinned) { if (p) ptx_unpin_host_buffer(p); p = nullptr; }
     if (g_multi) ptx_multi_destroy(g_multi);
     else ptx_destroy(g_tracer);
@@ -450,8 +456,9 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
     g_output_on_device = false;
     // the reference re-reads camera and traceDepth on every call (src/pathtrace.cu:434-436)
     const bool apps = pathtraceOptions().apps_variant != 0;
+    const ptx_camera cam = hst_scene->state.camera;
     if (g_multi) {               // several devices: every device its tile, then the row blocks into device 0's frame
-        check(ptx_multi_set_camera(g_multi, hst_scene->state.camera.c_abi(), hst_scene->state.traceDepth), "pathtrace camera");
+        check(ptx_multi_set_camera(g_multi, &cam, hst_scene->state.traceDepth), "pathtrace camera");
         check(ptx_multi_iterate(g_multi, iter), "pathtrace");
         check(ptx_multi_read_image(g_multi, &hst_scene->state.image[0].x), "image readback");      // assemble + :555-556
         if (!apps) write_preview(iter, pbo);                                                       // from the assembled frame
@@ -465,7 +472,7 @@ void mi355x::pathtrace_raw(void *pbo, int frame, int iter) {
         moments_step(iter);
         return;
     }
-    check(ptx_set_camera(g_tracer, hst_scene->state.camera.c_abi(), hst_scene->state.traceDepth), "pathtrace camera");
+    check(ptx_set_camera(g_tracer, &cam, hst_scene->state.traceDepth), "pathtrace camera");
     check(ptx_iterate(g_tracer, iter), "pathtrace");
     // apps/src builds with AI_DENOISE: no preview from here (sendToGPU shows the denoised frame), the albedo AOV comes back
     // with the image (apps/src/pathtrace.cu:658-669)

@@ -42,6 +42,7 @@
 #include <type_traits>
 #include <utility>
 #include <cstddef>
+#include <cstring>
 
 namespace mi355x {
 namespace detail {
@@ -149,7 +150,7 @@ typedef ptx_geom Geom;            // src/sceneStructs.h:50-69 (POD subset the tr
 typedef ptx_material Material;    // src/sceneStructs.h:71-81
 
 // src/sceneStructs.h:83-92 -- the reference's member names and (glm-like) member types; the bytes are ptx_camera's, so the veneer hands
-// `&state.camera` to the C ABI as it is (asserted below)
+// bytes of `state.camera` to the C ABI as they are (asserted below), copied with memcpy in either direction
 struct Camera {
     mi355x::ivec2 resolution;
     mi355x::vec3 position;
@@ -161,10 +162,11 @@ struct Camera {
     mi355x::vec2 pixelLength;
     Camera() = default;
     Camera(const ptx_camera &c) { *this = c; }
-    Camera &operator=(const ptx_camera &c) { *reinterpret_cast<ptx_camera *>(this) = c; return *this; }
+    Camera &operator=(const ptx_camera &c) { std::memcpy(this, &c, sizeof c); return *this; }
+    operator ptx_camera() const { ptx_camera c; std::memcpy(&c, this, sizeof c); return c; }
+    // (the address alone, for a caller that hands it on; the veneer itself converts by value, above)
     ptx_camera *c_abi() { return reinterpret_cast<ptx_camera *>(this); }
     const ptx_camera *c_abi() const { return reinterpret_cast<const ptx_camera *>(this); }
-    operator ptx_camera() const { return *c_abi(); }
 };
 static_assert(std::is_standard_layout<Camera>::value && std::is_trivially_copyable<Camera>::value, "Camera crosses the C ABI as bytes");
 static_assert(sizeof(Camera) == sizeof(ptx_camera) && alignof(Camera) == alignof(ptx_camera), "Camera = ptx_camera");
@@ -228,7 +230,8 @@ public:
     PerformanceTimer &operator=(PerformanceTimer &&) = delete;
 private:
     friend void mi355x_timer_note_pathtrace(PerformanceTimer &);
-    void *event_start = nullptr, *event_end = nullptr;       // hipEvent_t (this header does not need HIP's)
+    friend void mi355x_timer_release(PerformanceTimer &);
+    struct TimedRegion *gpu_region = nullptr;                 // start/endGpuTimer's two events, from a start to its end (pt_handle.h: this header does not need HIP's)
     long long time_start_cpu_ns = 0;
     bool cpu_timer_started = false, gpu_timer_started = false;
     bool gpu_interval_is_callers = false;                     // the last GPU figure came from start/endGpuTimer, not from pathtrace()

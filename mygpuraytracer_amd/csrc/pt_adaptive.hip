@@ -200,7 +200,7 @@ int alloc_adaptive(ptx_adaptive *a) {
     PT_HC(a->d_out.alloc(bytes));
     PT_HC(hipHostMalloc(&a->h_out, bytes, hipHostMallocDefault));
     PT_HC(a->d_frame.alloc(3 * (size_t)a->w * a->h));
-    PT_HC(hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
+    PT_HC(a->ev.create(hipEventDisableTiming));
     return clear_adaptive(a);
 }
 

@@ -25,8 +25,7 @@
 
 #include "../../include/mi355x_pathtracer.h"
 #include "../../include/mi355x_stream_compaction.h"
-
-extern "C" void ptx_internal_set_error(const char *msg);
+#include "pt_handle.h"
 
 namespace {
 
@@ -44,9 +43,6 @@ constexpr u64 ST_AGGREGATE = 1ull << 32;                       // low word = thi
 constexpr u64 ST_INCLUSIVE = 2ull << 32;                       // low word = total of this tile and everything before it
 
 thread_local float g_gpu_ms = 0.f, g_cpu_ms = 0.f;
-
-int sc_fail(const std::string &m) { ptx_internal_set_error(m.c_str()); return PTX_ERR_HIP; }
-#define SC_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 // inclusive prefix sum over the lanes of a wave in the vector ALU's own lane network (DPP), as pt_kernels.hip's waveInclusiveScan: four
 // shifted adds inside the rows of 16 lanes, lane 15 of a row broadcast into the next row (rows 1 and 3), lane 31 into the upper half.
@@ -210,11 +206,20 @@ int onepass_device(int n, int *d_out, const int *d_in, int *d_count, void *d_ws,
     const int ntiles = sc_tiles(n);
     unsigned *ticket = (unsigned *)d_ws;
     u64 *status = (u64 *)((char *)d_ws + SC_HEAD);
-    SC_CHECK(hipMemsetAsync(d_ws, 0, SC_HEAD + sizeof(u64) * (size_t)ntiles, st));
+    PT_HC(hipMemsetAsync(d_ws, 0, SC_HEAD + sizeof(u64) * (size_t)ntiles, st));
     if (compact) hipLaunchKernelGGL((k_onepass<true, SC_COMPACT_THREADS>), dim3(ntiles), dim3(SC_COMPACT_THREADS), 0, st, n, d_in, d_out, ticket, status, d_count);
     else hipLaunchKernelGGL((k_onepass<false, SC_SCAN_THREADS>), dim3(ntiles), dim3(SC_SCAN_THREADS), 0, st, n, d_in, d_out, ticket, status, d_count);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
+}
+
+// what the host-pointer entry points time: `run` on the null stream between the two events of a timed region, the milliseconds in g_gpu_ms
+template <class Run> int timed_on_null_stream(Run run) {
+    TimedRegion timed;
+    PT_HC(timed.begin(0));
+    const int rc = run();
+    PT_HC(timed.end(&g_gpu_ms));
+    return rc;
 }
 
 // host-pointer scan shared by the three reference entry points (naive.cu:32, efficient.cu:35, thrust.cu:20)
@@ -225,22 +230,28 @@ int host_scan(int n, int *odata, const int *idata) {
         ptx_internal_set_error("no HIP device available; the GPU scan has no CPU path (use sc_cpu_scan)");
         return PTX_ERR_NODEVICE;
     }
-    int *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
-    hipEvent_t e0, e1;
-    SC_CHECK(hipMalloc(&d_in, sizeof(int) * (size_t)n));
-    SC_CHECK(hipMalloc(&d_out, sizeof(int) * (size_t)n));
-    SC_CHECK(hipMalloc(&d_ws, sc_scan_workspace_bytes(n)));
-    SC_CHECK(hipMemcpy(d_in, idata, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    SC_CHECK(hipEventCreate(&e0)); SC_CHECK(hipEventCreate(&e1));
-    SC_CHECK(hipEventRecord(e0, 0));
-    int rc = onepass_device(n, d_out, d_in, nullptr, d_ws, 0, false);
-    SC_CHECK(hipEventRecord(e1, 0));
-    SC_CHECK(hipEventSynchronize(e1));
-    SC_CHECK(hipEventElapsedTime(&g_gpu_ms, e0, e1));
-    if (rc == PTX_OK) SC_CHECK(hipMemcpy(odata, d_out, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(d_in); hipFree(d_out); hipFree(d_ws);
+    DevBuf<int> d_in, d_out;
+    DevBuf<char> d_ws;
+    PT_HC(d_in.upload(idata, (size_t)n));
+    PT_HC(d_out.alloc((size_t)n));
+    PT_HC(d_ws.alloc(sc_scan_workspace_bytes(n)));
+    const int rc = timed_on_null_stream([&] { return onepass_device(n, d_out, d_in, nullptr, d_ws, 0, false); });
+    if (rc == PTX_OK) PT_HC(d_out.download(odata));
     return rc;
+}
+
+// host-pointer compaction (efficient.cu:79-136): *count survivors in odata
+int compact_host(int n, int *odata, const int *idata, int *count) {
+    DevBuf<int> d_in, d_out, d_count;
+    DevBuf<char> d_ws;
+    PT_HC(d_in.upload(idata, (size_t)n));
+    PT_HC(d_out.alloc((size_t)n));
+    PT_HC(d_count.alloc(1));
+    PT_HC(d_ws.alloc(sc_scan_workspace_bytes(n)));
+    if (const int rc = timed_on_null_stream([&] { return sc_compact_device(n, d_out, d_in, d_count, d_ws, nullptr); })) return rc;
+    PT_HC(d_count.download(count));
+    if (*count > 0) PT_HC(hipMemcpy(odata, d_out, sizeof(int) * (size_t)*count, hipMemcpyDeviceToHost));
+    return PTX_OK;
 }
 
 struct CpuTimer {
@@ -454,7 +465,7 @@ int records_device(const char *what, int n, int nkeys, int descending, bool flag
     }
     if (int rc = sr_no_device(what)) return rc;
     if (n == 0) {
-        if (d_totals) SC_CHECK(hipMemsetAsync(d_totals, 0, sizeof(int) * (size_t)ntotals, st));
+        if (d_totals) PT_HC(hipMemsetAsync(d_totals, 0, sizeof(int) * (size_t)ntotals, st));
         return PTX_OK;
     }
     const int tiles = sr_tiles(n), m = nkeys * tiles;
@@ -462,26 +473,15 @@ int records_device(const char *what, int n, int nkeys, int descending, bool flag
     SrKeys K;
     K.keys = (const char *)d_keys; K.stride = stride; K.nkeys = nkeys; K.flags = flags; K.descending = descending != 0;
     hipLaunchKernelGGL(k_records_count, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, table);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     if (int rc = onepass_device(m, table, table, nullptr, d_ws, st, false)) return rc;
     hipLaunchKernelGGL(k_records_move, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, (const int *)table, sr_array(d_out_a, d_in_a, bytes_a),
                        sr_array(has_b ? d_out_b : nullptr, has_b ? d_in_b : nullptr, has_b ? bytes_b : 4), d_perm, d_totals, ntotals, compact ? 1 : 0);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 
 // host-pointer forms: allocate, copy in, run on the null stream, copy out -- as sc_efficient_compact does for ints
-struct SrDeviceBuffers {
-    void *p[8] = {};
-    int used = 0;
-    ~SrDeviceBuffers() { for (int i = 0; i < used; i++) hipFree(p[i]); }
-    hipError_t get(void **out, size_t bytes) {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 4);
-        if (e == hipSuccess) p[used++] = *out;
-        return e;
-    }
-};
-
 int records_host(const char *what, int n, int nkeys, int descending, bool flags, bool compact, const int *keys,
                  void *out_a, const void *in_a, int bytes_a, void *out_b, const void *in_b, int bytes_b, int *perm, int *totals, int ntotals) {
     const bool has_b = out_b || in_b || bytes_b;
@@ -489,35 +489,24 @@ int records_host(const char *what, int n, int nkeys, int descending, bool flags,
     if (n > 0 && (!keys || !out_a || !in_a || (has_b && (!out_b || !in_b)))) return sr_invalid(what, "a host pointer", 0, "is null");
     if (int rc = sr_no_device(what)) return rc;
     if (n == 0) { for (int k = 0; totals && k < ntotals; k++) totals[k] = 0; return PTX_OK; }
-    SrDeviceBuffers dev;
-    void *d_keys = nullptr, *d_in_a = nullptr, *d_out_a = nullptr, *d_in_b = nullptr, *d_out_b = nullptr, *d_perm = nullptr, *d_tot = nullptr, *d_ws = nullptr;
+    DevBuf<int> d_keys, d_perm, d_tot;                         // (d_in_b, d_out_b and d_perm stay NULL where the caller has none)
+    DevBuf<char> d_in_a, d_out_a, d_in_b, d_out_b, d_ws;
     const size_t na = (size_t)n * bytes_a, nb = has_b ? (size_t)n * bytes_b : 0;
-    SC_CHECK(dev.get(&d_keys, sizeof(int) * (size_t)n));
-    SC_CHECK(dev.get(&d_in_a, na)); SC_CHECK(dev.get(&d_out_a, na));
-    if (has_b) { SC_CHECK(dev.get(&d_in_b, nb)); SC_CHECK(dev.get(&d_out_b, nb)); }
-    if (perm) SC_CHECK(dev.get(&d_perm, sizeof(int) * (size_t)n));
-    SC_CHECK(dev.get(&d_tot, sizeof(int) * (size_t)ntotals));
-    SC_CHECK(dev.get(&d_ws, sc_records_workspace_bytes(n, nkeys)));
-    SC_CHECK(hipMemcpy(d_keys, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    SC_CHECK(hipMemcpy(d_in_a, in_a, na, hipMemcpyHostToDevice));
-    if (has_b) SC_CHECK(hipMemcpy(d_in_b, in_b, nb, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    SC_CHECK(hipEventCreate(&e0)); SC_CHECK(hipEventCreate(&e1));
-    SC_CHECK(hipEventRecord(e0, 0));
-    const int rc = records_device(what, n, nkeys, descending, flags, compact, d_keys, 4, d_out_a, d_in_a, bytes_a, d_out_b, d_in_b, bytes_b,
-                                  (int *)d_perm, (int *)d_tot, ntotals, d_ws, 0);
-    SC_CHECK(hipEventRecord(e1, 0));
-    SC_CHECK(hipEventSynchronize(e1));
-    SC_CHECK(hipEventElapsedTime(&g_gpu_ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (rc != PTX_OK) return rc;
+    PT_HC(d_keys.upload(keys, (size_t)n));
+    PT_HC(d_in_a.upload(in_a, na)); PT_HC(d_out_a.alloc(na));
+    if (has_b) { PT_HC(d_in_b.upload(in_b, nb)); PT_HC(d_out_b.alloc(nb)); }
+    if (perm) PT_HC(d_perm.alloc((size_t)n));
+    PT_HC(d_tot.alloc((size_t)ntotals));
+    PT_HC(d_ws.alloc(sc_records_workspace_bytes(n, nkeys)));
+    if (const int rc = timed_on_null_stream([&] { return records_device(what, n, nkeys, descending, flags, compact, d_keys, 4, d_out_a, d_in_a, bytes_a,
+                                                                        d_out_b, d_in_b, bytes_b, d_perm, d_tot, ntotals, d_ws, 0); })) return rc;
     int first = 0;                                             // partition / compaction: the count; what compaction wrote ends there
-    SC_CHECK(hipMemcpy(&first, d_tot, sizeof(int), hipMemcpyDeviceToHost));
-    if (totals) SC_CHECK(hipMemcpy(totals, d_tot, sizeof(int) * (size_t)ntotals, hipMemcpyDeviceToHost));
+    PT_HC(hipMemcpy(&first, d_tot, sizeof(int), hipMemcpyDeviceToHost));
+    if (totals) PT_HC(d_tot.download(totals));
     const size_t written = compact ? (size_t)first : (size_t)n;
-    if (written) SC_CHECK(hipMemcpy(out_a, d_out_a, written * bytes_a, hipMemcpyDeviceToHost));
-    if (has_b && written) SC_CHECK(hipMemcpy(out_b, d_out_b, written * bytes_b, hipMemcpyDeviceToHost));
-    if (perm && written) SC_CHECK(hipMemcpy(perm, d_perm, sizeof(int) * written, hipMemcpyDeviceToHost));
+    if (written) PT_HC(hipMemcpy(out_a, d_out_a, written * bytes_a, hipMemcpyDeviceToHost));
+    if (has_b && written) PT_HC(hipMemcpy(out_b, d_out_b, written * bytes_b, hipMemcpyDeviceToHost));
+    if (perm && written) PT_HC(hipMemcpy(perm, d_perm, sizeof(int) * written, hipMemcpyDeviceToHost));
     return PTX_OK;
 }
 
@@ -749,15 +738,15 @@ int radix_device(const char *what, int n, int key_type, int descending, int begi
         const bool last = p + 1 == passes;
         unsigned *u_out = last ? nullptr : buf[2 * (p & 1)], *i_out = buf[2 * (p & 1) + 1];
         hipLaunchKernelGGL(k_radix_count, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, table);
-        SC_CHECK(hipGetLastError());
+        PT_HC(hipGetLastError());
         if (int rc = onepass_device((1 << K.bits) * tiles, table, table, nullptr, d_ws, st, false)) return rc;
         hipLaunchKernelGGL(k_radix_move, dim3(tiles), dim3(SR_THREADS), 0, st, n, tiles, K, (const int *)table, u_out, i_out);
-        SC_CHECK(hipGetLastError());
+        PT_HC(hipGetLastError());
         K.u_in = u_out; K.i_in = i_out;
     }
     hipLaunchKernelGGL(k_radix_gather, dim3(tiles), dim3(SR_THREADS), 0, st, n, K, (const unsigned *)K.i_in, sr_array(d_out_a, d_in_a, bytes_a),
                        sr_array(has_b ? d_out_b : nullptr, has_b ? d_in_b : nullptr, has_b ? bytes_b : 4), d_perm, (unsigned *)d_keys_out);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 
@@ -768,32 +757,21 @@ int radix_host(const char *what, int n, int key_type, int descending, int begin_
     if (n > 0 && (!keys || !out_a || !in_a || (has_b && (!out_b || !in_b)))) return sr_invalid(what, "a host pointer", 0, "is null");
     if (int rc = sr_no_device(what)) return rc;
     if (n == 0) return PTX_OK;
-    SrDeviceBuffers dev;
-    void *d_keys = nullptr, *d_in_a = nullptr, *d_out_a = nullptr, *d_in_b = nullptr, *d_out_b = nullptr, *d_perm = nullptr, *d_kout = nullptr, *d_ws = nullptr;
-    const size_t na = (size_t)n * bytes_a, nb = has_b ? (size_t)n * bytes_b : 0, nk = sizeof(int) * (size_t)n;
-    SC_CHECK(dev.get(&d_keys, nk));
-    SC_CHECK(dev.get(&d_in_a, na)); SC_CHECK(dev.get(&d_out_a, na));
-    if (has_b) { SC_CHECK(dev.get(&d_in_b, nb)); SC_CHECK(dev.get(&d_out_b, nb)); }
-    if (perm) SC_CHECK(dev.get(&d_perm, nk));
-    if (keys_out) SC_CHECK(dev.get(&d_kout, nk));
-    SC_CHECK(dev.get(&d_ws, sc_radix_workspace_bytes(n)));
-    SC_CHECK(hipMemcpy(d_keys, keys, nk, hipMemcpyHostToDevice));
-    SC_CHECK(hipMemcpy(d_in_a, in_a, na, hipMemcpyHostToDevice));
-    if (has_b) SC_CHECK(hipMemcpy(d_in_b, in_b, nb, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    SC_CHECK(hipEventCreate(&e0)); SC_CHECK(hipEventCreate(&e1));
-    SC_CHECK(hipEventRecord(e0, 0));
-    const int rc = radix_device(what, n, key_type, descending, begin_bit, end_bit, d_keys, 4, d_out_a, d_in_a, bytes_a, d_out_b, d_in_b, bytes_b,
-                                (int *)d_perm, d_kout, d_ws, 0);
-    SC_CHECK(hipEventRecord(e1, 0));
-    SC_CHECK(hipEventSynchronize(e1));
-    SC_CHECK(hipEventElapsedTime(&g_gpu_ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (rc != PTX_OK) return rc;
-    SC_CHECK(hipMemcpy(out_a, d_out_a, na, hipMemcpyDeviceToHost));
-    if (has_b) SC_CHECK(hipMemcpy(out_b, d_out_b, nb, hipMemcpyDeviceToHost));
-    if (perm) SC_CHECK(hipMemcpy(perm, d_perm, nk, hipMemcpyDeviceToHost));
-    if (keys_out) SC_CHECK(hipMemcpy(keys_out, d_kout, nk, hipMemcpyDeviceToHost));
+    DevBuf<int> d_keys, d_perm, d_kout;                        // (d_in_b, d_out_b, d_perm and d_kout stay NULL where the caller has none)
+    DevBuf<char> d_in_a, d_out_a, d_in_b, d_out_b, d_ws;
+    const size_t na = (size_t)n * bytes_a, nb = has_b ? (size_t)n * bytes_b : 0;
+    PT_HC(d_keys.upload(keys, (size_t)n));
+    PT_HC(d_in_a.upload(in_a, na)); PT_HC(d_out_a.alloc(na));
+    if (has_b) { PT_HC(d_in_b.upload(in_b, nb)); PT_HC(d_out_b.alloc(nb)); }
+    if (perm) PT_HC(d_perm.alloc((size_t)n));
+    if (keys_out) PT_HC(d_kout.alloc((size_t)n));
+    PT_HC(d_ws.alloc(sc_radix_workspace_bytes(n)));
+    if (const int rc = timed_on_null_stream([&] { return radix_device(what, n, key_type, descending, begin_bit, end_bit, d_keys, 4, d_out_a, d_in_a, bytes_a,
+                                                                      d_out_b, d_in_b, bytes_b, d_perm, d_kout, d_ws, 0); })) return rc;
+    PT_HC(d_out_a.download(out_a));
+    if (has_b) PT_HC(d_out_b.download(out_b));
+    if (perm) PT_HC(d_perm.download(perm));
+    if (keys_out) PT_HC(d_kout.download(keys_out));
     return PTX_OK;
 }
 
@@ -850,29 +828,8 @@ int sc_efficient_compact(int n, int *odata, const int *idata) {
         ptx_internal_set_error("no HIP device available; the GPU compaction has no CPU path (use sc_cpu_compact_*)");
         return -1;
     }
-    int *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr, *d_count = nullptr;
-    hipEvent_t e0, e1;
-#define SCC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { sc_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); return -1; } } while (0)
-    SCC(hipMalloc(&d_in, sizeof(int) * (size_t)n));
-    SCC(hipMalloc(&d_out, sizeof(int) * (size_t)n));
-    SCC(hipMalloc(&d_count, sizeof(int)));
-    SCC(hipMalloc(&d_ws, sc_scan_workspace_bytes(n)));
-    SCC(hipMemcpy(d_in, idata, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    SCC(hipEventCreate(&e0)); SCC(hipEventCreate(&e1));
-    SCC(hipEventRecord(e0, 0));
-    int rc = sc_compact_device(n, d_out, d_in, d_count, d_ws, nullptr);
-    SCC(hipEventRecord(e1, 0));
-    SCC(hipEventSynchronize(e1));
-    SCC(hipEventElapsedTime(&g_gpu_ms, e0, e1));
     int count = -1;
-    if (rc == PTX_OK) {
-        SCC(hipMemcpy(&count, d_count, sizeof(int), hipMemcpyDeviceToHost));
-        if (count > 0) SCC(hipMemcpy(odata, d_out, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
-    }
-#undef SCC
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(d_in); hipFree(d_out); hipFree(d_ws); hipFree(d_count);
-    return count;
+    return compact_host(n, odata, idata, &count) == PTX_OK ? count : -1;      // (the reference's int: -1 for every failure)
 }
 
 unsigned long long sc_scan_workspace_bytes(int n) {
@@ -891,7 +848,7 @@ int sc_scan_device(int n, int *d_odata, const int *d_idata, void *d_workspace, v
 int sc_compact_device(int n, int *d_odata, const int *d_idata, int *d_count, void *d_workspace, void *stream) {
     if (!d_count) { ptx_internal_set_error("null device pointer"); return PTX_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
-    if (n <= 0) { SC_CHECK(hipMemsetAsync(d_count, 0, sizeof(int), st)); return PTX_OK; }
+    if (n <= 0) { PT_HC(hipMemsetAsync(d_count, 0, sizeof(int), st)); return PTX_OK; }
     if (!d_odata || !d_idata || !d_workspace) { ptx_internal_set_error("null device pointer"); return PTX_ERR_INVALID; }
     if (((uintptr_t)d_workspace) & 7) { ptx_internal_set_error("workspace must be 8-byte aligned"); return PTX_ERR_INVALID; }
     return onepass_device(n, d_odata, d_idata, d_count, d_workspace, st, true);
@@ -906,7 +863,7 @@ int sc_map_to_boolean_device(int n, int *d_bools, const int *d_idata, void *stre
     const int n4 = (((uintptr_t)d_bools | (uintptr_t)d_idata) & 15) == 0 ? n / 4 : 0;
     const int work = n4 + (n - 4 * n4);
     hipLaunchKernelGGL(k_map_to_boolean, dim3((unsigned)std::min(8192, (work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, n4, d_bools, d_idata);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 
@@ -914,7 +871,7 @@ int sc_scatter_device(int n, int *d_odata, const int *d_idata, const int *d_bool
     if (n <= 0) return PTX_OK;
     if (!d_odata || !d_idata || !d_bools || !d_indices) { ptx_internal_set_error("null device pointer"); return PTX_ERR_INVALID; }
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)std::min(8192, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_odata, d_idata, d_bools, d_indices);
-    SC_CHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 

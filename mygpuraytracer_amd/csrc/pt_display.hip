@@ -225,7 +225,7 @@ int alloc_display(ptx_display *d) {
     PT_HC(d->d_state.alloc(1));
     PT_HC(d->d_state.zero());
     PT_HC(d->d_codes.alloc(n));
-    PT_HC(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
+    PT_HC(d->ev.create(hipEventDisableTiming));
     return PTX_OK;
 }
 

@@ -26,15 +26,7 @@
 
 namespace {
 
-thread_local std::string g_last_error;
-int set_error(int code, const std::string &msg) { g_last_error = msg; return code; }
-
-#define HIPCHECK(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
-    } while (0)
+thread_local std::string g_last_error;      // (written through ptx_internal_set_error: pt_fail and PT_HC, pt_handle.h)
 
 // debug capture: the sorted stream materialised -- what the next k_bounce would read, resolved the slow, obvious way from the same
 // tables (run prefixes by one thread, a binary search per position), so that the parity tests see the order the kernels define
@@ -278,7 +270,7 @@ void ahead_discard(ptx_tracer *t);
 // enqueues k_tile_mask (pt_adaptive.hip: this unit holds the tracer's own kernels only) on the tracer's stream: the base table and the
 // flags into the effective table, and the flags into the tracer's copy
 int apply_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
-    HIPCHECK(pt_tile_mask_enqueue(t->stream, t->maxTiles, d_flags, t->d_tile_active.p, t->d_tile_geoms.p, t->d_tile_eff.p));
+    PT_HC(pt_tile_mask_enqueue(t->stream, t->maxTiles, d_flags, t->d_tile_active.p, t->d_tile_geoms.p, t->d_tile_eff.p));
     return PTX_OK;
 }
 
@@ -289,8 +281,8 @@ int update_tile_geoms(ptx_tracer *t) {
     if (dof && t->dbg.no_tile_geoms_dof) return PTX_OK;
     std::vector<uint32_t> masks;
     tile_geom_masks(t->cam, t->tm.tile_rows, t->tm.tile_rank, t->tm.tile_world, t->tm.owned, t->maxTiles, t->ngeoms, t->h_aabb.data(), dof, masks);
-    HIPCHECK(hipMemcpyAsync(t->d_tile_geoms, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));      // (masks is a local)
+    PT_HC(hipMemcpyAsync(t->d_tile_geoms, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));      // (masks is a local)
     t->tile_geoms_valid = true;
     if (t->mask_set) return apply_tile_mask(t, t->d_tile_active);      // the mask outlives a camera change
     return PTX_OK;
@@ -298,8 +290,8 @@ int update_tile_geoms(ptx_tracer *t) {
 
 int mask_buffers(ptx_tracer *t) {                       // (on the first mask)
     if (t->d_tile_eff) return PTX_OK;
-    HIPCHECK(t->d_tile_active.alloc((size_t)t->maxTiles));
-    HIPCHECK(t->d_tile_eff.alloc((size_t)t->maxTiles));
+    PT_HC(t->d_tile_active.alloc((size_t)t->maxTiles));
+    PT_HC(t->d_tile_eff.alloc((size_t)t->maxTiles));
     return PTX_OK;
 }
 
@@ -321,7 +313,7 @@ const char *pt_active_tiles_problem(const ptx_tracer *t, int ntiles, int &code) 
 // is written by a launch of its own; d_flags: one byte per tile on the device
 int pt_set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
     if (const int rc = mask_buffers(t)) return rc;
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     ahead_discard(t);
     if (const int rc = apply_tile_mask(t, d_flags ? d_flags : t->d_tile_active.p)) return rc;
     t->mask_set = true;
@@ -330,23 +322,12 @@ int pt_set_tile_mask(ptx_tracer *t, const uint8_t *d_flags) {
 
 namespace {
 
-int free_tracer(ptx_tracer *t) {
-    if (!t) return PTX_OK;
+void free_tracer(ptx_tracer *t) {
+    if (!t) return;
     hipSetDevice(t->device);
     if (t->stream) hipStreamSynchronize(t->stream);
     for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) hipStreamSynchronize(t->lane_stream[l]);      // work traced ahead
-    for (hipEvent_t e : t->kev) hipEventDestroy(e);
-    if (t->ev_start) hipEventDestroy(t->ev_start);
-    if (t->ev_stop) hipEventDestroy(t->ev_stop);
-    for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) hipStreamDestroy(t->lane_stream[l]);
-    if (t->ev_fork) hipEventDestroy(t->ev_fork);
-    for (hipEvent_t e : t->ev_join) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : t->ev_chain) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : t->ev_ahead0) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : t->ev_ahead1) if (e) hipEventDestroy(e);
-    if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
-    delete t;                                            // (the device buffers go with it: DevBuf)
-    return PTX_OK;
+    delete t;                                            // (buffers, events and streams go with it, in that order: pt_tracer.h)
 }
 
 // The specialised variants k_bounce<., ., FAST> hard-wire option values inside the kernel (sort = 1, no cache fill, no albedo, per-
@@ -396,7 +377,7 @@ int launch_bounce(const ptx_tracer *t, bool first, int mode, bool needs_albedo, 
     const char *why = fast_violation(t, mode, first, needs_albedo, bp);
     bool fast = !t->dbg.no_fast && !why;
     if (t->dbg.force_fast) {
-        if (why) return set_error(PTX_ERR_INVALID, std::string("specialised k_bounce requested outside its preconditions: ") + why);
+        if (why) return pt_fail(PTX_ERR_INVALID, std::string("specialised k_bounce requested outside its preconditions: ") + why);
         fast = true;
     }
     if (!t->dbg.no_last && !last_violation(t, mode, first, bp)) {
@@ -442,18 +423,18 @@ struct KernelTimer {
     int begin(int kind) const {
         if (!t->ktiming) return PTX_OK;
         if (t->kev_used + 2 > t->kev.size()) {
-            hipEvent_t a, b2;
-            HIPCHECK(hipEventCreate(&a)); HIPCHECK(hipEventCreate(&b2));
-            t->kev.push_back(a); t->kev.push_back(b2);
+            OwnedEvent a, b2;
+            PT_HC(a.create()); PT_HC(b2.create());
+            t->kev.push_back(std::move(a)); t->kev.push_back(std::move(b2));
         }
         if (t->kev_kind.size() < t->kev.size() / 2) t->kev_kind.resize(t->kev.size() / 2);
         t->kev_kind[t->kev_used / 2] = kind;
-        HIPCHECK(hipEventRecord(t->kev[t->kev_used], stream));
+        PT_HC(hipEventRecord(t->kev[t->kev_used], stream));
         return PTX_OK;
     }
     int end() const {
         if (!t->ktiming) return PTX_OK;
-        HIPCHECK(hipEventRecord(t->kev[t->kev_used + 1], stream));
+        PT_HC(hipEventRecord(t->kev[t->kev_used + 1], stream));
         t->kev_used += 2;
         return PTX_OK;
     }
@@ -564,13 +545,13 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
     // per-bounce totals and group totals are accumulated with atomics, and the lit planes are set bit by bit: the lane's previous set
     // left them zero (k_stats, k_gather) -- unless the lane is marked, then all of its segments are cleared here, once
     if (t->aux_dirty[lane]) {
-        HIPCHECK(hipMemsetAsync(v.total, 0, sizeof(int32_t) * t->seg_totals * (size_t)t->kmax, stream));
+        PT_HC(hipMemsetAsync(v.total, 0, sizeof(int32_t) * t->seg_totals * (size_t)t->kmax, stream));
         if (t->d_part)                               // (the planes: behind each segment's radiance, cap / 32 words per segment)
-            HIPCHECK(hipMemset2DAsync(t->d_part + s.seg0 * t->seg_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
+            PT_HC(hipMemset2DAsync(t->d_part + s.seg0 * t->seg_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part, 0,
                                       (size_t)t->cap / 8, (size_t)t->kmax, stream));
         t->aux_dirty[lane] = false;
     }
-    if (s.fill_cache) HIPCHECK(hipMemsetAsync(t->d_emit_count, 0, sizeof(int32_t), stream));
+    if (s.fill_cache) PT_HC(hipMemsetAsync(t->d_emit_count, 0, sizeof(int32_t), stream));
     for (int b = 0; b < t->traceDepth; b++) {
         const bool first = b == 0;
         if (first && s.use_cache) {
@@ -590,7 +571,7 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
         const int gx_b = first ? p.gx_first : p.gx_later;                       // this launch's workgroups per segment
         int rc;
         if (t->split_mesh) {       // pass 1 parks the mesh candidates, k_mesh searches them, k_finish shades what it found, pass 2 ranks
-            HIPCHECK(hipMemsetAsync(bp.item_count, 0, sizeof(int32_t) * 2 * (size_t)K, stream));
+            PT_HC(hipMemsetAsync(bp.item_count, 0, sizeof(int32_t) * 2 * (size_t)K, stream));
             if ((rc = kt.begin(first ? 0 : 1)) != PTX_OK) return rc;
             if ((rc = launch_bounce(t, first, 1, needs_albedo, dim3(gx_b, K), p.lds_bounce, stream, bp)) != PTX_OK) return rc;
             if ((rc = kt.end()) != PTX_OK || (rc = kt.begin(2)) != PTX_OK) return rc;
@@ -605,8 +586,8 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
             if ((rc = kt.end()) != PTX_OK) return rc;
         }
         if (first && s.fill_cache) {
-            HIPCHECK(hipMemcpyAsync(t->d_cache_totals, v.totals(0, 0), sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToDevice, stream));
-            HIPCHECK(hipMemcpyAsync(t->d_cache_super, v.supers(0, 0), sizeof(int32_t) * 2 * nb * t->nsuper, hipMemcpyDeviceToDevice, stream));
+            PT_HC(hipMemcpyAsync(t->d_cache_totals, v.totals(0, 0), sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToDevice, stream));
+            PT_HC(hipMemcpyAsync(t->d_cache_super, v.supers(0, 0), sizeof(int32_t) * 2 * nb * t->nsuper, hipMemcpyDeviceToDevice, stream));
             t->cache_gx = gx_b;
             t->cache_dir_bins = bp.dir_bins; t->cache_ntab_bins = bp.ntab_bins; t->cache_idx16 = bp.idx16; t->cache_loop = (bp.loop_idx & 1) != 0;
             t->cache_valid = true;
@@ -616,20 +597,20 @@ int enqueue_batch_body(ptx_tracer *t, int iter_first, int K, int stride, int lan
             hipLaunchKernelGGL(k_capture_prefix, dim3(1), dim3(64), 0, stream, bp.chunk, (int)p.chunk_cap, nb * gx_b, gs, ga);
             hipLaunchKernelGGL(k_capture, dim3(std::min(1024, (t->cap + 255) / 256)), dim3(256), 0, stream, bp.stage, bp.chunk, (int)p.chunk_cap,
                                nb * gx_b, gs, ga, t->cap, t->d_cap, t->d_cap_f, bp.idx16, bp.loop_idx, nb);
-            HIPCHECK(hipMemcpyAsync(t->d_cap + 3 * (size_t)t->cap, v.totals(b, 1), sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, stream));
+            PT_HC(hipMemcpyAsync(t->d_cap + 3 * (size_t)t->cap, v.totals(b, 1), sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, stream));
             t->cap_filled = true;
         }
     }
     if (defer) {                                     // render-ahead: gather and statistics follow per iteration (ahead_finish_segment)
         t->ahead[lane].use_cache = s.use_cache;
         t->ahead[lane].dir_bins = s.dir_bins; t->ahead[lane].ntab_bins = s.ntab_bins;
-        HIPCHECK(hipGetLastError());
+        PT_HC(hipGetLastError());
         return PTX_OK;
     }
-    if (prev_lane >= 0 && prev_lane != lane) HIPCHECK(hipStreamWaitEvent(stream, t->ev_chain[prev_lane], 0));      // the previous batch's gather + stats
+    if (prev_lane >= 0 && prev_lane != lane) PT_HC(hipStreamWaitEvent(stream, t->ev_chain[prev_lane], 0));      // the previous batch's gather + stats
     launch_gather_stats(t, stream, s.seg0, K, s.use_cache, s.dir_bins, s.ntab_bins);
-    if (t->lanes > 1) HIPCHECK(hipEventRecord(t->ev_chain[lane], stream));
-    HIPCHECK(hipGetLastError());
+    if (t->lanes > 1) PT_HC(hipEventRecord(t->ev_chain[lane], stream));
+    PT_HC(hipGetLastError());
     t->iterations += K;
     return PTX_OK;
 }
@@ -666,12 +647,12 @@ bool ahead_possible(const ptx_tracer *t, int iter) {
 int ahead_start(ptx_tracer *t, int lane, int first) {
     hipStream_t ls = t->lane_stream[lane];
     ahead_fold_time(t, lane);                            // the events are about to be re-recorded
-    HIPCHECK(hipEventRecord(t->ev_fork, t->stream));     // after everything on the main stream so far: the cache fill, and the
-    HIPCHECK(hipStreamWaitEvent(ls, t->ev_fork, 0));     // gathers that still read this lane's buffers
-    HIPCHECK(hipEventRecord(t->ev_ahead0[lane], ls));
+    PT_HC(hipEventRecord(t->ev_fork, t->stream));     // after everything on the main stream so far: the cache fill, and the
+    PT_HC(hipStreamWaitEvent(ls, t->ev_fork, 0));     // gathers that still read this lane's buffers
+    PT_HC(hipEventRecord(t->ev_ahead0[lane], ls));
     int rc = enqueue_batch(t, first, t->kmax, 1, lane, -1, true);
     if (rc != PTX_OK) return rc;
-    HIPCHECK(hipEventRecord(t->ev_ahead1[lane], ls));
+    PT_HC(hipEventRecord(t->ev_ahead1[lane], ls));
     ptx_tracer::Ahead &a = t->ahead[lane];
     a.first = first; a.count = t->kmax; a.next = first; a.unfolded = 0; a.valid = true; a.timed = true;
     return PTX_OK;
@@ -683,12 +664,72 @@ int ahead_finish_segment(ptx_tracer *t, int lane, int seg) {
     const ptx_tracer::Ahead &a = t->ahead[lane];
     const bool was_dirty = t->aux_dirty[lane];
     t->aux_dirty[lane] = true;                           // (until both are enqueued)
-    HIPCHECK(hipStreamWaitEvent(t->stream, t->ev_ahead1[lane], 0));
+    PT_HC(hipStreamWaitEvent(t->stream, t->ev_ahead1[lane], 0));
     launch_gather_stats(t, t->stream, (size_t)lane * t->kmax + seg, 1, a.use_cache, a.dir_bins, a.ntab_bins);
-    HIPCHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     t->aux_dirty[lane] = was_dirty;
     t->iterations += 1;
     return PTX_OK;
+}
+
+// The kernel tables of arithmetic level `arith` -- the plain ones (PTX_DEBUG_NO_UNIT_RSQRT) where `plain` -- out of the ten exports of
+// the kernel units (pt_tracer.h; a weak one whose object was not linked is null), or the refusal, in the order ptx_create has always
+// given them.  (a missing kernel is an error, never a quiet return to the full bounce)
+int kernel_tables(int arith, bool plain, const KernelSet **ks, const LastKernelSet **ksl) {
+    typedef const void *(*Export)(void);
+    static const struct { Export kernels, last; } table[3][2] = {
+        {{ptx_arith_kernels_0, ptx_arith_last_0}, {ptx_arith_kernels_0p, ptx_arith_last_0p}},
+        {{ptx_arith_kernels_1, ptx_arith_last_1}, {ptx_arith_kernels_1p, ptx_arith_last_1p}},
+        {{ptx_arith_kernels_2, ptx_arith_last_2}, {ptx_arith_kernels_2, ptx_arith_last_2}}};      // (level 2 takes the hardware's seeds either way)
+    if (arith < 0 || arith > 2) return pt_fail(PTX_ERR_INVALID, "ptx_options.arith: 0 (exact), 1 (contracted) or 2 (fast)");
+    const auto get = [](Export f) { return f ? f() : nullptr; };
+    const std::string level = std::to_string(arith);
+    *ks = static_cast<const KernelSet *>(get(table[arith][0].kernels));
+    if (!*ks) return pt_fail(PTX_ERR_UNSUPPORTED, "this library was built without the code object of arithmetic level " + level);
+    if ((*ks)->arith != arith) return pt_fail(PTX_ERR_HIP, "arithmetic code object mismatch");
+    *ksl = static_cast<const LastKernelSet *>(get(table[arith][0].last));
+    if (!*ksl) return pt_fail(PTX_ERR_UNSUPPORTED, "this library was built without the last-bounce code object of arithmetic level " + level);
+    if ((*ksl)->arith != arith) return pt_fail(PTX_ERR_HIP, "arithmetic code object mismatch (last bounce)");
+    if (!plain) return PTX_OK;
+    *ks = static_cast<const KernelSet *>(get(table[arith][1].kernels));
+    *ksl = static_cast<const LastKernelSet *>(get(table[arith][1].last));
+    if (!*ks || !*ksl) return pt_fail(PTX_ERR_UNSUPPORTED, "PTX_DEBUG_NO_UNIT_RSQRT: this library was built without the plain code objects of arithmetic level " + level);
+    if ((*ks)->arith != arith || (*ksl)->arith != arith) return pt_fail(PTX_ERR_HIP, "arithmetic code object mismatch (plain)");
+    return PTX_OK;
+}
+
+// ptx_create's step 6: the main stream (the caller's, or one of the tracer's own), the loop timing's events and, with more than one
+// lane, each lane's stream and events.  The first failure is handed back; what was made by then is the tracer's and goes with it.
+hipError_t create_streams_and_events(ptx_tracer *t, hipStream_t callers) {
+#define HE(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+    if (callers) t->stream.borrow(callers);
+    else {
+        // the main stream carries what a caller waits for (per-call gather, preview, frame read-back) while the other lanes
+        // trace ahead in the background: it gets the highest priority, so that those short kernels are not queued behind
+        // the bounce kernels' workgroups
+        int prio_lo = 0, prio_hi = 0;
+        if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) { prio_lo = prio_hi = 0; (void)hipGetLastError(); }
+        if (t->dbg.no_priority) prio_hi = prio_lo;
+        HE(t->stream.create(hipStreamNonBlocking, prio_hi));
+    }
+    HE(t->ev_start.create()); HE(t->ev_stop.create());
+    if (t->lanes <= 1) return hipSuccess;
+    HE(t->ev_fork.create(hipEventDisableTiming));
+    for (int l = 0; l < t->lanes; l++) {
+        if (l) {
+            // every lane at the device's highest priority, like the main stream: measured, not reasoned -- sets of equal
+            // priority at that level dispatch 2 % faster than at the default level (C4 wall 0.216 -> 0.211 ms), any
+            // mix of levels lies in between, the veneer's per-call loop does not care
+            int prio_lo = 0, prio = 0;
+            if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio) != hipSuccess || t->dbg.no_priority) { prio = 0; (void)hipGetLastError(); }
+            if (t->dbg.has_lane_prio) prio = t->dbg.lane_prio[l];
+            HE(t->lane_stream[l].create(hipStreamNonBlocking, prio));
+        }
+        HE(t->ev_join[l].create(hipEventDisableTiming)); HE(t->ev_chain[l].create(hipEventDisableTiming));
+        if (l) { HE(t->ev_ahead0[l].create()); HE(t->ev_ahead1[l].create()); }
+    }
+    return hipSuccess;
+#undef HE
 }
 
 }  // namespace
@@ -736,59 +777,40 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
                          const ptx_camera *camera, int trace_depth, const ptx_options *options, float *external_image,
                          void *stream, ptx_tracer **out, int kmax_cap, bool *oom, int *kmax_used) {
     // ---- 1. the arguments
-    if (!out) return set_error(PTX_ERR_INVALID, "out is NULL");
+    if (!out) return pt_fail(PTX_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (ngeoms < 0 || nmaterials < 0 || (ngeoms && !geoms) || (nmaterials && !materials) || !camera)
-        return set_error(PTX_ERR_INVALID, "missing scene arrays");
-    if (camera->resolution[0] <= 0 || camera->resolution[1] <= 0) return set_error(PTX_ERR_INVALID, "resolution must be positive");
-    if (trace_depth < 1) return set_error(PTX_ERR_UNSUPPORTED, "trace depth must be >= 1");
-    if (nmaterials >= (1 << BIN_BITS) || ngeoms > 32767) return set_error(PTX_ERR_UNSUPPORTED, "more than 65535 materials or 32767 geoms");
+        return pt_fail(PTX_ERR_INVALID, "missing scene arrays");
+    if (camera->resolution[0] <= 0 || camera->resolution[1] <= 0) return pt_fail(PTX_ERR_INVALID, "resolution must be positive");
+    if (trace_depth < 1) return pt_fail(PTX_ERR_UNSUPPORTED, "trace depth must be >= 1");
+    if (nmaterials >= (1 << BIN_BITS) || ngeoms > 32767) return pt_fail(PTX_ERR_UNSUPPORTED, "more than 65535 materials or 32767 geoms");
     ptx_options opt;
     if (options) opt = *options; else ptx_default_options(&opt);
-    if (opt.bounding_box) return set_error(PTX_ERR_UNSUPPORTED, "BOUNDING_BOX culling is off in the reference and not implemented");
+    if (opt.bounding_box) return pt_fail(PTX_ERR_UNSUPPORTED, "BOUNDING_BOX culling is off in the reference and not implemented");
     if (opt.tile_world < 1) opt.tile_world = 1;
     if (opt.tile_world > 1 && (opt.tile_rows < 1 || opt.tile_rank < 0 || opt.tile_rank >= opt.tile_world))
-        return set_error(PTX_ERR_INVALID, "bad tile split");
+        return pt_fail(PTX_ERR_INVALID, "bad tile split");
     for (int i = 0; i < ngeoms; i++) {
         if (geoms[i].materialid < 0 || geoms[i].materialid >= nmaterials)
-            return set_error(PTX_ERR_INVALID, "geom " + std::to_string(i) + " refers to a material that does not exist");
-        if (geoms[i].faceSize < 0 || (geoms[i].faceSize > 0 && !geoms[i].faces)) return set_error(PTX_ERR_INVALID, "bad face array");
+            return pt_fail(PTX_ERR_INVALID, "geom " + std::to_string(i) + " refers to a material that does not exist");
+        if (geoms[i].faceSize < 0 || (geoms[i].faceSize > 0 && !geoms[i].faces)) return pt_fail(PTX_ERR_INVALID, "bad face array");
     }
     // ---- 2. the device and the code object of the arithmetic level
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return set_error(PTX_ERR_NODEVICE, "no HIP device available; this library has no CPU path");
+        return pt_fail(PTX_ERR_NODEVICE, "no HIP device available; this library has no CPU path");
     int dev = opt.device;
-    if (dev < 0) HIPCHECK(hipGetDevice(&dev));
-    if (dev >= ndev) return set_error(PTX_ERR_INVALID, "device ordinal out of range");
-    HIPCHECK(hipSetDevice(dev));
-    const KernelSet *ks = static_cast<const KernelSet *>(ptx_arith_kernels_0());
-    if (opt.arith != PTX_ARITH_EXACT) {
-        const void *tab = opt.arith == 1 ? (ptx_arith_kernels_1 ? ptx_arith_kernels_1() : nullptr)
-                        : opt.arith == 2 ? (ptx_arith_kernels_2 ? ptx_arith_kernels_2() : nullptr) : nullptr;
-        if (opt.arith < 0 || opt.arith > 2) return set_error(PTX_ERR_INVALID, "ptx_options.arith: 0 (exact), 1 (contracted) or 2 (fast)");
-        if (!tab) return set_error(PTX_ERR_UNSUPPORTED, "this library was built without the code object of arithmetic level " + std::to_string(opt.arith));
-        ks = static_cast<const KernelSet *>(tab);
-        if (ks->arith != opt.arith) return set_error(PTX_ERR_HIP, "arithmetic code object mismatch");
-    }
-    // (a missing kernel is an error, never a quiet return to the full bounce)
-    const void *ltab = opt.arith == 1 ? (ptx_arith_last_1 ? ptx_arith_last_1() : nullptr) : opt.arith == 2 ? (ptx_arith_last_2 ? ptx_arith_last_2() : nullptr) : ptx_arith_last_0();
-    if (!ltab) return set_error(PTX_ERR_UNSUPPORTED, "this library was built without the last-bounce code object of arithmetic level " + std::to_string(opt.arith));
-    const LastKernelSet *ksl = static_cast<const LastKernelSet *>(ltab);
-    if (ksl->arith != opt.arith) return set_error(PTX_ERR_HIP, "arithmetic code object mismatch (last bounce)");
+    if (dev < 0) PT_HC(hipGetDevice(&dev));
+    if (dev >= ndev) return pt_fail(PTX_ERR_INVALID, "device ordinal out of range");
+    PT_HC(hipSetDevice(dev));
+    const DebugSwitches dbg = read_debug_switches();     // (once: nothing below, and no later call, looks at the environment again)
+    const KernelSet *ks = nullptr; const LastKernelSet *ksl = nullptr;
+    if (const int rc = kernel_tables(opt.arith, dbg.no_unit_rsqrt, &ks, &ksl)) return rc;
     ptx_tracer *t = new ptx_tracer;
-    auto fail = [&](int code) { free_tracer(t); return code; };
-#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; set_error(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(PTX_ERR_HIP); } } while (0)
-    t->ks = ks; t->ksl = ksl;
+    auto fail = [&](int code) { free_tracer(t); return code; };      // (sets the device; what the half-made tracer owns goes with it)
+#define HC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (e_ == hipErrorOutOfMemory) *oom = true; return fail(pt_fail(PTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); } } while (0)
+    t->ks = ks; t->ksl = ksl; t->dbg = dbg;
     t->device = dev; t->opt = opt; t->traceDepth = t->maxBounces = trace_depth; t->ngeoms = ngeoms; t->nmats = nmaterials;
-    t->dbg = read_debug_switches();                      // (once: nothing below, and no later call, looks at the environment again)
-    if (t->dbg.no_unit_rsqrt && opt.arith < 2) {         // (level 2 takes the hardware's seeds either way)
-        const void *tab = opt.arith == 1 ? (ptx_arith_kernels_1p ? ptx_arith_kernels_1p() : nullptr) : (ptx_arith_kernels_0p ? ptx_arith_kernels_0p() : nullptr);
-        const void *last = opt.arith == 1 ? (ptx_arith_last_1p ? ptx_arith_last_1p() : nullptr) : (ptx_arith_last_0p ? ptx_arith_last_0p() : nullptr);
-        if (!tab || !last) { set_error(PTX_ERR_UNSUPPORTED, "PTX_DEBUG_NO_UNIT_RSQRT: this library was built without the plain code objects of arithmetic level " + std::to_string(opt.arith)); return fail(PTX_ERR_UNSUPPORTED); }
-        t->ks = static_cast<const KernelSet *>(tab); t->ksl = static_cast<const LastKernelSet *>(last);
-        if (t->ks->arith != opt.arith || t->ksl->arith != opt.arith) { set_error(PTX_ERR_HIP, "arithmetic code object mismatch (plain)"); return fail(PTX_ERR_HIP); }
-    }
     t->sort_by_material = opt.sort_by_material != 0;
     hipDeviceProp_t prop;
     HC(hipGetDeviceProperties(&prop, dev));
@@ -816,41 +838,13 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
         size_t mem_free = 0, mem_total = 0;
         if (opt.batch <= 0 && hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { mem_free = mem_total = 0; (void)hipGetLastError(); }
         const LaunchPlan plan = plan_launch_sets(t->tm.owned, t->nbins, t->maxTiles, opt, kmax_cap, mem_free, mem_total, t->dbg.mem_budget_mb);
-        if (!plan.refusal.empty()) { set_error(PTX_ERR_UNSUPPORTED, plan.refusal); return fail(PTX_ERR_UNSUPPORTED); }
+        if (!plan.refusal.empty()) { pt_fail(PTX_ERR_UNSUPPORTED, plan.refusal); return fail(PTX_ERR_UNSUPPORTED); }
         t->kmax = *kmax_used = plan.kmax;
         t->lanes = plan.lanes;
         ix_budget = launch_budget_bytes(mem_free, mem_total, t->dbg.mem_budget_mb);
     }
     // ---- 6. streams and events
-    if (stream) { t->stream = (hipStream_t)stream; t->own_stream = false; }
-    else {
-        // the main stream carries what a caller waits for (per-call gather, preview, frame read-back) while the other lanes
-        // trace ahead in the background: it gets the highest priority, so that those short kernels are not queued behind
-        // the bounce kernels' workgroups
-        int prio_lo = 0, prio_hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) { prio_lo = prio_hi = 0; (void)hipGetLastError(); }
-        if (t->dbg.no_priority) prio_hi = prio_lo;
-        HC(hipStreamCreateWithPriority(&t->stream, hipStreamNonBlocking, prio_hi));
-        t->own_stream = true;
-    }
-    HC(hipEventCreate(&t->ev_start)); HC(hipEventCreate(&t->ev_stop));
-    if (t->lanes > 1) {
-        HC(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-        for (int l = 0; l < t->lanes; l++) {
-            if (l) {
-                // every lane at the device's highest priority, like the main stream: measured, not reasoned -- sets of equal
-                // priority at that level dispatch 2 % faster than at the default level (C4 wall 0.216 -> 0.211 ms), any
-                // mix of levels lies in between, the veneer's per-call loop does not care
-                int prio_lo = 0, prio = 0;
-                if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio) != hipSuccess || t->dbg.no_priority) { prio = 0; (void)hipGetLastError(); }
-                if (t->dbg.has_lane_prio) prio = t->dbg.lane_prio[l];
-                HC(hipStreamCreateWithPriority(&t->lane_stream[l], hipStreamNonBlocking, prio));
-            }
-            HC(hipEventCreateWithFlags(&t->ev_join[l], hipEventDisableTiming));
-            HC(hipEventCreateWithFlags(&t->ev_chain[l], hipEventDisableTiming));
-            if (l) { HC(hipEventCreate(&t->ev_ahead0[l])); HC(hipEventCreate(&t->ev_ahead1[l])); }
-        }
-    }
+    HC(create_streams_and_events(t, (hipStream_t)stream));
     // ---- 7. upload the scene, allocate the streams' buffers
     HC(t->d_geoms.upload(hs.geoms)); HC(t->d_mats.upload(hs.mats)); HC(t->d_faces.upload(hs.faces)); HC(t->d_texels.upload(hs.texels));
     HC(t->d_tri9.upload(hs.tri9)); HC(t->d_gtab.upload(hs.gtab)); HC(t->d_aabb.upload(hs.aabb_ch)); HC(t->d_objcull.upload(hs.objcull));
@@ -919,7 +913,7 @@ static int create_tracer(int ngeoms, const ptx_geom *geoms, int nmaterials, cons
 }
 
 int ptx_create_from_scene(const ptx_scene *s, const ptx_options *options, float *external_image, void *stream, ptx_tracer **out) {
-    if (!s) return set_error(PTX_ERR_INVALID, "null scene");
+    if (!s) return pt_fail(PTX_ERR_INVALID, "null scene");
     return ptx_create(ptx_scene_num_geoms(s), ptx_scene_geoms(s), ptx_scene_num_materials(s), ptx_scene_materials(s),
                       ptx_scene_camera(const_cast<ptx_scene *>(s)), ptx_scene_trace_depth(s), options, external_image, stream, out);
 }
@@ -927,10 +921,10 @@ int ptx_create_from_scene(const ptx_scene *s, const ptx_options *options, float 
 void ptx_destroy(ptx_tracer *t) { free_tracer(t); }
 
 int ptx_set_camera(ptx_tracer *t, const ptx_camera *camera, int trace_depth) {
-    if (!t || !camera) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t || !camera) return pt_fail(PTX_ERR_INVALID, "null argument");
     if (camera->resolution[0] != t->cam.resx || camera->resolution[1] != t->cam.resy)
-        return set_error(PTX_ERR_INVALID, "resolution is fixed at create (buffer sizes, src/pathtrace.cu:104-109)");
-    if (trace_depth < 1 || trace_depth > t->maxBounces) return set_error(PTX_ERR_INVALID, "trace depth exceeds the depth given at create");
+        return pt_fail(PTX_ERR_INVALID, "resolution is fixed at create (buffer sizes, src/pathtrace.cu:104-109)");
+    if (trace_depth < 1 || trace_depth > t->maxBounces) return pt_fail(PTX_ERR_INVALID, "trace depth exceeds the depth given at create");
     {   // the reference-shaped loop sets the camera before every iteration (src/pathtrace.cu:434-436): the same values
         // again change nothing, so neither the first-bounce cache nor what was traced ahead is thrown away
         DCamera same;
@@ -938,8 +932,8 @@ int ptx_set_camera(ptx_tracer *t, const ptx_camera *camera, int trace_depth) {
         camera_to_device(*camera, same);
         if (trace_depth == t->traceDepth && memcmp(&same, &t->cam, sizeof same) == 0) return PTX_OK;
     }
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     ahead_discard(t);
     camera_to_device(*camera, t->cam);
     t->traceDepth = trace_depth;
@@ -953,31 +947,31 @@ int ptx_tile_pixels(void) { return TILE; }
 int ptx_num_tiles(const ptx_tracer *t) { return t ? t->maxTiles : 0; }
 
 int ptx_set_active_tiles(ptx_tracer *t, const uint8_t *host_active, int ntiles) {
-    if (!t || !host_active) return set_error(PTX_ERR_INVALID, "ptx_set_active_tiles: null tracer or mask");
+    if (!t || !host_active) return pt_fail(PTX_ERR_INVALID, "ptx_set_active_tiles: null tracer or mask");
     int code = 0;
-    if (const char *why = pt_active_tiles_problem(t, ntiles, code)) return set_error(code, std::string("ptx_set_active_tiles: ") + why);
-    HIPCHECK(hipSetDevice(t->device));
+    if (const char *why = pt_active_tiles_problem(t, ntiles, code)) return pt_fail(code, std::string("ptx_set_active_tiles: ") + why);
+    PT_HC(hipSetDevice(t->device));
     if (const int rc = mask_buffers(t)) return rc;
-    HIPCHECK(hipStreamSynchronize(t->stream));           // (no launch reads the flags now: only k_tile_mask does, on this stream)
-    HIPCHECK(hipMemcpy(t->d_tile_active, host_active, (size_t)ntiles, hipMemcpyHostToDevice));
+    PT_HC(hipStreamSynchronize(t->stream));           // (no launch reads the flags now: only k_tile_mask does, on this stream)
+    PT_HC(hipMemcpy(t->d_tile_active, host_active, (size_t)ntiles, hipMemcpyHostToDevice));
     return pt_set_tile_mask(t, nullptr);
 }
 
 int ptx_clear_active_tiles(ptx_tracer *t) {
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_clear_active_tiles: null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "ptx_clear_active_tiles: null tracer");
     if (!t->mask_set) return PTX_OK;
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     ahead_discard(t);
     t->mask_set = false;
     return PTX_OK;
 }
 
 int ptx_reset_image(ptx_tracer *t) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipMemsetAsync(t->d_image, 0, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, t->stream));
-    HIPCHECK(hipMemsetAsync(t->d_stats, 0, sizeof(int64_t) * 69, t->stream));
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipMemsetAsync(t->d_image, 0, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, t->stream));
+    PT_HC(hipMemsetAsync(t->d_stats, 0, sizeof(int64_t) * 69, t->stream));
     t->iterations = 0; t->loop_ms_total = 0.0; t->cache_valid = false;
     for (int l = 0; l < MAX_LANES; l++) t->aux_dirty[l] = true;
     return PTX_OK;
@@ -991,8 +985,8 @@ namespace { __global__ void k_hold(long long ticks) { const long long t0 = wall_
 static int fold_render_time(ptx_tracer *t) {
     if (!t->timing_valid) return PTX_OK;
     float ms = 0.f;
-    HIPCHECK(hipEventSynchronize(t->ev_stop));
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev_start, t->ev_stop));
+    PT_HC(hipEventSynchronize(t->ev_stop));
+    PT_HC(hipEventElapsedTime(&ms, t->ev_start, t->ev_stop));
     t->loop_ms_total += ms;
     t->timing_valid = false;
     return PTX_OK;
@@ -1001,21 +995,21 @@ static int fold_render_time(ptx_tracer *t) {
 int ptx_render(ptx_tracer *t, int iter_first, int count) { return ptx_render_strided(t, iter_first, count, 1); }
 
 int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    if (stride < 1) return set_error(PTX_ERR_INVALID, "ptx_render_strided: stride must be >= 1");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    if (stride < 1) return pt_fail(PTX_ERR_INVALID, "ptx_render_strided: stride must be >= 1");
     if (count <= 0) return PTX_OK;
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     ahead_discard(t);
     if (const int rc = fold_render_time(t)) return rc;      // (before the events are reused)
     // (the one switch read per call, not at create: tools/gpu_prequeue.py toggles it on a live tracer)
     if (const char *e = getenv("PTX_DEBUG_PREQUEUE_US")) hipLaunchKernelGGL(k_hold, dim3(1), dim3(64), 0, t->stream, (long long)atoi(e) * 100);      // (100 MHz)
-    HIPCHECK(hipEventRecord(t->ev_start, t->stream));
+    PT_HC(hipEventRecord(t->ev_start, t->stream));
     // per-kernel timing and the debug capture look at one launch set at a time
     const int kb = sets_per_call(count, t->kmax, t->lanes, t->tm.owned, t->dbg.split_min_paths, t->dbg.nsets);
     const int nl = (t->lanes > 1 && !t->ktiming && t->capture_bounce < 0 && count > kb) ? t->lanes : 1;
     auto fork = [&]() -> int {                           // the other lanes start after what is on the main stream so far
-        HIPCHECK(hipEventRecord(t->ev_fork, t->stream));
-        for (int l = 1; l < nl; l++) HIPCHECK(hipStreamWaitEvent(t->lane_stream[l], t->ev_fork, 0));
+        PT_HC(hipEventRecord(t->ev_fork, t->stream));
+        for (int l = 1; l < nl; l++) PT_HC(hipStreamWaitEvent(t->lane_stream[l], t->ev_fork, 0));
         return PTX_OK;
     };
     if (nl > 1) { int rc = fork(); if (rc != PTX_OK) return rc; }
@@ -1041,25 +1035,25 @@ int ptx_render_strided(ptx_tracer *t, int iter_first, int count, int stride) {
     }
     for (int l = 1; l < nl; l++)
         if (used[l]) {
-            HIPCHECK(hipEventRecord(t->ev_join[l], t->lane_stream[l]));
-            HIPCHECK(hipStreamWaitEvent(t->stream, t->ev_join[l], 0));
+            PT_HC(hipEventRecord(t->ev_join[l], t->lane_stream[l]));
+            PT_HC(hipStreamWaitEvent(t->stream, t->ev_join[l], 0));
         }
-    HIPCHECK(hipEventRecord(t->ev_stop, t->stream));
+    PT_HC(hipEventRecord(t->ev_stop, t->stream));
     t->timing_valid = true;
     return PTX_OK;
 }
 
 int ptx_set_render_ahead(ptx_tracer *t, int on) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
     if (!on) ahead_discard(t);
     t->render_ahead = on != 0;
     return PTX_OK;
 }
 
 int ptx_iterate(ptx_tracer *t, int iter) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
     if (!ahead_possible(t, iter)) return ptx_render(t, iter, 1);
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     if (t->ahead_cur < 0 || !t->ahead[t->ahead_cur].valid || t->ahead[t->ahead_cur].next != iter) {
         // nothing traced ahead for this iteration (first call, or the sequence jumped): start at it
         ahead_discard(t);
@@ -1090,66 +1084,66 @@ int ptx_iterate(ptx_tracer *t, int iter) {
 }
 
 int ptx_synchronize(ptx_tracer *t) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     return PTX_OK;
 }
 
 int ptx_read_image(ptx_tracer *t, float *host_rgb) {
-    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipMemcpyAsync(host_rgb, t->d_image, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !host_rgb) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipMemcpyAsync(host_rgb, t->d_image, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     return PTX_OK;
 }
 
 // the accumulation buffer back from a checkpoint (W*H*3 floats, the layout ptx_read_image returns)
 int ptx_write_image(ptx_tracer *t, const float *host_rgb) {
-    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipMemcpyAsync(t->d_image, host_rgb, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyHostToDevice, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !host_rgb) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipMemcpyAsync(t->d_image, host_rgb, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyHostToDevice, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     return PTX_OK;
 }
 
 int ptx_read_albedo(ptx_tracer *t, float *host_rgb) {
-    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
-    if (!t->d_albedo) return set_error(PTX_ERR_INVALID, "the albedo AOV exists only with options.apps_variant = 1");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipMemcpyAsync(host_rgb, t->d_albedo, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !host_rgb) return pt_fail(PTX_ERR_INVALID, "null argument");
+    if (!t->d_albedo) return pt_fail(PTX_ERR_INVALID, "the albedo AOV exists only with options.apps_variant = 1");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipMemcpyAsync(host_rgb, t->d_albedo, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, hipMemcpyDeviceToHost, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     return PTX_OK;
 }
 
 // sendToGPU + sendDenosiedImageToPBO (apps/src/pathtrace.cu:96-116,673-685): a finished host frame -> 8-bit, no /iter
 int ptx_write_denoised_pbo(ptx_tracer *t, const float *host_rgb, uint8_t *host_rgba) {
-    if (!t || !host_rgb || !host_rgba) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
+    if (!t || !host_rgb || !host_rgba) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     DevBuf<float> d_in; DevBuf<uchar4> d_out;
-    HIPCHECK(d_in.alloc(3 * n));
-    HIPCHECK(d_out.alloc(n));
-    HIPCHECK(hipMemcpyAsync(d_in, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
+    PT_HC(d_in.alloc(3 * n));
+    PT_HC(d_out.alloc(n));
+    PT_HC(hipMemcpyAsync(d_in, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
     hipLaunchKernelGGL(k_pbo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, d_out.p, (int)n, 1, d_in.p);   // iter = 1: pix / 1
     hipError_t e = hipMemcpyAsync(host_rgba, d_out, 4 * n, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e != hipSuccess) return set_error(PTX_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return pt_fail(PTX_ERR_HIP, hipGetErrorString(e));
     return PTX_OK;
 }
 
 // sendToGPU itself (apps/src/pathtrace.cu:673-685): host frame in, the preview written to a DEVICE pbo, as the reference's
 // mapped GL buffer is
 int ptx_write_denoised_pbo_device(ptx_tracer *t, const float *host_rgb, void *device_uchar4) {
-    if (!t || !host_rgb) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t || !host_rgb) return pt_fail(PTX_ERR_INVALID, "null argument");
     if (!device_uchar4) return PTX_OK;                    // NULL pbo => skip, like ptx_write_pbo_device
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_denoised) HIPCHECK(t->d_denoised.alloc(3 * n));      // dev_denoised_output, kept like the reference's
-    HIPCHECK(hipMemcpyAsync(t->d_denoised, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
+    if (!t->d_denoised) PT_HC(t->d_denoised.alloc(3 * n));      // dev_denoised_output, kept like the reference's
+    PT_HC(hipMemcpyAsync(t->d_denoised, host_rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice, t->stream));
     hipLaunchKernelGGL(k_pbo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, (int)n, 1, t->d_denoised);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));            // host_rgb may be reused by the caller right away
+    PT_HC(hipGetLastError());
+    PT_HC(hipStreamSynchronize(t->stream));            // host_rgb may be reused by the caller right away
     return PTX_OK;
 }
 
@@ -1158,26 +1152,26 @@ void *ptx_stream(ptx_tracer *t) { return t ? (void *)t->stream : nullptr; }
 int ptx_owned_pixels(const ptx_tracer *t) { return t ? t->tm.owned : 0; }
 
 int ptx_write_pbo_device(ptx_tracer *t, int iter, void *device_uchar4) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
     if (!device_uchar4) return PTX_OK;                    // NULL pbo => skip (the reference would fault)
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     int n = t->cam.resx * t->cam.resy;
     hipLaunchKernelGGL(k_pbo, dim3((n + 255) / 256), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, n, iter, t->d_image);
-    HIPCHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 
 int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
-    if (!t || !host_rgba) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
+    if (!t || !host_rgba) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
     size_t n = (size_t)t->cam.resx * t->cam.resy;
     // the staging buffer stays with the tracer: hipFree would wait for the whole device, i.e. for work traced ahead
-    if (!t->d_pbo) HIPCHECK(t->d_pbo.alloc(n));
+    if (!t->d_pbo) PT_HC(t->d_pbo.alloc(n));
     int rc = ptx_write_pbo_device(t, iter, t->d_pbo);
     if (rc == PTX_OK) {
         hipError_t e = hipMemcpyAsync(host_rgba, t->d_pbo, n * 4, hipMemcpyDeviceToHost, t->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-        if (e != hipSuccess) rc = set_error(PTX_ERR_HIP, hipGetErrorString(e));
+        if (e != hipSuccess) rc = pt_fail(PTX_ERR_HIP, hipGetErrorString(e));
     }
     return rc;
 }
@@ -1186,27 +1180,27 @@ int ptx_write_pbo(ptx_tracer *t, int iter, uint8_t *host_rgba) {
 // The G-buffer of the current camera on the tracer's stream, buffers allocated on first use
 extern "C++" int pt_ensure_gbuffer(ptx_tracer *t) {
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
-    if (!t->d_gbuf) HIPCHECK(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
+    if (!t->d_gbuf) PT_HC(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
     const DScene sc = t->scene();
     if (t->guide_bounces > 0) {                          // either mode followed through mirrors and glass (pt_guides_follow.hip): the same arrays
         const bool sampled = t->guide_count > 0;         // (the pixel-centre mode: one ray, no jitter, no lens -- k_gbuffer's ray)
         const int beff = std::max(std::min(t->guide_bounces, t->traceDepth - 1), 0);      // a path of depth d has at most d segments
-        HIPCHECK(pt_guides_follow_enqueue(t->stream, sc, t->cam, t->traceDepth, sampled ? t->opt.antialiasing : 0, sampled ? t->opt.depth_of_field : 0,
+        PT_HC(pt_guides_follow_enqueue(t->stream, sc, t->cam, t->traceDepth, sampled ? t->opt.antialiasing : 0, sampled ? t->opt.depth_of_field : 0,
                                           sampled ? t->guide_first : 1, sampled ? t->guide_count : 1, beff,
                                           t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n)));
         t->gbuf_valid = true;
         return PTX_OK;
     }
     if (t->guide_count > 0) {                            // sampled guides (pt_guides.hip): the same arrays, the coverage in alb.w
-        HIPCHECK(pt_guides_enqueue(t->stream, sc, t->cam, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, t->guide_first, t->guide_count,
+        PT_HC(pt_guides_enqueue(t->stream, sc, t->cam, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, t->guide_first, t->guide_count,
                                    t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n)));
         t->gbuf_valid = true;
         return PTX_OK;
     }
     hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->stream, sc, t->cam, t->traceDepth,
                        t->d_gbuf, t->d_gbuf + n, t->d_gbuf + 2 * n, reinterpret_cast<int2 *>(t->d_gbuf + 3 * n));
-    HIPCHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     t->gbuf_valid = true;
     return PTX_OK;
 }
@@ -1216,14 +1210,14 @@ static_assert(sizeof(DCamera) == sizeof(ptx_camera), "camera layout");
 // ---- sampled guides (pt_guides.hip; definition in include/mi355x_pathtracer.h) ------------------------------------------------------
 static const int GUIDE_SAMPLES_MAX = 4096;
 int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count) {
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: null tracer");
-    if (iter_first < 1) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first must be >= 1 (iterations count from 1)");
-    if (count < 0) return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: count must be >= 0 (0: the pixel-centre guides)");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_samples: null tracer");
+    if (iter_first < 1) return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first must be >= 1 (iterations count from 1)");
+    if (count < 0) return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_samples: count must be >= 0 (0: the pixel-centre guides)");
     if (count > GUIDE_SAMPLES_MAX)
-        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: count " + std::to_string(count) + " exceeds the cap of " +
+        return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_samples: count " + std::to_string(count) + " exceeds the cap of " +
                                               std::to_string(GUIDE_SAMPLES_MAX) + " samples per pixel");
     if (iter_first > INT32_MAX - GUIDE_SAMPLES_MAX)
-        return set_error(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first + count would pass the largest iteration number");
+        return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_samples: iter_first + count would pass the largest iteration number");
     if (const int rc = pt_whole_frame_problem("ptx_set_guide_samples", t)) return rc;
     if (count == t->guide_count && (count == 0 || iter_first == t->guide_first)) return PTX_OK;      // (the same guides: nothing is stale)
     t->guide_first = iter_first; t->guide_count = count;
@@ -1232,7 +1226,7 @@ int ptx_set_guide_samples(ptx_tracer *t, int iter_first, int count) {
 }
 
 int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count) {
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_get_guide_samples: null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "ptx_get_guide_samples: null tracer");
     if (iter_first) *iter_first = t->guide_first;
     if (count) *count = t->guide_count;
     return PTX_OK;
@@ -1241,10 +1235,10 @@ int ptx_get_guide_samples(const ptx_tracer *t, int *iter_first, int *count) {
 // ---- guides through mirrors and glass (pt_guides_follow.hip; definition in include/mi355x_pathtracer.h) -------------------------------
 static const int GUIDE_BOUNCES_MAX = 64;
 int ptx_set_guide_bounces(ptx_tracer *t, int bounces) {
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: null tracer");
-    if (bounces < 0) return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces must be >= 0 (0: the first surface)");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_bounces: null tracer");
+    if (bounces < 0) return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces must be >= 0 (0: the first surface)");
     if (bounces > GUIDE_BOUNCES_MAX)
-        return set_error(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces " + std::to_string(bounces) + " exceeds the cap of " +
+        return pt_fail(PTX_ERR_INVALID, "ptx_set_guide_bounces: bounces " + std::to_string(bounces) + " exceeds the cap of " +
                                               std::to_string(GUIDE_BOUNCES_MAX) + " continuations per ray");
     if (const int rc = pt_whole_frame_problem("ptx_set_guide_bounces", t)) return rc;
     if (bounces == t->guide_bounces) return PTX_OK;      // (the same guides: nothing is stale)
@@ -1254,35 +1248,35 @@ int ptx_set_guide_bounces(ptx_tracer *t, int bounces) {
 }
 
 int ptx_get_guide_bounces(const ptx_tracer *t, int *bounces) {
-    if (!t) return set_error(PTX_ERR_INVALID, "ptx_get_guide_bounces: null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "ptx_get_guide_bounces: null tracer");
     if (bounces) *bounces = t->guide_bounces;
     return PTX_OK;
 }
 
 int ptx_write_denoised_pbo_from_device(ptx_tracer *t, void *device_uchar4) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    if (!t->dn_done) return set_error(PTX_ERR_INVALID, "ptx_write_denoised_pbo_from_device: no ptx_denoise on this tracer yet");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    if (!t->dn_done) return pt_fail(PTX_ERR_INVALID, "ptx_write_denoised_pbo_from_device: no ptx_denoise on this tracer yet");
     if (!device_uchar4) return PTX_OK;                    // NULL pbo => skip, like ptx_write_pbo_device
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     const int n = t->cam.resx * t->cam.resy;
     hipLaunchKernelGGL(k_pbo, dim3((n + 255) / 256), dim3(256), 0, t->stream, (uchar4 *)device_uchar4, n, 1, t->d_dn_out);   // iter = 1: no /iter
-    HIPCHECK(hipGetLastError());
+    PT_HC(hipGetLastError());
     return PTX_OK;
 }
 
 int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32_t *ids2, float *t1, uint8_t *hit1) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
     if (t->tm.tile_world > 1)
-        return set_error(PTX_ERR_INVALID, "ptx_read_gbuffer: this tracer renders a row tile (tile_world > 1); the denoiser needs the whole frame");
-    HIPCHECK(hipSetDevice(t->device));
+        return pt_fail(PTX_ERR_INVALID, "ptx_read_gbuffer: this tracer renders a row tile (tile_world > 1); the denoiser needs the whole frame");
+    PT_HC(hipSetDevice(t->device));
     const int rc = pt_ensure_gbuffer(t);
     if (rc != PTX_OK) return rc;
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     std::vector<float4> g(3 * n);
     std::vector<int2> ids(n);
-    HIPCHECK(hipMemcpyAsync(g.data(), t->d_gbuf, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipMemcpyAsync(ids.data(), t->d_gbuf + 3 * n, sizeof(int2) * n, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipMemcpyAsync(g.data(), t->d_gbuf, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, t->stream));
+    PT_HC(hipMemcpyAsync(ids.data(), t->d_gbuf + 3 * n, sizeof(int2) * n, hipMemcpyDeviceToHost, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     for (size_t i = 0; i < n; i++) {
         const float4 &nh = g[i], &xt = g[n + i], &al = g[2 * n + i];
         if (pos3) { pos3[3 * i] = xt.x; pos3[3 * i + 1] = xt.y; pos3[3 * i + 2] = xt.z; }
@@ -1296,15 +1290,15 @@ int ptx_read_gbuffer(ptx_tracer *t, float *pos3, float *nrm3, float *alb3, int32
 }
 
 int ptx_read_guide_coverage(ptx_tracer *t, float *coverage1) {
-    if (!t || !coverage1) return set_error(PTX_ERR_INVALID, "ptx_read_guide_coverage: null tracer or buffer");
+    if (!t || !coverage1) return pt_fail(PTX_ERR_INVALID, "ptx_read_guide_coverage: null tracer or buffer");
     if (const int rc = pt_whole_frame_problem("ptx_read_guide_coverage", t)) return rc;
-    HIPCHECK(hipSetDevice(t->device));
+    PT_HC(hipSetDevice(t->device));
     if (const int rc = pt_ensure_gbuffer(t)) return rc;
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     // the fourth float of the albedo records; the pixel-centre guides write 0 there, their coverage is the hit flag: nh's fourth float
     std::vector<float4> a(n);
-    HIPCHECK(hipMemcpyAsync(a.data(), t->d_gbuf + (t->guide_count > 0 ? 2 * n : 0), sizeof(float4) * n, hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipMemcpyAsync(a.data(), t->d_gbuf + (t->guide_count > 0 ? 2 * n : 0), sizeof(float4) * n, hipMemcpyDeviceToHost, t->stream));
+    PT_HC(hipStreamSynchronize(t->stream));
     for (size_t i = 0; i < n; i++) coverage1[i] = a[i].w;
     return PTX_OK;
 }
@@ -1328,11 +1322,11 @@ double ptx_last_loop_ms(ptx_tracer *t) {
 }
 
 int ptx_get_stats(ptx_tracer *t, ptx_stats *out) {
-    if (!t || !out) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !out) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     int64_t h[69];
-    HIPCHECK(hipMemcpy(h, t->d_stats, sizeof h, hipMemcpyDeviceToHost));
+    PT_HC(hipMemcpy(h, t->d_stats, sizeof h, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
     out->bounces = t->traceDepth;
     for (int b = 0; b < 64 && b < t->traceDepth; b++) out->rays_per_bounce[b] = h[b];
@@ -1346,7 +1340,7 @@ int ptx_get_stats(ptx_tracer *t, ptx_stats *out) {
 }
 
 int ptx_get_stats_sized(ptx_tracer *t, void *out, size_t out_bytes) {
-    if (!t || !out) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t || !out) return pt_fail(PTX_ERR_INVALID, "null argument");
     ptx_stats s;
     const int rc = ptx_get_stats(t, &s);
     if (rc != PTX_OK) return rc;
@@ -1361,21 +1355,21 @@ size_t ptx_sizeof_stats(void) { return sizeof(ptx_stats); }
 
 // ---- per-stage entry points -----------------------------------------------------------------------------------
 #define KAT_PROLOGUE                                                        \
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");               \
-    HIPCHECK(hipSetDevice(t->device));                                      \
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");               \
+    PT_HC(hipSetDevice(t->device));                                      \
+    PT_HC(hipStreamSynchronize(t->stream));
 
 // n rays against one geom, `width` floats out per ray: the whole intersection test (10) or its triangle part (8)
 static int kat_rays(ptx_tracer *t, int geom, int n, const float *rays6, float *out, int width) {
     KAT_PROLOGUE
-    if (geom < 0 || geom >= t->ngeoms) return set_error(PTX_ERR_INVALID, "geom index out of range");
+    if (geom < 0 || geom >= t->ngeoms) return pt_fail(PTX_ERR_INVALID, "geom index out of range");
     if (n <= 0) return PTX_OK;
     DevBuf<float> d_in, d_out;
-    HIPCHECK(d_in.upload(rays6, 6 * (size_t)n));
-    HIPCHECK(d_out.alloc(width * (size_t)n));
+    PT_HC(d_in.upload(rays6, 6 * (size_t)n));
+    PT_HC(d_out.alloc(width * (size_t)n));
     { const DScene sc = t->scene(); (width == 10 ? t->ks->kat_geom : t->ks->kat_obj_tri)(dim3((n + 255) / 256), t->stream, &sc, geom, n, d_in, d_out); }
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_out.download(out));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_out.download(out));
     return PTX_OK;
 }
 int ptx_kat_geom_test(ptx_tracer *t, int geom, int n, const float *rays6, float *out10) { return kat_rays(t, geom, n, rays6, out10, 10); }
@@ -1384,12 +1378,12 @@ int ptx_kat_obj_tri_test(ptx_tracer *t, int geom, int n, const float *rays6, flo
 int ptx_kat_jittered_hemisphere(ptx_tracer *t, int n, const float *normals3, const int32_t *seeds3, int max_iter, float *out3) {
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
-    if (max_iter < 1) return set_error(PTX_ERR_INVALID, "max_iter must be >= 1");
+    if (max_iter < 1) return pt_fail(PTX_ERR_INVALID, "max_iter must be >= 1");
     DevBuf<float> d_n, d_o; DevBuf<int32_t> d_s;
-    HIPCHECK(d_n.upload(normals3, 3 * (size_t)n)); HIPCHECK(d_o.alloc(3 * (size_t)n)); HIPCHECK(d_s.upload(seeds3, 3 * (size_t)n));
+    PT_HC(d_n.upload(normals3, 3 * (size_t)n)); PT_HC(d_o.alloc(3 * (size_t)n)); PT_HC(d_s.upload(seeds3, 3 * (size_t)n));
     t->ks->kat_jittered(dim3((n + 255) / 256), t->stream, n, d_n.p, d_s.p, max_iter, d_o.p);
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_o.download(out3));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_o.download(out3));
     return PTX_OK;
 }
 
@@ -1397,22 +1391,22 @@ int ptx_kat_compute_intersections(ptx_tracer *t, int n, const void *paths44, voi
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i;
-    HIPCHECK(d_p.upload(paths44, (size_t)n));
-    HIPCHECK(d_i.alloc((size_t)n));
+    PT_HC(d_p.upload(paths44, (size_t)n));
+    PT_HC(d_i.alloc((size_t)n));
     { const DScene sc = t->scene(); t->ks->kat_intersect(dim3((n + 255) / 256), t->stream, &sc, n, d_p.p, d_i.p); }
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_i.download(isects32));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_i.download(isects32));
     return PTX_OK;
 }
 
 int ptx_kat_tile_intersect(ptx_tracer *t, int n, const void *paths44, void *isects32, int split) {
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
-    if (!t->cull || !t->tri_lds) return set_error(PTX_ERR_UNSUPPORTED, "this scene does not take the tile path (candidate masks / LDS tables are off)");
-    if (split && !t->d_bvh_root) return set_error(PTX_ERR_UNSUPPORTED, "no mesh of this scene has a BVH: nothing for the split mesh search to do");
+    if (!t->cull || !t->tri_lds) return pt_fail(PTX_ERR_UNSUPPORTED, "this scene does not take the tile path (candidate masks / LDS tables are off)");
+    if (split && !t->d_bvh_root) return pt_fail(PTX_ERR_UNSUPPORTED, "no mesh of this scene has a BVH: nothing for the split mesh search to do");
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i;
-    HIPCHECK(d_p.upload(paths44, (size_t)n));
-    HIPCHECK(d_i.alloc((size_t)n));
+    PT_HC(d_p.upload(paths44, (size_t)n));
+    PT_HC(d_i.alloc((size_t)n));
     // the scene as enqueue_batch hands it to k_bounce (tables staged; split: without the triangle tables) and as k_mesh gets it
     DScene sc = t->scene();
     sc.tri_lds = t->tri_lds; sc.ntri_lds = (split || t->split_mesh) ? 0 : t->ntri_lds; sc.cull = t->cull ? 2 : 0;      // (the caller's rays can start anywhere: cullMask, FAR ORIGINS)
@@ -1423,16 +1417,16 @@ int ptx_kat_tile_intersect(ptx_tracer *t, int n, const void *paths44, void *isec
     {   // ptx_create sized k_bounce's LDS against the device (stepping the tables down where needed); this kernel adds the walks'
         // stacks on top of the same layout, so it is checked here, where the caller can be told, not at the launch
         int lim = 0;
-        HIPCHECK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
+        PT_HC(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
         if (lds > (size_t)lim)
-            return set_error(PTX_ERR_UNSUPPORTED, "ptx_kat_tile_intersect needs " + std::to_string(lds) + " bytes of LDS per workgroup (scene tables + " +
+            return pt_fail(PTX_ERR_UNSUPPORTED, "ptx_kat_tile_intersect needs " + std::to_string(lds) + " bytes of LDS per workgroup (scene tables + " +
                              std::to_string(t->bvh_stack) + " stack entries per lane), the device offers " + std::to_string(lim));
     }
     const dim3 grid((unsigned)std::min(1024, (n + TILE - 1) / TILE));
     t->ks->kat_tile(split ? 1 : 0, grid, lds, t->stream, &sc, &scg, n, d_p.p, d_i.p, t->uses_uv);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_i.download(isects32));
+    PT_HC(hipGetLastError());
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_i.download(isects32));
     return PTX_OK;
 }
 
@@ -1440,10 +1434,10 @@ int ptx_kat_shade(ptx_tracer *t, int iter, int n, const int32_t *idx, const void
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<HostPath> d_p; DevBuf<HostIsect> d_i; DevBuf<int32_t> d_x;
-    HIPCHECK(d_p.upload(paths44, (size_t)n)); HIPCHECK(d_i.upload(isects32, (size_t)n)); HIPCHECK(d_x.upload(idx, (size_t)n));
+    PT_HC(d_p.upload(paths44, (size_t)n)); PT_HC(d_i.upload(isects32, (size_t)n)); PT_HC(d_x.upload(idx, (size_t)n));
     { const DScene sc = t->scene(); t->ks->kat_shade(dim3((n + 255) / 256), t->stream, &sc, iter, n, d_x.p, d_i.p, d_p.p); }
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_p.download(paths44));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_p.download(paths44));
     return PTX_OK;
 }
 
@@ -1451,10 +1445,10 @@ int ptx_kat_generate(ptx_tracer *t, int iter, void *paths44) {
     KAT_PROLOGUE
     int n = t->cam.resx * t->cam.resy;
     DevBuf<HostPath> d_p;
-    HIPCHECK(d_p.alloc((size_t)n));
+    PT_HC(d_p.alloc((size_t)n));
     t->ks->kat_generate(dim3((n + 255) / 256), t->stream, &t->cam, iter, t->traceDepth, t->opt.antialiasing, t->opt.depth_of_field, d_p.p);
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(d_p.download(paths44));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(d_p.download(paths44));
     return PTX_OK;
 }
 
@@ -1463,49 +1457,49 @@ int ptx_kat_libm(ptx_tracer *t, int n, const float *x, float *sin_out, float *co
     KAT_PROLOGUE
     if (n <= 0) return PTX_OK;
     DevBuf<float> dx, ds, dc, dxy, dpo; DevBuf<double> dpw, dp5;
-    HIPCHECK(dx.upload(x, (size_t)n)); HIPCHECK(ds.alloc((size_t)n)); HIPCHECK(dc.alloc((size_t)n));
-    HIPCHECK(dxy.upload(powf_xy, 2 * (size_t)n)); HIPCHECK(dpo.alloc((size_t)n));
-    HIPCHECK(dpw.upload(pw_in, (size_t)n)); HIPCHECK(dp5.alloc((size_t)n));
+    PT_HC(dx.upload(x, (size_t)n)); PT_HC(ds.alloc((size_t)n)); PT_HC(dc.alloc((size_t)n));
+    PT_HC(dxy.upload(powf_xy, 2 * (size_t)n)); PT_HC(dpo.alloc((size_t)n));
+    PT_HC(dpw.upload(pw_in, (size_t)n)); PT_HC(dp5.alloc((size_t)n));
     t->ks->kat_libm(dim3((n + 255) / 256), t->stream, n, dx.p, ds.p, dc.p, dpw.p, dp5.p, dxy.p, dpo.p);
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(ds.download(sin_out)); HIPCHECK(dc.download(cos_out)); HIPCHECK(dp5.download(pow5_out)); HIPCHECK(dpo.download(powf_out));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(ds.download(sin_out)); PT_HC(dc.download(cos_out)); PT_HC(dp5.download(pow5_out)); PT_HC(dpo.download(powf_out));
     return PTX_OK;
 }
 
 int ptx_kat_fast_exact(ptx_tracer *t, int64_t mismatches[3]) {
     KAT_PROLOGUE
-    if (!mismatches) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!mismatches) return pt_fail(PTX_ERR_INVALID, "null argument");
     DevBuf<unsigned long long> d;
-    HIPCHECK(d.alloc(3));
-    HIPCHECK(hipMemsetAsync(d.p, 0, 3 * sizeof(unsigned long long), t->stream));
+    PT_HC(d.alloc(3));
+    PT_HC(hipMemsetAsync(d.p, 0, 3 * sizeof(unsigned long long), t->stream));
     hipLaunchKernelGGL(k_kat_fast_exact, dim3(t->cus * 8), dim3(256), 0, t->stream, d.p);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipGetLastError());
+    PT_HC(hipStreamSynchronize(t->stream));
     unsigned long long h[3];
-    HIPCHECK(d.download(h));
+    PT_HC(d.download(h));
     for (int k = 0; k < 3; k++) mismatches[k] = (int64_t)h[k];
     return PTX_OK;
 }
 
 int ptx_kat_unit_rsqrt(ptx_tracer *t, int exponent_reps, int64_t random_sets, int64_t counts[4]) {
     KAT_PROLOGUE
-    if (!counts || exponent_reps < 0 || random_sets < 0) return set_error(PTX_ERR_INVALID, "bad argument");
+    if (!counts || exponent_reps < 0 || random_sets < 0) return pt_fail(PTX_ERR_INVALID, "bad argument");
     DevBuf<unsigned long long> d;
-    HIPCHECK(d.alloc(4));
-    HIPCHECK(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), t->stream));
+    PT_HC(d.alloc(4));
+    PT_HC(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), t->stream));
     launch_kat_unit_rsqrt(t->cus, t->stream, d.p, exponent_reps, (unsigned long long)random_sets);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    PT_HC(hipGetLastError());
+    PT_HC(hipStreamSynchronize(t->stream));
     unsigned long long h[4];
-    HIPCHECK(d.download(h));
+    PT_HC(d.download(h));
     for (int k = 0; k < 4; k++) counts[k] = (int64_t)h[k];
     return PTX_OK;
 }
 
 int ptx_set_kernel_timing(ptx_tracer *t, int on) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     ahead_discard(t);
     t->ktiming = on != 0;
     t->kev_used = 0;
@@ -1513,13 +1507,13 @@ int ptx_set_kernel_timing(ptx_tracer *t, int on) {
 }
 
 int ptx_get_kernel_times(ptx_tracer *t, double ms_by_kind[4], int64_t launches_by_kind[4]) {
-    if (!t || !ms_by_kind || !launches_by_kind) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !ms_by_kind || !launches_by_kind) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     for (int k = 0; k < 4; k++) { ms_by_kind[k] = 0.0; launches_by_kind[k] = 0; }
     for (size_t i = 0; i + 1 < t->kev_used; i += 2) {
         float ms = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms, t->kev[i], t->kev[i + 1]));
+        PT_HC(hipEventElapsedTime(&ms, t->kev[i], t->kev[i + 1]));
         int kind = t->kev_kind[i / 2];
         ms_by_kind[kind] += ms; launches_by_kind[kind]++;
     }
@@ -1529,20 +1523,20 @@ int ptx_get_kernel_times(ptx_tracer *t, double ms_by_kind[4], int64_t launches_b
 
 // diagnostic build (-DPT_STAMPS): cycles per phase of k_bounce summed over waves: [0..4] first bounce, [8..12] later bounces
 int ptx_debug_read_stamps(ptx_tracer *t, unsigned long long out48[48]) {
-    if (!t || !out48) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t || !out48) return pt_fail(PTX_ERR_INVALID, "null argument");
     memset(out48, 0, sizeof(unsigned long long) * 48);
     if (!t->d_stamps) return PTX_OK;
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(out48, t->d_stamps, sizeof(unsigned long long) * 48, hipMemcpyDeviceToHost));
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
+    PT_HC(hipMemcpy(out48, t->d_stamps, sizeof(unsigned long long) * 48, hipMemcpyDeviceToHost));
     {   // -DPT_WGCLOCK: the per-workgroup wall-clock slots summed per kind into [32..36] (first bounce) and [40..44] (later bounces)
         std::vector<unsigned long long> w((size_t)2 * 64 * 4096 * 5);
-        HIPCHECK(hipMemcpy(w.data(), t->d_stamps + 48, sizeof(unsigned long long) * w.size(), hipMemcpyDeviceToHost));
+        PT_HC(hipMemcpy(w.data(), t->d_stamps + 48, sizeof(unsigned long long) * w.size(), hipMemcpyDeviceToHost));
         for (int kind = 0; kind < 2; kind++)
             for (size_t k = 0; k < (size_t)64 * 4096; k++)
                 for (int f = 0; f < 5; f++) out48[32 + kind * 8 + f] += w[((size_t)kind * 64 * 4096 + k) * 5 + f];
     }
-    HIPCHECK(hipMemset(t->d_stamps, 0, sizeof(unsigned long long) * (48 + 2 * 64 * 4096 * 5)));
+    PT_HC(hipMemset(t->d_stamps, 0, sizeof(unsigned long long) * (48 + 2 * 64 * 4096 * 5)));
     return PTX_OK;
 }
 
@@ -1554,15 +1548,17 @@ int ptx_debug_bounce_occupancy(ptx_tracer *t, int lds_bytes) {
     const int ntri_lds = t->split_mesh ? 0 : t->ntri_lds;
     const int triWords = t->tri_lds ? sceneTableWords(ntri_lds, t->nmats, t->ngeoms) : 0;
     size_t lds = lds_bytes > 0 ? (size_t)lds_bytes : sizeof(int32_t) * (bounceLdsWords(triWords, t->nbins) - (17 - REC_ROWS_FAST0) * TILE);
-    return static_cast<const KernelSet *>(ptx_arith_kernels_0())->bounce_occupancy(lds);
+    const KernelSet *ks = nullptr; const LastKernelSet *ksl = nullptr;      // (the exact level's, whatever the tracer's)
+    if (kernel_tables(PTX_ARITH_EXACT, false, &ks, &ksl)) return -1;
+    return ks->bounce_occupancy(lds);
 }
 
 // Host-only: what pt_prepare_scene decided for one mesh geom, and which walk each caller of the mesh search takes for it -- the rules of
 // k_mesh's set-up (pt_kernels.hip: wideok), of meshKey (pt_device.h: wideok / ordered) and of ptx_create's bvh_stack, restated on the host copies.
 int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]) {
-    if (!t || !out8) return set_error(PTX_ERR_INVALID, "null argument");
-    if (geom < 0 || geom >= t->ngeoms || (size_t)geom >= t->h_roots.size()) return set_error(PTX_ERR_INVALID, "geom index out of range");
-    if (t->h_geom_type[geom] != G_OBJ) return set_error(PTX_ERR_INVALID, "ptx_debug_mesh_plan: the geom is not a mesh");
+    if (!t || !out8) return pt_fail(PTX_ERR_INVALID, "null argument");
+    if (geom < 0 || geom >= t->ngeoms || (size_t)geom >= t->h_roots.size()) return pt_fail(PTX_ERR_INVALID, "geom index out of range");
+    if (t->h_geom_type[geom] != G_OBJ) return pt_fail(PTX_ERR_INVALID, "ptx_debug_mesh_plan: the geom is not a mesh");
     const int root = t->h_roots[geom], depth = t->h_depths[geom], wroot = t->h_wroots[geom], wneed = t->h_wneeds[geom];
     // (the four-wide tables reach the device only when some tree has four-wide nodes: ptx_create, step 7)
     const bool wide = root >= 0 && wroot >= 0 && t->d_bvh_wroot && wneed <= t->bvh_stack;
@@ -1576,7 +1572,7 @@ int ptx_debug_mesh_plan(ptx_tracer *t, int geom, int32_t out8[8]) {
 // Host-only: the layout of the local index this tracer's launches use (pt_plan.h, IndexPlan) -- what the tests of both forms assert the
 // code path by.
 int ptx_debug_index_plan(ptx_tracer *t, int64_t out8[8]) {
-    if (!t || !out8) return set_error(PTX_ERR_INVALID, "null argument");
+    if (!t || !out8) return pt_fail(PTX_ERR_INVALID, "null argument");
     const IndexPlan &x = t->ix;
     out8[0] = x.loop ? 1 : 0; out8[1] = x.n2_log2; out8[2] = x.words; out8[3] = (int64_t)x.entries; out8[4] = (int64_t)x.seg_words;
     out8[5] = x.bytes_per_path; out8[6] = t->cap; out8[7] = x.why_code;
@@ -1584,16 +1580,16 @@ int ptx_debug_index_plan(ptx_tracer *t, int64_t out8[8]) {
 }
 
 int ptx_debug_aux_nonzero(ptx_tracer *t, int64_t out3[3]) {
-    if (!t || !out3) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) HIPCHECK(hipStreamSynchronize(t->lane_stream[l]));
+    if (!t || !out3) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
+    for (int l = 1; l < MAX_LANES; l++) if (t->lane_stream[l]) PT_HC(hipStreamSynchronize(t->lane_stream[l]));
     const size_t nseg = (size_t)t->kmax * t->lanes, words = (size_t)t->cap / 32;
     std::vector<int32_t> tot(t->seg_totals * nseg);
     std::vector<uint32_t> planes(t->d_part ? words * nseg : 0);
-    HIPCHECK(hipMemcpy(tot.data(), t->d_totals, t->totals_bytes, hipMemcpyDeviceToHost));
+    PT_HC(hipMemcpy(tot.data(), t->d_totals, t->totals_bytes, hipMemcpyDeviceToHost));
     if (t->d_part)
-        HIPCHECK(hipMemcpy2D(planes.data(), sizeof(uint32_t) * words, t->d_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part,
+        PT_HC(hipMemcpy2D(planes.data(), sizeof(uint32_t) * words, t->d_part + 3 * (size_t)t->cap, sizeof(float) * t->seg_part,
                              sizeof(uint32_t) * words, nseg, hipMemcpyDeviceToHost));
     int64_t nz_planes = 0, nz_totals = 0, dirty = 0;
     for (int l = 0; l < t->lanes; l++) {
@@ -1611,45 +1607,45 @@ int ptx_debug_aux_nonzero(ptx_tracer *t, int64_t out3[3]) {
 }
 
 int ptx_debug_set_capture(ptx_tracer *t, int bounce) {
-    if (!t) return set_error(PTX_ERR_INVALID, "null tracer");
-    HIPCHECK(hipSetDevice(t->device));
+    if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    PT_HC(hipSetDevice(t->device));
     t->capture_bounce = bounce;
     t->cap_filled = false;
     if (bounce >= 0 && !t->d_cap) {
         // pix, stream index, material|geom [cap each], the bounce's totals [nbins], run prefixes of the capture [2][nbins x grid_seg + 1]
-        HIPCHECK(t->d_cap.alloc(3 * (size_t)t->cap + (size_t)t->nbins + 2 * ((size_t)t->nbins * t->grid_seg + 1)));
-        HIPCHECK(t->d_cap_f.alloc(SOA_LOGICAL_FLOATS * (size_t)t->cap));
+        PT_HC(t->d_cap.alloc(3 * (size_t)t->cap + (size_t)t->nbins + 2 * ((size_t)t->nbins * t->grid_seg + 1)));
+        PT_HC(t->d_cap_f.alloc(SOA_LOGICAL_FLOATS * (size_t)t->cap));
     }
     return PTX_OK;
 }
 
 int ptx_debug_read_stream(ptx_tracer *t, int *n_out, int32_t *pixel_index, int32_t *stream_idx, int32_t *material,
                           float *fields14, int cap) {
-    if (!t || !n_out) return set_error(PTX_ERR_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(t->device));
-    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (!t || !n_out) return pt_fail(PTX_ERR_INVALID, "null argument");
+    PT_HC(hipSetDevice(t->device));
+    PT_HC(hipStreamSynchronize(t->stream));
     *n_out = 0;
-    if (!t->cap_filled) return set_error(PTX_ERR_INVALID, "nothing captured");
+    if (!t->cap_filled) return pt_fail(PTX_ERR_INVALID, "nothing captured");
     std::vector<int32_t> tot((size_t)t->nbins);
-    HIPCHECK(hipMemcpy(tot.data(), t->d_cap + 3 * (size_t)t->cap, sizeof(int32_t) * tot.size(), hipMemcpyDeviceToHost));
+    PT_HC(hipMemcpy(tot.data(), t->d_cap + 3 * (size_t)t->cap, sizeof(int32_t) * tot.size(), hipMemcpyDeviceToHost));
     int n = 0;
     for (int v : tot) n += v;
     *n_out = n;
     int m = n < cap ? n : cap;
     if (m > 0) {
-        HIPCHECK(hipMemcpy(pixel_index, t->d_cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+        PT_HC(hipMemcpy(pixel_index, t->d_cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
         if (t->tm.tile_world > 1)             // paths carry their slot among the owned pixels: report the pixel (x + y*W)
             for (int k = 0; k < m; k++) {
                 const int slot = pixel_index[k] & 0x0fffffff, r = slot / t->tm.W, x = slot - r * t->tm.W, blk = r / t->tm.tile_rows;
                 pixel_index[k] = x + ((blk * t->tm.tile_world + t->tm.tile_rank) * t->tm.tile_rows + (r - blk * t->tm.tile_rows)) * t->tm.W;
             }
-        HIPCHECK(hipMemcpy(stream_idx, t->d_cap + t->cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+        PT_HC(hipMemcpy(stream_idx, t->d_cap + t->cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
         std::vector<int32_t> mg((size_t)m);
-        HIPCHECK(hipMemcpy(mg.data(), t->d_cap + 2 * (size_t)t->cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+        PT_HC(hipMemcpy(mg.data(), t->d_cap + 2 * (size_t)t->cap, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
         for (int k = 0; k < m; k++) material[k] = mg[k] & 0xffff;
         if (fields14)       // 14 rows of m floats: px py pz dx dy dz cr cg cb nx ny nz u v
             for (int f = 0; f < SOA_LOGICAL_FLOATS; f++)
-                HIPCHECK(hipMemcpy(fields14 + (size_t)f * m, t->d_cap_f + (size_t)f * t->cap, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
+                PT_HC(hipMemcpy(fields14 + (size_t)f * m, t->d_cap_f + (size_t)f * t->cap, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
     }
     return PTX_OK;
 }

@@ -222,7 +222,7 @@ int alloc_moments(ptx_moments *m) {
     PT_HC(m->d_mb.alloc((size_t)pt_moments_pairs(m->w) * m->h));
     m->st.snap = m->d_snap; m->st.mean = m->d_mean; m->st.ma = m->d_ma; m->st.mb = m->d_mb;
     PT_HC(m->d_part.alloc((size_t)grid.x * grid.y + 1));
-    PT_HC(hipEventCreateWithFlags(&m->ev, hipEventDisableTiming));
+    PT_HC(m->ev.create(hipEventDisableTiming));
     return PTX_OK;
 }
 

@@ -342,7 +342,7 @@ int alloc_nn(ptx_nn *n) {
     PT_HC(n->d_scratch.alloc(at));
     PT_HC(n->d_scale.alloc(1));
     PT_HC(n->d_scale.zero());
-    PT_HC(hipEventCreateWithFlags(&n->ev, hipEventDisableTiming));
+    PT_HC(n->ev.create(hipEventDisableTiming));
     return PTX_OK;
 }
 

@@ -247,7 +247,7 @@ static int alloc_temporal(ptx_temporal *t) {
     }
     PT_HC(t->d_mix.alloc(3 * n));
     PT_HC(t->d_hn.alloc(n));
-    PT_HC(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
+    PT_HC(t->ev.create(hipEventDisableTiming));
     return PTX_OK;
 }
 

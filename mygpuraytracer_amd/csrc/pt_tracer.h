@@ -33,9 +33,15 @@ extern "C" const void *ptx_arith_last_1p(void) __attribute__((weak));
 // ---------------------------------------------------------------------------------------------------------------
 struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on and the debug switches `dbg`, pt_plan.h; what the scene decides, pt_scene.h)
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    // Every stream and event, declared in front of the buffers and in this order.  Members go in the reverse of their declaration: a tracer
+    // that is deleted frees its buffers first, then destroys its events (kev first, ev_start last), then the lane streams, the main stream
+    // last.  free_tracer has synchronised every stream by then -- nothing is enqueued, no wait is pending, no buffer is in use -- so any
+    // order would be safe; this one lets go of what was recorded before what it was recorded on.
+    OwnedStream stream;                           // the caller's (borrowed: never destroyed) or the tracer's own
+    OwnedStream lane_stream[MAX_LANES];           // (lanes, below) [0] = `stream` and stays empty, the others are the tracer's own
+    OwnedEvent ev_start, ev_stop, ev_fork, ev_join[MAX_LANES], ev_chain[MAX_LANES];
+    OwnedEvent ev_ahead0[MAX_LANES], ev_ahead1[MAX_LANES];      // (render-ahead, below)
+    std::vector<OwnedEvent> kev;                  // per-kernel timing, below: pairs (start, stop)
     bool timing_valid = false;
     ptx_options opt{};
     DCamera cam{};
@@ -73,9 +79,8 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     int nsuper = 1;
     size_t totals_bytes = 0, seg_totals = 0, field_stride = 0, seg_part = 0;
     int kmax = 1;                                        // iterations per launch set (segments)
-    // (lanes, pt_plan.h: each launch set in flight runs on a stream of its own with its own kmax segments of every per-iteration buffer)
-    hipStream_t lane_stream[MAX_LANES] = {};      // [0] = `stream`, the others are the tracer's own
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {}, ev_chain[MAX_LANES] = {};
+    // (lanes, pt_plan.h: each launch set in flight runs on a stream of its own -- lane_stream, with ev_fork / ev_join / ev_chain -- and
+    // with its own kmax segments of every per-iteration buffer)
     // Render-ahead for the one-iteration-per-call shape (ptx_iterate = the reference's pathtrace(iter)): lanes 1 and 2 take
     // turns tracing the NEXT kmax iterations into their per-iteration radiance buffers while the caller works the current
     // batch off, one k_gather (+ k_stats) per call on the main stream.  What a call returns is unchanged: the image holds
@@ -86,7 +91,6 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     int ahead_cur = -1, ahead_nxt = -1;                  // lane whose batch is being consumed / lane holding the batch after it
     bool render_ahead = false;
     int last_ahead_lane = -1;                            // != -1: the previous operation was a call served from that lane's batch
-    hipEvent_t ev_ahead0[MAX_LANES] = {}, ev_ahead1[MAX_LANES] = {};
     // The lit planes and totals of a lane's segments are zero between its launch sets: the set's k_gather and k_stats clear what they
     // read.  Where that may not hold -- nothing has run yet, a traced-ahead batch was dropped unfinished, a set ended early on an error,
     // the image was reset -- the lane's next set starts with a full clear of both (enqueue_batch).
@@ -118,10 +122,9 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     bool cache_valid = false;
     int64_t iterations = 0;
     double loop_ms_total = 0.0;
-    // optional per-kernel timing (bench.py's roofline leg): events around every launch of an iteration
+    // optional per-kernel timing (bench.py's roofline leg): events around every launch of an iteration (kev)
     bool ktiming = false;
-    std::vector<hipEvent_t> kev;                         // pairs (start, stop)
-    std::vector<int> kev_kind;                           // per pair: 0 k_bounce<first>, 1 k_bounce, 2 k_mesh + k_finish, 3 pass 2 of the split bounce (the ranking pass)
+    std::vector<int> kev_kind;                           // per pair of kev: 0 k_bounce<first>, 1 k_bounce, 2 k_mesh + k_finish, 3 pass 2 of the split bounce (the ranking pass)
     size_t kev_used = 0;
     // debug capture
     int capture_bounce = -1;
@@ -140,8 +143,8 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
         return s;
     }
     bool cache_active() const { return opt.cache_first_bounce && !opt.antialiasing && !opt.depth_of_field; }
-    const KernelSet *ks = static_cast<const KernelSet *>(ptx_arith_kernels_0());      // the code object the arithmetic-bearing kernels are launched from (ptx_options.arith)
-    const LastKernelSet *ksl = static_cast<const LastKernelSet *>(ptx_arith_last_0());    // ... and the same level's light-only last bounce
+    const KernelSet *ks = nullptr;      // the code object the arithmetic-bearing kernels are launched from (ptx_options.arith)
+    const LastKernelSet *ksl = nullptr;    // ... and the same level's light-only last bounce
 };
 
 // ---- pt_engine.hip's, for pt_post.hip ---------------------------------------------------------------------------
