@@ -718,8 +718,9 @@ int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin
  *     {upsample (nearest, 2x), concat with the skip, dec_conv<l>a, dec_conv<l>b}, then dec_conv0.  Skips: pool3, pool2, pool1, the
  *     network's input; the upsampled tensor comes first in the channel order.  All convolutions are 3 x 3 with zero padding and a ReLU,
  *     except dec_conv0, which has none.  Channel counts are the blob's: enc_conv0 takes 3, 6 or 9, dec_conv0 gives 3, none above 256.
- *   Frame: W x H zero-padded on the right and bottom to multiples of 16, the image at the top left; one tile is the whole frame, at
- *     most 7680 x 4320.
+ *   Frame: W x H zero-padded on the right and bottom to multiples of 16, the image at the top left.  ptx_nn_create runs the frame as
+ *     one tile, at most 7680 x 4320; ptx_nn_create_tiled splits it into overlapping tiles under a memory limit (Tiles, below), up to
+ *     16384 x 16384.
  *   Arithmetic: activations are fp16 (round to nearest even), channels-last, each tensor's channel count zero-padded to a multiple of
  *     16 (the two sources of a concat separately).  Weights are rounded to fp16 once, at create; biases stay fp32.  A convolution's
  *     output = the fp32 sum, in any order, of the exact fp16 x fp16 products, plus the bias; ReLU; one rounding to fp16.  dec_conv0's
@@ -734,10 +735,24 @@ int  ptx_debug_display_blocks(int w, int h, int *hk, int *wk, int32_t *row_begin
  *   scale: input_scale when it is not NaN; else, with hdr, the display transform's block meter at key 0.18 on rgb / samples (steps 1
  *     and 2 above, its kernels; the value stays on the device, and the meter's sanitising rule holds where it differs from OIDN's);
  *     else 1.
+ *   Tiles (OIDN's maxMemoryMB, restated; csrc/pt_nn_tiles.h): scratch(tw, th) = the activations' bytes of a tw x th frame with this
+ *     blob; the limit is max_memory_mb * 2^20 bytes, 0 = none.  From tiles_y = tiles_x = 1, tileH = pad16(H), tileW = pad16(W): while
+ *     scratch(tileW, tileH) is above the limit or the tile above 7680 x 4320 -- if tileH > 288 and tileH > tileW, one more tile in y
+ *     and tileH = max(pad16(ceil((H - 192) / tiles_y)) + 192, 288); else if tileW > 288 the same in x; else stop (a 288 x 288 tile
+ *     above the limit is accepted).  Then tiles_y = H > tileH ? ceil((H - 192) / (tileH - 192)) : 1, and so in x.  Tile (i, j) reads
+ *     the window at y = i (tileH - 192), h = min(H - y, tileH) (x, w likewise), zero-padded to multiples of 16 as a frame is, and
+ *     keeps it minus 96 rows / columns on each side where another tile follows.  The kept rectangles cover the frame once; origins
+ *     are multiples of 16 and a kept pixel is at least 96 pixels (half the receptive field of 174, rounded up to 16) from a cut, so
+ *     it sees the data it sees in the whole frame: a tiled run gives the bits of a one-tile run.  The scale is the whole frame's:
+ *     the meter runs once.  With more than one tile the result may not overlap the inputs in memory.
  * A handle serves one W x H on one device with one blob, across tracers and streams, with ptx_display's event ordering. */
 #define PTX_NN_LAYERS 16
-#define PTX_NN_MAX_WIDTH 7680
+#define PTX_NN_MAX_WIDTH 7680                      /* of one tile */
 #define PTX_NN_MAX_HEIGHT 4320
+#define PTX_NN_TILE_ALIGN 16
+#define PTX_NN_TILE_OVERLAP 96
+#define PTX_NN_MIN_TILE 288                        /* 3 * PTX_NN_TILE_OVERLAP */
+#define PTX_NN_MAX_FRAME 16384                     /* of a tiled handle, each way */
 typedef struct ptx_nn ptx_nn;                      /* opaque: packed weights, scratch, the meter; one W x H on one device */
 typedef struct ptx_nn_params {
     int   hdr;                 /* 0 / 1: the PU transfer and an unbounded colour; default 0 */
@@ -753,15 +768,38 @@ typedef struct ptx_nn_info {
     uint64_t scratch_bytes;                        /* the activations' device memory, planned at create */
     uint64_t macs;                                 /* multiply-adds of one run: the sum over layers of 9 Cin Cout padded pixels at its level */
 } ptx_nn_info;
+typedef struct ptx_nn_tile {
+    int x, y, w, h;                                /* the window read */
+    int out_x, out_y, out_w, out_h;                /* the rectangle kept, in frame coordinates */
+} ptx_nn_tile;
+typedef struct ptx_nn_tiling {
+    int      width, height;
+    int      tile_width, tile_height;              /* the buffer every tile fits in, multiples of 16 */
+    int      tiles_x, tiles_y;
+    int      max_memory_mb;                        /* 0: no memory limit, only the tile cap */
+    uint64_t scratch_bytes;                        /* of one tile_width x tile_height tile */
+    uint64_t macs;                                 /* summed over the tiles' padded windows */
+} ptx_nn_tiling;
 void   ptx_default_nn_params(ptx_nn_params *p);
 size_t ptx_sizeof_nn_params(void);
 size_t ptx_sizeof_nn_info(void);
+size_t ptx_sizeof_nn_tile(void);
+size_t ptx_sizeof_nn_tiling(void);
 int  ptx_nn_create(int device, int width, int height, const void *tza, size_t bytes, ptx_nn **out);
 int  ptx_nn_create_from_file(int device, int width, int height, const char *path, ptx_nn **out);
+/* The same under a memory limit (Tiles, above): frames up to 16384 x 16384; max_memory_mb 0 = no limit, < 0 refused.  With 0 and a
+ * frame within 7680 x 4320 the handle is ptx_nn_create's.  On a tiled handle ptx_nn_get_info reports the tile buffer's padded size,
+ * the tile's scratch_bytes and the summed macs. */
+int  ptx_nn_create_tiled(int device, int width, int height, const void *tza, size_t bytes, int max_memory_mb, ptx_nn **out);
+int  ptx_nn_create_from_file_tiled(int device, int width, int height, const char *path, int max_memory_mb, ptx_nn **out);
 void ptx_nn_destroy(ptx_nn *n);                    /* NULL is a no-op; waits for its last use */
 int  ptx_nn_get_info(ptx_nn *n, ptx_nn_info *out);
+/* The handle's tile plan, and the first min(cap, tiles_x * tiles_y) tiles in execution order (row-major); tiles may be NULL */
+int  ptx_nn_get_tiling(ptx_nn *n, ptx_nn_tiling *tiling, ptx_nn_tile *tiles, int cap);
 /* One denoise of a W*H*3 float frame on the handle's device, on `stream` (NULL = the default stream): rgb / samples in, out_rgb out.
- * alb3 / nrm3 (W*H*3 floats each) are required exactly when the blob takes 6 / 9 inputs and refused otherwise.  p NULL = defaults. */
+ * alb3 / nrm3 (W*H*3 floats each) are required exactly when the blob takes 6 / 9 inputs and refused otherwise.  p NULL = defaults.
+ * On a handle with more than one tile, out_rgb's bytes may not overlap those of rgb, alb3 or nrm3 (PTX_ERR_INVALID): a later tile
+ * reads pixels that an earlier tile's result would have replaced. */
 int  ptx_nn_denoise_device(ptx_nn *n, const float *device_rgb, float samples, const float *device_alb3, const float *device_nrm3,
                            const ptx_nn_params *p, float *device_out_rgb, void *stream);
 /* the same from host frames through staging buffers the handle owns; waits */
@@ -788,6 +826,9 @@ int  ptx_kat_nn_transfer(int device, int w, int h, const float *rgb, const float
 int  ptx_debug_tza_list(const void *tza, size_t bytes, char *out, size_t cap, size_t *needed);
 /* Host only: the plan of the blob (the refusals of ptx_nn_create that need no device); out may be NULL */
 int  ptx_debug_nn_plan(const void *tza, size_t bytes, ptx_nn_info *out);
+/* Host only: the tile plan ptx_nn_create_tiled would make (its refusals that need no device); tiles as in ptx_nn_get_tiling */
+int  ptx_debug_nn_tiling(const void *tza, size_t bytes, int width, int height, int max_memory_mb, ptx_nn_tiling *tiling, ptx_nn_tile *tiles,
+                         int cap);
 
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's

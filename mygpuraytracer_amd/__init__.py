@@ -31,6 +31,9 @@ from .api import (  # noqa: F401
     nn_denoise_buffers,
     debug_tza_list,
     debug_nn_plan,
+    debug_nn_tiling,
+    NNTile,
+    NNTiling,
     kat_nn_conv,
     kat_nn_transfer,
     Scene,

@@ -481,6 +481,32 @@ class NNInfo(C.Structure):
                 ("scratch_bytes", C.c_uint64), ("macs", C.c_uint64)]
 
 
+class NNTile(C.Structure):
+    """ptx_nn_tile: the window a tile reads and the rectangle it keeps, in frame coordinates"""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int),
+                ("out_x", C.c_int), ("out_y", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int)]
+
+
+class NNTiling(C.Structure):
+    """ptx_nn_tiling (include/mi355x_pathtracer.h, "Tiles")"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("tile_width", C.c_int), ("tile_height", C.c_int), ("tiles_x", C.c_int),
+                ("tiles_y", C.c_int), ("max_memory_mb", C.c_int), ("scratch_bytes", C.c_uint64), ("macs", C.c_uint64)]
+
+
+def _nn_tiling_dict(call, what, tiles=True):
+    """call(tiling, tiles, cap) -> rc, twice: the plan, then its tiles as dicts in execution order"""
+    t = NNTiling()
+    _check(call(C.byref(t), None, 0), what)
+    out = {k: getattr(t, k) for k, _ in NNTiling._fields_}
+    if tiles:
+        n = t.tiles_x * t.tiles_y
+        arr = (NNTile * n)()
+        _check(call(C.byref(t), arr, n), what)
+        rows = np.frombuffer(arr, np.int32).reshape(n, len(NNTile._fields_)).copy()
+        out["tiles"] = rows if tiles == "array" else [dict(zip((k for k, _ in NNTile._fields_), (int(v) for v in r))) for r in rows]
+    return out
+
+
 def default_nn_params(**kw):
     """ptx_default_nn_params with keyword overrides (hdr, srgb, input_scale)."""
     return _default_params(NNParams, "ptx_default_nn_params", ("hdr", "srgb"), **kw)
@@ -523,23 +549,46 @@ def debug_nn_plan(tza):
     return _nn_info_dict(info)
 
 
+def debug_nn_tiling(tza, width, height, max_memory_mb=0, tiles=True):
+    """ptx_debug_nn_tiling: the tile plan NN(width, height, tza, max_memory_mb=...) would run by, as a dict (ptx_nn_tiling's fields, and
+    `tiles`: ptx_nn_tile's fields per tile in execution order; tiles="array": as an (n, 8) int32 array, x y w h out_x out_y out_w out_h;
+    tiles=False: left out); no device needed."""
+    blob, ptr = _blob_buffer(tza)
+    L = load_library()
+    return _nn_tiling_dict(lambda t, a, n: L.ptx_debug_nn_tiling(ptr, len(blob), int(width), int(height), int(max_memory_mb), t, a, n),
+                           "ptx_debug_nn_tiling", tiles)
+
+
 class NN(_Owned):
     """The network denoiser on one device (opaque ptx_nn): Open Image Denoise's RT filter run from the caller's TZA weights (`tza`:
     bytes, or a path) for one W x H.  host(rgb, albedo, normal) denoises a numpy frame, device(...) a frame on the device,
-    Tracer.denoise_nn(nn, spp) a tracer's; params are ptx_nn_params' fields as keywords."""
+    Tracer.denoise_nn(nn, spp) a tracer's; params are ptx_nn_params' fields as keywords.  max_memory_mb None: the frame is one tile
+    (ptx_nn_create, at most 7680 x 4320); a number: ptx_nn_create_tiled, overlapping tiles whose scratch fits that many MiB (0: no
+    limit but the tile cap), frames up to 16384 x 16384, the same bits as one tile."""
 
     _destroy = "ptx_nn_destroy"
 
-    def __init__(self, width, height, tza, device=0):
+    def __init__(self, width, height, tza, device=0, max_memory_mb=None):
         self.lib = load_library()
         h = vp()
+        size = (int(device), int(width), int(height))
         if isinstance(tza, (str, os.PathLike)):
-            _check(self.lib.ptx_nn_create_from_file(int(device), int(width), int(height), os.fsencode(tza), C.byref(h)), "ptx_nn_create_from_file")
+            if max_memory_mb is None:
+                _check(self.lib.ptx_nn_create_from_file(*size, os.fsencode(tza), C.byref(h)), "ptx_nn_create_from_file")
+            else:
+                _check(self.lib.ptx_nn_create_from_file_tiled(*size, os.fsencode(tza), int(max_memory_mb), C.byref(h)), "ptx_nn_create_from_file_tiled")
         else:
             blob, ptr = _blob_buffer(tza)
-            _check(self.lib.ptx_nn_create(int(device), int(width), int(height), ptr, len(blob), C.byref(h)), "ptx_nn_create")
+            if max_memory_mb is None:
+                _check(self.lib.ptx_nn_create(*size, ptr, len(blob), C.byref(h)), "ptx_nn_create")
+            else:
+                _check(self.lib.ptx_nn_create_tiled(*size, ptr, len(blob), int(max_memory_mb), C.byref(h)), "ptx_nn_create_tiled")
         self.h = h
         self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
+
+    def tiling(self, tiles=True):
+        """ptx_nn_get_tiling as a dict: ptx_nn_tiling's fields and `tiles`, ptx_nn_tile's fields per tile in execution order"""
+        return _nn_tiling_dict(lambda t, a, n: self.lib.ptx_nn_get_tiling(self.h, t, a, n), "ptx_nn_get_tiling", tiles)
 
     def info(self):
         """ptx_nn_get_info as a dict: sizes, input_channels, layers = [(name, cin, cout)], scratch_bytes, macs"""
@@ -574,13 +623,13 @@ class NN(_Owned):
         return np.float32(s.value)
 
 
-def nn_denoise_buffers(tza, rgb, albedo=None, normal=None, samples=1, device=0, **params):
-    """The network denoiser alone on host arrays of one (H, W, 3) frame: a handle for the frame's size from `tza` (bytes or a path), one
-    NN.host call.  Returns the denoised (H, W, 3) float32.  Needs a HIP device: there is no CPU path."""
+def nn_denoise_buffers(tza, rgb, albedo=None, normal=None, samples=1, device=0, max_memory_mb=None, **params):
+    """The network denoiser alone on host arrays of one (H, W, 3) frame: a handle for the frame's size from `tza` (bytes or a path;
+    max_memory_mb as NN's), one NN.host call.  Returns the denoised (H, W, 3) float32.  Needs a HIP device: there is no CPU path."""
     rgb = np.ascontiguousarray(rgb, np.float32)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
         raise PathTracerError("nn_denoise_buffers: rgb must be (H, W, 3)")
-    with NN(rgb.shape[1], rgb.shape[0], tza, device=device) as nn:
+    with NN(rgb.shape[1], rgb.shape[0], tza, device=device, max_memory_mb=max_memory_mb) as nn:
         return nn.host(rgb, albedo, normal, samples=samples, **params)
 
 
@@ -1004,6 +1053,14 @@ def load_library():
     L.ptx_kat_nn_transfer.restype, L.ptx_kat_nn_transfer.argtypes = i, [i, i, i, vp, vp, vp, i, i, f, i, vp]
     L.ptx_debug_tza_list.restype, L.ptx_debug_tza_list.argtypes = i, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ptx_debug_nn_plan.restype, L.ptx_debug_nn_plan.argtypes = i, [vp, C.c_size_t, C.POINTER(NNInfo)]
+    L.ptx_sizeof_nn_tile.restype = L.ptx_sizeof_nn_tiling.restype = C.c_size_t
+    if L.ptx_sizeof_nn_tile() != C.sizeof(NNTile) or L.ptx_sizeof_nn_tiling() != C.sizeof(NNTiling):
+        raise PathTracerError("%s has network tile structs of %d and %d B, this module expects %d and %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_nn_tile(), L.ptx_sizeof_nn_tiling(), C.sizeof(NNTile), C.sizeof(NNTiling)))
+    L.ptx_nn_create_tiled.restype, L.ptx_nn_create_tiled.argtypes = i, [i, i, i, vp, C.c_size_t, i, C.POINTER(vp)]
+    L.ptx_nn_create_from_file_tiled.restype, L.ptx_nn_create_from_file_tiled.argtypes = i, [i, i, i, C.c_char_p, i, C.POINTER(vp)]
+    L.ptx_nn_get_tiling.restype, L.ptx_nn_get_tiling.argtypes = i, [vp, C.POINTER(NNTiling), C.POINTER(NNTile), i]
+    L.ptx_debug_nn_tiling.restype, L.ptx_debug_nn_tiling.argtypes = i, [vp, C.c_size_t, i, i, i, C.POINTER(NNTiling), C.POINTER(NNTile), i]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]

@@ -176,7 +176,8 @@ int main(int argc, char **argv) {
     ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
     std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step, nn_path;
-    int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0, guide_bounces = 0;
+    int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0, guide_bounces = 0, nn_max_memory = 0;
+    bool nn_max_memory_set = false;
     ptx_options &opt = pathtraceOptions();
     ptx_display_params &disp = g_display.params;
     ptx_default_display_params(&disp);
@@ -205,6 +206,7 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--nn") { need(1); nn_path = argv[++i]; }
         else if (a == "--nn-hdr") nnParams().hdr = 1;
+        else if (a == "--nn-max-memory") { need(1); nn_max_memory = atoi(argv[++i]); nn_max_memory_set = true; }
         else if (a == "--denoise-passes") { need(1); dparams.passes = atoi(argv[++i]); }
         else if (a == "--frames") { need(1); frames = atoi(argv[++i]); }
         else if (a == "--frame-step") { need(1); frame_step = argv[++i]; }
@@ -253,6 +255,8 @@ int main(int argc, char **argv) {
     const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of measure_every iterations, a ptx_moments_add after each
     if (!nn_path.empty() && !denoise) { fprintf(stderr, "--nn needs --denoise\n"); return 1; }
     if (nnParams().hdr && nn_path.empty()) { fprintf(stderr, "--nn-hdr needs --nn FILE\n"); return 1; }
+    if (nn_max_memory_set && nn_path.empty()) { fprintf(stderr, "--nn-max-memory needs --nn FILE\n"); return 1; }
+    if (nn_max_memory_set && nn_max_memory < 0) { fprintf(stderr, "--nn-max-memory needs MB >= 0 (0: no memory limit)\n"); return 1; }
     if (!nn_path.empty() && (temporal || variance || measured || frames > 0)) { fprintf(stderr, "--nn does not combine with --temporal, --variance, --measured or --frames\n"); return 1; }
     if (measured && !denoise) { fprintf(stderr, "--measured needs --denoise\n"); return 1; }
     if (measure_every < 1) { fprintf(stderr, "--measure-every needs K >= 1\n"); return 1; }
@@ -393,7 +397,9 @@ int main(int argc, char **argv) {
         if (guide_bounces > 0 && ptx_set_guide_bounces(t, guide_bounces) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         if (guide_samples > 0 && ptx_set_guide_samples(t, 1, std::min(guide_samples, n)) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         ptx_nn *nn = nullptr;
-        if (!nn_path.empty() && ptx_nn_create_from_file(opt.device < 0 ? 0 : opt.device, width, height, nn_path.c_str(), &nn) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
+        const int nn_device = opt.device < 0 ? 0 : opt.device;
+        if (!nn_path.empty() && (nn_max_memory_set ? ptx_nn_create_from_file_tiled(nn_device, width, height, nn_path.c_str(), nn_max_memory, &nn)
+                                                   : ptx_nn_create_from_file(nn_device, width, height, nn_path.c_str(), &nn)) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         const int rc = nn ? ptx_denoise_nn(t, nn, &nnParams(), n)
                      : measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
                      : variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);

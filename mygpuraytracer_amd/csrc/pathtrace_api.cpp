@@ -30,7 +30,7 @@ bool g_variance_params_init = false;
 ptx_temporal *g_temporal = nullptr;  // GPUdenoise's history with denoiseTemporal() on: kept across pathtraceFree / pathtraceInit
 int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
 ptx_nn *g_nn = nullptr;              // GPUdenoise's network with nnWeights() set: kept like g_temporal
-int g_nn_key[3] = {0, 0, 0};         // its device, width, height
+int g_nn_key[4] = {0, 0, 0, 0};      // its device, width, height, nnMaxMemoryMB()
 std::string g_nn_path;               // ... and the weight file it was made from
 int g_device = 0;                    // the device of g_tracer
 ptx_moments *g_moments = nullptr;    // pathtrace()'s batch means with momentsBatch() > 0: created on first use
@@ -260,6 +260,11 @@ bool &denoiseMeasured() {
 std::string &nnWeights() {
     static std::string path;
     return path;
+}
+
+int &nnMaxMemoryMB() {
+    static int mb = -1;
+    return mb;
 }
 
 ptx_nn_params &nnParams() {
@@ -526,13 +531,14 @@ void GPUdenoise(bool keep_on_device) {
             exit(EXIT_FAILURE);
         }
         const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
-        const int key[3] = {g_device, w, h};
+        const int key[4] = {g_device, w, h, nnMaxMemoryMB()};
         if (g_nn && (memcmp(key, g_nn_key, sizeof key) != 0 || g_nn_path != nnWeights())) {
             ptx_nn_destroy(g_nn);
             g_nn = nullptr;
         }
         if (!g_nn) {
-            check(ptx_nn_create_from_file(g_device, w, h, nnWeights().c_str(), &g_nn), "GPUdenoise");
+            check(nnMaxMemoryMB() < 0 ? ptx_nn_create_from_file(g_device, w, h, nnWeights().c_str(), &g_nn)
+                                      : ptx_nn_create_from_file_tiled(g_device, w, h, nnWeights().c_str(), nnMaxMemoryMB(), &g_nn), "GPUdenoise");
             memcpy(g_nn_key, key, sizeof key);
             g_nn_path = nnWeights();
         }

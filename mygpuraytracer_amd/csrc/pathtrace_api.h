@@ -300,8 +300,11 @@ bool &denoiseMeasured();
 // 1.4.x weight file, with nnParams() (hdr, srgb, input_scale), in place of the a-trous filter; albedo and normals come from the G-buffer
 // in the guide mode that is set.  The handle is created on first use, recreated when the file, the device or the resolution changes,
 // and freed by GPUdenoiseRelease().  Empty (the default): the calls made are exactly those above.  Not combined with denoiseTemporal(),
-// denoiseVariance() or denoiseMeasured().
+// denoiseVariance() or denoiseMeasured().  nnMaxMemoryMB() = M >= 0 makes that handle with ptx_nn_create_from_file_tiled: overlapping
+// tiles whose activations fit M MiB (OIDN's maxMemoryMB; 0 = no limit but the tile cap), the same bits as one tile; -1 (the default):
+// ptx_nn_create_from_file, one tile.  A change recreates the handle.
 std::string &nnWeights();
+int &nnMaxMemoryMB();
 ptx_nn_params &nnParams();
 // Adaptive sampling by tiles (ptx_adaptive_*): adaptiveTarget() = E > 0 together with momentsBatch() = k makes pathtrace(), after every
 // k-th call, count those k iterations tile by tile (ptx_adaptive_add, in place of the plain moments add) and switch off the tiles whose

@@ -1,11 +1,13 @@
 // pt_nn.hip -- the network denoiser (ptx_nn_* of include/mi355x_pathtracer.h): Open Image Denoise's RT filter, a U-Net of sixteen
 // 3 x 3 convolutions, run from a caller's TZA weight blob on the matrix cores.  ptx_denoise_nn is pt_post.hip's: it needs the tracer's
-// buffers and stream.  The blob and the plan are pt_tza.h's (host only); the state's layout is in pt_nn.h; the arithmetic is defined in
-// the public header and restated by tests/unet_ref.py.
+// buffers and stream.  The blob and the plan are pt_tza.h's, the memory model and the tiles of a handle made under a memory limit
+// pt_nn_tiles.h's (both host only); the state's layout is in pt_nn.h; the arithmetic is defined in the public header and restated by
+// tests/unet_ref.py, the tile rule by tests/nn_tiles_ref.py.
 //
 // Kernels (the unit has optimisation flags of its own, see the Makefile; -ffp-contract=off stays, the transfer functions are restated):
-//   k_nn_input  : one thread per pixel of the padded frame: colour / albedo / normal sanitised and transferred into the network's
-//       input, 16 fp16 channels per pixel (two 16-byte stores), zeros right of and below the image.  The scale is a launch argument or
+//   k_nn_input  : one thread per pixel of a tile's padded window (one tile: the padded frame; the window's origin in the frame and the
+//       frame's row stride are launch arguments): colour / albedo / normal sanitised and transferred into the network's
+//       input, 16 fp16 channels per pixel (two 16-byte stores), zeros right of and below the window.  The scale is a launch argument or
 //       read from the meter's state record on the device; thread 0 leaves the one it used in d_scale.
 //   k_nn_conv<NCO> : one convolution as an implicit GEMM on v_mfma_f32_16x16x32_f16, M = Cout, N = pixels, K = 9 Cin.  A workgroup of
 //       256 (4 waves) computes a tile of TILE x TILE = 16 x 16 output pixels for NCO blocks of 16 output channels (NCO = 1 .. 8, the
@@ -19,8 +21,10 @@
 //       the second the skip, each with its own padded channel block, so no upsampled or concatenated tensor exists.  Pooled form: the
 //       2 x 2 maximum is taken in registers (rows of one lane, then the neighbour column by a shuffle) and only the pooled tensor is
 //       written.  dec_conv0's form writes its fp32 sums, four floats per pixel.
-//   k_nn_output : one thread per pixel of the image: dec_conv0's three fp32 channels sanitised, the inverse transfer, 1 / scale.
-// No atomics; every sum has one order: the same bits on every run.
+//   k_nn_output : one thread per pixel of the rectangle a tile keeps (one tile: the image): dec_conv0's three fp32 channels sanitised,
+//       the inverse transfer, 1 / scale, written to the rectangle's place in the frame.
+// No atomics; every sum has one order, which does not depend on where a pixel lies: the same bits on every run, and a tiled run
+// (pt_nn_tiles.h) gives the bits of a one-tile run.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -71,7 +75,8 @@ __device__ __forceinline__ float transfer_inverse(float x, int mode, float xmax)
 }
 
 struct InputArgs {
-    int w, h, wp, hp;
+    int w, h, wp, hp;                         // the window and its padded size
+    int x0, y0, W;                            // the window's origin in the frame, the frame's row stride in pixels
     const float *rgb, *alb, *nrm;
     int alb_stride, nrm_stride;
     float samples, scale;
@@ -91,13 +96,13 @@ __global__ __launch_bounds__(NT) void k_nn_input(InputArgs a) {
     const int y = (int)(idx / a.wp), x = (int)(idx - (size_t)y * a.wp);
     float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const bool inside = x < a.w && y < a.h;
-    const size_t p = (size_t)y * a.w + x;
+    const size_t p = ((size_t)a.y0 + y) * a.W + a.x0 + x;
     if (inside) {
         for (int c = 0; c < 3; c++)
             v[c] = transfer_forward(sanitise((a.rgb[3 * p + c] / a.samples) * s, 0.f, a.hdr ? FLT_MAX : 1.f), a.mode, a.norm);
         if (a.alb) for (int c = 0; c < 3; c++) v[3 + c] = sanitise(a.alb[(size_t)a.alb_stride * p + c], 0.f, 1.f);
         if (a.nrm) for (int c = 0; c < 3; c++) v[6 + c] = sanitise(a.nrm[(size_t)a.nrm_stride * p + c], -1.f, 1.f) * 0.5f + 0.5f;
-        if (a.raw) for (int c = 0; c < 9; c++) a.raw[9 * p + c] = v[c];
+        if (a.raw) for (int c = 0; c < 9; c++) a.raw[9 * ((size_t)y * a.w + x) + c] = v[c];
     }
     half8 lo, hi = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int c = 0; c < 8; c++) lo[c] = (_Float16)v[c];
@@ -107,12 +112,14 @@ __global__ __launch_bounds__(NT) void k_nn_input(InputArgs a) {
 }
 
 struct OutputArgs {
-    int w, h, wp;
+    int w, h, wp;                             // the rectangle kept; the tile's padded width
+    int ix, iy;                               // where the rectangle begins in the tile's output
+    int ox, oy, W;                            // ... and in the frame; the frame's row stride in pixels
     const float *net;                         // [hp][wp][4] fp32
     const float *scale;
     int mode, hdr;
     float xmax;
-    float *out;                               // [h][w][3]
+    float *out;                               // [H][W][3]
 };
 
 __global__ __launch_bounds__(NT) void k_nn_output(OutputArgs a) {
@@ -120,12 +127,13 @@ __global__ __launch_bounds__(NT) void k_nn_output(OutputArgs a) {
     if (idx >= (size_t)a.w * a.h) return;
     const int y = (int)(idx / a.w), x = (int)(idx - (size_t)y * a.w);
     const float s = *a.scale, inv = s != 0.f ? 1.f / s : 0.f;
-    const float4 n = reinterpret_cast<const float4 *>(a.net)[(size_t)y * a.wp + x];
+    const float4 n = reinterpret_cast<const float4 *>(a.net)[((size_t)a.iy + y) * a.wp + a.ix + x];
+    const size_t p = ((size_t)a.oy + y) * a.W + a.ox + x;
     const float in[3] = {n.x, n.y, n.z};
     for (int c = 0; c < 3; c++) {
         float v = transfer_inverse(sanitise(in[c], 0.f, FLT_MAX), a.mode, a.xmax);
         if (!a.hdr) v = fminf(v, 1.f);
-        a.out[3 * idx + c] = v * inv;
+        a.out[3 * p + c] = v * inv;
     }
 }
 
@@ -299,18 +307,16 @@ int launch_conv(hipStream_t st, const ConvArgs &a, int cout) {
     return PTX_OK;
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 thread_local const PtNnPlan *tl_plan = nullptr;      // ptx_nn_create's plan, for alloc_nn (pt_handle_create hands over the handle alone)
+thread_local int tl_max_memory_mb = 0;               // ... and ptx_nn_create_tiled's limit
 
 int alloc_nn(ptx_nn *n) {
     const PtNnPlan &plan = *tl_plan;
-    n->wp = pad16(n->w); n->hp = pad16(n->h); n->ic = plan.ic;
+    n->tiling = pt_nn_tiling(plan, n->w, n->h, tl_max_memory_mb);
+    n->wp = n->tiling.tile_width; n->hp = n->tiling.tile_height; n->ic = plan.ic;
     PT_HC(hipSetDevice(n->device));
-    // where each layer's output lives: 0 .. 2 = the skips pool1 .. pool3, 3 / 4 = the two arenas
-    static const int place[PT_NN_LAYERS] = {3, 0, 1, 2, 3, 4, 3, 4, 3, 4, 3, 4, 3, 4, 3, 4};
-    size_t skip[3] = {0, 0, 0}, arena[2] = {0, 0};
-    n->macs = 0;
+    const PtNnScratch scratch = pt_nn_scratch(plan, n->wp, n->hp);
+    n->macs = pt_nn_tiling_macs(plan, n->tiling);
     for (int i = 0; i < PT_NN_LAYERS; i++) {
         const PtNnLayer &P = plan.layers[i];
         PtNnLayerDev &L = n->L[i];
@@ -318,11 +324,7 @@ int alloc_nn(ptx_nn *n) {
         L.c0p = pad16(P.cin0); L.c1p = P.cin1 ? pad16(P.cin1) : 0; L.coutp = pad16(P.cout);
         L.level = P.level; L.src0 = P.src0; L.src1 = P.src1; L.relu = P.relu; L.pool = P.pool; L.upsample = P.upsample;
         snprintf(n->names[i], sizeof n->names[i], "%s", P.name);
-        const size_t px = (size_t)(n->hp >> P.level) * (n->wp >> P.level);
-        n->macs += (uint64_t)px * 9u * (uint64_t)(P.cin0 + P.cin1) * (uint64_t)P.cout;
-        const size_t bytes = i == PT_NN_LAYERS - 1 ? px * 4 * sizeof(float) : (P.pool ? px / 4 : px) * L.coutp * 2;
-        if (place[i] < 3) skip[place[i]] = align256(bytes);
-        else arena[place[i] - 3] = std::max(arena[place[i] - 3], align256(bytes));
+        L.out_offset = scratch.out_offset[i];
         const PtTzaTensor *wt = P.weight;
         const int cin = P.cin0 + P.cin1;
         std::vector<uint16_t> w;
@@ -332,14 +334,8 @@ int alloc_nn(ptx_nn *n) {
         PT_HC(L.w.upload(w));
         PT_HC(L.b.upload(b));
     }
-    const size_t in_bytes = align256((size_t)n->hp * n->wp * 16 * 2);
-    size_t at = 0;
-    n->in_offset = at; at += in_bytes;
-    size_t skip_at[3], arena_at[2];
-    for (int k = 0; k < 3; k++) { skip_at[k] = at; at += skip[k]; }
-    for (int k = 0; k < 2; k++) { arena_at[k] = at; at += arena[k]; }
-    for (int i = 0; i < PT_NN_LAYERS; i++) n->L[i].out_offset = place[i] < 3 ? skip_at[place[i]] : arena_at[place[i] - 3];
-    PT_HC(n->d_scratch.alloc(at));
+    n->in_offset = scratch.in_offset;
+    PT_HC(n->d_scratch.alloc(scratch.total));
     PT_HC(n->d_scale.alloc(1));
     PT_HC(n->d_scale.zero());
     PT_HC(n->ev.create(hipEventDisableTiming));
@@ -384,6 +380,41 @@ int device_problem(const char *fn, int device) {
     return PTX_OK;
 }
 
+int read_file(const char *fn, const char *path, std::vector<uint8_t> &blob) {
+    if (!path) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": path is NULL");
+    FILE *f = fopen(path, "rb");
+    if (!f) return pt_fail(PTX_ERR_IO, std::string(fn) + ": cannot open " + path);
+    uint8_t buf[65536];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) blob.insert(blob.end(), buf, buf + got);
+    fclose(f);
+    return PTX_OK;
+}
+
+// What ptx_nn_create_tiled refuses without a device, before pt_handle_create's own checks: the blob, the limit, a frame above the cap
+int tiled_problem(const char *fn, const void *tza, size_t bytes, int width, int height, int max_memory_mb, PtNnPlan &plan) {
+    std::string err;
+    if (!pt_nn_plan(tza, bytes, plan, err)) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": " + err);
+    if (max_memory_mb < 0) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": max_memory_mb must be >= 0 (0: no memory limit)");
+    if (width > PTX_NN_MAX_FRAME || height > PTX_NN_MAX_FRAME)
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": bad frame size (a tiled frame is at most 16384 x 16384)");
+    return PTX_OK;
+}
+
+void fill_tiling(const PtNnTiling &t, size_t scratch_bytes, uint64_t macs, ptx_nn_tiling *o, ptx_nn_tile *tiles, int cap) {
+    *o = ptx_nn_tiling();
+    o->width = t.width; o->height = t.height; o->tile_width = t.tile_width; o->tile_height = t.tile_height;
+    o->tiles_x = t.tiles_x; o->tiles_y = t.tiles_y; o->max_memory_mb = t.max_memory_mb;
+    o->scratch_bytes = scratch_bytes; o->macs = macs;
+    for (int k = 0; tiles && k < cap && k < t.count(); k++) tiles[k] = pt_nn_tile_at(t, k);
+}
+
+// the byte ranges [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
 }  // namespace
 
 ptx_nn::~ptx_nn() { if (meter) ptx_display_destroy(meter); }
@@ -400,11 +431,16 @@ int pt_nn_enqueue(ptx_nn *n, hipStream_t st, const float *rgb, float samples, co
                   const ptx_nn_params &p, float *out_rgb) {
     const bool automatic = isnan(p.input_scale) && p.hdr;
     if (automatic && !n->meter)
-        if (const int rc = ptx_display_create(n->device, n->w, n->h, &n->meter)) return rc;
+        if (const int rc = ptx_display_create(n->device, n->w, n->h, &n->meter)) {
+            if (rc == PTX_ERR_INVALID && (n->w > PTX_NN_MAX_WIDTH || n->h > PTX_NN_MAX_HEIGHT))
+                return pt_fail(rc, "the network denoiser's automatic hdr scale is refused at " + std::to_string(n->w) + " x " + std::to_string(n->h) +
+                                       ": the display handle that meters the frame refuses this size (give ptx_nn_params.input_scale)");
+            return rc;
+        }
     PT_HC(n->wait_stream(st));
     uint8_t *base = n->d_scratch;
     InputArgs ia;
-    ia.w = n->w; ia.h = n->h; ia.wp = n->wp; ia.hp = n->hp;
+    ia.W = n->w;
     ia.rgb = rgb; ia.alb = alb; ia.nrm = nrm; ia.alb_stride = alb_stride; ia.nrm_stride = nrm_stride;
     ia.samples = samples; ia.scale = isnan(p.input_scale) ? 1.f : p.input_scale;
     ia.scale_ptr = nullptr;
@@ -416,27 +452,35 @@ int pt_nn_enqueue(ptx_nn *n, hipStream_t st, const float *rgb, float samples, co
     ia.mode = mode_of(p); ia.hdr = p.hdr; ia.norm = pu_norm();
     ia.out = reinterpret_cast<uint16_t *>(base + n->in_offset);
     ia.raw = nullptr;
-    if (const int rc = launch_input(st, ia)) return rc;
-    for (int i = 0; i < PT_NN_LAYERS; i++) {
-        const PtNnLayerDev &L = n->L[i];
-        auto tensor = [&](int src) { return reinterpret_cast<const uint16_t *>(base + (src == -1 ? n->in_offset : n->L[src].out_offset)); };
-        ConvArgs a;
-        a.src0 = tensor(L.src0); a.src1 = L.src1 == -2 ? nullptr : tensor(L.src1);
-        a.w = L.w; a.bias = L.b;
-        const bool last = i == PT_NN_LAYERS - 1;
-        a.out = last ? nullptr : reinterpret_cast<uint16_t *>(base + L.out_offset);
-        a.out32 = last ? reinterpret_cast<float *>(base + L.out_offset) : nullptr;
-        a.W = n->wp >> L.level; a.H = n->hp >> L.level;
-        a.c0p = L.c0p; a.c1p = L.c1p; a.coutp = L.coutp; a.nchunks = (L.c0p + L.c1p + CHUNK - 1) / CHUNK;
-        a.upsample = L.upsample; a.pool = L.pool; a.relu = L.relu;
-        if (const int rc = launch_conv(st, a, L.cout)) return rc;
-    }
     OutputArgs oa;
-    oa.w = n->w; oa.h = n->h; oa.wp = n->wp;
+    oa.W = n->w;
     oa.net = reinterpret_cast<const float *>(base + n->L[PT_NN_LAYERS - 1].out_offset);
     oa.scale = n->d_scale; oa.mode = mode_of(p); oa.hdr = p.hdr; oa.xmax = pu_xmax();
     oa.out = out_rgb;
-    if (const int rc = launch_output(st, oa)) return rc;
+    // every tile in the handle's one scratch, a smaller tile in a prefix of each tensor; the scale is the frame's, the same for each
+    for (int k = 0; k < n->tiling.count(); k++) {
+        const ptx_nn_tile T = pt_nn_tile_at(n->tiling, k);
+        const int wp = pad16(T.w), hp = pad16(T.h);
+        ia.w = T.w; ia.h = T.h; ia.wp = wp; ia.hp = hp; ia.x0 = T.x; ia.y0 = T.y;
+        if (const int rc = launch_input(st, ia)) return rc;
+        for (int i = 0; i < PT_NN_LAYERS; i++) {
+            const PtNnLayerDev &L = n->L[i];
+            auto tensor = [&](int src) { return reinterpret_cast<const uint16_t *>(base + (src == -1 ? n->in_offset : n->L[src].out_offset)); };
+            ConvArgs a;
+            a.src0 = tensor(L.src0); a.src1 = L.src1 == -2 ? nullptr : tensor(L.src1);
+            a.w = L.w; a.bias = L.b;
+            const bool last = i == PT_NN_LAYERS - 1;
+            a.out = last ? nullptr : reinterpret_cast<uint16_t *>(base + L.out_offset);
+            a.out32 = last ? reinterpret_cast<float *>(base + L.out_offset) : nullptr;
+            a.W = wp >> L.level; a.H = hp >> L.level;
+            a.c0p = L.c0p; a.c1p = L.c1p; a.coutp = L.coutp; a.nchunks = (L.c0p + L.c1p + CHUNK - 1) / CHUNK;
+            a.upsample = L.upsample; a.pool = L.pool; a.relu = L.relu;
+            if (const int rc = launch_conv(st, a, L.cout)) return rc;
+        }
+        oa.w = T.out_w; oa.h = T.out_h; oa.wp = wp;
+        oa.ix = T.out_x - T.x; oa.iy = T.out_y - T.y; oa.ox = T.out_x; oa.oy = T.out_y;
+        if (const int rc = launch_output(st, oa)) return rc;
+    }
     PT_HC(n->record(st));
     return PTX_OK;
 }
@@ -452,6 +496,8 @@ void ptx_default_nn_params(ptx_nn_params *p) {
 
 size_t ptx_sizeof_nn_params(void) { return sizeof(ptx_nn_params); }
 size_t ptx_sizeof_nn_info(void) { return sizeof(ptx_nn_info); }
+size_t ptx_sizeof_nn_tile(void) { return sizeof(ptx_nn_tile); }
+size_t ptx_sizeof_nn_tiling(void) { return sizeof(ptx_nn_tiling); }
 
 int ptx_debug_tza_list(const void *tza, size_t bytes, char *out, size_t cap, size_t *needed) {
     std::vector<PtTzaTensor> tensors;
@@ -491,15 +537,43 @@ int ptx_nn_create(int device, int width, int height, const void *tza, size_t byt
 
 int ptx_nn_create_from_file(int device, int width, int height, const char *path, ptx_nn **out) {
     if (out) *out = nullptr;
-    if (!path) return pt_fail(PTX_ERR_INVALID, "ptx_nn_create_from_file: path is NULL");
-    FILE *f = fopen(path, "rb");
-    if (!f) return pt_fail(PTX_ERR_IO, std::string("ptx_nn_create_from_file: cannot open ") + path);
     std::vector<uint8_t> blob;
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) blob.insert(blob.end(), buf, buf + got);
-    fclose(f);
+    if (const int rc = read_file("ptx_nn_create_from_file", path, blob)) return rc;
     return ptx_nn_create(device, width, height, blob.data(), blob.size(), out);
+}
+
+int ptx_nn_create_tiled(int device, int width, int height, const void *tza, size_t bytes, int max_memory_mb, ptx_nn **out) {
+    if (out) *out = nullptr;
+    PtNnPlan plan;
+    if (const int rc = tiled_problem("ptx_nn_create_tiled", tza, bytes, width, height, max_memory_mb, plan)) return rc;
+    tl_plan = &plan; tl_max_memory_mb = max_memory_mb;
+    const int rc = pt_handle_create("ptx_nn_create_tiled", "the network denoiser", device, width, height, (long long)PTX_NN_MAX_FRAME * PTX_NN_MAX_FRAME, out, alloc_nn);
+    tl_plan = nullptr; tl_max_memory_mb = 0;
+    return rc;
+}
+
+int ptx_nn_create_from_file_tiled(int device, int width, int height, const char *path, int max_memory_mb, ptx_nn **out) {
+    if (out) *out = nullptr;
+    std::vector<uint8_t> blob;
+    if (const int rc = read_file("ptx_nn_create_from_file_tiled", path, blob)) return rc;
+    return ptx_nn_create_tiled(device, width, height, blob.data(), blob.size(), max_memory_mb, out);
+}
+
+int ptx_debug_nn_tiling(const void *tza, size_t bytes, int width, int height, int max_memory_mb, ptx_nn_tiling *tiling, ptx_nn_tile *tiles, int cap) {
+    const char *fn = "ptx_debug_nn_tiling";
+    PtNnPlan plan;
+    if (const int rc = tiled_problem(fn, tza, bytes, width, height, max_memory_mb, plan)) return rc;
+    if (!tiling) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": tiling is NULL");
+    if (width < 1 || height < 1) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": bad frame size");
+    const PtNnTiling t = pt_nn_tiling(plan, width, height, max_memory_mb);
+    fill_tiling(t, pt_nn_scratch(plan, t.tile_width, t.tile_height).total, pt_nn_tiling_macs(plan, t), tiling, tiles, cap);
+    return PTX_OK;
+}
+
+int ptx_nn_get_tiling(ptx_nn *n, ptx_nn_tiling *tiling, ptx_nn_tile *tiles, int cap) {
+    if (!n || !tiling) return pt_fail(PTX_ERR_INVALID, "ptx_nn_get_tiling: null handle or tiling");
+    fill_tiling(n->tiling, n->d_scratch.n, n->macs, tiling, tiles, cap);
+    return PTX_OK;
 }
 
 void ptx_nn_destroy(ptx_nn *n) { pt_handle_destroy(n); }
@@ -533,6 +607,14 @@ int ptx_nn_denoise_device(ptx_nn *n, const float *device_rgb, float samples, con
     if ((device_nrm3 != nullptr) != (n->ic >= 9))
         return pt_fail(PTX_ERR_INVALID, std::string("ptx_nn_denoise_device: the weights take ") + std::to_string(n->ic) + " input channels: normals " +
                                             (n->ic >= 9 ? "are required" : "must be NULL"));
+    if (n->tiling.count() > 1) {
+        const size_t frame = 3 * sizeof(float) * (size_t)n->w * n->h;
+        const void *in[3] = {device_rgb, device_alb3, device_nrm3};
+        for (const void *src : in)
+            if (src && ranges_overlap(device_out_rgb, frame, src, frame))
+                return pt_fail(PTX_ERR_INVALID, "ptx_nn_denoise_device: with more than one tile the result may not overlap the colour, albedo or normal "
+                                                "frame in memory (a later tile reads pixels an earlier tile's result would have replaced)");
+    }
     PT_HC(hipSetDevice(n->device));
     return pt_nn_enqueue(n, (hipStream_t)stream, device_rgb, samples, device_alb3, 3, device_nrm3, 3, p, device_out_rgb);
 }
@@ -632,7 +714,7 @@ int ptx_kat_nn_transfer(int device, int w, int h, const float *rgb, const float 
         PT_HC(d_in.alloc(pxp * 16));
         PT_HC(d_out.alloc(9 * px));
         InputArgs ia;
-        ia.w = w; ia.h = h; ia.wp = wp; ia.hp = hp;
+        ia.w = w; ia.h = h; ia.wp = wp; ia.hp = hp; ia.x0 = ia.y0 = 0; ia.W = w;
         ia.rgb = d_rgb; ia.alb = alb3 ? d_alb.p : nullptr; ia.nrm = nrm3 ? d_nrm.p : nullptr; ia.alb_stride = ia.nrm_stride = 3;
         ia.samples = 1.f; ia.scale = scale; ia.scale_ptr = nullptr; ia.scale_out = d_scale;
         ia.mode = mode_of(p); ia.hdr = hdr; ia.norm = pu_norm();
@@ -646,7 +728,7 @@ int ptx_kat_nn_transfer(int device, int w, int h, const float *rgb, const float 
         PT_HC(d_net.upload(net));
         PT_HC(d_out.alloc(3 * px));
         OutputArgs oa;
-        oa.w = w; oa.h = h; oa.wp = wp; oa.net = d_net; oa.scale = d_scale; oa.mode = mode_of(p); oa.hdr = hdr; oa.xmax = pu_xmax(); oa.out = d_out;
+        oa.w = w; oa.h = h; oa.wp = wp; oa.ix = oa.iy = oa.ox = oa.oy = 0; oa.W = w; oa.net = d_net; oa.scale = d_scale; oa.mode = mode_of(p); oa.hdr = hdr; oa.xmax = pu_xmax(); oa.out = d_out;
         if (const int rc = launch_output(nullptr, oa)) return rc;
     }
     PT_HC(hipDeviceSynchronize());
