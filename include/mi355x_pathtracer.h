@@ -830,6 +830,78 @@ int  ptx_debug_nn_plan(const void *tza, size_t bytes, ptx_nn_info *out);
 int  ptx_debug_nn_tiling(const void *tza, size_t bytes, int width, int height, int max_memory_mb, ptx_nn_tiling *tiling, ptx_nn_tile *tiles,
                          int cap);
 
+/* ---- network denoiser: prefiltered guides (OIDN's cleanAux), csrc/pt_nn_aux.hip --------------------------------------------------------
+ * The guides of a path tracer are noisy where they are honest (sampled guides, guides followed through glass).  OIDN's answer is to
+ * denoise the albedo image and the normal image each on its own first -- the RT filter called without a colour image, with the weight
+ * files rt_alb / rt_nrm -- and to give the main network, with weights trained for clean guides (rt_hdr_calb_cnrm, rt_ldr_calb_cnrm),
+ * the results.  A ptx_nn_prefilter holds one or both of those 3-input networks for one W x H on one device; additive, like everything
+ * in this section.  No trained weights ship and nothing here claims image quality.  Definition (tests/unet_aux_ref.py restates it):
+ *   Network, frame, arithmetic, tiles: the network denoiser's, above, on a blob whose enc_conv0 takes 3 channels.
+ *   scale = input_scale, or 1 when that is NaN; there is no meter.  Every step below is one IEEE fp32 operation.
+ *   Albedo in:  v = (a / 1) * scale; NaN -> 0; clamp to [0, 1]; the sRGB curve (srgb == 0) or nothing (srgb != 0): the colour path of
+ *     the network denoiser with hdr == 0 and samples == 1.  Albedo out: that path's output: NaN -> 0, clamp to [0, FLT_MAX], the inverse
+ *     curve, min(., 1), times 1 / scale.
+ *   Normal in:  v = n * scale; NaN -> 0; clamp to [-1, 1]; v * 0.5 + 0.5; no curve.  Normal out: NaN -> 0; clamp to [0, FLT_MAX];
+ *     v * 2 - 1; max(., -1); min(., 1); times 1 / scale (0 when scale is 0).
+ *   In both the three values fill channels 0 .. 2 of the network's input and the result is three floats per pixel.
+ *   Refused, as the RT filter refuses them: an hdr prefilter (the params have no such field), srgb on a normal image, a blob that takes
+ *     more than the image (6 or 9 input channels).
+ *   Memory: both networks' packed weights, one W*H*3 clean image per network, and ONE activation scratch of the larger plan's size
+ *     under the handle's tile limit -- the networks run one after the other on the caller's stream.
+ *   Cache (ptx_denoise_nn_prefiltered): guides belong to a camera, not to a sample.  A tracer's G-buffer carries a serial from a
+ *     process-wide counter, renewed whenever the G-buffer is computed again (a new camera, ptx_set_guide_samples / _bounces with other
+ *     values).  The handle remembers the serial, the params and the networks of its last run through that call; a call with the same
+ *     ones runs no prefilter network and leaves `runs` as it is.  ptx_nn_prefilter_run_* always run and forget the serial, as
+ *     ptx_nn_prefilter_invalidate does. */
+#define PTX_NN_AUX_ALBEDO 1
+#define PTX_NN_AUX_NORMAL 2
+typedef struct ptx_nn_prefilter ptx_nn_prefilter;  /* opaque: two networks' weights, their one scratch, the clean images */
+typedef struct ptx_nn_prefilter_params {
+    int   srgb;                /* albedo only: 0 = the sRGB curve (default), 1 = none */
+    float input_scale;         /* NaN = 1 (default); else finite and > 0 */
+} ptx_nn_prefilter_params;
+typedef struct ptx_nn_prefilter_info {
+    int         width, height, has_albedo, has_normal;
+    ptx_nn_info albedo, normal;                    /* of each network that is there (scratch_bytes: its own plan's); else zeros */
+    uint64_t    scratch_bytes;                     /* the one allocation: the larger of the two plans' */
+    uint64_t    runs;                              /* calls that ran a prefilter network */
+} ptx_nn_prefilter_info;
+void   ptx_default_nn_prefilter_params(ptx_nn_prefilter_params *p);
+size_t ptx_sizeof_nn_prefilter_params(void);
+size_t ptx_sizeof_nn_prefilter_info(void);
+/* Either blob may be NULL (no network for that image), not both.  max_memory_mb < 0: each network runs the frame as one tile
+ * (ptx_nn_create's cap); else as ptx_nn_create_tiled. */
+int  ptx_nn_prefilter_create(int device, int width, int height, const void *alb_tza, size_t alb_bytes, const void *nrm_tza, size_t nrm_bytes,
+                             int max_memory_mb, ptx_nn_prefilter **out);
+int  ptx_nn_prefilter_create_from_files(int device, int width, int height, const char *alb_path, const char *nrm_path, int max_memory_mb,
+                                        ptx_nn_prefilter **out);
+void ptx_nn_prefilter_destroy(ptx_nn_prefilter *pf);       /* NULL is a no-op; waits for its last use */
+int  ptx_nn_prefilter_get_info(ptx_nn_prefilter *pf, ptx_nn_prefilter_info *out);
+/* Both networks on `stream` (NULL = the default stream), into the clean images the handle owns.  An image is W*H pixels with a
+ * stride of 3 or 4 floats (4: 16-byte aligned), required exactly where the handle has a network for it, NULL elsewhere. */
+int  ptx_nn_prefilter_run_device(ptx_nn_prefilter *pf, const float *device_alb, int alb_stride, const float *device_nrm, int nrm_stride,
+                                 const ptx_nn_prefilter_params *p, void *stream);
+/* the same from host images of W*H*3 floats; waits; out_* (optional) receive the clean images */
+int  ptx_nn_prefilter_run_host(ptx_nn_prefilter *pf, const float *alb3, const float *nrm3, const ptx_nn_prefilter_params *p, float *out_alb3,
+                               float *out_nrm3);
+/* the clean images on the device, W*H*3 floats each (NULL where the handle has no network); valid after the run's work */
+int  ptx_nn_prefilter_device_clean(ptx_nn_prefilter *pf, const float **alb3, const float **nrm3);
+int  ptx_nn_prefilter_read(ptx_nn_prefilter *pf, float *alb3, float *nrm3);       /* either may be NULL; waits */
+int  ptx_nn_prefilter_invalidate(ptx_nn_prefilter *pf);    /* the next ptx_denoise_nn_prefiltered runs the networks again */
+/* ptx_denoise_nn with the main network's guides prefiltered: a main network of 6 inputs gets the clean albedo (refused when pf has no
+ * albedo network); one of 9 inputs gets each guide clean where pf has a network for it, else the G-buffer's own; one of 3 inputs is
+ * refused.  The colour path, the scale and the meter are ptx_denoise_nn's, and so are its refusals, for both handles.  pp NULL =
+ * defaults.  The clean images are cached per G-buffer (Cache, above). */
+int  ptx_denoise_nn_prefiltered(ptx_tracer *t, ptx_nn *main_nn, ptx_nn_prefilter *pf, const ptx_nn_params *p, const ptx_nn_prefilter_params *pp,
+                                int spp);
+/* The two kernels of the prefilter alone on a w x h image of three floats per pixel.  inverse == 0: the input kernel, out3 = what the
+ * network would get, before the rounding to fp16; inverse != 0: in3 is the network's output, out3 the output kernel's result.  scale
+ * finite and >= 0. */
+int  ptx_kat_nn_transfer_aux(int device, int w, int h, int kind, const float *in3, int srgb, float scale, int inverse, float *out3);
+/* Host only: what ptx_nn_prefilter_create and a run would refuse without a device: the blobs (NULL: none), the params (NULL: defaults) */
+int  ptx_debug_nn_prefilter_problem(const void *alb_tza, size_t alb_bytes, const void *nrm_tza, size_t nrm_bytes,
+                                    const ptx_nn_prefilter_params *p);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
  *      reprojection alone and needs no tracer ------------------------------------------------------------------- */

@@ -666,6 +666,122 @@ def kat_nn_transfer(rgb, albedo=None, normal=None, hdr=0, srgb=0, scale=1.0, inv
     return out
 
 
+NN_AUX_ALBEDO, NN_AUX_NORMAL = 1, 2
+
+
+class NNPrefilterParams(C.Structure):
+    """ptx_nn_prefilter_params (include/mi355x_pathtracer.h; defaults from ptx_default_nn_prefilter_params: srgb 0, input_scale NaN = 1).
+    There is no hdr field: a prefilter in hdr mode is refused."""
+    _fields_ = [("srgb", C.c_int), ("input_scale", C.c_float)]
+
+
+class NNPrefilterInfo(C.Structure):
+    """ptx_nn_prefilter_info (include/mi355x_pathtracer.h)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("has_albedo", C.c_int), ("has_normal", C.c_int),
+                ("albedo", NNInfo), ("normal", NNInfo), ("scratch_bytes", C.c_uint64), ("runs", C.c_uint64)]
+
+
+def default_nn_prefilter_params(**kw):
+    """ptx_default_nn_prefilter_params with keyword overrides (srgb, input_scale); any other keyword, hdr among them, is refused."""
+    for k in kw:
+        if k not in ("srgb", "input_scale"):
+            raise PathTracerError("ptx_nn_prefilter_params has no field %r (a prefilter takes srgb and input_scale; hdr is refused)" % k)
+    return _default_params(NNPrefilterParams, "ptx_default_nn_prefilter_params", ("srgb",), **kw)
+
+
+def _opt_blob(tza):
+    """(keep-alive, pointer, length) of an optional blob"""
+    if tza is None:
+        return None, None, 0
+    blob, ptr = _blob_buffer(tza)
+    return blob, ptr, len(blob)
+
+
+def debug_nn_prefilter_problem(albedo_tza=None, normal_tza=None, **params):
+    """ptx_debug_nn_prefilter_problem: raises PathTracerError with what NNPrefilter(.., albedo_tza, normal_tza) or a run with these
+    params (srgb, input_scale) would refuse without a device; returns None when there is nothing."""
+    p = default_nn_prefilter_params(**params)
+    a, b = _opt_blob(albedo_tza), _opt_blob(normal_tza)
+    _check(load_library().ptx_debug_nn_prefilter_problem(a[1], a[2], b[1], b[2], C.byref(p)), "ptx_debug_nn_prefilter_problem")
+
+
+class NNPrefilter(_Owned):
+    """The prefilter of the network denoiser's guides on one device (opaque ptx_nn_prefilter; OIDN's cleanAux): a 3-input network for
+    the albedo image, one for the normal image, or both (`albedo_tza`, `normal_tza`: bytes or paths, both of one kind), for one W x H.
+    host(albedo, normal) cleans numpy images; Tracer.denoise_nn(nn, spp, prefilter=pf) cleans a tracer's guides, once per G-buffer.
+    max_memory_mb None: each network runs the frame as one tile; a number: as NN's."""
+
+    _destroy = "ptx_nn_prefilter_destroy"
+
+    def __init__(self, width, height, albedo_tza=None, normal_tza=None, device=0, max_memory_mb=None):
+        self.lib = load_library()
+        h = vp()
+        size = (int(device), int(width), int(height))
+        mb = -1 if max_memory_mb is None else int(max_memory_mb)
+        given = [t for t in (albedo_tza, normal_tza) if t is not None]
+        if given and all(isinstance(t, (str, os.PathLike)) for t in given):
+            enc = lambda t: None if t is None else os.fsencode(t)
+            _check(self.lib.ptx_nn_prefilter_create_from_files(*size, enc(albedo_tza), enc(normal_tza), mb, C.byref(h)), "ptx_nn_prefilter_create_from_files")
+        else:
+            a, b = _opt_blob(albedo_tza), _opt_blob(normal_tza)
+            _check(self.lib.ptx_nn_prefilter_create(*size, a[1], a[2], b[1], b[2], mb, C.byref(h)), "ptx_nn_prefilter_create")
+        self.h = h
+        self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
+        self.has_albedo, self.has_normal = albedo_tza is not None, normal_tza is not None
+
+    def info(self):
+        """ptx_nn_prefilter_get_info as a dict: width, height, albedo / normal (NN.info()'s dict, or None), scratch_bytes, runs"""
+        info = NNPrefilterInfo()
+        _check(self.lib.ptx_nn_prefilter_get_info(self.h, C.byref(info)), "ptx_nn_prefilter_get_info")
+        return dict(width=info.width, height=info.height, albedo=_nn_info_dict(info.albedo) if info.has_albedo else None,
+                    normal=_nn_info_dict(info.normal) if info.has_normal else None, scratch_bytes=info.scratch_bytes, runs=info.runs)
+
+    def _result(self, pair):
+        return pair[0] if not self.has_normal else pair[1] if not self.has_albedo else pair
+
+    def host(self, albedo=None, normal=None, **params):
+        """host images (H, W, 3), each given exactly when the handle has a network for it; returns the clean (H, W, 3) float32 image,
+        or the pair (albedo, normal) of a handle with both networks"""
+        n = self.width * self.height * 3
+        frames = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (albedo, normal)]
+        for a in frames:
+            if a is not None and a.size != n:
+                raise ValueError("NNPrefilter.host: an image has %d floats, the handle's size needs %d" % (a.size, n))
+        p = default_nn_prefilter_params(**params)
+        outs = [np.zeros((self.height, self.width, 3), np.float32) if has else None for has in (self.has_albedo, self.has_normal)]
+        _check(self.lib.ptx_nn_prefilter_run_host(self.h, _opt_ptr(frames[0]), _opt_ptr(frames[1]), C.byref(p), _opt_ptr(outs[0]), _opt_ptr(outs[1])),
+               "ptx_nn_prefilter_run_host")
+        return self._result(outs)
+
+    def device(self, albedo_ptr=None, normal_ptr=None, albedo_stride=3, normal_stride=3, stream=0, **params):
+        """images at device pointers with a stride of 3 or 4 floats per pixel, enqueued on `stream`; read() has the result"""
+        p = default_nn_prefilter_params(**params)
+        opt = lambda a: vp(a) if a else None
+        _check(self.lib.ptx_nn_prefilter_run_device(self.h, opt(albedo_ptr), int(albedo_stride), opt(normal_ptr), int(normal_stride), C.byref(p),
+                                                    opt(stream)), "ptx_nn_prefilter_run_device")
+
+    def read(self):
+        """the clean images of the last run, as host() returns them"""
+        outs = [np.zeros((self.height, self.width, 3), np.float32) if has else None for has in (self.has_albedo, self.has_normal)]
+        _check(self.lib.ptx_nn_prefilter_read(self.h, _opt_ptr(outs[0]), _opt_ptr(outs[1])), "ptx_nn_prefilter_read")
+        return self._result(outs)
+
+    def invalidate(self):
+        """the next Tracer.denoise_nn(.., prefilter=self) runs the networks again"""
+        _check(self.lib.ptx_nn_prefilter_invalidate(self.h), "ptx_nn_prefilter_invalidate")
+
+
+def kat_nn_transfer_aux(image, kind, srgb=0, scale=1.0, inverse=False, device=0):
+    """ptx_kat_nn_transfer_aux on an (H, W, 3) float32 image: the prefilter's input kernel (the three fp32 values per pixel before the
+    rounding to fp16) or, inverse, its output kernel on a network output; kind NN_AUX_ALBEDO or NN_AUX_NORMAL."""
+    image = np.ascontiguousarray(image, np.float32)
+    h, w = image.shape[:2]
+    out = np.zeros((h, w, 3), np.float32)
+    _check(load_library().ptx_kat_nn_transfer_aux(int(device), w, h, int(kind), _ptr(image), int(srgb), float(scale), int(bool(inverse)), _ptr(out)),
+           "ptx_kat_nn_transfer_aux")
+    return out
+
+
 def _frame_arrays(fn, rgb, albedo, normal, position, hit):
     """one (H, W) frame as the ptx_denoise_buffers* entry points take it: h, w, rgb (H, W, 3) float32, albedo (or None) / normal /
     position (H*W, 3) float32, hit (H*W) uint8"""
@@ -1061,6 +1177,24 @@ def load_library():
     L.ptx_nn_create_from_file_tiled.restype, L.ptx_nn_create_from_file_tiled.argtypes = i, [i, i, i, C.c_char_p, i, C.POINTER(vp)]
     L.ptx_nn_get_tiling.restype, L.ptx_nn_get_tiling.argtypes = i, [vp, C.POINTER(NNTiling), C.POINTER(NNTile), i]
     L.ptx_debug_nn_tiling.restype, L.ptx_debug_nn_tiling.argtypes = i, [vp, C.c_size_t, i, i, i, C.POINTER(NNTiling), C.POINTER(NNTile), i]
+    L.ptx_sizeof_nn_prefilter_params.restype = L.ptx_sizeof_nn_prefilter_info.restype = C.c_size_t
+    if L.ptx_sizeof_nn_prefilter_params() != C.sizeof(NNPrefilterParams) or L.ptx_sizeof_nn_prefilter_info() != C.sizeof(NNPrefilterInfo):
+        raise PathTracerError("%s: ptx_nn_prefilter_params / _info are %d / %d bytes in the library, %d / %d here" % (
+            LIB_PATH, L.ptx_sizeof_nn_prefilter_params(), L.ptx_sizeof_nn_prefilter_info(), C.sizeof(NNPrefilterParams), C.sizeof(NNPrefilterInfo)))
+    pfp = C.POINTER(NNPrefilterParams)
+    L.ptx_default_nn_prefilter_params.argtypes = [pfp]
+    L.ptx_nn_prefilter_create.restype, L.ptx_nn_prefilter_create.argtypes = i, [i, i, i, vp, C.c_size_t, vp, C.c_size_t, i, C.POINTER(vp)]
+    L.ptx_nn_prefilter_create_from_files.restype, L.ptx_nn_prefilter_create_from_files.argtypes = i, [i, i, i, C.c_char_p, C.c_char_p, i, C.POINTER(vp)]
+    L.ptx_nn_prefilter_destroy.restype, L.ptx_nn_prefilter_destroy.argtypes = None, [vp]
+    L.ptx_nn_prefilter_get_info.restype, L.ptx_nn_prefilter_get_info.argtypes = i, [vp, C.POINTER(NNPrefilterInfo)]
+    L.ptx_nn_prefilter_run_device.restype, L.ptx_nn_prefilter_run_device.argtypes = i, [vp, vp, i, vp, i, pfp, vp]
+    L.ptx_nn_prefilter_run_host.restype, L.ptx_nn_prefilter_run_host.argtypes = i, [vp, vp, vp, pfp, vp, vp]
+    L.ptx_nn_prefilter_device_clean.restype, L.ptx_nn_prefilter_device_clean.argtypes = i, [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.ptx_nn_prefilter_read.restype, L.ptx_nn_prefilter_read.argtypes = i, [vp, vp, vp]
+    L.ptx_nn_prefilter_invalidate.restype, L.ptx_nn_prefilter_invalidate.argtypes = i, [vp]
+    L.ptx_denoise_nn_prefiltered.restype, L.ptx_denoise_nn_prefiltered.argtypes = i, [vp, vp, vp, C.POINTER(NNParams), pfp, i]
+    L.ptx_kat_nn_transfer_aux.restype, L.ptx_kat_nn_transfer_aux.argtypes = i, [i, i, i, i, vp, i, f, i, vp]
+    L.ptx_debug_nn_prefilter_problem.restype, L.ptx_debug_nn_prefilter_problem.argtypes = i, [vp, C.c_size_t, vp, C.c_size_t, pfp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -1550,12 +1684,20 @@ class Tracer(_Owned):
                                              0 if min_batches is None else int(min_batches)), "ptx_denoise_adaptive")
         return self.read_denoised() if read else None
 
-    def denoise_nn(self, nn, spp, read=True, **params):
+    def denoise_nn(self, nn, spp, read=True, prefilter=None, prefilter_params=None, **params):
         """The network denoiser (ptx_denoise_nn) on the accumulation buffer / spp with albedo and normals from the G-buffer in the guide
         mode that is set, `nn` an NN of this tracer's size and device; params: ptx_nn_params' fields (hdr, srgb, input_scale).  Returns the
-        (H, W, 3) float32 frame (read=False: only enqueues it); the result is the tracer's denoised frame, as after denoise()."""
+        (H, W, 3) float32 frame (read=False: only enqueues it); the result is the tracer's denoised frame, as after denoise().
+        prefilter: an NNPrefilter of this size and device (ptx_denoise_nn_prefiltered): the main network gets its clean guides, which
+        are computed once per G-buffer; prefilter_params: a dict of ptx_nn_prefilter_params' fields (srgb, input_scale)."""
         p = default_nn_params(**params)
-        _check(self.lib.ptx_denoise_nn(self.h, nn.h, C.byref(p), int(spp)), "ptx_denoise_nn")
+        if prefilter is None:
+            if prefilter_params is not None:
+                raise PathTracerError("denoise_nn: prefilter_params without a prefilter")
+            _check(self.lib.ptx_denoise_nn(self.h, nn.h, C.byref(p), int(spp)), "ptx_denoise_nn")
+        else:
+            pp = default_nn_prefilter_params(**(prefilter_params or {}))
+            _check(self.lib.ptx_denoise_nn_prefiltered(self.h, nn.h, prefilter.h, C.byref(p), C.byref(pp), int(spp)), "ptx_denoise_nn_prefiltered")
         return self.read_denoised() if read else None
 
     def variance(self):

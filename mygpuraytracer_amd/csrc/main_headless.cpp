@@ -175,7 +175,7 @@ int main(int argc, char **argv) {
     ptx_moments_params mparams;
     ptx_default_moments_params(&mparams);
     ptx_denoise_params &dparams = denoiseParams();
-    std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step, nn_path;
+    std::string out_prefix, ckpt_path, resume_path, orbit_script, frame_step, nn_path, nn_albedo_path, nn_normal_path;
     int ckpt_every = 0, frames = 0, measure_every = 16, guide_samples = 0, guide_bounces = 0, nn_max_memory = 0;
     bool nn_max_memory_set = false;
     ptx_options &opt = pathtraceOptions();
@@ -206,6 +206,8 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--nn") { need(1); nn_path = argv[++i]; }
         else if (a == "--nn-hdr") nnParams().hdr = 1;
+        else if (a == "--nn-albedo") { need(1); nn_albedo_path = argv[++i]; }      // the guides prefiltered (ptx_denoise_nn_prefiltered): rt_alb / rt_nrm
+        else if (a == "--nn-normal") { need(1); nn_normal_path = argv[++i]; }
         else if (a == "--nn-max-memory") { need(1); nn_max_memory = atoi(argv[++i]); nn_max_memory_set = true; }
         else if (a == "--denoise-passes") { need(1); dparams.passes = atoi(argv[++i]); }
         else if (a == "--frames") { need(1); frames = atoi(argv[++i]); }
@@ -255,6 +257,8 @@ int main(int argc, char **argv) {
     const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of measure_every iterations, a ptx_moments_add after each
     if (!nn_path.empty() && !denoise) { fprintf(stderr, "--nn needs --denoise\n"); return 1; }
     if (nnParams().hdr && nn_path.empty()) { fprintf(stderr, "--nn-hdr needs --nn FILE\n"); return 1; }
+    if (!nn_albedo_path.empty() && nn_path.empty()) { fprintf(stderr, "--nn-albedo needs --nn FILE\n"); return 1; }
+    if (!nn_normal_path.empty() && nn_path.empty()) { fprintf(stderr, "--nn-normal needs --nn FILE\n"); return 1; }
     if (nn_max_memory_set && nn_path.empty()) { fprintf(stderr, "--nn-max-memory needs --nn FILE\n"); return 1; }
     if (nn_max_memory_set && nn_max_memory < 0) { fprintf(stderr, "--nn-max-memory needs MB >= 0 (0: no memory limit)\n"); return 1; }
     if (!nn_path.empty() && (temporal || variance || measured || frames > 0)) { fprintf(stderr, "--nn does not combine with --temporal, --variance, --measured or --frames\n"); return 1; }
@@ -400,11 +404,19 @@ int main(int argc, char **argv) {
         const int nn_device = opt.device < 0 ? 0 : opt.device;
         if (!nn_path.empty() && (nn_max_memory_set ? ptx_nn_create_from_file_tiled(nn_device, width, height, nn_path.c_str(), nn_max_memory, &nn)
                                                    : ptx_nn_create_from_file(nn_device, width, height, nn_path.c_str(), &nn)) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
-        const int rc = nn ? ptx_denoise_nn(t, nn, &nnParams(), n)
+        ptx_nn_prefilter *pf = nullptr;
+        if (nn && (!nn_albedo_path.empty() || !nn_normal_path.empty()) &&
+            ptx_nn_prefilter_create_from_files(nn_device, width, height, nn_albedo_path.empty() ? nullptr : nn_albedo_path.c_str(),
+                                               nn_normal_path.empty() ? nullptr : nn_normal_path.c_str(), nn_max_memory_set ? nn_max_memory : -1, &pf) != PTX_OK) {
+            fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1;
+        }
+        const int rc = pf ? ptx_denoise_nn_prefiltered(t, nn, pf, &nnParams(), nullptr, n)
+                     : nn ? ptx_denoise_nn(t, nn, &nnParams(), n)
                      : measured ? ptx_denoise_measured(t, pathtraceMoments(), &dparams, &varianceParams(), 0, n)
                      : variance ? ptx_denoise_variance(t, nullptr, &dparams, nullptr, &varianceParams(), n) : ptx_denoise(t, &dparams, n);
         if (rc != PTX_OK || ptx_read_denoised(t, den.data()) != PTX_OK) { fprintf(stderr, "denoise failed: %s\n", ptx_last_error()); return 1; }
         ptx_nn_destroy(nn);
+        ptx_nn_prefilter_destroy(pf);
         if (!frame_rgb8(1, width, height, den.data(), 1.0f, ss.str() + ".denoised.png", rgb8)) return 1;
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());

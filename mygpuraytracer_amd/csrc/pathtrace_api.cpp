@@ -32,6 +32,9 @@ int g_temporal_key[3] = {0, 0, 0};   // its device, width, height
 ptx_nn *g_nn = nullptr;              // GPUdenoise's network with nnWeights() set: kept like g_temporal
 int g_nn_key[4] = {0, 0, 0, 0};      // its device, width, height, nnMaxMemoryMB()
 std::string g_nn_path;               // ... and the weight file it was made from
+ptx_nn_prefilter *g_nn_pf = nullptr; // ... and the prefilter of its guides with nnAlbedoWeights() / nnNormalWeights() set, under the same key
+int g_nn_pf_key[4] = {0, 0, 0, 0};
+std::string g_nn_pf_path[2];         // ... and the weight files it was made from
 int g_device = 0;                    // the device of g_tracer
 ptx_moments *g_moments = nullptr;    // pathtrace()'s batch means with momentsBatch() > 0: created on first use
 int g_moments_key[3] = {0, 0, 0};    // its device, width, height
@@ -267,6 +270,23 @@ int &nnMaxMemoryMB() {
     return mb;
 }
 
+std::string &nnAlbedoWeights() {
+    static std::string path;
+    return path;
+}
+
+std::string &nnNormalWeights() {
+    static std::string path;
+    return path;
+}
+
+ptx_nn_prefilter_params &nnPrefilterParams() {
+    static ptx_nn_prefilter_params p;
+    static bool init = false;
+    if (!init) { ptx_default_nn_prefilter_params(&p); init = true; }
+    return p;
+}
+
 ptx_nn_params &nnParams() {
     static ptx_nn_params p;
     static bool init = false;
@@ -334,6 +354,8 @@ void GPUdenoiseRelease() {
     g_temporal = nullptr;
     ptx_nn_destroy(g_nn);
     g_nn = nullptr;
+    ptx_nn_prefilter_destroy(g_nn_pf);
+    g_nn_pf = nullptr;
     ptx_moments_destroy(g_moments);
     g_moments = nullptr;
     ptx_adaptive_destroy(g_adaptive);
@@ -525,6 +547,10 @@ void GPUdenoise(bool keep_on_device) {
     }
     apply_guide_samples("GPUdenoise", g_last_iter);
     apply_guide_bounces("GPUdenoise");
+    if (nnWeights().empty() && (!nnAlbedoWeights().empty() || !nnNormalWeights().empty())) {
+        fprintf(stderr, "GPUdenoise: nnAlbedoWeights() / nnNormalWeights() prefilter the guides of the network denoiser: they need nnWeights()\n");
+        exit(EXIT_FAILURE);
+    }
     if (!nnWeights().empty()) {
         if (denoiseTemporal() || denoiseVariance() || denoiseMeasured()) {
             fprintf(stderr, "GPUdenoise: nnWeights() does not combine with denoiseTemporal(), denoiseVariance() or denoiseMeasured()\n");
@@ -542,6 +568,19 @@ void GPUdenoise(bool keep_on_device) {
             memcpy(g_nn_key, key, sizeof key);
             g_nn_path = nnWeights();
         }
+        const bool prefilter = !nnAlbedoWeights().empty() || !nnNormalWeights().empty();
+        if (g_nn_pf && (!prefilter || memcmp(key, g_nn_pf_key, sizeof key) != 0 || g_nn_pf_path[0] != nnAlbedoWeights() || g_nn_pf_path[1] != nnNormalWeights())) {
+            ptx_nn_prefilter_destroy(g_nn_pf);
+            g_nn_pf = nullptr;
+        }
+        if (prefilter && !g_nn_pf) {
+            check(ptx_nn_prefilter_create_from_files(g_device, w, h, nnAlbedoWeights().empty() ? nullptr : nnAlbedoWeights().c_str(),
+                                                     nnNormalWeights().empty() ? nullptr : nnNormalWeights().c_str(), nnMaxMemoryMB(), &g_nn_pf), "GPUdenoise");
+            memcpy(g_nn_pf_key, key, sizeof key);
+            g_nn_pf_path[0] = nnAlbedoWeights(); g_nn_pf_path[1] = nnNormalWeights();
+        }
+        if (g_nn_pf) check(ptx_denoise_nn_prefiltered(g_tracer, g_nn, g_nn_pf, &nnParams(), &nnPrefilterParams(), g_last_iter), "GPUdenoise");
+        else
         check(ptx_denoise_nn(g_tracer, g_nn, &nnParams(), g_last_iter), "GPUdenoise");
     } else if (denoiseMeasured() && !denoiseTemporal()) {
         check(ptx_denoise_measured(g_tracer, g_moments, &denoiseParams(), &varianceParams(), 0, g_last_iter), "GPUdenoise");

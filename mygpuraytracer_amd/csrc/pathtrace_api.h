@@ -306,6 +306,13 @@ bool &denoiseMeasured();
 std::string &nnWeights();
 int &nnMaxMemoryMB();
 ptx_nn_params &nnParams();
+// The guides of that network prefiltered (ptx_denoise_nn_prefiltered; OIDN's cleanAux): nnAlbedoWeights() / nnNormalWeights() = the
+// 3-input weight files for an albedo image and a normal image (OIDN's rt_alb, rt_nrm; empty, the default = none).  With either set
+// and nnWeights() set GPUdenoise cleans that guide first, once per G-buffer, with nnPrefilterParams() (srgb, input_scale), and the
+// main network gets the clean image; nnMaxMemoryMB() applies to the prefilter's networks too.  Without nnWeights() they are refused.
+std::string &nnAlbedoWeights();
+std::string &nnNormalWeights();
+ptx_nn_prefilter_params &nnPrefilterParams();
 // Adaptive sampling by tiles (ptx_adaptive_*): adaptiveTarget() = E > 0 together with momentsBatch() = k makes pathtrace(), after every
 // k-th call, count those k iterations tile by tile (ptx_adaptive_add, in place of the plain moments add) and switch off the tiles whose
 // error is at E (ptx_adaptive_select): later calls trace the others only.  adaptiveStatus() is the last round's; adaptiveFrame() resolves

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 
 #include "../../include/mi355x_pathtracer.h"
@@ -967,8 +968,15 @@ int ptx_clear_active_tiles(ptx_tracer *t) {
     return PTX_OK;
 }
 
+// Every computation of any tracer's G-buffer has a number of its own, from 1 (ptx_tracer::gbuf_serial: what cached clean guides are of)
+static uint64_t next_gbuf_serial() {
+    static std::atomic<uint64_t> serial{0};
+    return ++serial;
+}
+
 int ptx_reset_image(ptx_tracer *t) {
     if (!t) return pt_fail(PTX_ERR_INVALID, "null tracer");
+    if (t->gbuf_serial) t->gbuf_serial = next_gbuf_serial();      // (the G-buffer stays; what was derived from it before the reset is not reused)
     PT_HC(hipSetDevice(t->device));
     PT_HC(hipMemsetAsync(t->d_image, 0, sizeof(float) * 3 * (size_t)t->cam.resx * t->cam.resy, t->stream));
     PT_HC(hipMemsetAsync(t->d_stats, 0, sizeof(int64_t) * 69, t->stream));
@@ -1182,8 +1190,9 @@ extern "C++" int pt_ensure_gbuffer(ptx_tracer *t) {
     const size_t n = (size_t)t->cam.resx * t->cam.resy;
     if (!t->d_gbuf) PT_HC(t->d_gbuf.alloc(3 * n + (n + 1) / 2));      // (+ the ids: an int2 per pixel)
     if (t->gbuf_valid) return PTX_OK;
+    t->gbuf_serial = next_gbuf_serial();
     const DScene sc = t->scene();
-    if (t->guide_bounces > 0) {                          // either mode followed through mirrors and glass (pt_guides_follow.hip): the same arrays
+    if (t->guide_bounces > 0) {                         // either mode followed through mirrors and glass (pt_guides_follow.hip): the same arrays
         const bool sampled = t->guide_count > 0;         // (the pixel-centre mode: one ray, no jitter, no lens -- k_gbuffer's ray)
         const int beff = std::max(std::min(t->guide_bounces, t->traceDepth - 1), 0);      // a path of depth d has at most d segments
         PT_HC(pt_guides_follow_enqueue(t->stream, sc, t->cam, t->traceDepth, sampled ? t->opt.antialiasing : 0, sampled ? t->opt.depth_of_field : 0,

@@ -1,7 +1,8 @@
 // pt_handle.h -- what the host units build their state from: the ptx_last_error of a failed call and the checked HIP call (of every
 // unit that calls HIP), the owned device array (DevBuf: the tracer's buffers, pt_tracer.h, and the handles'), the owned event and stream (OwnedEvent,
-// OwnedStream: the tracer's and the handles') with the timed region made of two such events, and the base of the five post-processing
-// handles (PtHandle: ptx_temporal and ptx_moments, pt_denoise.h; ptx_adaptive, pt_adaptive.h; ptx_display, pt_display.h; ptx_nn, pt_nn.h)
+// OwnedStream: the tracer's and the handles') with the timed region made of two such events, and the base of the six post-processing
+// handles (PtHandle: ptx_temporal and ptx_moments, pt_denoise.h; ptx_adaptive, pt_adaptive.h; ptx_display, pt_display.h; ptx_nn and
+// ptx_nn_prefilter, pt_nn.h)
 // with their one create and destroy path.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,7 +2,8 @@
 // 3 x 3 convolutions, run from a caller's TZA weight blob on the matrix cores.  ptx_denoise_nn is pt_post.hip's: it needs the tracer's
 // buffers and stream.  The blob and the plan are pt_tza.h's, the memory model and the tiles of a handle made under a memory limit
 // pt_nn_tiles.h's (both host only); the state's layout is in pt_nn.h; the arithmetic is defined in the public header and restated by
-// tests/unet_ref.py, the tile rule by tests/nn_tiles_ref.py.
+// tests/unet_ref.py, the tile rule by tests/nn_tiles_ref.py.  The per-tile loop (pt_nn_run_tiles) takes its two end stages from the
+// caller: k_nn_input / k_nn_output here, the prefilter's two kernels in pt_nn_aux.hip, which runs this unit's networks on its guides.
 //
 // Kernels (the unit has optimisation flags of its own, see the Makefile; -ffp-contract=off stays, the transfer functions are restated):
 //   k_nn_input  : one thread per pixel of a tile's padded window (one tile: the padded frame; the window's origin in the frame and the
@@ -36,9 +37,12 @@
 #include <vector>
 
 #include "pt_nn.h"
+#include "pt_nn_transfer.h"
 #include "pt_display.h"
 
 namespace {
+
+using namespace pt_nn_transfer;              // the transfer functions and their constants (shared with pt_nn_aux.hip)
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -46,33 +50,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 256, TILE = 16, HALO = TILE + 2, CHUNK = 32;
 constexpr int MAX_NCO = 8;
-
-// ---- transfer functions (OIDN core/color.ispc, restated) -----------------------------------------------------------------------------
-constexpr float PU_A = 1.41283765e+03f, PU_B = 1.64593172e+00f, PU_C = 4.31384981e-01f, PU_D = -2.94139609e-03f, PU_E = 1.92653254e-01f,
-                PU_F = 6.26026094e-03f, PU_G = 9.98620152e-01f, PU_Y0 = 1.57945760e-06f, PU_Y1 = 3.22087631e-02f, PU_X0 = 2.23151711e-03f,
-                PU_X1 = 3.70974749e-01f;
-constexpr float SRGB_A = 12.92f, SRGB_B = 1.055f, SRGB_C = 1.f / 2.4f, SRGB_D = -0.055f, SRGB_Y0 = 0.0031308f, SRGB_X0 = 0.04045f;
-enum { MODE_LINEAR = 0, MODE_SRGB = 1, MODE_PU = 2 };
-
-// PU(65504) in double from the fp32 constants, rounded once: the normalisation of the hdr mode and its reciprocal
-float pu_xmax() { return (float)((double)PU_E * log(65504.0 + (double)PU_F) + (double)PU_G); }
-float pu_norm() { return (float)(1.0 / (double)pu_xmax()); }
-
-__device__ __forceinline__ float sanitise(float v, float lo, float hi) { return v != v ? 0.f : fminf(fmaxf(v, lo), hi); }
-
-__device__ __forceinline__ float transfer_forward(float y, int mode, float norm) {
-    if (mode == MODE_LINEAR) return y;
-    if (mode == MODE_SRGB) return y <= SRGB_Y0 ? SRGB_A * y : SRGB_B * powf(y, SRGB_C) + SRGB_D;
-    const float x = y <= PU_Y0 ? PU_A * y : y <= PU_Y1 ? PU_B * powf(y, PU_C) + PU_D : PU_E * logf(y + PU_F) + PU_G;
-    return x * norm;
-}
-
-__device__ __forceinline__ float transfer_inverse(float x, int mode, float xmax) {
-    if (mode == MODE_LINEAR) return x;
-    if (mode == MODE_SRGB) return x <= SRGB_X0 ? x / SRGB_A : powf((x - SRGB_D) / SRGB_B, 1.f / SRGB_C);
-    x = x * xmax;
-    return x <= PU_X0 ? x / PU_A : x <= PU_X1 ? powf((x - PU_D) / PU_B, 1.f / PU_C) : expf((x - PU_G) / PU_E) - PU_F;
-}
 
 struct InputArgs {
     int w, h, wp, hp;                         // the window and its padded size
@@ -309,6 +286,7 @@ int launch_conv(hipStream_t st, const ConvArgs &a, int cout) {
 
 thread_local const PtNnPlan *tl_plan = nullptr;      // ptx_nn_create's plan, for alloc_nn (pt_handle_create hands over the handle alone)
 thread_local int tl_max_memory_mb = 0;               // ... and ptx_nn_create_tiled's limit
+thread_local uint8_t *tl_scratch = nullptr;          // ... and pt_nn_create_shared's scratch (NULL: the handle allocates its own)
 
 int alloc_nn(ptx_nn *n) {
     const PtNnPlan &plan = *tl_plan;
@@ -335,7 +313,12 @@ int alloc_nn(ptx_nn *n) {
         PT_HC(L.b.upload(b));
     }
     n->in_offset = scratch.in_offset;
-    PT_HC(n->d_scratch.alloc(scratch.total));
+    n->scratch_bytes = scratch.total;
+    if (tl_scratch) n->scratch = tl_scratch;
+    else {
+        PT_HC(n->d_scratch.alloc(scratch.total));
+        n->scratch = n->d_scratch;
+    }
     PT_HC(n->d_scale.alloc(1));
     PT_HC(n->d_scale.zero());
     PT_HC(n->ev.create(hipEventDisableTiming));
@@ -427,6 +410,41 @@ const char *pt_nn_params_problem(const ptx_nn_params &p, float samples) {
     return nullptr;
 }
 
+// the sixteen convolutions of one wp x hp tile in the handle's scratch
+static int run_layers(ptx_nn *n, hipStream_t st, int wp, int hp) {
+    uint8_t *base = n->scratch;
+    for (int i = 0; i < PT_NN_LAYERS; i++) {
+        const PtNnLayerDev &L = n->L[i];
+        auto tensor = [&](int src) { return reinterpret_cast<const uint16_t *>(base + (src == -1 ? n->in_offset : n->L[src].out_offset)); };
+        ConvArgs a;
+        a.src0 = tensor(L.src0); a.src1 = L.src1 == -2 ? nullptr : tensor(L.src1);
+        a.w = L.w; a.bias = L.b;
+        const bool last = i == PT_NN_LAYERS - 1;
+        a.out = last ? nullptr : reinterpret_cast<uint16_t *>(base + L.out_offset);
+        a.out32 = last ? reinterpret_cast<float *>(base + L.out_offset) : nullptr;
+        a.W = wp >> L.level; a.H = hp >> L.level;
+        a.c0p = L.c0p; a.c1p = L.c1p; a.coutp = L.coutp; a.nchunks = (L.c0p + L.c1p + CHUNK - 1) / CHUNK;
+        a.upsample = L.upsample; a.pool = L.pool; a.relu = L.relu;
+        if (const int rc = launch_conv(st, a, L.cout)) return rc;
+    }
+    return PTX_OK;
+}
+
+// every tile in the handle's one scratch, a smaller tile in a prefix of each tensor
+int pt_nn_run_tiles(ptx_nn *n, hipStream_t st, const PtNnStages &stages) {
+    uint8_t *base = n->scratch;
+    uint16_t *net_in = reinterpret_cast<uint16_t *>(base + n->in_offset);
+    const float *net_out = reinterpret_cast<const float *>(base + n->L[PT_NN_LAYERS - 1].out_offset);
+    for (int k = 0; k < n->tiling.count(); k++) {
+        const ptx_nn_tile T = pt_nn_tile_at(n->tiling, k);
+        const int wp = pad16(T.w), hp = pad16(T.h);
+        if (const int rc = stages.input(stages.ctx, st, T, wp, hp, net_in)) return rc;
+        if (const int rc = run_layers(n, st, wp, hp)) return rc;
+        if (const int rc = stages.output(stages.ctx, st, T, wp, net_out)) return rc;
+    }
+    return PTX_OK;
+}
+
 int pt_nn_enqueue(ptx_nn *n, hipStream_t st, const float *rgb, float samples, const float *alb, int alb_stride, const float *nrm, int nrm_stride,
                   const ptx_nn_params &p, float *out_rgb) {
     const bool automatic = isnan(p.input_scale) && p.hdr;
@@ -438,8 +456,8 @@ int pt_nn_enqueue(ptx_nn *n, hipStream_t st, const float *rgb, float samples, co
             return rc;
         }
     PT_HC(n->wait_stream(st));
-    uint8_t *base = n->d_scratch;
-    InputArgs ia;
+    struct Ends { InputArgs ia; OutputArgs oa; } e;
+    InputArgs &ia = e.ia;
     ia.W = n->w;
     ia.rgb = rgb; ia.alb = alb; ia.nrm = nrm; ia.alb_stride = alb_stride; ia.nrm_stride = nrm_stride;
     ia.samples = samples; ia.scale = isnan(p.input_scale) ? 1.f : p.input_scale;
@@ -450,39 +468,50 @@ int pt_nn_enqueue(ptx_nn *n, hipStream_t st, const float *rgb, float samples, co
     }
     ia.scale_out = n->d_scale;
     ia.mode = mode_of(p); ia.hdr = p.hdr; ia.norm = pu_norm();
-    ia.out = reinterpret_cast<uint16_t *>(base + n->in_offset);
     ia.raw = nullptr;
-    OutputArgs oa;
+    OutputArgs &oa = e.oa;
     oa.W = n->w;
-    oa.net = reinterpret_cast<const float *>(base + n->L[PT_NN_LAYERS - 1].out_offset);
     oa.scale = n->d_scale; oa.mode = mode_of(p); oa.hdr = p.hdr; oa.xmax = pu_xmax();
     oa.out = out_rgb;
-    // every tile in the handle's one scratch, a smaller tile in a prefix of each tensor; the scale is the frame's, the same for each
-    for (int k = 0; k < n->tiling.count(); k++) {
-        const ptx_nn_tile T = pt_nn_tile_at(n->tiling, k);
-        const int wp = pad16(T.w), hp = pad16(T.h);
-        ia.w = T.w; ia.h = T.h; ia.wp = wp; ia.hp = hp; ia.x0 = T.x; ia.y0 = T.y;
-        if (const int rc = launch_input(st, ia)) return rc;
-        for (int i = 0; i < PT_NN_LAYERS; i++) {
-            const PtNnLayerDev &L = n->L[i];
-            auto tensor = [&](int src) { return reinterpret_cast<const uint16_t *>(base + (src == -1 ? n->in_offset : n->L[src].out_offset)); };
-            ConvArgs a;
-            a.src0 = tensor(L.src0); a.src1 = L.src1 == -2 ? nullptr : tensor(L.src1);
-            a.w = L.w; a.bias = L.b;
-            const bool last = i == PT_NN_LAYERS - 1;
-            a.out = last ? nullptr : reinterpret_cast<uint16_t *>(base + L.out_offset);
-            a.out32 = last ? reinterpret_cast<float *>(base + L.out_offset) : nullptr;
-            a.W = wp >> L.level; a.H = hp >> L.level;
-            a.c0p = L.c0p; a.c1p = L.c1p; a.coutp = L.coutp; a.nchunks = (L.c0p + L.c1p + CHUNK - 1) / CHUNK;
-            a.upsample = L.upsample; a.pool = L.pool; a.relu = L.relu;
-            if (const int rc = launch_conv(st, a, L.cout)) return rc;
-        }
-        oa.w = T.out_w; oa.h = T.out_h; oa.wp = wp;
-        oa.ix = T.out_x - T.x; oa.iy = T.out_y - T.y; oa.ox = T.out_x; oa.oy = T.out_y;
-        if (const int rc = launch_output(st, oa)) return rc;
-    }
+    // the scale is the frame's, the same for each tile
+    PtNnStages stages;
+    stages.ctx = &e;
+    stages.input = [](void *ctx, hipStream_t s, const ptx_nn_tile &T, int wp, int hp, uint16_t *net_in) {
+        InputArgs a = static_cast<Ends *>(ctx)->ia;
+        a.w = T.w; a.h = T.h; a.wp = wp; a.hp = hp; a.x0 = T.x; a.y0 = T.y; a.out = net_in;
+        return launch_input(s, a);
+    };
+    stages.output = [](void *ctx, hipStream_t s, const ptx_nn_tile &T, int wp, const float *net_out) {
+        OutputArgs a = static_cast<Ends *>(ctx)->oa;
+        a.w = T.out_w; a.h = T.out_h; a.wp = wp; a.net = net_out;
+        a.ix = T.out_x - T.x; a.iy = T.out_y - T.y; a.ox = T.out_x; a.oy = T.out_y;
+        return launch_output(s, a);
+    };
+    if (const int rc = pt_nn_run_tiles(n, st, stages)) return rc;
     PT_HC(n->record(st));
     return PTX_OK;
+}
+
+int pt_nn_device_problem(const char *fn, int device) { return device_problem(fn, device); }
+int pt_nn_read_file(const char *fn, const char *path, std::vector<uint8_t> &blob) { return read_file(fn, path, blob); }
+
+// max_memory_mb < 0: one tile covers the frame (ptx_nn_create's rule and cap); else ptx_nn_create_tiled's
+int pt_nn_blob_problem(const char *fn, const void *tza, size_t bytes, int width, int height, int max_memory_mb, PtNnPlan &plan) {
+    if (max_memory_mb >= 0) return tiled_problem(fn, tza, bytes, width, height, max_memory_mb, plan);
+    std::string err;
+    if (!pt_nn_plan(tza, bytes, plan, err)) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": " + err);
+    if (width > PTX_NN_MAX_WIDTH || height > PTX_NN_MAX_HEIGHT)
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": bad frame size (one tile covers the frame; at most 7680 x 4320)");
+    return PTX_OK;
+}
+
+int pt_nn_create_shared(const char *fn, int device, int width, int height, const PtNnPlan &plan, int max_memory_mb, uint8_t *scratch, ptx_nn **out) {
+    const bool one = max_memory_mb < 0;
+    tl_plan = &plan; tl_max_memory_mb = one ? 0 : max_memory_mb; tl_scratch = scratch;
+    const long long cap = one ? (long long)PTX_NN_MAX_WIDTH * PTX_NN_MAX_HEIGHT : (long long)PTX_NN_MAX_FRAME * PTX_NN_MAX_FRAME;
+    const int rc = pt_handle_create(fn, "the network denoiser", device, width, height, cap, out, alloc_nn);
+    tl_plan = nullptr; tl_max_memory_mb = 0; tl_scratch = nullptr;
+    return rc;
 }
 
 extern "C" {
@@ -572,7 +601,7 @@ int ptx_debug_nn_tiling(const void *tza, size_t bytes, int width, int height, in
 
 int ptx_nn_get_tiling(ptx_nn *n, ptx_nn_tiling *tiling, ptx_nn_tile *tiles, int cap) {
     if (!n || !tiling) return pt_fail(PTX_ERR_INVALID, "ptx_nn_get_tiling: null handle or tiling");
-    fill_tiling(n->tiling, n->d_scratch.n, n->macs, tiling, tiles, cap);
+    fill_tiling(n->tiling, n->scratch_bytes, n->macs, tiling, tiles, cap);
     return PTX_OK;
 }
 
@@ -589,7 +618,7 @@ int ptx_nn_get_info(ptx_nn *n, ptx_nn_info *out) {
         out->cout[i] = n->L[i].cout;
         memcpy(out->name[i], n->names[i], sizeof out->name[i]);
     }
-    out->scratch_bytes = n->d_scratch.n;
+    out->scratch_bytes = n->scratch_bytes;
     out->macs = n->macs;
     return PTX_OK;
 }

@@ -310,6 +310,48 @@ int ptx_denoise_nn(ptx_tracer *t, ptx_nn *nn, const ptx_nn_params *params, int s
     return PTX_OK;
 }
 
+// The same with the guides prefiltered (pt_nn_aux.hip): the prefilter's networks on the G-buffer's arrays unless its clean images are
+// of this G-buffer already (the serial pt_ensure_gbuffer stamps, the params, the networks that ran), then the main network with a
+// clean image wherever pf has a network, all on the tracer's stream.
+int ptx_denoise_nn_prefiltered(ptx_tracer *t, ptx_nn *nn, ptx_nn_prefilter *pf, const ptx_nn_params *params, const ptx_nn_prefilter_params *pparams,
+                               int spp) {
+    const char *fn = "ptx_denoise_nn_prefiltered";
+    const ptx_nn_params p = params_or_default(params, ptx_default_nn_params);
+    const ptx_nn_prefilter_params pp = params_or_default(pparams, ptx_default_nn_prefilter_params);
+    if (spp < 1) return bad_spp(fn);
+    if (const char *why = pt_nn_params_problem(p, (float)spp)) return pt_fail(PTX_ERR_INVALID, why);
+    if (const char *why = pt_nn_prefilter_params_problem(pp)) return pt_fail(PTX_ERR_INVALID, why);
+    if (!t || !nn || !pf) return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": null tracer, network handle or prefilter handle");
+    if (const int rc = frame_handle_problem(fn, t, "network", *nn)) return rc;
+    if (const int rc = frame_handle_problem(fn, t, "prefilter", *pf)) return rc;
+    if (nn->ic < 6)
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the main weights take 3 input channels: there is no guide to prefilter (ptx_denoise_nn)");
+    if (nn->ic < 9 && !pf->net[0])
+        return pt_fail(PTX_ERR_INVALID, std::string(fn) + ": the main weights take colour and albedo, and the prefilter handle has no albedo network");
+    PT_HC(hipSetDevice(t->device));
+    const size_t n = (size_t)t->cam.resx * t->cam.resy;
+    if (!t->d_dn_out) PT_HC(t->d_dn_out.alloc(3 * n));
+    if (const int rc = pt_ensure_gbuffer(t)) return rc;
+    const float4 *g = t->d_gbuf;
+    const float *raw_alb = reinterpret_cast<const float *>(g + 2 * n), *raw_nrm = reinterpret_cast<const float *>(g);
+    const int mask = (pf->net[0] ? 1 : 0) | (pf->net[1] && nn->ic >= 9 ? 2 : 0);
+    const bool cached = pf->cache_serial != 0 && pf->cache_serial == t->gbuf_serial && (pf->cache_mask & mask) == mask &&
+                        memcmp(&pf->cache_params, &pp, sizeof pp) == 0;
+    if (!cached) {
+        pf->cache_serial = 0; pf->cache_mask = 0;
+        if (const int rc = pt_nn_prefilter_enqueue(pf, t->stream, mask, raw_alb, 4, raw_nrm, 4, pp)) return rc;
+        pf->cache_serial = t->gbuf_serial; pf->cache_mask = mask; pf->cache_params = pp;
+    } else {
+        PT_HC(pf->wait_stream(t->stream));                // (the clean images may have been written on another tracer's stream)
+    }
+    const bool clean_alb = (mask & 1) != 0, clean_nrm = (mask & 2) != 0;
+    const float *alb = clean_alb ? pf->d_clean[0].p : raw_alb, *nrm = nn->ic >= 9 ? (clean_nrm ? pf->d_clean[1].p : raw_nrm) : nullptr;
+    if (const int rc = pt_nn_enqueue(nn, t->stream, t->d_image, (float)spp, alb, clean_alb ? 3 : 4, nrm, clean_nrm ? 3 : 4, p, t->d_dn_out)) return rc;
+    PT_HC(pf->record(t->stream));                         // the handle's next run waits for this read of its clean images
+    t->dn_done = true;
+    return PTX_OK;
+}
+
 // ---- sample moments by batch means (pt_moments.hip; definition in include/mi355x_pathtracer.h) ---------------------------------------
 // The accumulation buffer is read on the tracer's stream, where every gather runs, those of iterations traced ahead included
 // (ahead_finish_segment): the order ptx_denoise's read of it has.

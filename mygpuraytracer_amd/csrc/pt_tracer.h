@@ -107,6 +107,7 @@ struct ptx_tracer : PlanFacts {       // (+ the sizes its launch plans depend on
     DevBuf<float4> d_gbuf, d_dn_tmp;
     DevBuf<float> d_dn_out;
     bool gbuf_valid = false, dn_done = false;            // G-buffer of the current camera / d_dn_out holds a result
+    uint64_t gbuf_serial = 0;                            // of the G-buffer's last computation, from a process-wide counter (0: none yet): what a prefilter's cached guides are of
     int guide_first = 1, guide_count = 0;                // ptx_set_guide_samples: count 0 = k_gbuffer's pixel-centre guides, else k_guides over these iterations
     int guide_bounces = 0;                               // ptx_set_guide_bounces: > 0 = k_guides_follow in either mode, the guide rays continued through mirrors and glass
     std::vector<uint8_t> h_spec;                         // per material: reflective or refractive (ptx_denoise_temporal's rule)
