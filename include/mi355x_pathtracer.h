@@ -115,13 +115,20 @@ typedef struct ptx_options {
     int32_t arith;               /* 0 = EXACT (default, and what every headline number is measured with): fp32 without contraction,
                                     IEEE division and square root, own correctly rounded sin/cos -- bit-identical to the CPU
                                     oracle.  1 = CONTRACTED: the same kernels compiled as a second code object with fused
-                                    multiply-adds and the hardware's reciprocal / square-root / sine instructions, i.e. the kind
-                                    of arithmetic the reference's real build runs (nvcc contracts by default); results agree with
-                                    EXACT within the statistical fp32 tolerance of DESIGN.md section 3 (tests/test_fp_tolerance.py),
-                                    not bit for bit.  PTX_ERR_UNSUPPORTED if the library was built without that code object.  */
+                                    multiply-adds wherever the expression tree allows (what nvcc's default --fmad=true does to
+                                    the reference's kernels); division and square root stay IEEE, sine and cosine are an fp32
+                                    routine of about one ulp.  2 = FAST: level 1 as a third code object with the hardware's
+                                    approximate reciprocal / square root / reciprocal square root (one ulp each, a quotient
+                                    a * rcp(b) about 2.5 ulp) and its sine / cosine / exp2 / log2 instructions.  Levels 1 and 2
+                                    agree with EXACT within the statistical fp32 tolerance of DESIGN.md section 3
+                                    (tests/test_fp_tolerance.py) and, stage by stage, stay within 2 x / 8 x EXACT's own distance
+                                    from a float64 reference (tests/test_gpu_arith_f64.py) -- never bit for bit.  ptx_create
+                                    returns PTX_ERR_UNSUPPORTED for a level whose code object the library was built without
+                                    (it never falls back to another level) and PTX_ERR_INVALID for a value outside 0 .. 2.  */
 } ptx_options;
 #define PTX_ARITH_EXACT 0
 #define PTX_ARITH_CONTRACTED 1
+#define PTX_ARITH_FAST 2
 
 typedef struct ptx_stats {
     int32_t bounces;                 /* bounce-loop passes of the last iteration                       */

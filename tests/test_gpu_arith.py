@@ -21,6 +21,17 @@ per stage on identical inputs:
                              within 1e-5 absolute (measured 3e-7),
                              colour within 8 ulp
   sin / cos                  2 ulp of 1 (measured 1)                      1e-5 absolute (v_sin_f32 / v_cos_f32: measured 5e-7)
+
+The bounds above are distances to level 0, set from what was measured.  The rule against the truth stands beside them in
+tests/test_gpu_arith_f64.py, on ray families built for the purpose (tests/arithcases.py):
+
+  the three intersection     on the rays where a float64 reference of the     the same with m = 8 (one ulp for the hardware's
+  tests against float64      same operation (tests/isect_f64.py), level 0     seeds and 2.5 ulp for a * rcp(b) against half an
+                             and this level report the same hit: rms and      ulp: 5, with margin)
+                             99th percentile of |level - reference| in t,
+                             point and normal <= 2 x max(level 0's, 1 u)
+                             (contraction only removes roundings);
+                             decisions as the reference's wherever level 0's are, elsewhere at most 2 x level 0's exceptions + 4
 """
 import os
 
