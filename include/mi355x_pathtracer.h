@@ -909,6 +909,59 @@ int  ptx_kat_nn_transfer_aux(int device, int w, int h, int kind, const float *in
 int  ptx_debug_nn_prefilter_problem(const void *alb_tza, size_t alb_bytes, const void *nrm_tza, size_t nrm_bytes,
                                     const ptx_nn_prefilter_params *p);
 
+/* ---- network denoiser: images (formats, strides, in place), csrc/pt_nn_image.hip ---------------------------------------------------------
+ * ptx_nn_denoise_* take W*H*3 packed floats.  A renderer's framebuffer is float4 or half4, often with a row pitch, and wants the
+ * result where the colour was.  These entry points run the same networks on images described as OIDN's setImage describes them
+ * (core/image.h: a format, a byte offset, a byte pixel stride, a byte row stride); additive, like everything in this section.
+ * Definition (tests/nn_image_ref.py restates it):
+ *   Image: ptr NULL = no such image.  size = 4 (PTX_NN_FORMAT_FLOAT3) or 2 (PTX_NN_FORMAT_HALF3) bytes per channel; a pixel_stride of
+ *     0 means 3 * size, a row_stride of 0 means width * pixel_stride.  Channel c (0 .. 2) of pixel (x, y) is the `size` bytes at
+ *     ptr + byte_offset + y * row_stride + x * pixel_stride + c * size, all of it size_t arithmetic.  No other byte is written, and
+ *     none is read but by the 16- / 8-byte load of a 16- / 8-byte aligned float / half image with a pixel stride of 16 / 8 bytes, which
+ *     takes the pixel's fourth channel along and drops it.
+ *   Refused (PTX_ERR_INVALID; ptx_last_error names the image and the rule), OIDN's checks: an unknown format; a pixel stride below the
+ *     pixel's size; a row stride below width * pixel_stride; a row stride that is no multiple of the pixel stride.  Ours, not OIDN's --
+ *     the device needs aligned channels: ptr + byte_offset, the pixel stride or the row stride no multiple of the channel size.
+ *   Formats: the inputs are all Float3 or all Half3 (UNetFilter::init); the output may be either.
+ *   Half in: widened exactly to fp32; every step after that is the packed path's.  Half out: fp16_rne(v > 65504 ? 65504 : v) of the fp32
+ *     value v the packed path would store (numpy: np.minimum(v, 65504).astype(np.float16)): +inf is never written, subnormals are kept.
+ *   Role, of a 3-input network's one image: PTX_NN_ROLE_COLOR is ptx_nn_denoise_device's arithmetic, whatever the input count.
+ *     PTX_NN_ROLE_ALBEDO / _NORMAL are the prefilter's "Albedo in / out" / "Normal in / out", above: no meter, scale = input_scale or
+ *     1; refused on a blob of 6 or 9 inputs, with hdr != 0, with samples != 1, and NORMAL with srgb != 0.
+ *   Automatic hdr scale: the block meter on the fp32 values of the colour image (halves widened).  A packed Float3 colour is metered
+ *     where it lies; any other layout is first gathered into a W*H*3 float buffer the handle owns (first need).
+ *   In place: an image's byte interval is [first channel byte of (0, 0), last channel byte of (W - 1, H - 1) + 1).  Where the
+ *     output's interval meets no input's, or the handle has one tile, every tile's result goes straight to the output (one tile: each
+ *     read of the input stage precedes each write of the output stage on the stream).  Where it meets one and the handle has more
+ *     than one tile, the tiles' results go to a W*H*3 fp32 temporary the handle owns -- allocated on first need beside the activation
+ *     scratch and outside max_memory_mb -- and a copy kernel writes it through the output's descriptor after the last tile, the half
+ *     conversion there.  All three ways give the same bits. */
+#define PTX_NN_FORMAT_FLOAT3 1
+#define PTX_NN_FORMAT_HALF3 2
+#define PTX_NN_ROLE_COLOR 0
+#define PTX_NN_ROLE_ALBEDO 1
+#define PTX_NN_ROLE_NORMAL 2
+typedef struct ptx_nn_image {
+    const void *ptr;           /* NULL: no such image */
+    int    format;             /* PTX_NN_FORMAT_FLOAT3 = 1, PTX_NN_FORMAT_HALF3 = 2 */
+    size_t byte_offset;        /* of pixel (0,0) from ptr */
+    size_t pixel_stride;       /* bytes; 0 = the pixel's size (12 / 6) */
+    size_t row_stride;         /* bytes; 0 = width * pixel_stride */
+} ptx_nn_image;
+size_t ptx_sizeof_nn_image(void);
+/* One denoise on `stream` (NULL = the default stream) of images on the handle's device.  albedo / normal (NULL, or ptr NULL: none) are
+ * required exactly when the blob takes 6 / 9 inputs; output is written (its ptr is not const to the callee).  p NULL = defaults. */
+int  ptx_nn_denoise_images_device(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
+                                  const ptx_nn_image *output, float samples, int role, const ptx_nn_params *p, void *stream);
+/* The same on host images, through staging buffers the handle owns; waits.  Each image's byte interval is staged: the inputs up, the
+ * output's interval up and back, so the bytes between its pixels come back unchanged.  Images whose intervals meet in the caller's
+ * memory meet the same way on the device.  What needs no device is refused before any device call: the params, the role's rules, the
+ * formats, then -- with a handle -- the images it needs and each descriptor. */
+int  ptx_nn_denoise_images_host(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
+                                const ptx_nn_image *output, float samples, int role, const ptx_nn_params *p);
+/* Host only: what a call would refuse of this descriptor for a width x height frame (is_output: it is named "output") */
+int  ptx_debug_nn_image_problem(int width, int height, const ptx_nn_image *img, int is_output);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
  *      reprojection alone and needs no tracer ------------------------------------------------------------------- */

@@ -559,6 +559,42 @@ def debug_nn_tiling(tza, width, height, max_memory_mb=0, tiles=True):
                            "ptx_debug_nn_tiling", tiles)
 
 
+NN_FORMAT_FLOAT3, NN_FORMAT_HALF3 = 1, 2
+NN_ROLES = {"color": 0, "albedo": 1, "normal": 2}
+
+
+class NNImage(C.Structure):
+    """ptx_nn_image (include/mi355x_pathtracer.h, "images"): ptr, format, and in bytes the offset of pixel (0, 0), the pixel stride
+    (0: packed, 12 / 6) and the row stride (0: width * pixel stride).  `keep` holds the array a descriptor was made from."""
+    _fields_ = [("ptr", vp), ("format", C.c_int), ("byte_offset", C.c_size_t), ("pixel_stride", C.c_size_t), ("row_stride", C.c_size_t)]
+    keep = None
+
+
+def nn_image_of(array_or_ptr, format=None, byte_offset=0, pixel_stride=0, row_stride=0):
+    """An NNImage of a numpy float32 / float16 array view of shape (H, W, >= 3) -- the pointer, offset and strides are the view's own,
+    which may be a slice of a float4 / half4 buffer or of padded rows -- or of a raw pointer (an integer; `format` NN_FORMAT_FLOAT3 or
+    NN_FORMAT_HALF3, the offset and strides in bytes as given)."""
+    if isinstance(array_or_ptr, np.ndarray):
+        a = array_or_ptr
+        if a.dtype not in (np.float32, np.float16) or a.ndim != 3 or a.shape[2] < 3:
+            raise PathTracerError("nn_image_of: an image is a float32 or float16 array of shape (H, W, >= 3)")
+        if a.strides[2] != a.itemsize or a.strides[0] <= 0 or a.strides[1] <= 0:
+            raise PathTracerError("nn_image_of: a pixel's channels must be consecutive and the strides positive")
+        img = NNImage(vp(a.ctypes.data), NN_FORMAT_FLOAT3 if a.dtype == np.float32 else NN_FORMAT_HALF3, 0, a.strides[1], a.strides[0])
+        img.keep = a
+        return img
+    if format not in (NN_FORMAT_FLOAT3, NN_FORMAT_HALF3):
+        raise PathTracerError("nn_image_of: a pointer needs format=NN_FORMAT_FLOAT3 or NN_FORMAT_HALF3")
+    return NNImage(vp(int(array_or_ptr)), int(format), int(byte_offset), int(pixel_stride), int(row_stride))
+
+
+def debug_nn_image_problem(width, height, image, is_output=False):
+    """ptx_debug_nn_image_problem: raises PathTracerError with what a call would refuse of this image (an NNImage, or an array for
+    nn_image_of) for a width x height frame; returns None when there is nothing.  No device needed."""
+    img = image if isinstance(image, NNImage) else nn_image_of(image)
+    _check(load_library().ptx_debug_nn_image_problem(int(width), int(height), C.byref(img), int(bool(is_output))), "ptx_debug_nn_image_problem")
+
+
 class NN(_Owned):
     """The network denoiser on one device (opaque ptx_nn): Open Image Denoise's RT filter run from the caller's TZA weights (`tza`:
     bytes, or a path) for one W x H.  host(rgb, albedo, normal) denoises a numpy frame, device(...) a frame on the device,
@@ -615,6 +651,32 @@ class NN(_Owned):
         _check(self.lib.ptx_nn_denoise_host(self.h, _ptr(frames[0]), float(samples), _opt_ptr(frames[1]), _opt_ptr(frames[2]), C.byref(p), _ptr(out)),
                "ptx_nn_denoise_host")
         return out
+
+    def _images(self, color, output, albedo, normal, role):
+        if role not in NN_ROLES:
+            raise PathTracerError("NN: role must be one of %s" % ", ".join(map(repr, NN_ROLES)))
+        descs = [a if a is None or isinstance(a, NNImage) else nn_image_of(a) for a in (color, albedo, normal, output)]
+        return descs, [None if d is None else C.byref(d) for d in descs]
+
+    def images_device(self, color, output, albedo=None, normal=None, samples=1, role="color", stream=0, **params):
+        """ptx_nn_denoise_images_device: images on the device as NNImage descriptors (nn_image_of(ptr, format=..)), enqueued on `stream`
+        (a hipStream_t as an integer).  role "albedo" / "normal": a 3-input network's image is that guide, as the prefilter takes it."""
+        p = default_nn_params(**params)
+        _, refs = self._images(color, output, albedo, normal, role)
+        _check(self.lib.ptx_nn_denoise_images_device(self.h, refs[0], refs[1], refs[2], refs[3], float(samples), NN_ROLES[role], C.byref(p),
+                                                     vp(stream) if stream else None), "ptx_nn_denoise_images_device")
+
+    def images_host(self, color, output, albedo=None, normal=None, samples=1, role="color", **params):
+        """ptx_nn_denoise_images_host: numpy float32 / float16 views of shape (H, W, >= 3) with any positive strides (or NNImage
+        descriptors of host memory); writes the three channels of every pixel of `output` in place and nothing else.  `output` may be,
+        or overlap, an input."""
+        p = default_nn_params(**params)
+        if isinstance(output, np.ndarray) and not output.flags.writeable:
+            raise PathTracerError("NN.images_host: the output array is not writeable")
+        keep, refs = self._images(color, output, albedo, normal, role)
+        _check(self.lib.ptx_nn_denoise_images_host(self.h, refs[0], refs[1], refs[2], refs[3], float(samples), NN_ROLES[role], C.byref(p)),
+               "ptx_nn_denoise_images_host")
+        del keep
 
     def scale(self):
         """the scale the last denoise's input kernel used (the metered exposure in hdr mode with an automatic scale)"""
@@ -1195,6 +1257,13 @@ def load_library():
     L.ptx_denoise_nn_prefiltered.restype, L.ptx_denoise_nn_prefiltered.argtypes = i, [vp, vp, vp, C.POINTER(NNParams), pfp, i]
     L.ptx_kat_nn_transfer_aux.restype, L.ptx_kat_nn_transfer_aux.argtypes = i, [i, i, i, i, vp, i, f, i, vp]
     L.ptx_debug_nn_prefilter_problem.restype, L.ptx_debug_nn_prefilter_problem.argtypes = i, [vp, C.c_size_t, vp, C.c_size_t, pfp]
+    L.ptx_sizeof_nn_image.restype = C.c_size_t
+    if L.ptx_sizeof_nn_image() != C.sizeof(NNImage):
+        raise PathTracerError("%s: ptx_nn_image is %d bytes in the library, %d here" % (LIB_PATH, L.ptx_sizeof_nn_image(), C.sizeof(NNImage)))
+    imp = C.POINTER(NNImage)
+    L.ptx_nn_denoise_images_device.restype, L.ptx_nn_denoise_images_device.argtypes = i, [vp, imp, imp, imp, imp, f, i, C.POINTER(NNParams), vp]
+    L.ptx_nn_denoise_images_host.restype, L.ptx_nn_denoise_images_host.argtypes = i, [vp, imp, imp, imp, imp, f, i, C.POINTER(NNParams)]
+    L.ptx_debug_nn_image_problem.restype, L.ptx_debug_nn_image_problem.argtypes = i, [i, i, imp, i]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]

@@ -46,6 +46,10 @@ struct ptx_nn : PtHandle {
     DevBuf<float> d_scale;
     ptx_display *meter = nullptr;
     DevBuf<float> d_stage[4];                     // ptx_nn_denoise_host's rgb, albedo, normal, result (first use)
+    // the image entry points' (pt_nn_image.hip), each on first need: the colour gathered for the meter and the in-place temporary,
+    // W*H*3 floats each; ptx_nn_denoise_images_host's colour, albedo, normal and output (with the inputs that meet it), in bytes
+    DevBuf<float> d_image_gather, d_image_tmp;
+    DevBuf<uint8_t> d_image_stage[4];
     ~ptx_nn();
 };
 

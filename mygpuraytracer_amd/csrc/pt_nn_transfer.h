@@ -1,7 +1,7 @@
 // pt_nn_transfer.h -- the network denoiser's transfer functions and their constants (OIDN core/color.ispc, restated; the definition is in
-// include/mi355x_pathtracer.h), for the two units whose kernels stand at the network's ends: pt_nn.hip (colour, with its guides as they
-// are) and pt_nn_aux.hip (an albedo or a normal image alone).  Every step is one IEEE fp32 operation under -ffp-contract=off, which both
-// units keep.  Not part of the C ABI.
+// include/mi355x_pathtracer.h), for the units whose kernels stand at the network's ends: pt_nn.hip (colour, with its guides as they
+// are), pt_nn_aux.hip (an albedo or a normal image alone) and pt_nn_image.hip (either, on described images).  Every step is one IEEE
+// fp32 operation under -ffp-contract=off, which all of them keep.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
