@@ -962,6 +962,54 @@ int  ptx_nn_denoise_images_host(ptx_nn *n, const ptx_nn_image *color, const ptx_
 /* Host only: what a call would refuse of this descriptor for a width x height frame (is_output: it is named "output") */
 int  ptx_debug_nn_image_problem(int width, int height, const ptx_nn_image *img, int is_output);
 
+/* ---- network denoiser: the lightmap filter (OIDN's RTLightmap), csrc/pt_nn_lightmap.hip ----------------------------------------------------
+ * OIDN's rtlightmap_hdr.tza and rtlightmap_dir.tza are the RT filter's U-Net with three inputs, so a lightmap network is a ptx_nn made
+ * from such a blob: handle, tiles, scratch and convolutions are the ones above, and two kernels of this unit stand at the network's
+ * ends.  Additive.  Images are ptx_nn_image descriptors under every rule of the section above: the refusals, the staging of host
+ * images, half in and out, in place (with the temporary and the copy-out where the handle has more than one tile).
+ * Definition (core/input_reorder.ispc, output_reorder.ispc, color.ispc restated; every step one IEEE fp32 operation; tests/nn_lightmap_ref.py
+ * restates it), per channel:
+ *   directional == 0, HDR: OIDN's Log transfer with hdr.  xmax = (float)log(65505.0) = 0x1.62e050p+3, norm = (float)(1.0 / (double)xmax)
+ *     = 0x1.71587ep-4, both formed in double on the host and rounded once.
+ *       in : v = in * scale; NaN -> 0; clamp to [0, FLT_MAX]; x = logf(v + 1.f) * norm
+ *       out: NaN -> 0; clamp to [0, FLT_MAX]; y = expf(x * xmax) - 1.f; y * (1 / scale), or 0 for scale 0
+ *     logf and expf are the correctly rounded functions (formed in double, rounded once): expf(a) - 1.f near 0 turns an ulp of expf
+ *     into 2^-23 absolute, and only the correctly rounded value keeps the result within 2^-24 / scale of the exact one.
+ *     scale: input_scale where it is set; with NaN the display unit's block meter at key 0.18 on the fp32 colour, exactly as
+ *     ptx_nn_denoise_images_* meters an hdr frame (a layout that is not packed Float3 is gathered first).
+ *   directional == 1: OIDN's Linear transfer with snorm, not hdr -- PTX_NN_ROLE_NORMAL's arithmetic to the bit:
+ *       in : v = in * scale; NaN -> 0; clamp to [-1, 1]; v * 0.5f + 0.5f
+ *       out: NaN -> 0; clamp to [0, FLT_MAX]; * 2 - 1; max(., -1); min(., 1); * (1 / scale)
+ *     scale: input_scale, or 1 for NaN.
+ *   Refused (PTX_ERR_INVALID), without a device: directional other than 0 or 1; an input_scale that is neither NaN nor finite and > 0;
+ *   an unknown format; then, with a handle: a blob of 6 or 9 inputs; what ptx_nn_denoise_images_* refuses of a descriptor. */
+int  ptx_nn_denoise_lightmap_device(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *output, int directional, float input_scale,
+                                    void *stream);
+int  ptx_nn_denoise_lightmap_host(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *output, int directional, float input_scale);
+/* Host only: the HDR mode's two constants as the kernels get them */
+void ptx_debug_nn_lightmap_constants(float *xmax, float *norm);
+
+/* ---- network denoiser: progress and cancellation, csrc/pt_nn_progress.h --------------------------------------------------------------------
+ * A monitor on a handle hears how far a denoise has come and may cancel it.  fn NULL: none (the default).
+ * With no monitor every call enqueues exactly what it enqueued before this section existed and waits where it waited.
+ * With a monitor, every ptx_nn_denoise_*, ptx_nn_denoise_images_* and ptx_nn_denoise_lightmap_* call on the handle RUNS TO COMPLETION
+ * BEFORE IT RETURNS, the _device forms included, and reports:
+ *   fn(user, 0.0) before any device work of the call is enqueued;
+ *   then fn(user, n) after every unit of work has finished on the device (an owned event recorded behind each is waited for): per
+ *   tile its input stage, each of its sixteen layers and its output stage, and the in-place copy-out where one runs.  n = finished
+ *   units / all units: it never decreases, and it is exactly 1.0 on the last report, which comes after the result is complete on the
+ *   device.  A frame of one tile reports 18 times after the first.  The host enqueues at most one tile beyond the tile whose reports
+ *   it is delivering.
+ * Cancel: when fn returns 0 nothing further is enqueued, the call waits for what is in flight and returns PTX_ERR_CANCELLED -- also
+ *   on the last report (n == 1), as OIDN's Progress::update has it.  The handle stays usable; a later call gives the right bits.  A
+ *   _host form has then not written the caller's output memory at all; after a _device form only bytes of the output's three
+ *   channels may have been written.
+ * The monitor is called on the calling thread and must not call into the same handle (ptx_nn_set_progress from it is refused).
+ * ptx_nn_prefilter_* and ptx_denoise_nn* on a tracer ignore the monitor. */
+#define PTX_ERR_CANCELLED 6    /* the progress monitor returned 0 */
+typedef int (*ptx_nn_progress_fn)(void *user, double n);   /* 0 = cancel */
+int  ptx_nn_set_progress(ptx_nn *n, ptx_nn_progress_fn fn, void *user);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
  *      reprojection alone and needs no tracer ------------------------------------------------------------------- */

@@ -11,6 +11,7 @@ tracer without the built library or without a HIP device raises.
 from .api import (  # noqa: F401
     LIB_PATH,
     PathTracerError,
+    Cancelled,
     Options,
     DenoiseParams,
     TemporalParams,
@@ -68,6 +69,6 @@ from .api import (  # noqa: F401
     load_library,
 )
 
-__all__ = ["LIB_PATH", "PathTracerError", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "NNParams", "NNInfo", "NN", "default_nn_params", "nn_denoise_buffers", "debug_tza_list", "debug_nn_plan", "kat_nn_conv", "kat_nn_transfer", "NNPrefilter", "NNPrefilterParams", "NNPrefilterInfo", "NN_AUX_ALBEDO", "NN_AUX_NORMAL", "default_nn_prefilter_params", "debug_nn_prefilter_problem", "kat_nn_transfer_aux", "NNImage", "NN_FORMAT_FLOAT3", "NN_FORMAT_HALF3", "nn_image_of", "debug_nn_image_problem", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
+__all__ = ["LIB_PATH", "PathTracerError", "Cancelled", "Options", "DenoiseParams", "TemporalParams", "VarianceParams", "MomentsParams", "MomentsSummary", "AdaptiveParams", "AdaptiveStatus", "Adaptive", "DisplayParams", "DisplayStatus", "Display", "default_display_params", "NNParams", "NNInfo", "NN", "default_nn_params", "nn_denoise_buffers", "debug_tza_list", "debug_nn_plan", "kat_nn_conv", "kat_nn_transfer", "NNPrefilter", "NNPrefilterParams", "NNPrefilterInfo", "NN_AUX_ALBEDO", "NN_AUX_NORMAL", "default_nn_prefilter_params", "debug_nn_prefilter_problem", "kat_nn_transfer_aux", "NNImage", "NN_FORMAT_FLOAT3", "NN_FORMAT_HALF3", "nn_image_of", "debug_nn_image_problem", "Scene", "Tracer", "Temporal", "Moments", "MultiTracer",
            "StreamCompaction", "build_library", "default_denoise_params", "default_temporal_params", "default_variance_params", "default_moments_params", "default_adaptive_params", "tile_pixels", "denoise_buffers",
            "denoise_buffers_variance", "reproject_buffers", "load_library"]

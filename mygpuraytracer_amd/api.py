@@ -41,6 +41,14 @@ class PathTracerError(RuntimeError):
     pass
 
 
+class Cancelled(PathTracerError):
+    """PTX_ERR_CANCELLED: a network denoiser's progress monitor (NN.set_progress) returned a falsy value"""
+
+
+PTX_ERR_CANCELLED = 6
+NN_PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double)      # ptx_nn_progress_fn
+
+
 class Material(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("specular_exponent", C.c_float), ("specular_color", C.c_float * 3),
                 ("hasReflective", C.c_float), ("hasRefractive", C.c_float), ("indexOfRefraction", C.c_float),
@@ -678,6 +686,43 @@ class NN(_Owned):
                "ptx_nn_denoise_images_host")
         del keep
 
+    def _lightmap(self, color, output):
+        descs = [a if isinstance(a, NNImage) else nn_image_of(a) for a in (color, output)]
+        return descs, [C.byref(d) for d in descs]
+
+    def lightmap_device(self, color, output, directional=False, input_scale=float("nan"), stream=0):
+        """ptx_nn_denoise_lightmap_device: OIDN's RTLightmap filter on a 3-input network, images on the device as NNImage descriptors
+        (nn_image_of(ptr, format=..)), enqueued on `stream`.  directional False: the HDR lightmap (input_scale NaN: metered); True: the
+        directional one (NaN: 1)."""
+        _, refs = self._lightmap(color, output)
+        _check(self.lib.ptx_nn_denoise_lightmap_device(self.h, refs[0], refs[1], int(directional), float(input_scale), vp(stream) if stream else None),
+               "ptx_nn_denoise_lightmap_device")
+
+    def lightmap_host(self, color, output, directional=False, input_scale=float("nan")):
+        """ptx_nn_denoise_lightmap_host: numpy float32 / float16 views of shape (H, W, >= 3), as images_host takes them; writes the
+        three channels of every pixel of `output` and nothing else.  `output` may be, or overlap, `color`."""
+        if isinstance(output, np.ndarray) and not output.flags.writeable:
+            raise PathTracerError("NN.lightmap_host: the output array is not writeable")
+        keep, refs = self._lightmap(color, output)
+        _check(self.lib.ptx_nn_denoise_lightmap_host(self.h, refs[0], refs[1], int(directional), float(input_scale)), "ptx_nn_denoise_lightmap_host")
+        del keep
+
+    def set_progress(self, monitor):
+        """ptx_nn_set_progress: `monitor(n)` hears 0, then the finished share of the work after every stage of every tile, last exactly
+        1; a falsy return value cancels the call, which raises Cancelled.  None: no monitor.  With a monitor every denoise on the
+        handle returns only after it has completed."""
+        if monitor is None:
+            self._progress = None
+            _check(self.lib.ptx_nn_set_progress(self.h, NN_PROGRESS_FN(), None), "ptx_nn_set_progress")
+            return
+
+        def call(_user, n):
+            return 1 if monitor(n) else 0
+
+        fn = NN_PROGRESS_FN(call)
+        _check(self.lib.ptx_nn_set_progress(self.h, fn, None), "ptx_nn_set_progress")
+        self._progress = fn                      # kept alive while the handle may call it
+
     def scale(self):
         """the scale the last denoise's input kernel used (the metered exposure in hdr mode with an automatic scale)"""
         s = C.c_float()
@@ -1264,6 +1309,10 @@ def load_library():
     L.ptx_nn_denoise_images_device.restype, L.ptx_nn_denoise_images_device.argtypes = i, [vp, imp, imp, imp, imp, f, i, C.POINTER(NNParams), vp]
     L.ptx_nn_denoise_images_host.restype, L.ptx_nn_denoise_images_host.argtypes = i, [vp, imp, imp, imp, imp, f, i, C.POINTER(NNParams)]
     L.ptx_debug_nn_image_problem.restype, L.ptx_debug_nn_image_problem.argtypes = i, [i, i, imp, i]
+    L.ptx_nn_denoise_lightmap_device.restype, L.ptx_nn_denoise_lightmap_device.argtypes = i, [vp, imp, imp, i, f, vp]
+    L.ptx_nn_denoise_lightmap_host.restype, L.ptx_nn_denoise_lightmap_host.argtypes = i, [vp, imp, imp, i, f]
+    L.ptx_debug_nn_lightmap_constants.restype, L.ptx_debug_nn_lightmap_constants.argtypes = None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.ptx_nn_set_progress.restype, L.ptx_nn_set_progress.argtypes = i, [vp, NN_PROGRESS_FN, vp]
     L.ptx_get_stats.restype, L.ptx_get_stats.argtypes = i, [vp, C.POINTER(Stats)]
     L.ptx_get_stats_sized.restype, L.ptx_get_stats_sized.argtypes = i, [vp, vp, C.c_size_t]
     L.ptx_owned_pixels.restype, L.ptx_owned_pixels.argtypes = i, [vp]
@@ -1348,6 +1397,8 @@ def load_library():
 
 
 def _check(rc, what):
+    if rc == PTX_ERR_CANCELLED:
+        raise Cancelled("%s was cancelled (code %d): %s" % (what, rc, load_library().ptx_last_error().decode()))
     if rc != PTX_OK:
         raise PathTracerError("%s failed (code %d): %s" % (what, rc, load_library().ptx_last_error().decode()))
 

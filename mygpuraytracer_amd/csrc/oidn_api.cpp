@@ -47,6 +47,7 @@ Failure ptx_failure(int rc, const char *during) {
     if (rc == PTX_ERR_NODEVICE) return {Error::UnsupportedHardware, msg};
     if (rc == PTX_ERR_IO) return {Error::InvalidOperation, msg};
     if (rc == PTX_ERR_INVALID) return {Error::InvalidArgument, msg};
+    if (rc == PTX_ERR_CANCELLED) return {Error::Cancelled, "execution was cancelled"};
     if (rc == PTX_ERR_HIP && msg.find("out of memory") != std::string::npos) return {Error::OutOfMemory, msg};
     return {Error::Unknown, msg};
 }
@@ -54,6 +55,7 @@ Failure ptx_failure(int rc, const char *during) {
 struct ImageParam {
     bool set = false;
     void *ptr = nullptr;
+    detail::Ref<detail::Buffer> buffer;      // of an image set from a buffer: kept alive with the image
     Format format = Format::Undefined;
     size_t width = 0, height = 0, offset = 0, pixel_stride = 0, row_stride = 0;
 };
@@ -75,8 +77,21 @@ struct Device {
     ErrorState error;
     ErrorFunction fn = nullptr;
     void *user = nullptr;
-    bool committed = false, images_on_device = false;
+    bool committed = false, images_on_device = false, lightmap = false;
     int ordinal = 0;
+    int num_threads = 0, set_affinity = 1, verbose = 0;      // OIDN's CPU device's: kept and read back, no effect
+};
+
+struct Buffer {
+    std::atomic<int> refs{1};
+    Device *device = nullptr;       // retained
+    void *ptr = nullptr;
+    size_t size = 0;
+    bool owned = false;
+    ~Buffer() {
+        if (owned) free(ptr);
+        if (device) release(device);
+    }
 };
 
 struct Filter {
@@ -86,6 +101,10 @@ struct Filter {
     void *user_weights = nullptr;
     size_t user_weights_size = 0;
     unsigned long long weights_version = 0;
+    bool lightmap = false, directional = false;      // the RTLightmap filter; its one bool
+    ProgressMonitorFunction progress = nullptr;
+    void *progress_user = nullptr;
+    bool empty = false;                              // committed with images of size 0: no network, execute does nothing
     bool hdr = false, srgb = false, clean_aux = false;
     int max_memory_mb = 3000;
     float input_scale = NAN;
@@ -116,11 +135,14 @@ void retain(Device *d) { d->refs.fetch_add(1, std::memory_order_relaxed); }
 void release(Device *d) { if (d->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete d; }
 void retain(Filter *f) { f->refs.fetch_add(1, std::memory_order_relaxed); }
 void release(Filter *f) { if (f->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete f; }
+void retain(Buffer *b) { b->refs.fetch_add(1, std::memory_order_relaxed); }
+void release(Buffer *b) { if (b->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete b; }
 
 }  // namespace detail
 
 namespace {
 
+using detail::Buffer;
 using detail::Device;
 using detail::Filter;
 
@@ -185,8 +207,10 @@ void commit_filter(Filter *f) {
         std::lock_guard<std::mutex> lock(d->mutex);
         committed = d->committed; ordinal = d->ordinal;
     }
-    if (!committed) throw Failure{Error::InvalidOperation, "the device is not committed"};
     const ImageParam *im = f->image;
+    // images of size 0 need no device: every other check is made, no network is built
+    const bool empty = im[3].set && (im[3].width == 0 || im[3].height == 0);
+    if (!committed && !empty) throw Failure{Error::InvalidOperation, "the device is not committed"};
     // unet.cpp:250-278
     if (!im[0].set && !im[1].set && !im[2].set) throw Failure{Error::InvalidOperation, "input image not specified"};
     if (!im[3].set) throw Failure{Error::InvalidOperation, "output image not specified"};
@@ -204,7 +228,8 @@ void commit_filter(Filter *f) {
     // unet.cpp:290-336
     int role = 0;
     const char *why = nullptr;
-    const char *name = detail::weightsName(im[0].set, im[1].set, im[2].set, f->hdr, f->srgb, f->clean_aux, &role, &why);
+    const char *name = f->lightmap ? detail::lightmapWeightsName(f->directional)
+                                   : detail::weightsName(im[0].set, im[1].set, im[2].set, f->hdr, f->srgb, f->clean_aux, &role, &why);
     if (!name) throw Failure{Error::InvalidOperation, why};
     Filter::Key key;
     key.width = im[3].width; key.height = im[3].height; key.max_memory_mb = f->max_memory_mb; key.inputs = inputs;
@@ -216,15 +241,28 @@ void commit_filter(Filter *f) {
             throw Failure{Error::InvalidOperation, std::string("no weights: none ship; set the \"weights\" data, or setWeightsDirectory() / MI355X_OIDN_WEIGHTS for ") + name + ".tza"};
         key.file = dir + "/" + name + ".tza";
     }
-    if (!f->nn || !(key == f->key)) {
-        if (key.width < 1 || key.height < 1 || key.width > PTX_NN_MAX_FRAME || key.height > PTX_NN_MAX_FRAME)
-            throw Failure{Error::InvalidOperation, "unsupported image size"};
+    if (empty || !f->nn || !(key == f->key)) {
+        if (key.width > PTX_NN_MAX_FRAME || key.height > PTX_NN_MAX_FRAME) throw Failure{Error::InvalidOperation, "unsupported image size"};
         std::vector<unsigned char> file;
         const void *blob = f->user_weights;
         size_t bytes = f->user_weights_size;
         if (!f->user_weights) {
             read_file(key.file, file);
             blob = file.data(); bytes = file.size();
+        }
+        if (empty) {
+            ptx_nn_info info;
+            const int rc = ptx_debug_nn_plan(blob, bytes, &info);                 // host only: the blob is a network, or is refused as one
+            if (rc != PTX_OK) throw Failure{Error::InvalidOperation, std::string("building the network: ") + ptx_last_error()};
+            if (info.input_channels != 3 * inputs)
+                throw Failure{Error::InvalidOperation, "building the network: the weights take " + std::to_string(info.input_channels) +
+                                                           " input channels, the filter has " + std::to_string(inputs) + " input image(s)"};
+            if (f->nn) ptx_nn_destroy(f->nn);
+            f->nn = nullptr; f->key = Filter::Key();
+            f->role = role; f->empty = true;
+            for (int k = 0; k < 4; k++) f->committed[k] = im[k];
+            f->dirty = false;
+            return;
         }
         ptx_nn *made = nullptr;
         const int rc = ptx_nn_create_tiled(ordinal, (int)key.width, (int)key.height, blob, bytes, f->max_memory_mb, &made);
@@ -236,13 +274,20 @@ void commit_filter(Filter *f) {
         if (f->nn) ptx_nn_destroy(f->nn);
         f->nn = made; f->key = key; f->builds++;
     }
-    f->role = role;
+    f->role = role; f->empty = false;
     for (int k = 0; k < 4; k++) f->committed[k] = im[k];
     f->dirty = false;
 }
 
+// ptx_nn_progress_fn over the filter's bool monitor
+int progress_trampoline(void *user, double n) {
+    Filter *f = static_cast<Filter *>(user);
+    return f->progress(f->progress_user, n) ? 1 : 0;
+}
+
 void execute_filter(Filter *f) {
-    if (f->dirty || !f->nn) throw Failure{Error::InvalidOperation, "changes to the filter are not committed"};
+    if (f->dirty || (!f->nn && !f->empty)) throw Failure{Error::InvalidOperation, "changes to the filter are not committed"};
+    if (f->empty) return;
     bool on_device;
     {
         std::lock_guard<std::mutex> lock(f->device->mutex);
@@ -257,14 +302,18 @@ void execute_filter(Filter *f) {
     ptx_nn_params p;
     ptx_default_nn_params(&p);
     p.hdr = f->hdr; p.srgb = f->srgb; p.input_scale = f->input_scale;
+    int rc = ptx_nn_set_progress(f->nn, f->progress ? progress_trampoline : nullptr, f);
+    if (rc != PTX_OK) throw ptx_failure(rc, "execute");
     if (on_device) {
-        int rc = ptx_nn_denoise_images_device(f->nn, first, alb, nrm, &d[3], 1.f, f->role, &p, nullptr);
+        rc = f->lightmap ? ptx_nn_denoise_lightmap_device(f->nn, &d[0], &d[3], f->directional, f->input_scale, nullptr)
+                         : ptx_nn_denoise_images_device(f->nn, first, alb, nrm, &d[3], 1.f, f->role, &p, nullptr);
         if (rc != PTX_OK) throw ptx_failure(rc, "execute");
         float scale;
         rc = ptx_nn_read_scale(f->nn, &scale);      // waits for the handle's event
         if (rc != PTX_OK) throw ptx_failure(rc, "execute");
     } else {
-        const int rc = ptx_nn_denoise_images_host(f->nn, first, alb, nrm, &d[3], 1.f, f->role, &p);
+        rc = f->lightmap ? ptx_nn_denoise_lightmap_host(f->nn, &d[0], &d[3], f->directional, f->input_scale)
+                         : ptx_nn_denoise_images_host(f->nn, first, alb, nrm, &d[3], 1.f, f->role, &p);
         if (rc != PTX_OK) throw ptx_failure(rc, "execute");
     }
 }
@@ -276,12 +325,15 @@ void setWeightsDirectory(const char *dir) {
     g_weights_dir = dir ? dir : "";
 }
 
-DeviceRef newDevice(DeviceType type) {
+DeviceRef detail::newDevice(DeviceType type, bool filterRTLightmap) {
     (void)type;                      // Default and CPU alike: the one kind of device here is a HIP device, chosen at commit
     Device *d = new (std::nothrow) Device();
     if (!d) report(nullptr, {Error::OutOfMemory, "out of memory"});
+    else d->lightmap = filterRTLightmap;
     return DeviceRef(d);
 }
+
+DeviceRef newDevice(DeviceType type) { return detail::newDevice(type, false); }
 
 // ---- DeviceRef -------------------------------------------------------------------------------------------------------------------------
 void DeviceRef::commit() {
@@ -332,7 +384,9 @@ void DeviceRef::set(const char *name, bool value) {
         std::unique_lock<std::mutex> lock(d->mutex);
         if (d->committed) throw Failure{Error::InvalidOperation, "device parameters are set before commit"};
         if (!strcmp(name, "imagesOnDevice")) d->images_on_device = value;
-        // (setAffinity, verbose and the like belong to OIDN's CPU device: accepted and without effect)
+        else if (!strcmp(name, "filterRTLightmap")) d->lightmap = value;
+        else if (!strcmp(name, "setAffinity")) d->set_affinity = value;      // (OIDN's CPU device's: kept, without effect)
+        else if (!strcmp(name, "verbose")) d->verbose = value;
     });
 }
 
@@ -344,6 +398,10 @@ void DeviceRef::set(const char *name, int value) {
         if (d->committed) throw Failure{Error::InvalidOperation, "device parameters are set before commit"};
         if (!strcmp(name, "deviceOrdinal")) d->ordinal = value;
         else if (!strcmp(name, "imagesOnDevice")) d->images_on_device = value != 0;
+        else if (!strcmp(name, "filterRTLightmap")) d->lightmap = value != 0;
+        else if (!strcmp(name, "numThreads")) d->num_threads = value;
+        else if (!strcmp(name, "setAffinity")) d->set_affinity = value != 0;
+        else if (!strcmp(name, "verbose")) d->verbose = value;
     });
 }
 
@@ -357,22 +415,93 @@ int DeviceRef::get1i(const char *name) {
         std::unique_lock<std::mutex> lock(d->mutex);
         if (!strcmp(name, "imagesOnDevice")) value = d->images_on_device;
         else if (!strcmp(name, "deviceOrdinal")) value = d->ordinal;
+        else if (!strcmp(name, "filterRTLightmap")) value = d->lightmap;
+        else if (!strcmp(name, "numThreads")) value = d->num_threads;
+        else if (!strcmp(name, "setAffinity")) value = d->set_affinity;
+        else if (!strcmp(name, "verbose")) value = d->verbose;
+        else if (!strcmp(name, "version")) value = 10402;                    // the interface restated here: OIDN 1.4.2's
+        else if (!strcmp(name, "versionMajor")) value = 1;
+        else if (!strcmp(name, "versionMinor")) value = 4;
+        else if (!strcmp(name, "versionPatch")) value = 2;
         else throw Failure{Error::InvalidArgument, "unknown device parameter"};
     });
     return value;
 }
 
-FilterRef DeviceRef::newFilter(const char *type) {
+FilterRef DeviceRef::newFilter(const char *type) const {
     Device *d = h.get();
     Filter *f = nullptr;
     guard(d, [&] {
         if (!d) throw NULL_HANDLE;
-        if (!type || strcmp(type, "RT")) throw Failure{Error::InvalidArgument, "unknown filter type (the RT filter is the one offered)"};
+        bool lightmap_offered;
+        {
+            std::lock_guard<std::mutex> lock(d->mutex);
+            lightmap_offered = d->lightmap;
+        }
+        const bool lightmap = type && !strcmp(type, "RTLightmap");
+        if (lightmap && !lightmap_offered)
+            throw Failure{Error::InvalidArgument, "unknown filter type (the RTLightmap filter is offered to a device with filterRTLightmap set)"};
+        if (!type || (strcmp(type, "RT") && !lightmap)) throw Failure{Error::InvalidArgument, "unknown filter type (the RT filter is the one offered)"};
         f = new Filter();
+        f->lightmap = lightmap;
         detail::retain(d);
         f->device = d;
     });
     return FilterRef(f);
+}
+
+BufferRef DeviceRef::newBuffer(size_t byteSize) const {
+    Device *d = h.get();
+    Buffer *b = nullptr;
+    guard(d, [&] {
+        if (!d) throw NULL_HANDLE;
+        void *ptr = nullptr;
+        if (byteSize) {
+            const size_t rounded = (byteSize + 127) / 128 * 128;
+            if (rounded < byteSize || !(ptr = aligned_alloc(128, rounded))) throw std::bad_alloc();
+        }
+        b = new (std::nothrow) Buffer();
+        if (!b) { free(ptr); throw std::bad_alloc(); }
+        b->ptr = ptr; b->size = byteSize; b->owned = true;
+        detail::retain(d);
+        b->device = d;
+    });
+    return BufferRef(b);
+}
+
+BufferRef DeviceRef::newBuffer(void *ptr, size_t byteSize) const {
+    Device *d = h.get();
+    Buffer *b = nullptr;
+    guard(d, [&] {
+        if (!d) throw NULL_HANDLE;
+        if (!ptr && byteSize) throw Failure{Error::InvalidArgument, "buffer pointer null"};
+        b = new Buffer();
+        b->ptr = ptr; b->size = byteSize;
+        detail::retain(d);
+        b->device = d;
+    });
+    return BufferRef(b);
+}
+
+// ---- BufferRef -------------------------------------------------------------------------------------------------------------------------
+void *BufferRef::getData() const { return h.get() ? h.get()->ptr : nullptr; }
+size_t BufferRef::getSize() const { return h.get() ? h.get()->size : 0; }
+
+void *BufferRef::map(Access access, size_t byteOffset, size_t byteSize) {
+    (void)access;
+    Buffer *b = h.get();
+    void *at = nullptr;
+    guard(b ? b->device : nullptr, [&] {
+        if (!b) throw NULL_HANDLE;
+        if (byteOffset > b->size || byteSize > b->size - byteOffset) throw Failure{Error::InvalidArgument, "buffer region out of range"};
+        at = b->ptr ? static_cast<char *>(b->ptr) + byteOffset : nullptr;
+    });
+    return at;
+}
+
+void BufferRef::unmap(void *mappedPtr) {
+    (void)mappedPtr;                 // host memory: nothing to write back
+    if (!h.get()) report(nullptr, NULL_HANDLE);
 }
 
 // ---- FilterRef -------------------------------------------------------------------------------------------------------------------------
@@ -383,11 +512,59 @@ void FilterRef::setImage(const char *name, void *ptr, Format format, size_t widt
         if (!f) throw NULL_HANDLE;
         const int k = image_slot(name);
         if (k < 0) throw Failure{Error::InvalidArgument, "unknown filter parameter"};
+        if (f->lightmap && (k == 1 || k == 2)) throw Failure{Error::InvalidArgument, "unknown filter parameter"};
         ImageParam &im = f->image[k];
         im.set = ptr != nullptr;     // (a null pointer removes the image, as OIDN's does)
+        im.buffer = detail::Ref<Buffer>();
         im.ptr = ptr; im.format = format; im.width = width; im.height = height;
         im.offset = byteOffset; im.pixel_stride = bytePixelStride; im.row_stride = byteRowStride;
         f->dirty = true;
+    });
+}
+
+void FilterRef::setImage(const char *name, const BufferRef &buffer, Format format, size_t width, size_t height, size_t byteOffset,
+                         size_t bytePixelStride, size_t byteRowStride) {
+    Filter *f = h.get();
+    guard(f ? f->device : nullptr, [&] {
+        if (!f) throw NULL_HANDLE;
+        const int k = image_slot(name);
+        if (k < 0 || (f->lightmap && (k == 1 || k == 2))) throw Failure{Error::InvalidArgument, "unknown filter parameter"};
+        Buffer *b = buffer.getHandle();
+        if (!b) throw Failure{Error::InvalidArgument, "invalid handle"};
+        {
+            std::lock_guard<std::mutex> lock(f->device->mutex);
+            if (f->device->images_on_device)
+                throw Failure{Error::InvalidOperation, "a buffer is host memory: with imagesOnDevice set, images are device pointers"};
+        }
+        // the image's byte interval, from the buffer's start: [byteOffset, the last channel byte of the last pixel + 1)
+        const size_t pixel = detail::formatChannels(format) * detail::formatChannelSize(format);
+        if (!pixel) throw Failure{Error::InvalidArgument, "invalid image format"};
+        const size_t ps = bytePixelStride ? bytePixelStride : pixel;
+        const size_t rs = byteRowStride ? byteRowStride : width * ps;
+        if (byteOffset > b->size) throw Failure{Error::InvalidArgument, "buffer region out of range"};
+        if (width && height) {
+            // (height - 1) * rs + (width - 1) * ps + pixel, refused where it overflows or leaves the buffer
+            const size_t room = b->size - byteOffset;
+            if (pixel > room || (width - 1) > (room - pixel) / ps) throw Failure{Error::InvalidArgument, "buffer region out of range"};
+            const size_t row = (width - 1) * ps + pixel;
+            if (height > 1 && (rs == 0 || (height - 1) > (room - row) / rs)) throw Failure{Error::InvalidArgument, "buffer region out of range"};
+        }
+        ImageParam &im = f->image[k];
+        im.set = true;
+        im.buffer = detail::Ref<Buffer>();
+        detail::retain(b);
+        im.buffer = detail::Ref<Buffer>(b);
+        im.ptr = b->ptr; im.format = format; im.width = width; im.height = height;
+        im.offset = byteOffset; im.pixel_stride = bytePixelStride; im.row_stride = byteRowStride;
+        f->dirty = true;
+    });
+}
+
+void FilterRef::setProgressMonitorFunction(ProgressMonitorFunction fn, void *userPtr) {
+    Filter *f = h.get();
+    guard(f ? f->device : nullptr, [&] {
+        if (!f) throw NULL_HANDLE;
+        f->progress = fn; f->progress_user = fn ? userPtr : nullptr;      // read by execute: no commit needed
     });
 }
 
@@ -440,10 +617,12 @@ void FilterRef::set(const char *name, int value) {
     Filter *f = h.get();
     guard(f ? f->device : nullptr, [&] {
         if (!f || !name) throw NULL_HANDLE;
-        if (!strcmp(name, "hdr")) f->hdr = value != 0;
+        if (!strcmp(name, "maxMemoryMB")) f->max_memory_mb = value;
+        else if (f->lightmap && !strcmp(name, "directional")) f->directional = value != 0;
+        else if (f->lightmap) throw Failure{Error::InvalidArgument, "unknown filter parameter"};      // hdr, srgb, cleanAux: RTLightmapFilter::set1b has none
+        else if (!strcmp(name, "hdr")) f->hdr = value != 0;
         else if (!strcmp(name, "srgb")) f->srgb = value != 0;
         else if (!strcmp(name, "cleanAux")) f->clean_aux = value != 0;
-        else if (!strcmp(name, "maxMemoryMB")) f->max_memory_mb = value;
         else throw Failure{Error::InvalidArgument, "unknown filter parameter"};
         f->dirty = true;
     });
@@ -466,10 +645,13 @@ int FilterRef::get1i(const char *name) {
     int value = 0;
     guard(f ? f->device : nullptr, [&] {
         if (!f || !name) throw NULL_HANDLE;
-        if (!strcmp(name, "hdr")) value = f->hdr;
+        if (!strcmp(name, "maxMemoryMB")) value = f->max_memory_mb;
+        else if (f->lightmap && !strcmp(name, "directional")) value = f->directional;
+        else if (f->lightmap && (!strcmp(name, "hdr") || !strcmp(name, "srgb") || !strcmp(name, "cleanAux")))
+            throw Failure{Error::InvalidArgument, "unknown filter parameter"};
+        else if (!strcmp(name, "hdr")) value = f->hdr;
         else if (!strcmp(name, "srgb")) value = f->srgb;
         else if (!strcmp(name, "cleanAux")) value = f->clean_aux;
-        else if (!strcmp(name, "maxMemoryMB")) value = f->max_memory_mb;
         else if (!strcmp(name, "alignment")) value = PTX_NN_TILE_ALIGN;
         else if (!strcmp(name, "overlap")) value = PTX_NN_TILE_OVERLAP;
         else if (!strcmp(name, "networkBuilds")) value = f->builds;

@@ -20,6 +20,7 @@
 #include "pt_handle.h"
 #include "pt_tza.h"
 #include "pt_nn_tiles.h"
+#include "pt_nn_progress.h"
 
 struct ptx_display;
 
@@ -50,6 +51,9 @@ struct ptx_nn : PtHandle {
     // W*H*3 floats each; ptx_nn_denoise_images_host's colour, albedo, normal and output (with the inputs that meet it), in bytes
     DevBuf<float> d_image_gather, d_image_tmp;
     DevBuf<uint8_t> d_image_stage[4];
+    // the progress monitor (pt_nn_progress.h) and, made by the first call under one, the markers behind two tiles' stages and the copy-out
+    PtNnProgress progress;
+    std::vector<OwnedEvent> progress_ev;
     ~ptx_nn();
 };
 
@@ -73,6 +77,15 @@ struct PtNnStages {
     int (*output)(void *ctx, hipStream_t st, const ptx_nn_tile &T, int wp, const float *net_out);
 };
 int pt_nn_run_tiles(ptx_nn *n, hipStream_t st, const PtNnStages &stages);
+
+// The progress monitor around one ptx_nn_denoise* call (`fn`).  begin: where the handle has a monitor and no call has begun yet, the
+// first report (0, before anything is enqueued); *mine says that this call began it and ends it.  PTX_ERR_CANCELLED where the monitor
+// cancels.  While a call has begun, pt_nn_run_tiles reports after every stage of every tile has finished and returns only then;
+// pt_nn_progress_frame_unit does the same for what the caller has just enqueued on st behind the tiles (the copy-out).  A cancel waits
+// for what is in flight on st.  end(mine, rc) hands rc back.  Without a monitor none of them enqueues, records or waits for anything.
+int pt_nn_progress_begin(const char *fn, ptx_nn *n, bool copy_out, bool *mine);
+int pt_nn_progress_frame_unit(ptx_nn *n, hipStream_t st);
+int pt_nn_progress_end(ptx_nn *n, bool mine, int rc);
 
 // ptx_nn_create_tiled's create path for a network whose scratch is `scratch`, the caller's allocation of at least the plan's bytes under
 // this limit (pt_nn_scratch of pt_nn_tiling's tile buffer); max_memory_mb < 0: one tile, as ptx_nn_create.  `fn` names the entry point.

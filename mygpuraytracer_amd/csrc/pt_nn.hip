@@ -410,8 +410,8 @@ const char *pt_nn_params_problem(const ptx_nn_params &p, float samples) {
     return nullptr;
 }
 
-// the sixteen convolutions of one wp x hp tile in the handle's scratch
-static int run_layers(ptx_nn *n, hipStream_t st, int wp, int hp) {
+// the sixteen convolutions of one wp x hp tile in the handle's scratch; ev: NULL, or sixteen events, one recorded behind each layer
+static int run_layers(ptx_nn *n, hipStream_t st, int wp, int hp, OwnedEvent *ev = nullptr) {
     uint8_t *base = n->scratch;
     for (int i = 0; i < PT_NN_LAYERS; i++) {
         const PtNnLayerDev &L = n->L[i];
@@ -426,12 +426,81 @@ static int run_layers(ptx_nn *n, hipStream_t st, int wp, int hp) {
         a.c0p = L.c0p; a.c1p = L.c1p; a.coutp = L.coutp; a.nchunks = (L.c0p + L.c1p + CHUNK - 1) / CHUNK;
         a.upsample = L.upsample; a.pool = L.pool; a.relu = L.relu;
         if (const int rc = launch_conv(st, a, L.cout)) return rc;
+        if (ev) PT_HC(hipEventRecord(ev[i], st));
     }
     return PTX_OK;
 }
 
+static_assert(PT_NN_TILE_UNITS == PT_NN_LAYERS + 2, "a tile's units: input, the layers, output");
+
+// a cancel: nothing further is enqueued, and the call returns after what is in flight on st
+static int cancelled(ptx_nn *n, hipStream_t st) {
+    const double at = n->progress.done >= n->progress.total ? 1.0 : (double)n->progress.done / (double)n->progress.total;
+    PT_HC(hipStreamSynchronize(st));
+    return pt_fail(PTX_ERR_CANCELLED, "the network denoiser's progress monitor cancelled the call at n = " + std::to_string(at));
+}
+
+// the markers of two tiles' stages and, last, of the copy-out
+static int progress_events(ptx_nn *n) {
+    while (n->progress_ev.size() < 2 * PT_NN_TILE_UNITS + 1) {
+        OwnedEvent e;
+        PT_HC(e.create(hipEventDisableTiming));
+        n->progress_ev.push_back(std::move(e));
+    }
+    return PTX_OK;
+}
+
+int pt_nn_progress_begin(const char *fn, ptx_nn *n, bool copy_out, bool *mine) {
+    *mine = false;
+    if (!n->progress.fn || n->progress.running) return PTX_OK;
+    if (!n->progress.begin(n->tiling.count(), copy_out))
+        return pt_fail(PTX_ERR_CANCELLED, std::string(fn) + ": the progress monitor cancelled the call at n = 0, before anything was enqueued");
+    *mine = true;
+    return PTX_OK;
+}
+
+int pt_nn_progress_frame_unit(ptx_nn *n, hipStream_t st) {
+    if (!n->progress.running) return PTX_OK;
+    if (const int rc = progress_events(n)) return rc;
+    OwnedEvent &e = n->progress_ev[2 * PT_NN_TILE_UNITS];
+    PT_HC(hipEventRecord(e, st));
+    PT_HC(hipEventSynchronize(e));
+    return n->progress.unit() ? PTX_OK : cancelled(n, st);
+}
+
+int pt_nn_progress_end(ptx_nn *n, bool mine, int rc) {
+    if (mine) n->progress.end();
+    return rc;
+}
+
+// the tile loop of a call under a monitor: a marker behind every stage, the reports one tile behind the enqueue (pt_nn_progress.h)
+static int run_tiles_reporting(ptx_nn *n, hipStream_t st, const PtNnStages &stages) {
+    if (const int rc = progress_events(n)) return rc;
+    uint8_t *base = n->scratch;
+    uint16_t *net_in = reinterpret_cast<uint16_t *>(base + n->in_offset);
+    const float *net_out = reinterpret_cast<const float *>(base + n->L[PT_NN_LAYERS - 1].out_offset);
+    auto enqueue = [&](int k) {
+        const ptx_nn_tile T = pt_nn_tile_at(n->tiling, k);
+        const int wp = pad16(T.w), hp = pad16(T.h);
+        OwnedEvent *ev = &n->progress_ev[(size_t)(k & 1) * PT_NN_TILE_UNITS];
+        if (const int rc = stages.input(stages.ctx, st, T, wp, hp, net_in)) return rc;
+        PT_HC(hipEventRecord(ev[0], st));
+        if (const int rc = run_layers(n, st, wp, hp, ev + 1)) return rc;
+        if (const int rc = stages.output(stages.ctx, st, T, wp, net_out)) return rc;
+        PT_HC(hipEventRecord(ev[PT_NN_TILE_UNITS - 1], st));
+        return (int)PTX_OK;
+    };
+    auto wait = [&](int k, int s) {
+        PT_HC(hipEventSynchronize(n->progress_ev[(size_t)(k & 1) * PT_NN_TILE_UNITS + s]));
+        return (int)PTX_OK;
+    };
+    const int rc = pt_nn_progress_tiles(n->progress, n->tiling.count(), enqueue, wait);
+    return rc == PTX_ERR_CANCELLED ? cancelled(n, st) : rc;
+}
+
 // every tile in the handle's one scratch, a smaller tile in a prefix of each tensor
 int pt_nn_run_tiles(ptx_nn *n, hipStream_t st, const PtNnStages &stages) {
+    if (n->progress.running) return run_tiles_reporting(n, st, stages);
     uint8_t *base = n->scratch;
     uint16_t *net_in = reinterpret_cast<uint16_t *>(base + n->in_offset);
     const float *net_out = reinterpret_cast<const float *>(base + n->L[PT_NN_LAYERS - 1].out_offset);
@@ -645,7 +714,9 @@ int ptx_nn_denoise_device(ptx_nn *n, const float *device_rgb, float samples, con
                                                 "frame in memory (a later tile reads pixels an earlier tile's result would have replaced)");
     }
     PT_HC(hipSetDevice(n->device));
-    return pt_nn_enqueue(n, (hipStream_t)stream, device_rgb, samples, device_alb3, 3, device_nrm3, 3, p, device_out_rgb);
+    bool mine;
+    if (const int rc = pt_nn_progress_begin("ptx_nn_denoise_device", n, false, &mine)) return rc;
+    return pt_nn_progress_end(n, mine, pt_nn_enqueue(n, (hipStream_t)stream, device_rgb, samples, device_alb3, 3, device_nrm3, 3, p, device_out_rgb));
 }
 
 int ptx_nn_denoise_host(ptx_nn *n, const float *rgb, float samples, const float *alb3, const float *nrm3, const ptx_nn_params *params, float *out_rgb) {
@@ -653,17 +724,29 @@ int ptx_nn_denoise_host(ptx_nn *n, const float *rgb, float samples, const float 
     const size_t count = 3 * (size_t)n->w * n->h;
     PT_HC(hipSetDevice(n->device));
     PT_HC(n->wait_host());
+    bool mine;
+    if (const int rc = pt_nn_progress_begin("ptx_nn_denoise_host", n, false, &mine)) return rc;
     const float *host[3] = {rgb, alb3, nrm3};
     for (int k = 0; k < 4; k++) {
         if (k < 3 && !host[k]) continue;
-        if (!n->d_stage[k]) PT_HC(n->d_stage[k].alloc(count));
-        if (k < 3) PT_HC(hipMemcpy(n->d_stage[k], host[k], sizeof(float) * count, hipMemcpyHostToDevice));
+        hipError_t e = hipSuccess;
+        if (!n->d_stage[k]) e = n->d_stage[k].alloc(count);
+        if (e == hipSuccess && k < 3) e = hipMemcpy(n->d_stage[k], host[k], sizeof(float) * count, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return pt_nn_progress_end(n, mine, pt_fail(PTX_ERR_HIP, std::string("ptx_nn_denoise_host: staging: ") + hipGetErrorString(e)));
     }
-    if (const int rc = ptx_nn_denoise_device(n, n->d_stage[0], samples, alb3 ? n->d_stage[1].p : nullptr, nrm3 ? n->d_stage[2].p : nullptr, params,
-                                             n->d_stage[3], nullptr))
+    if (const int rc = pt_nn_progress_end(n, mine, ptx_nn_denoise_device(n, n->d_stage[0], samples, alb3 ? n->d_stage[1].p : nullptr,
+                                                                         nrm3 ? n->d_stage[2].p : nullptr, params, n->d_stage[3], nullptr)))
         return rc;
     PT_HC(hipEventSynchronize(n->ev));
     PT_HC(hipMemcpy(out_rgb, n->d_stage[3], sizeof(float) * count, hipMemcpyDeviceToHost));
+    return PTX_OK;
+}
+
+int ptx_nn_set_progress(ptx_nn *n, ptx_nn_progress_fn fn, void *user) {
+    if (!n) return pt_fail(PTX_ERR_INVALID, "ptx_nn_set_progress: null handle");
+    if (n->progress.running) return pt_fail(PTX_ERR_INVALID, "ptx_nn_set_progress: called from the monitor of a running call");
+    n->progress.fn = fn;
+    n->progress.user = fn ? user : nullptr;
     return PTX_OK;
 }
 

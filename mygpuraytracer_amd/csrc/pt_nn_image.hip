@@ -17,6 +17,8 @@
 // a pixel stride of 8 one 8-byte load (the fourth channel comes along and is dropped); every other layout one load per channel.
 // Stores touch the three channels alone: three 4-byte stores, or for halves three 2-byte stores (a 4-byte and a 2-byte one where the
 // pixels are 4-byte aligned).  A half is fp16_rne(v > 65504 ? 65504 : v).  No atomics, no LDS, no scratch.
+// (The view, its loads and its stores are pt_nn_image_dev.h's, shared with pt_nn_lightmap.hip, which also launches the gather and the
+// copy through the host functions at the end of this unit and stages host images through pt_nn_image_host_call.)
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -27,6 +29,7 @@
 
 #include "pt_nn.h"
 #include "pt_nn_image.h"
+#include "pt_nn_image_dev.h"
 #include "pt_nn_transfer.h"
 #include "pt_display.h"
 
@@ -34,57 +37,7 @@ namespace {
 
 using namespace pt_nn_transfer;
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
 constexpr int NT = 256;
-
-// a view on the device.  wide: loads a pixel at once (see above); pair: half stores as 4 + 2 bytes
-struct Img {
-    uint8_t *base;                            // NULL: no image
-    size_t ps, rs;
-    int half, wide, pair;
-};
-
-__device__ __forceinline__ void load3(const Img &im, size_t x, size_t y, float v[3]) {
-    const uint8_t *p = im.base + y * im.rs + x * im.ps;
-    if (!im.half) {
-        if (im.wide) {
-            const float4 r = *reinterpret_cast<const float4 *>(p);
-            v[0] = r.x; v[1] = r.y; v[2] = r.z;
-        } else {
-            const float *f = reinterpret_cast<const float *>(p);
-            v[0] = f[0]; v[1] = f[1]; v[2] = f[2];
-        }
-    } else {
-        if (im.wide) {
-            const half4 r = *reinterpret_cast<const half4 *>(p);
-            v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
-        } else {
-            const _Float16 *f = reinterpret_cast<const _Float16 *>(p);
-            v[0] = (float)f[0]; v[1] = (float)f[1]; v[2] = (float)f[2];
-        }
-    }
-}
-
-__device__ __forceinline__ _Float16 to_half(float v) { return (_Float16)(v > 65504.f ? 65504.f : v); }
-
-__device__ __forceinline__ void store3(const Img &im, size_t x, size_t y, const float v[3]) {
-    uint8_t *p = im.base + y * im.rs + x * im.ps;
-    if (!im.half) {
-        float *f = reinterpret_cast<float *>(p);
-        f[0] = v[0]; f[1] = v[1]; f[2] = v[2];
-    } else if (im.pair) {
-        half2v lo;
-        lo[0] = to_half(v[0]); lo[1] = to_half(v[1]);
-        *reinterpret_cast<half2v *>(p) = lo;
-        reinterpret_cast<_Float16 *>(p)[2] = to_half(v[2]);
-    } else {
-        _Float16 *f = reinterpret_cast<_Float16 *>(p);
-        f[0] = to_half(v[0]); f[1] = to_half(v[1]); f[2] = to_half(v[2]);
-    }
-}
 
 struct ImgInputArgs {
     int w, h, wp, hp;                         // the window and its padded size
@@ -197,27 +150,6 @@ template <class K, class A> int launch(K kernel, hipStream_t st, size_t n, const
     return PTX_OK;
 }
 
-Img device_image(const PtNnImageView &v) {
-    Img im;
-    im.base = reinterpret_cast<uint8_t *>(v.base);
-    im.ps = v.pixel_stride; im.rs = v.row_stride;
-    im.half = v.format == PTX_NN_FORMAT_HALF3;
-    const size_t pixel = im.half ? 8 : 16;    // of four channels
-    im.wide = v.base && v.pixel_stride == pixel && v.base % pixel == 0 && v.row_stride % pixel == 0;
-    im.pair = im.half && v.base % 4 == 0 && v.pixel_stride % 4 == 0 && v.row_stride % 4 == 0;
-    return im;
-}
-
-PtNnImageView packed_view(const float *p, int width) {
-    PtNnImageView v;
-    v.base = (uintptr_t)p; v.format = PTX_NN_FORMAT_FLOAT3; v.pixel_stride = 12; v.row_stride = 12 * (size_t)width;
-    return v;
-}
-
-bool is_packed_float(const PtNnImageView &v, int width) {
-    return v.format == PTX_NN_FORMAT_FLOAT3 && v.pixel_stride == 12 && v.row_stride == 12 * (size_t)width;
-}
-
 const char *const IMAGE_NAME[4] = {"colour", "albedo", "normal", "output"};
 const char *const ROLE_NAME[3] = {"colour", "albedo", "normal"};
 
@@ -284,16 +216,7 @@ int images_enqueue(ptx_nn *n, hipStream_t st, const PtNnImageView v[4], float sa
     // same -- every read of the input stage (and of the gather) precedes every write of the output stage on the stream.  It meets one
     // and there are more tiles: a later tile's window would read what an earlier tile's result replaced, so the tiles write a packed
     // float temporary, which k_nn_image_copy moves through the output's descriptor after the last tile.
-    uintptr_t olo, ohi;
-    pt_nn_image_interval(v[3], n->w, n->h, olo, ohi);
-    bool meets = false;
-    for (int k = 0; k < 3; k++) {
-        if (!v[k].base) continue;
-        uintptr_t lo, hi;
-        pt_nn_image_interval(v[k], n->w, n->h, lo, hi);
-        meets = meets || pt_nn_intervals_meet(olo, ohi, lo, hi);
-    }
-    const bool staged = meets && n->tiling.count() > 1;
+    const bool staged = pt_nn_image_staged(n, v);
     const size_t count = 3 * (size_t)n->w * n->h;
     const bool gather = automatic && !is_packed_float(v[0], n->w);
     PT_HC(n->wait_stream(st));
@@ -309,9 +232,7 @@ int images_enqueue(ptx_nn *n, hipStream_t st, const PtNnImageView v[4], float sa
     if (automatic) {
         const float *rgb = reinterpret_cast<const float *>(v[0].base);
         if (gather) {
-            ImgFrameArgs ga;
-            ga.w = n->w; ga.h = n->h; ga.img = ia.col; ga.packed = n->d_image_gather;
-            if (const int rc = launch(k_nn_image_gather, st, (size_t)n->w * n->h, ga)) return rc;
+            if (const int rc = pt_nn_image_gather_enqueue(st, n->w, n->h, v[0], n->d_image_gather)) return rc;
             rgb = n->d_image_gather;
         }
         if (const int rc = pt_display_meter_enqueue(n->meter, st, rgb, samples, 0.18f)) return rc;
@@ -338,9 +259,8 @@ int images_enqueue(ptx_nn *n, hipStream_t st, const PtNnImageView v[4], float sa
     };
     if (const int rc = pt_nn_run_tiles(n, st, stages)) return rc;
     if (staged) {
-        ImgFrameArgs ca;
-        ca.w = n->w; ca.h = n->h; ca.img = device_image(v[3]); ca.packed = n->d_image_tmp;
-        if (const int rc = launch(k_nn_image_copy, st, (size_t)n->w * n->h, ca)) return rc;
+        if (const int rc = pt_nn_image_copy_enqueue(st, n->w, n->h, n->d_image_tmp, v[3])) return rc;
+        if (const int rc = pt_nn_progress_frame_unit(n, st)) return rc;
     }
     PT_HC(n->record(st));
     return PTX_OK;
@@ -362,38 +282,33 @@ hipError_t ensure(DevBuf<uint8_t> &b, size_t bytes) {
 
 }  // namespace
 
-extern "C" {
-
-size_t ptx_sizeof_nn_image(void) { return sizeof(ptx_nn_image); }
-
-int ptx_debug_nn_image_problem(int width, int height, const ptx_nn_image *img, int is_output) {
-    const std::string fn = "ptx_debug_nn_image_problem";
-    if (width < 1 || height < 1 || width > PTX_NN_MAX_FRAME || height > PTX_NN_MAX_FRAME) return pt_fail(PTX_ERR_INVALID, fn + ": bad frame size");
-    if (!img || !img->ptr) return pt_fail(PTX_ERR_INVALID, fn + ": no image (a NULL descriptor or ptr)");
-    PtNnImageView v;
-    const std::string why = pt_nn_image_view(width, height, *img, v);
-    if (!why.empty()) return pt_fail(PTX_ERR_INVALID, fn + ": the " + (is_output ? "output" : "input") + " image: " + why);
-    return PTX_OK;
+int pt_nn_image_gather_enqueue(hipStream_t st, int w, int h, const PtNnImageView &img, float *packed) {
+    ImgFrameArgs a;
+    a.w = w; a.h = h; a.img = device_image(img); a.packed = packed;
+    return launch(k_nn_image_gather, st, (size_t)w * h, a);
 }
 
-int ptx_nn_denoise_images_device(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
-                                 const ptx_nn_image *output, float samples, int role, const ptx_nn_params *params, void *stream) {
-    const ptx_nn_params p = params_or_default(params);
-    const ptx_nn_image *const img[4] = {color, albedo, normal, output};
-    PtNnImageView v[4];
-    if (const int rc = images_problem("ptx_nn_denoise_images_device", n, img, samples, role, p, v)) return rc;
-    PT_HC(hipSetDevice(n->device));
-    return images_enqueue(n, (hipStream_t)stream, v, samples, role, p);
+int pt_nn_image_copy_enqueue(hipStream_t st, int w, int h, const float *packed, const PtNnImageView &img) {
+    ImgFrameArgs a;
+    a.w = w; a.h = h; a.img = device_image(img); a.packed = const_cast<float *>(packed);
+    return launch(k_nn_image_copy, st, (size_t)w * h, a);
 }
 
-int ptx_nn_denoise_images_host(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
-                               const ptx_nn_image *output, float samples, int role, const ptx_nn_params *params) {
-    const ptx_nn_params p = params_or_default(params);
-    const ptx_nn_image *const img[4] = {color, albedo, normal, output};
-    PtNnImageView v[4];
-    if (const int rc = images_problem("ptx_nn_denoise_images_host", n, img, samples, role, p, v)) return rc;
-    PT_HC(hipSetDevice(n->device));
-    PT_HC(n->wait_host());
+bool pt_nn_image_staged(const ptx_nn *n, const PtNnImageView v[4]) {
+    uintptr_t olo, ohi;
+    pt_nn_image_interval(v[3], n->w, n->h, olo, ohi);
+    bool meets = false;
+    for (int k = 0; k < 3; k++) {
+        if (!v[k].base) continue;
+        uintptr_t lo, hi;
+        pt_nn_image_interval(v[k], n->w, n->h, lo, hi);
+        meets = meets || pt_nn_intervals_meet(olo, ohi, lo, hi);
+    }
+    return meets && n->tiling.count() > 1;
+}
+
+// the staging between pt_nn_image_host_call's first report and its end
+static int host_call_staged(ptx_nn *n, const PtNnImageView v[4], int (*enqueue)(void *ctx, ptx_nn *n, const PtNnImageView d[4]), void *ctx) {
     // Each image's interval in a buffer of its own, but the inputs whose interval meets the output's: those go up with it, in one
     // buffer that spans them, so that images which share bytes in the caller's memory share them on the device.  A device address keeps
     // the host address's residue mod 16: the same alignment, the same loads and stores.
@@ -423,10 +338,57 @@ int ptx_nn_denoise_images_host(ptx_nn *n, const ptx_nn_image *color, const ptx_n
         PT_HC(hipMemcpy(at, reinterpret_cast<const void *>(lo[k]), (size_t)(hi[k] - lo[k]), hipMemcpyHostToDevice));
         d[k].base = (uintptr_t)at;
     }
-    if (const int rc = images_enqueue(n, nullptr, d, samples, role, p)) return rc;
+    if (const int rc = enqueue(ctx, n, d)) return rc;
     PT_HC(hipEventSynchronize(n->ev));
     PT_HC(hipMemcpy(reinterpret_cast<void *>(lo[3]), span + (lo[3] - span_lo), (size_t)(hi[3] - lo[3]), hipMemcpyDeviceToHost));
     return PTX_OK;
+}
+
+int pt_nn_image_host_call(const char *fn, ptx_nn *n, const PtNnImageView v[4], int (*enqueue)(void *ctx, ptx_nn *n, const PtNnImageView d[4]), void *ctx) {
+    PT_HC(n->wait_host());
+    bool mine;
+    if (const int rc = pt_nn_progress_begin(fn, n, pt_nn_image_staged(n, v), &mine)) return rc;
+    return pt_nn_progress_end(n, mine, host_call_staged(n, v, enqueue, ctx));
+}
+
+extern "C" {
+
+size_t ptx_sizeof_nn_image(void) { return sizeof(ptx_nn_image); }
+
+int ptx_debug_nn_image_problem(int width, int height, const ptx_nn_image *img, int is_output) {
+    const std::string fn = "ptx_debug_nn_image_problem";
+    if (width < 1 || height < 1 || width > PTX_NN_MAX_FRAME || height > PTX_NN_MAX_FRAME) return pt_fail(PTX_ERR_INVALID, fn + ": bad frame size");
+    if (!img || !img->ptr) return pt_fail(PTX_ERR_INVALID, fn + ": no image (a NULL descriptor or ptr)");
+    PtNnImageView v;
+    const std::string why = pt_nn_image_view(width, height, *img, v);
+    if (!why.empty()) return pt_fail(PTX_ERR_INVALID, fn + ": the " + (is_output ? "output" : "input") + " image: " + why);
+    return PTX_OK;
+}
+
+int ptx_nn_denoise_images_device(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
+                                 const ptx_nn_image *output, float samples, int role, const ptx_nn_params *params, void *stream) {
+    const ptx_nn_params p = params_or_default(params);
+    const ptx_nn_image *const img[4] = {color, albedo, normal, output};
+    PtNnImageView v[4];
+    if (const int rc = images_problem("ptx_nn_denoise_images_device", n, img, samples, role, p, v)) return rc;
+    PT_HC(hipSetDevice(n->device));
+    bool mine;
+    if (const int rc = pt_nn_progress_begin("ptx_nn_denoise_images_device", n, pt_nn_image_staged(n, v), &mine)) return rc;
+    return pt_nn_progress_end(n, mine, images_enqueue(n, (hipStream_t)stream, v, samples, role, p));
+}
+
+int ptx_nn_denoise_images_host(ptx_nn *n, const ptx_nn_image *color, const ptx_nn_image *albedo, const ptx_nn_image *normal,
+                               const ptx_nn_image *output, float samples, int role, const ptx_nn_params *params) {
+    const ptx_nn_params p = params_or_default(params);
+    const ptx_nn_image *const img[4] = {color, albedo, normal, output};
+    PtNnImageView v[4];
+    if (const int rc = images_problem("ptx_nn_denoise_images_host", n, img, samples, role, p, v)) return rc;
+    PT_HC(hipSetDevice(n->device));
+    struct Call { float samples; int role; ptx_nn_params p; } c = {samples, role, p};
+    return pt_nn_image_host_call("ptx_nn_denoise_images_host", n, v, [](void *ctx, ptx_nn *h, const PtNnImageView d[4]) {
+        const Call &k = *static_cast<Call *>(ctx);
+        return images_enqueue(h, nullptr, d, k.samples, k.role, k.p);
+    }, &c);
 }
 
 }  // extern "C"
