@@ -1010,6 +1010,122 @@ void ptx_debug_nn_lightmap_constants(float *xmax, float *norm);
 typedef int (*ptx_nn_progress_fn)(void *user, double n);   /* 0 = cancel */
 int  ptx_nn_set_progress(ptx_nn *n, ptx_nn_progress_fn fn, void *user);
 
+/* ---- image metrics: MSE, PSNR, L1, MAPE, SMAPE, gradient, SSIM, MS-SSIM and the error count, csrc/pt_metrics.hip --------------------------
+ * How good a frame is against a reference frame, on the device, every figure in one call.  It stands where OIDN's training/compare_image.py
+ * (mse, psnr, ssim, msssim), training/ssim.py (SSIM, MS-SSIM), training/loss.py (l1, l2, mape, smape, ssim, msssim, l1_msssim, l1_grad)
+ * and apps/utils/image_io.cpp:435-462 (compareImage: what oidnDenoise --ref prints) stand there.  Additive: one more handle, no existing
+ * entry point, default or struct changes.  Definition (tests/metrics_ref.py restates it in float64 and in float32):
+ *   Images: a (the test image) and b (the reference image) are ptx_nn_image descriptors of one W x H under every rule of "images" above
+ *     (formats, strides, offset, refusals; halves widened exactly).  Each has a divisor, samples_a / samples_b, finite and > 0.
+ *   Sanitise (training/image.py:69, np.nan_to_num): r = the channel as stored; s = r / samples (an IEEE division); NaN -> 0, +inf ->
+ *     FLT_MAX, -inf -> -FLT_MAX.  nonfinite_a / nonfinite_b count the stored channels r that are NaN or +-inf.
+ *   Transform t(s), every step one IEEE fp32 operation:
+ *     PTX_METRICS_NONE  t = s.
+ *     PTX_METRICS_SRGB  t = 12.92 s for s <= 0.0031308, else 1.055 powf(s, 1 / 2.4) - 0.055 (csrc/pt_nn_transfer.h's forward curve).
+ *     PTX_METRICS_HDR   t = srgb(tonemap(s * exposure)) (training/dataset.py:200-205).  tonemap (training/color.py:181-194) is Hable's
+ *       curve: e(v) = (v (0.22 v + 0.03) + 0.002) / (v (0.22 v + 0.30) + 0.06) - 0.01 / 0.30, tonemap(x) = min(e(x * 1.758141) / e(11.2), 1),
+ *       the four constants and e(11.2) formed in double and rounded once.  x * 1.758141 is held to [-2^60, 2^60] inside the curve, where
+ *       the curve has long been clamped: FLT_MAX does not become inf / inf.  An `exposure` of NaN is the automatic one: the display
+ *       transform's block meter (above, steps 1 and 2) at key 0.18 on b over samples_b, i.e. 0.18 over the metered geometric-mean
+ *       luminance -- ptx_display_status.metered of that frame, the scale the network's hdr path takes.  (A layout of b that is not
+ *       packed Float3 is gathered first.)
+ *     PTX_METRICS_SNORM t = s * 0.5 + 0.5 (dataset.py:206-208).
+ *     Under SRGB and HDR an infinite t (12.92 * -FLT_MAX; the curve at one of its two poles below 0) is held to +-FLT_MAX.
+ *   Pointwise, on ta = t(a), tb = t(b), over all N = 3 W H samples, each term in fp32: d = ta - tb;
+ *     mse = mean d d; l1 = mean |d|; mape = mean |d| / (|tb| + 0.01f); smape = mean |d| / (|ta| + |tb| + 0.01f);
+ *     psnr = 10 log10(1 / mse), in double on the host (+inf for mse 0).
+ *     grad (image.py:34-38 under L1; needs W, H >= 2): over i < H - 1, j < W - 1 and the three channels, the mean of
+ *     |(ta[i+1][j] - ta[i][j]) - (tb[i+1][j] - tb[i][j])| and |(ta[i][j+1] - ta[i][j]) - (tb[i][j+1] - tb[i][j])|, 6 (W-1)(H-1) terms.
+ *     l1_msssim = 0.16 l1 + 0.84 (1 - msssim), in double on the host.
+ *   compareImage, on sa, sb (after the divisor, before the transform), as image_io.cpp writes it: error = |sb - sa|; where sb != 0,
+ *     error = (error / sb < error) ? error / sb : error -- a negative sb makes the error negative, as there; max_error = the maximum over
+ *     max(0, error); num_errors = the count of error > threshold.
+ *   SSIM (ssim.py, data_range 1) per channel on planar ta, tb: an 11-tap window g, the fp32 values of exp(-k^2 / 4.5) / sum (k = -5 .. 5;
+ *     ptx_metrics_plan.taps), applied along x and then along y in valid mode, each filter a left-to-right fp32 sum of products, to
+ *     x, y, x x, y y, x y.  With m1, m2 the filtered x, y: s1 = f(xx) - m1 m1, s2 = f(yy) - m2 m2, s12 = f(xy) - m1 m2,
+ *     cs = (2 s12 + C2) / (s1 + s2 + C2), l = (2 m1 m2 + C1) / (m1 m1 + m2 m2 + C1), C1 = 0.01^2, C2 = 0.03^2 as floats; the map value is
+ *     l cs.  ssim_c[c] = the mean of the (H - 10)(W - 10) map values, ssim = the mean over channels.  Needs min(W, H) >= 11.
+ *   MS-SSIM (needs min(W, H) > 160): five scales, weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 (as floats); between scales
+ *     avg_pool2d(kernel 2, padding (H % 2, W % 2)) as PyTorch defines it: zeros on both sides, which count in the divisor of 4, output
+ *     floor((H + 2 p - 2) / 2) + 1.  mcs[s][c] = the mean of cs on scales 0 .. 3 and of l cs on scale 4;
+ *     msssim_c[c] = prod_s max(mcs[s][c], 0)^weight[s], msssim = the mean over channels (double, on the host).
+ *   Sums: every mean is a sum in fp64 -- per-workgroup partials in a fixed tree, then one finishing workgroup in a fixed order -- divided
+ *     on the host.  No floating-point atomics: two calls on the same data return the same bits.
+ *   Where a metric is not defined for the size its fields are NaN and its bit of `valid` is clear; the call succeeds and fills the rest.
+ *   A bit of `valid` is also clear where its metric came out NaN: samples near FLT_MAX (a sanitised infinity under NONE, SRGB, SNORM)
+ *   have squares of +inf, and the window's f(xx) - m1 m1 is then inf - inf, here as in ssim.py.  A set bit means a number.
+ *   The pointwise fields have no bit: an infinity in one image makes mse and l1 +inf, and +FLT_MAX against -FLT_MAX at one sample
+ *   makes smape inf / inf = NaN, as in loss.py.
+ * Calls WAIT for the result (psnr, msssim and the means are finished on the host).  A handle serves one W x H on one device with
+ * ptx_display's event ordering. */
+#define PTX_METRICS_NONE 0
+#define PTX_METRICS_SRGB 1
+#define PTX_METRICS_HDR 2
+#define PTX_METRICS_SNORM 3
+#define PTX_METRICS_VALID_SSIM 1
+#define PTX_METRICS_VALID_MSSSIM 2
+#define PTX_METRICS_VALID_GRAD 4
+#define PTX_METRICS_SCALES 5
+#define PTX_METRICS_TAPS 11
+typedef struct ptx_metrics ptx_metrics;            /* opaque: the planar pyramid of both images, the partial sums; one W x H on one device */
+typedef struct ptx_metrics_params {
+    int   transform;           /* PTX_METRICS_*; default PTX_METRICS_NONE */
+    float exposure;            /* HDR: finite and > 0, or NaN = metered on b; default NaN */
+    float threshold;           /* compareImage's; finite, >= 0; default 0.01 */
+    float samples_a, samples_b;/* the divisors; default 1 */
+    int   pointwise_only;      /* 0 / 1: leave SSIM and MS-SSIM out (their fields NaN, their bits clear, no map); default 0 */
+} ptx_metrics_params;
+typedef struct ptx_metrics_result {
+    size_t   struct_size;      /* set by the CALLER to sizeof(ptx_metrics_result) as it knows it: no byte beyond is written */
+    double   mse, psnr, l1, mape, smape, grad, l1_msssim;
+    double   ssim, msssim;
+    double   ssim_c[3], msssim_c[3];
+    double   mcs[PTX_METRICS_SCALES][3];           /* [scale][channel]; scale 4 holds l cs */
+    double   max_error;
+    uint64_t num_errors, nonfinite_a, nonfinite_b;
+    float    exposure;         /* the one used (HDR), else 1 */
+    int      valid;            /* PTX_METRICS_VALID_* */
+} ptx_metrics_result;
+typedef struct ptx_metrics_plan {
+    int    ssim_valid, msssim_valid;
+    int    scales;             /* levels held: 5 with MS-SSIM, else 1 (the pointwise terms and grad read level 0) */
+    int    w[PTX_METRICS_SCALES], h[PTX_METRICS_SCALES];           /* of every scale the rule defines, held or not */
+    int    tile_w, tile_h;     /* k_metrics_ssim's output tile */
+    int    blocks[PTX_METRICS_SCALES];             /* its workgroups per scale (0: none run) */
+    int    prep_blocks, grad_blocks;
+    size_t level_offset[PTX_METRICS_SCALES];       /* floats, into one image's pyramid */
+    size_t pyramid_floats;     /* one image's pyramid: 3 w h over the levels held */
+    size_t partial_doubles;    /* all partial sums */
+    size_t map_floats;         /* (W - 10)(H - 10), or 0 */
+    float  taps[PTX_METRICS_TAPS];
+    float  weights[PTX_METRICS_SCALES];
+} ptx_metrics_plan;
+void   ptx_default_metrics_params(ptx_metrics_params *p);
+size_t ptx_sizeof_metrics_params(void);
+size_t ptx_sizeof_metrics_result(void);
+size_t ptx_sizeof_metrics_plan(void);
+int  ptx_metrics_create(int device, int width, int height, ptx_metrics **out);   /* PTX_ERR_NODEVICE without a device; at most 16384 x 16384 */
+void ptx_metrics_destroy(ptx_metrics *m);          /* NULL is a no-op; waits for its last use */
+/* a, b: images on the handle's device, compared on `stream` (NULL = the default stream; the caller orders their producers before it
+ * there).  p NULL = defaults.  map_or_null: (H - 10)(W - 10) floats on the device that receive the full-resolution SSIM map, the mean
+ * over channels ((v0 + v1) + v2) / 3 in fp32; refused where SSIM is not defined.  out->struct_size is read first (a sized struct: a
+ * later library with more fields writes no more than that).  Refused before any device call: bad params, a NULL image, a bad descriptor. */
+int  ptx_metrics_compare_device(ptx_metrics *m, const ptx_nn_image *a, const ptx_nn_image *b, const ptx_metrics_params *p,
+                                ptx_metrics_result *out, float *device_map_or_null, void *stream);
+/* The same on host images: each image's byte interval is staged into a buffer the handle owns; host_map_or_null is host memory. */
+int  ptx_metrics_compare_host(ptx_metrics *m, const ptx_nn_image *a, const ptx_nn_image *b, const ptx_metrics_params *p,
+                              ptx_metrics_result *out, float *host_map_or_null);
+/* The tracer's frame as a: source PTX_DISPLAY_IMAGE = the accumulation buffer over spp (samples_a is not read), PTX_DISPLAY_DENOISED =
+ * the last ptx_denoise* result over 1.  b describes HOST memory and is staged.  Runs on the tracer's stream behind every iteration
+ * rendered so far; the accumulation buffer, the statistics and what later iterations compute are untouched.  Refusals as
+ * ptx_display_tracer's. */
+int  ptx_metrics_tracer(ptx_metrics *m, ptx_tracer *t, int source, int spp, const ptx_nn_image *b, const ptx_metrics_params *p,
+                        ptx_metrics_result *out);
+/* Host only: the scale sizes, window taps and buffer sizes of a w x h handle */
+int  ptx_debug_metrics_plan(int w, int h, ptx_metrics_plan *out);
+/* Host only: what a compare call would refuse of these params (NULL: the defaults) and descriptors for a width x height frame */
+int  ptx_debug_metrics_problem(int width, int height, const ptx_nn_image *a, const ptx_nn_image *b, const ptx_metrics_params *p);
+
 /* ---- per-stage entry points (parity tests; same record layouts as the reference's PathSegment 44 B and
  *      ShadeableIntersection 32 B, host arrays in/out, the work runs on the device); ptx_kat_reproject, at the end, is the denoiser's
  *      reprojection alone and needs no tracer ------------------------------------------------------------------- */

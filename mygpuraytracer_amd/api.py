@@ -473,6 +473,116 @@ class Display(_Owned):
         return {k: getattr(out, k) for k, _ in DisplayStatus._fields_}
 
 
+METRICS_NONE, METRICS_SRGB, METRICS_HDR, METRICS_SNORM = 0, 1, 2, 3
+METRICS_VALID_SSIM, METRICS_VALID_MSSSIM, METRICS_VALID_GRAD = 1, 2, 4
+METRICS_SCALES, METRICS_TAPS = 5, 11
+_METRICS_TRANSFORMS = dict(none=METRICS_NONE, srgb=METRICS_SRGB, hdr=METRICS_HDR, snorm=METRICS_SNORM)
+
+
+class MetricsParams(C.Structure):
+    """ptx_metrics_params (include/mi355x_pathtracer.h, "image metrics"; defaults from ptx_default_metrics_params)."""
+    _fields_ = [("transform", C.c_int), ("exposure", C.c_float), ("threshold", C.c_float), ("samples_a", C.c_float), ("samples_b", C.c_float), ("pointwise_only", C.c_int)]
+
+
+class MetricsResult(C.Structure):
+    """ptx_metrics_result: a sized struct, struct_size set by the caller."""
+    _fields_ = [("struct_size", C.c_size_t), ("mse", C.c_double), ("psnr", C.c_double), ("l1", C.c_double), ("mape", C.c_double),
+                ("smape", C.c_double), ("grad", C.c_double), ("l1_msssim", C.c_double), ("ssim", C.c_double), ("msssim", C.c_double),
+                ("ssim_c", C.c_double * 3), ("msssim_c", C.c_double * 3), ("mcs", (C.c_double * 3) * METRICS_SCALES), ("max_error", C.c_double),
+                ("num_errors", C.c_uint64), ("nonfinite_a", C.c_uint64), ("nonfinite_b", C.c_uint64), ("exposure", C.c_float), ("valid", C.c_int)]
+
+
+class MetricsPlan(C.Structure):
+    """ptx_metrics_plan: scale sizes, window taps and buffer sizes of a W x H handle."""
+    _fields_ = [("ssim_valid", C.c_int), ("msssim_valid", C.c_int), ("scales", C.c_int), ("w", C.c_int * METRICS_SCALES), ("h", C.c_int * METRICS_SCALES),
+                ("tile_w", C.c_int), ("tile_h", C.c_int), ("blocks", C.c_int * METRICS_SCALES), ("prep_blocks", C.c_int), ("grad_blocks", C.c_int),
+                ("level_offset", C.c_size_t * METRICS_SCALES), ("pyramid_floats", C.c_size_t), ("partial_doubles", C.c_size_t),
+                ("map_floats", C.c_size_t), ("taps", C.c_float * METRICS_TAPS), ("weights", C.c_float * METRICS_SCALES)]
+
+
+def default_metrics_params(**kw):
+    """ptx_default_metrics_params with keyword overrides (transform, exposure, threshold, samples_a, samples_b, pointwise_only); transform takes the
+    PTX_METRICS_* numbers or "none" / "srgb" / "hdr" / "snorm"; exposure None = NaN = metered on b."""
+    kw = {k: v for k, v in kw.items() if v is not None}
+    if isinstance(kw.get("transform"), str):
+        kw["transform"] = _METRICS_TRANSFORMS[kw["transform"]]
+    return _default_params(MetricsParams, "ptx_default_metrics_params", ("transform", "pointwise_only"), **kw)
+
+
+def _struct_value(v):
+    if isinstance(v, C.Array):
+        return np.array([_struct_value(x) for x in v])
+    return v
+
+
+def _metrics_dict(r):
+    return {k: _struct_value(getattr(r, k)) for k, _ in MetricsResult._fields_ if k != "struct_size"}
+
+
+def debug_metrics_plan(width, height):
+    """ptx_debug_metrics_plan as a dict (arrays as numpy arrays).  No device needed."""
+    out = MetricsPlan()
+    _check(load_library().ptx_debug_metrics_plan(int(width), int(height), C.byref(out)), "ptx_debug_metrics_plan")
+    return {k: _struct_value(getattr(out, k)) for k, _ in MetricsPlan._fields_}
+
+
+def debug_metrics_problem(width, height, a, b, **params):
+    """ptx_debug_metrics_problem: raises PathTracerError with what a compare call would refuse of these images (NNImage, or arrays for
+    nn_image_of; None: no image) and params for a width x height frame.  No device needed."""
+    p = default_metrics_params(**params)
+    imgs = [None if x is None else C.byref(x if isinstance(x, NNImage) else nn_image_of(x)) for x in (a, b)]
+    _check(load_library().ptx_debug_metrics_problem(int(width), int(height), imgs[0], imgs[1], C.byref(p)), "ptx_debug_metrics_problem")
+
+
+class Metrics(_Owned):
+    """Image metrics on one device (opaque ptx_metrics): MSE, PSNR, L1, MAPE, SMAPE, gradient, compareImage's count and maximum, SSIM and
+    MS-SSIM of a test image `a` against a reference image `b` of one W x H, in one call that returns a dict of ptx_metrics_result's
+    fields.  host(a, b) takes numpy views (or NNImage descriptors of host memory), device(a, b) NNImage descriptors of device memory,
+    Tracer.compare(metrics, reference, spp) a tracer's frame."""
+
+    _destroy = "ptx_metrics_destroy"
+
+    def __init__(self, width, height, device=0):
+        self.lib = load_library()
+        h = vp()
+        _check(self.lib.ptx_metrics_create(int(device), int(width), int(height), C.byref(h)), "ptx_metrics_create")
+        self.h = h
+        self.device_ordinal, self.width, self.height = int(device), int(width), int(height)
+
+    def _image(self, x):
+        if isinstance(x, NNImage):
+            return x
+        x = np.asarray(x)
+        if x.ndim == 2:
+            x = x.reshape(self.height, self.width, -1)
+        return nn_image_of(x)
+
+    def host(self, a, b, transform="none", exposure=None, threshold=None, samples_a=1, samples_b=1, want_map=False, pointwise_only=0):
+        """a, b: float32 / float16 views of shape (H, W, >= 3) with any positive strides ((W*H, 3) is reshaped).  want_map: the dict
+        also holds "map", the full-resolution SSIM map (H - 10, W - 10) float32, the mean over channels."""
+        p = default_metrics_params(transform=transform, exposure=exposure, threshold=threshold, samples_a=samples_a, samples_b=samples_b,
+                                   pointwise_only=int(pointwise_only))
+        ia, ib = self._image(a), self._image(b)
+        out = MetricsResult(struct_size=C.sizeof(MetricsResult))
+        smap = np.zeros((max(self.height - 10, 0), max(self.width - 10, 0)), np.float32) if want_map else None
+        _check(self.lib.ptx_metrics_compare_host(self.h, C.byref(ia), C.byref(ib), C.byref(p), C.byref(out), _ptr(smap) if want_map else None),
+               "ptx_metrics_compare_host")
+        d = _metrics_dict(out)
+        if want_map:
+            d["map"] = smap
+        return d
+
+    def device(self, a, b, transform="none", exposure=None, threshold=None, samples_a=1, samples_b=1, map_ptr=None, stream=0, pointwise_only=0):
+        """a, b: NNImage descriptors of device memory (nn_image_of(ptr, format=..)); map_ptr: a device pointer to (H - 10)(W - 10) floats
+        or None; compared on `stream` (a hipStream_t as an integer); waits for the result."""
+        p = default_metrics_params(transform=transform, exposure=exposure, threshold=threshold, samples_a=samples_a, samples_b=samples_b,
+                                   pointwise_only=int(pointwise_only))
+        out = MetricsResult(struct_size=C.sizeof(MetricsResult))
+        _check(self.lib.ptx_metrics_compare_device(self.h, C.byref(a), C.byref(b), C.byref(p), C.byref(out), vp(map_ptr) if map_ptr else None,
+                                                   vp(stream) if stream else None), "ptx_metrics_compare_device")
+        return _metrics_dict(out)
+
+
 NN_LAYERS = 16
 
 
@@ -1258,6 +1368,25 @@ def load_library():
     L.ptx_display_read_blocks.restype, L.ptx_display_read_blocks.argtypes = i, [vp, vp]
     L.ptx_display_get_status.restype, L.ptx_display_get_status.argtypes = i, [vp, C.POINTER(DisplayStatus)]
     L.ptx_debug_display_blocks.restype, L.ptx_debug_display_blocks.argtypes = i, [i, i, C.POINTER(i), C.POINTER(i), vp, vp]
+    # image metrics
+    L.ptx_sizeof_metrics_params.restype = L.ptx_sizeof_metrics_result.restype = L.ptx_sizeof_metrics_plan.restype = C.c_size_t
+    if (L.ptx_sizeof_metrics_params() != C.sizeof(MetricsParams) or L.ptx_sizeof_metrics_result() != C.sizeof(MetricsResult)
+            or L.ptx_sizeof_metrics_plan() != C.sizeof(MetricsPlan)):
+        raise PathTracerError("%s has metrics structs of %d, %d and %d B, this module expects %d, %d and %d B: rebuild the library" % (
+            LIB_PATH, L.ptx_sizeof_metrics_params(), L.ptx_sizeof_metrics_result(), L.ptx_sizeof_metrics_plan(), C.sizeof(MetricsParams),
+            C.sizeof(MetricsResult), C.sizeof(MetricsPlan)))
+    L.ptx_default_metrics_params.argtypes = [C.POINTER(MetricsParams)]
+    L.ptx_metrics_create.restype, L.ptx_metrics_create.argtypes = i, [i, i, i, C.POINTER(vp)]
+    L.ptx_metrics_destroy.restype, L.ptx_metrics_destroy.argtypes = None, [vp]
+    L.ptx_metrics_compare_device.restype = i
+    L.ptx_metrics_compare_device.argtypes = [vp, C.POINTER(NNImage), C.POINTER(NNImage), C.POINTER(MetricsParams), C.POINTER(MetricsResult), vp, vp]
+    L.ptx_metrics_compare_host.restype = i
+    L.ptx_metrics_compare_host.argtypes = [vp, C.POINTER(NNImage), C.POINTER(NNImage), C.POINTER(MetricsParams), C.POINTER(MetricsResult), vp]
+    L.ptx_metrics_tracer.restype = i
+    L.ptx_metrics_tracer.argtypes = [vp, vp, i, i, C.POINTER(NNImage), C.POINTER(MetricsParams), C.POINTER(MetricsResult)]
+    L.ptx_debug_metrics_plan.restype, L.ptx_debug_metrics_plan.argtypes = i, [i, i, C.POINTER(MetricsPlan)]
+    L.ptx_debug_metrics_problem.restype = i
+    L.ptx_debug_metrics_problem.argtypes = [i, i, C.POINTER(NNImage), C.POINTER(NNImage), C.POINTER(MetricsParams)]
     # network denoiser
     L.ptx_sizeof_nn_params.restype = L.ptx_sizeof_nn_info.restype = C.c_size_t
     if L.ptx_sizeof_nn_params() != C.sizeof(NNParams) or L.ptx_sizeof_nn_info() != C.sizeof(NNInfo):
@@ -1819,6 +1948,17 @@ class Tracer(_Owned):
             pp = default_nn_prefilter_params(**(prefilter_params or {}))
             _check(self.lib.ptx_denoise_nn_prefiltered(self.h, nn.h, prefilter.h, C.byref(p), C.byref(pp), int(spp)), "ptx_denoise_nn_prefiltered")
         return self.read_denoised() if read else None
+
+    def compare(self, metrics, reference, spp, source="image", **params):
+        """ptx_metrics_tracer: the accumulation buffer over spp (source "image") or the last denoised frame (source "denoised") against
+        `reference`, a host image as Metrics.host takes it, on the tracer's stream; params: transform, exposure, threshold, samples_b.
+        Returns Metrics.host's dict.  Nothing of the tracer changes."""
+        p = default_metrics_params(**params)
+        src = _DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        ib = metrics._image(reference)
+        out = MetricsResult(struct_size=C.sizeof(MetricsResult))
+        _check(self.lib.ptx_metrics_tracer(metrics.h, self.h, src, int(spp), C.byref(ib), C.byref(p), C.byref(out)), "ptx_metrics_tracer")
+        return _metrics_dict(out)
 
     def variance(self):
         """The last denoise_variance's input variance v0 = V / n and the last pass's variance, (H, W) float32 each."""

@@ -44,6 +44,13 @@
 //                                                                      pixel-centre pinhole ray: ptx_set_guide_samples.  Not with --temporal.)
 //                                  [--guide-bounces B]   (with the same: every guide ray followed through at most B mirrors / glass surfaces to the
 //                                                                      surface seen in them: ptx_set_guide_bounces.  Not with --temporal.)
+//                                  [--compare REF.pfm [--compare-denoised] [--compare-transform none|srgb|hdr|snorm] [--compare-exposure E]
+//                                   [--compare-threshold T]]   (after the render: the frame on the device -- with --compare-denoised the
+//                                                                      denoised one -- against REF.pfm, a file as --pfm writes them, read
+//                                                                      back by the writer's own rule; one line `metrics: {json}`:
+//                                                                      ptx_metrics_tracer.  Not with --frames or --adaptive.)
+//   mi355x_pathtrace --compare-files A.pfm B.pfm [--compare-transform ..] [--compare-exposure E] [--compare-threshold T] [--device K]
+//                                                                     (no scene: A against the reference B, the same line)
 //                                  [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]   (the display
 //                                                                      transform, ptx_display_*: when any is given, every .png and
 //                                                                      .denoised.png takes its bytes from it -- automatic exposure from block
@@ -163,11 +170,91 @@ static int run_frames(Scene *scene, int frames, const std::string &orbit_script,
     return 0;
 }
 
+// --compare / --compare-files: the image metrics (ptx_metrics_*) as one line `metrics: {json}`; NaN, Infinity and -Infinity as Python's
+// json module reads them.
+struct CompareFlags {
+    std::string ref, file_a, file_b;
+    bool denoised = false;
+    ptx_metrics_params params;
+};
+static bool compare_flag(CompareFlags &c, const std::string &a, int argc, char **argv, int &i) {
+    auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "%s needs %d value(s)\n", a.c_str(), n); exit(1); } };
+    if (a == "--compare") { need(1); c.ref = argv[++i]; }
+    else if (a == "--compare-denoised") c.denoised = true;
+    else if (a == "--compare-transform") {
+        need(1);
+        const std::string v = argv[++i];
+        c.params.transform = v == "none" ? PTX_METRICS_NONE : v == "srgb" ? PTX_METRICS_SRGB : v == "hdr" ? PTX_METRICS_HDR : v == "snorm" ? PTX_METRICS_SNORM : -1;
+        if (c.params.transform < 0) { fprintf(stderr, "--compare-transform needs none, srgb, hdr or snorm\n"); exit(1); }
+    }
+    else if (a == "--compare-exposure") { need(1); c.params.exposure = (float)atof(argv[++i]); }
+    else if (a == "--compare-threshold") { need(1); c.params.threshold = (float)atof(argv[++i]); }
+    else return false;
+    return true;
+}
+static std::string json_number(double v) {
+    if (v != v) return "NaN";
+    if (v > 1.7976931348623157e308) return "Infinity";
+    if (v < -1.7976931348623157e308) return "-Infinity";
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+static void print_metrics(const ptx_metrics_result &r) {
+    std::ostringstream o;
+    auto triple = [&](const double *v) { return "[" + json_number(v[0]) + ", " + json_number(v[1]) + ", " + json_number(v[2]) + "]"; };
+    o << "{\"mse\": " << json_number(r.mse) << ", \"psnr\": " << json_number(r.psnr) << ", \"l1\": " << json_number(r.l1) << ", \"mape\": "
+      << json_number(r.mape) << ", \"smape\": " << json_number(r.smape) << ", \"grad\": " << json_number(r.grad) << ", \"l1_msssim\": "
+      << json_number(r.l1_msssim) << ", \"ssim\": " << json_number(r.ssim) << ", \"msssim\": " << json_number(r.msssim) << ", \"ssim_c\": "
+      << triple(r.ssim_c) << ", \"msssim_c\": " << triple(r.msssim_c) << ", \"mcs\": [";
+    for (int s = 0; s < PTX_METRICS_SCALES; s++) o << (s ? ", " : "") << triple(r.mcs[s]);
+    o << "], \"max_error\": " << json_number(r.max_error) << ", \"num_errors\": " << (unsigned long long)r.num_errors << ", \"nonfinite_a\": "
+      << (unsigned long long)r.nonfinite_a << ", \"nonfinite_b\": " << (unsigned long long)r.nonfinite_b << ", \"exposure\": "
+      << json_number((double)r.exposure) << ", \"valid\": " << r.valid << "}";
+    printf("metrics: %s\n", o.str().c_str());
+}
+static ptx_nn_image packed_image(const std::vector<float> &rgb) {
+    ptx_nn_image img = ptx_nn_image();
+    img.ptr = rgb.data();
+    img.format = PTX_NN_FORMAT_FLOAT3;
+    return img;
+}
+// --compare-files A.pfm B.pfm: a against the reference b, no scene -- the counterpart of OIDN's training/compare_image.py
+static int compare_files(const CompareFlags &c, int device) {
+    std::vector<float> a, b;
+    int wa, ha, wb, hb;
+    std::string why;
+    if (!ptimg::read_pfm(c.file_a, wa, ha, a, why) || !ptimg::read_pfm(c.file_b, wb, hb, b, why)) { fprintf(stderr, "%s\n", why.c_str()); return 1; }
+    if (wa != wb || ha != hb) { fprintf(stderr, "--compare-files: %s is %d x %d, %s is %d x %d\n", c.file_a.c_str(), wa, ha, c.file_b.c_str(), wb, hb); return 1; }
+    ptx_metrics *m = nullptr;
+    ptx_metrics_result r = ptx_metrics_result();
+    r.struct_size = sizeof r;
+    const ptx_nn_image ia = packed_image(a), ib = packed_image(b);
+    const bool ok = ptx_metrics_create(device, wa, ha, &m) == PTX_OK && ptx_metrics_compare_host(m, &ia, &ib, &c.params, &r, nullptr) == PTX_OK;
+    ptx_metrics_destroy(m);
+    if (!ok) { fprintf(stderr, "compare failed: %s\n", ptx_last_error()); return 1; }
+    print_metrics(r);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2 || !strcmp(argv[1], "--help")) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K] [--guide-bounces B] [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--depth D] [--iterations N] [--out PREFIX] [--pfm] [--hdr] [--no-aa] [--dof] [--no-sort] [--no-cache] [--device K] [--arith 0|1|2] [--checkpoint FILE [--checkpoint-every N]] [--resume FILE] [--orbit SCRIPT] [--per-call [--no-render-ahead]] [--denoise [--denoise-passes N]] [--frames K --frame-step SCRIPT] [--temporal] [--variance [--phi-luminance X]] [--until-error E [--error-floor F]] [--measured [--measure-every K]] [--adaptive E [--measure-every K] [--error-floor F] [--adaptive-denoise [--denoise-passes N] [--phi-luminance X]]] [--guide-samples K] [--guide-bounces B] [--tonemap clamp|reinhard|aces] [--exposure auto|<scale>] [--srgb] [--dither] [--adapt A] [--compare REF.pfm [--compare-denoised] [--compare-transform none|srgb|hdr|snorm] [--compare-exposure E] [--compare-threshold T]]\n       %s --compare-files A.pfm B.pfm [--compare-transform ..] [--compare-exposure E] [--compare-threshold T] [--device K]\n", argv[0], argv[0]);
         return argc < 2;
+    }
+    CompareFlags cmp;
+    ptx_default_metrics_params(&cmp.params);
+    if (!strcmp(argv[1], "--compare-files")) {   // no scene: mi355x_pathtrace --compare-files A.pfm B.pfm [--compare-transform ..] [--device K]
+        if (argc < 4) { fprintf(stderr, "--compare-files needs A.pfm B.pfm\n"); return 1; }
+        cmp.file_a = argv[2]; cmp.file_b = argv[3];
+        int device = 0;
+        for (int i = 4; i < argc; i++) {
+            const std::string a = argv[i];
+            if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
+            else if (!compare_flag(cmp, a, argc, argv, i) || !cmp.ref.empty() || cmp.denoised) { fprintf(stderr, "unknown option %s with --compare-files\n", a.c_str()); return 1; }
+        }
+        return compare_files(cmp, device);
     }
     int resw = 0, resh = 0, depth = 0, iterations = 0;
     bool pfm = false, hdr = false, per_call = false, denoise = false, temporal = false, variance = false, measured = false, adaptive_denoise = false;
@@ -251,9 +338,12 @@ int main(int argc, char **argv) {
             g_display.on = true;
         }
         else if (a == "--measure-every") { need(1); measure_every = atoi(argv[++i]); }
+        else if (compare_flag(cmp, a, argc, argv, i)) {}
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
     }
     g_display.device = opt.device < 0 ? 0 : opt.device;
+    if (cmp.denoised && (cmp.ref.empty() || !denoise)) { fprintf(stderr, "--compare-denoised needs --compare REF.pfm and --denoise\n"); return 1; }
+    if (!cmp.ref.empty() && (frames > 0 || adaptive >= 0.0)) { fprintf(stderr, "--compare does not combine with --frames or --adaptive\n"); return 1; }
     const bool batches = until_error >= 0.0 || measured;      // the render goes in batches of measure_every iterations, a ptx_moments_add after each
     if (!nn_path.empty() && !denoise) { fprintf(stderr, "--nn needs --denoise\n"); return 1; }
     if (nnParams().hdr && nn_path.empty()) { fprintf(stderr, "--nn-hdr needs --nn FILE\n"); return 1; }
@@ -429,6 +519,22 @@ int main(int argc, char **argv) {
         if (!ptimg::write_png_rgb8(ss.str() + ".denoised.png", width, height, rgb8.data())) { fprintf(stderr, "cannot write %s.denoised.png\n", ss.str().c_str()); return 1; }
         printf("Saved %s.denoised.png.\n", ss.str().c_str());
         if (pfm) { ptimg::write_pfm(ss.str() + ".denoised.pfm", width, height, den, 1.0f); printf("Saved %s.denoised.pfm.\n", ss.str().c_str()); }
+    }
+    if (!cmp.ref.empty() && n > 0) {            // the frame (or the denoised one) on the device against REF.pfm, a file as --pfm writes them
+        std::vector<float> ref;
+        int wr, hr;
+        std::string why;
+        if (!ptimg::read_pfm(cmp.ref, wr, hr, ref, why)) { fprintf(stderr, "%s\n", why.c_str()); return 1; }
+        if (wr != width || hr != height) { fprintf(stderr, "--compare: %s is %d x %d, the frame is %d x %d\n", cmp.ref.c_str(), wr, hr, width, height); return 1; }
+        ptx_metrics *m = nullptr;
+        ptx_metrics_result r = ptx_metrics_result();
+        r.struct_size = sizeof r;
+        const ptx_nn_image ib = packed_image(ref);
+        const bool ok = ptx_metrics_create(opt.device < 0 ? 0 : opt.device, width, height, &m) == PTX_OK &&
+                        ptx_metrics_tracer(m, t, cmp.denoised ? PTX_DISPLAY_DENOISED : PTX_DISPLAY_IMAGE, n, &ib, &cmp.params, &r) == PTX_OK;
+        ptx_metrics_destroy(m);
+        if (!ok) { fprintf(stderr, "compare failed: %s\n", ptx_last_error()); return 1; }
+        print_metrics(r);
     }
     if (hdr) {                                                                          // img.saveHDR, main.cpp:101
         std::vector<float> mean;

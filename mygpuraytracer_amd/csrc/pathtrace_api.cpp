@@ -45,6 +45,8 @@ std::vector<float> g_adaptive_denoised;      // adaptiveDenoisedFrame()'s
 ptx_display *g_display = nullptr;    // the preview's display transform with displayTransform() on: created on first use
 int g_display_key[3] = {0, 0, 0};    // its device, width, height
 ptx_display_status g_display_status = {};
+ptx_metrics *g_metrics = nullptr;    // compareToReference's handle: created on first use
+int g_metrics_key[3] = {0, 0, 0};    // its device, width, height
 std::vector<uint8_t> g_display_codes;        // sendToGPU's codes of a host frame on their way to the pbo
 int g_calls = 0;                     // pathtrace() calls since pathtraceInit
 
@@ -347,7 +349,34 @@ static void write_preview(int iter, void *pbo) {
     check(ptx_display_tracer(g_display, g_tracer, PTX_DISPLAY_IMAGE, iter, &displayParams(), pbo), "pathtrace display");
 }
 
+ptx_metrics_params &metricsParams() {
+    static ptx_metrics_params p;
+    static bool init = false;
+    if (!init) { ptx_default_metrics_params(&p); init = true; }
+    return p;
+}
+
+ptx_metrics_result compareToReference(const float *rgb, int iter, bool denoised) {
+    if (g_multi) { fprintf(stderr, "compareToReference: the metrics run on one device; pathtraceDevices() names several\n"); exit(EXIT_FAILURE); }
+    const int w = hst_scene->state.camera.resolution[0], h = hst_scene->state.camera.resolution[1];
+    const int key[3] = {g_device, w, h};
+    if (g_metrics && memcmp(key, g_metrics_key, sizeof key) != 0) { ptx_metrics_destroy(g_metrics); g_metrics = nullptr; }
+    if (!g_metrics) {
+        check(ptx_metrics_create(g_device, w, h, &g_metrics), "compareToReference");
+        memcpy(g_metrics_key, key, sizeof key);
+    }
+    ptx_nn_image ref = ptx_nn_image();
+    ref.ptr = rgb;
+    ref.format = PTX_NN_FORMAT_FLOAT3;
+    ptx_metrics_result r = ptx_metrics_result();
+    r.struct_size = sizeof r;
+    check(ptx_metrics_tracer(g_metrics, g_tracer, denoised ? PTX_DISPLAY_DENOISED : PTX_DISPLAY_IMAGE, iter, &ref, &metricsParams(), &r), "compareToReference");
+    return r;
+}
+
 void GPUdenoiseRelease() {
+    ptx_metrics_destroy(g_metrics);
+    g_metrics = nullptr;
     ptx_display_destroy(g_display);
     g_display = nullptr;
     ptx_temporal_destroy(g_temporal);

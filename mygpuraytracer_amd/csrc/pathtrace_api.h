@@ -342,6 +342,12 @@ void pathtraceAdaptiveStep(int k);
 bool &displayTransform();
 ptx_display_params &displayParams();
 const ptx_display_status &displayStatus();
+// Image metrics (ptx_metrics_*): the current frame -- the accumulation buffer over `iter` samples, or with denoised = true the frame
+// GPUdenoise(true) left on the device -- against a host reference of W*H*3 packed floats, with metricsParams()
+// (ptx_default_metrics_params until changed).  The module-level handle is made on first use and freed by GPUdenoiseRelease().  One
+// device only; an error prints and exits, as everywhere in this veneer.
+ptx_metrics_params &metricsParams();
+ptx_metrics_result compareToReference(const float *rgb, int iter, bool denoised = false);
 void GPUdenoiseRelease();
 
 namespace mi355x {

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <cstring>
 #include <vector>
 
@@ -198,6 +199,30 @@ inline bool write_pfm(const std::string &path, int w, int h, const float *sum_rg
         fwrite(row.data(), sizeof(float), row.size(), f);
     }
     fclose(f);
+    return true;
+}
+
+// write_pfm's inverse: a colour PFM of either byte order as top-row-first W*H*3 floats (the writer stores the bottom row first and does
+// not mirror).  why: what is wrong with the file.
+inline bool read_pfm(const std::string &path, int &w, int &h, std::vector<float> &rgb, std::string &why) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { why = "cannot open " + path; return false; }
+    char magic[3] = {0, 0, 0};
+    double scale = 0.0;
+    w = h = 0;
+    const bool head = fscanf(f, "%2s %d %d %lf", magic, &w, &h, &scale) == 4 && fgetc(f) != EOF;
+    if (!head || strcmp(magic, "PF") != 0 || w < 1 || h < 1 || w > 16384 || h > 16384 || scale == 0.0) {
+        fclose(f);
+        why = path + " is not a colour PFM of at most 16384 x 16384";
+        return false;
+    }
+    rgb.resize((size_t)w * h * 3);
+    bool ok = true;
+    for (int y = h - 1; y >= 0 && ok; y--) ok = fread(&rgb[(size_t)y * w * 3], sizeof(float), (size_t)w * 3, f) == (size_t)w * 3;
+    fclose(f);
+    if (!ok) { why = path + " is shorter than its header says"; return false; }
+    if (scale > 0.0)                                                 // big-endian samples
+        for (float &v : rgb) { uint8_t *b = reinterpret_cast<uint8_t *>(&v); std::swap(b[0], b[3]); std::swap(b[1], b[2]); }
     return true;
 }
 

@@ -18,6 +18,7 @@
 #include "pt_adaptive.h"
 #include "pt_display.h"
 #include "pt_nn.h"
+#include "pt_metrics.h"
 
 namespace {
 
@@ -446,6 +447,29 @@ int ptx_display_tracer(ptx_display *d, ptx_tracer *t, int source, int spp, const
     PT_HC(hipSetDevice(t->device));
     return pt_display_enqueue(d, t->stream, source == PTX_DISPLAY_IMAGE ? (const float *)t->d_image : (const float *)t->d_dn_out, samples, p,
                               device_uchar4);
+}
+
+// ---- image metrics (pt_metrics.hip; definition in include/mi355x_pathtracer.h) -------------------------------------------------------
+// The tracer's frame against a host reference, on the tracer's stream: reads the accumulation buffer or the denoised frame, writes
+// only the handle's own buffers.
+int ptx_metrics_tracer(ptx_metrics *m, ptx_tracer *t, int source, int spp, const ptx_nn_image *b, const ptx_metrics_params *params,
+                       ptx_metrics_result *out) {
+    ptx_metrics_params p = params_or_default(params, ptx_default_metrics_params);
+    if (source != PTX_DISPLAY_IMAGE && source != PTX_DISPLAY_DENOISED)
+        return pt_fail(PTX_ERR_INVALID, "ptx_metrics_tracer: source must be PTX_DISPLAY_IMAGE or PTX_DISPLAY_DENOISED");
+    if (source == PTX_DISPLAY_IMAGE && spp < 1) return bad_spp("ptx_metrics_tracer");
+    p.samples_a = source == PTX_DISPLAY_IMAGE ? (float)spp : 1.f;
+    if (!m || !t || !out) return pt_fail(PTX_ERR_INVALID, "ptx_metrics_tracer: null metrics handle, tracer or result");
+    if (out->struct_size < sizeof(size_t)) return pt_fail(PTX_ERR_INVALID, "ptx_metrics_tracer: ptx_metrics_result.struct_size is not set");
+    PtNnImageView va, vb, db;
+    if (const int rc = pt_metrics_problem("ptx_metrics_tracer", m->w, m->h, nullptr, false, b, p, &va, &vb)) return rc;
+    if (const int rc = frame_handle_problem("ptx_metrics_tracer", t, "metrics", *m)) return rc;
+    if (source == PTX_DISPLAY_DENOISED && !t->dn_done) return pt_fail(PTX_ERR_INVALID, "ptx_metrics_tracer: no ptx_denoise on this tracer yet");
+    PT_HC(hipSetDevice(t->device));
+    if (const int rc = pt_metrics_stage(m, 1, vb, &db)) return rc;
+    va.base = (uintptr_t)(source == PTX_DISPLAY_IMAGE ? (const float *)t->d_image : (const float *)t->d_dn_out);
+    va.format = PTX_NN_FORMAT_FLOAT3; va.pixel_stride = 12; va.row_stride = 12 * (size_t)m->w;
+    return pt_metrics_compare(m, t->stream, va, db, p, out, nullptr);
 }
 
 }  // extern "C"
